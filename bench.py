@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s of the MI355X-native engine on BASELINE.json's headline configuration.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one greedy decode token (one pass of the hot path over the resident weights, batch 1).  The
@@ -11,7 +11,15 @@ exactly K tokens timed between (barrier + device synchronize) pairs; rank 0 prin
 every rank runs an independent whole-model replica on its own GPU (the path has no exchange step),
 `value` = N*K / max-over-ranks time, scaling = weak.
 
-Besides the contract fields the line carries
+A plain run does only what the headline needs: load, prompt, warm-up, the K timed steps, the JSON line.
+--dump-outputs DIR writes, after the timed steps, what the timed path returned (rank 0):
+  tokens.npy            -- the K token ids of the timed steps (float64), the last one from the last step
+  last_step_logits.npy  -- the last timed step's logits (float32, vocab): that step run once more on the same token and position
+Weights and prompt are seeded, so two builds given the same arguments can be compared output for output.
+
+--full adds everything else, each measured in the same process after the headline: the fields below, the
+shader clock of the timed workload (`sclk_mhz`) and config.prompt_pass (--prompt-bench).  Besides the contract
+fields a --full line carries
   roofline     -- HBM roofline of the dominant kernel (the dequant-fused GEMV): algorithmic bytes per launch /
                   average launch duration measured with HIP event pairs on the compute stream
   cpu_baseline -- the reference's own CLI + host loop (oracle/_ref/ntransformer_cpu: reference src/main.cpp, engine.cpp,
@@ -61,6 +69,10 @@ def parse():
     ap.add_argument("--no-also", action="store_true", help="skip the other BASELINE configurations (8B Q4_K_M, 70B Q4_K_M, 70B Q6_K, 8B Q8_0 behind 3900- and 32768-token prompts)")
     ap.add_argument("--no-pmc-note", action="store_true")
     ap.add_argument("--prompt-bench", type=int, default=1024, help="also time one prompt pass of this many tokens (0 = skip); reported under config.prompt_pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, shader clock, prompt pass, the other configurations, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/*.npy (see the module docstring)")
     return ap.parse_args()
 
 
@@ -105,7 +117,7 @@ def cpu_baseline_reference_cli(args, spec):
         raise FileNotFoundError("oracle/_ref/ntransformer_cpu is not built (make -C oracle ref, needs /root/reference)")
     threads, info = host_cpu_budget()
     gguf_bytes = 9.2e9 if args.model == "8b" else 1e9
-    path = _scratch_file("_bench_cpu_%s_%s.gguf" % (args.model, args.mix.lower()), gguf_bytes)
+    path = _scratch_file("_bench_cpu_%s_%s_%d.gguf" % (args.model, args.mix.lower(), os.getpid()), gguf_bytes)   # (per process: shared directory)
     if path is None:
         raise RuntimeError("no scratch space for the %.1f GB GGUF" % (gguf_bytes / 1e9))
     t0 = time.perf_counter()
@@ -221,9 +233,25 @@ def activation_form(mix, repack=True):
     return "f32" if (mix in ("Q8_0", "Q4_0", "F16", "F32") or not repack) else "int24-block"
 
 
-def run_workload(args, model, mix, steps, warmup, timed, sync, prompt_len=None, ctx=None):
+def dump_outputs(eng, args, out, tok, pos_end, dump_dir):
+    """--dump-outputs: the token ids the timed call returned and the logits of its last step.  The path keeps no logits on the host
+    (the greedy token is picked on the device), so that step is run once more on its own input token and position: the KV row it
+    writes holds the same values, everything before it is unchanged."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    last_in = out[-2] if len(out) > 1 else tok
+    if args.no_fuse:
+        logits = eng.forward([last_in], pos_end - 1)
+    else:
+        logits = eng.decode_fused(last_in, pos_end - 1, graph=not args.no_graph)
+    np.save(os.path.join(dump_dir, "tokens.npy"), np.asarray(out, dtype=np.float64))
+    np.save(os.path.join(dump_dir, "last_step_logits.npy"), np.asarray(logits, dtype=np.float32))
+
+
+def run_workload(args, model, mix, steps, warmup, timed, sync, prompt_len=None, ctx=None, dump_dir=None):
     """Load `model`:`mix` resident, prompt + first token untimed, `warmup` tokens untimed, exactly `steps` greedy decode
-    tokens timed by `timed` (replica.timed_steps partial).  Returns the measurements (rank-local roofline included)."""
+    tokens timed by `timed` (replica.timed_steps partial).  Returns the measurements; with --full the rank-local roofline,
+    shader clock and prompt pass too."""
     import numpy as np
     from ntransformer_amd import engine as E
     spec = E.synth_spec(model, mix)
@@ -252,6 +280,14 @@ def run_workload(args, model, mix, steps, warmup, timed, sync, prompt_len=None, 
     pos += warmup
     elapsed, _, out = timed(lambda k: eng.decode_greedy_steps(tok, pos, k), steps)
     pos_end = pos + steps
+    if dump_dir:
+        dump_outputs(eng, args, out, tok, pos_end, dump_dir)
+    res = {"spec": spec, "prompt_len": prompt_len, "elapsed": elapsed, "pos": pos, "pos_end": pos_end, "t_load": t_load,
+           "b_tok": eng.bytes_per_token(pos + steps // 2), "path": eng.decode_path() if hasattr(eng, "decode_path") else None,
+           "resident_bytes": eng.resident_weight_bytes() if hasattr(eng, "resident_weight_bytes") else None, "ctx": ctx}
+    if not args.full:
+        eng.close()
+        return res
     sclk = None
     try:   # the average shader clock of the same workload, over 32 more steps right behind the timed region (a one-wave kernel beside them on
         # another stream: ntk_debug_sclk_begin / _end): lets a profiled pass be compared with an un-profiled one
@@ -267,9 +303,7 @@ def run_workload(args, model, mix, steps, warmup, timed, sync, prompt_len=None, 
             sclk = round(c.mhz, 1) if c.mhz else None
     except Exception:
         sclk = None
-    res = {"spec": spec, "prompt_len": prompt_len, "elapsed": elapsed, "pos": pos, "pos_end": pos_end, "t_load": t_load, "sclk_mhz": sclk,
-           "b_tok": eng.bytes_per_token(pos + steps // 2), "path": eng.decode_path() if hasattr(eng, "decode_path") else None,
-           "resident_bytes": eng.resident_weight_bytes() if hasattr(eng, "resident_weight_bytes") else None, "ctx": ctx}
+    res["sclk_mhz"] = sclk
 
     # ---- roofline of the dominant kernel, measured live with HIP events on the compute stream over a few eagerly
     # launched tokens (the fused launch sequence: the persistent token kernel has no per-operator boundaries to put
@@ -416,9 +450,10 @@ def main():
     def timed_local(fn, k):
         return replica.timed_steps(fn, k, sync, None, None)
 
-    r = run_workload(args, args.model, args.mix, args.steps, args.warmup, timed_all_ranks, sync)
+    r = run_workload(args, args.model, args.mix, args.steps, args.warmup, timed_all_ranks, sync,
+                     dump_dir=args.dump_outputs if rank == 0 else None)
     headline = (args.model, args.mix) == ("8b", "Q8_0")
-    if rank != 0 and world > 1 and headline and not args.no_also:   # (rank 0 runs it below, inside the collective timing: same order on every rank)
+    if args.full and rank != 0 and world > 1 and headline and not args.no_also:   # (rank 0 runs it below, inside the collective timing: same order on every rank)
         try:
             keep_pb, args.prompt_bench = args.prompt_bench, 0
             run_workload(args, "70b", "Q6_K", 64, min(args.warmup, 8), timed_all_ranks, sync)
@@ -433,7 +468,7 @@ def main():
             "metric": "decode tokens/sec (Llama-3.1-8B Q8_0 class, resident weights, greedy, batch 1)" if headline
                       else "decode tokens/sec (%s %s, resident weights, greedy, batch 1)" % (args.model, args.mix),
             "value": round(tok_s, 3), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "sclk_mhz": r["sclk_mhz"], "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "sclk_mhz": r.get("sclk_mhz"), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": round(tok_s / REF_3090_TOK_S, 3) if headline else None,   # whole-job value / the published single-GPU number
             "vs_baseline_per_gpu": round(tok_s / world / REF_3090_TOK_S, 3) if headline else None,
             "dtype": "f32", "activation_form": activation_form(args.mix, not args.no_repack), "data": "synthetic",   # (forms: ACTIVATION_FORMS above / DESIGN 3.1-3.2)
@@ -445,8 +480,10 @@ def main():
                        "algorithmic_bytes_per_token": r["b_tok"], "load_seconds": round(r["t_load"], 2),
                        "prompt_pass": r.get("prompt")},
             "hbm_fraction_of_8TBs_end_to_end": round(r["b_tok"] * tok_s / world / (HBM_PEAK_GBS * 1e9), 4),
-            "roofline": roofline_block(args, args.model, args.mix, r),
+            "roofline": roofline_block(args, args.model, args.mix, r) if args.full else None,
         }
+        if not args.full:   # measured by --full only
+            del line["sclk_mhz"], line["roofline"], line["config"]["prompt_pass"]
         # ---- the other BASELINE configurations under the same clock: compact entries (the whole line stays under 5 KB) ----
         def also_entry(key, model, mix, steps, a, nrep):
             a_tok_s = nrep * steps / a["elapsed"]
@@ -462,10 +499,11 @@ def main():
             if a.get("prompt") and "tokens_per_s" in a["prompt"]:
                 e["prompt_tok_s"] = a["prompt"]["tokens_per_s"]
             return e
-        line["config"]["also_legend"] = ("k = model_mix[_ctx<prompt tokens>]; value tokens/s; frac = algorithmic bytes/token x tokens/s / 8 TB/s; roofline (GEMV launches): frac_events (live HIP "
-                                         "events), frac_trace / us_trace (committed rocprofv3 trace), traffic (PMC bytes per launch); resident_GB = weights in HBM; prompt_tok_s = 1024-token "
-                                         "prompt pass; _xN_per_gpu = N sequences / streams over ONE copy of the weights (nt_engine_load_shared), no batching: all tokens / wall time")
-        if headline and not args.no_also:
+        if args.full:
+            line["config"]["also_legend"] = ("k = model_mix[_ctx<prompt tokens>]; value tokens/s; frac = algorithmic bytes/token x tokens/s / 8 TB/s; roofline (GEMV launches): frac_events (live HIP "
+                                             "events), frac_trace / us_trace (committed rocprofv3 trace), traffic (PMC bytes per launch); resident_GB = weights in HBM; prompt_tok_s = 1024-token "
+                                             "prompt pass; _xN_per_gpu = N sequences / streams over ONE copy of the weights (nt_engine_load_shared), no batching: all tokens / wall time")
+        if args.full and headline and not args.no_also:
             also = []
             # (the last one: decode behind a 32768-token prompt -- 4.3 GB of KV cache per token, a third of the bytes: contexts beyond 4096)
             plan = ((("8b", "Q4_K_M", 128, None), ("70b", "Q4_K_M", 64, None), ("70b", "Q6_K", 64, None), ("8b", "Q8_0", 64, 3900), ("8b", "Q8_0", 32, 32768))
@@ -489,7 +527,7 @@ def main():
                     except Exception as e:
                         also.append({"k": "8b_q8_0_x%d_per_gpu" % nseq, "value": None, "error": repr(e)[:200]})
             line["config"]["also"] = also
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (the replicas of an N > 1 run would wait on it)
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (the replicas of an N > 1 run would wait on it)
             try:
                 line["cpu_baseline"] = cpu_baseline_reference_cli(args, r["spec"])
             except Exception as e:   # the GPU number must survive a CPU-side problem

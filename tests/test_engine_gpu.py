@@ -110,7 +110,7 @@ def test_8b_width_slice_matches_oracle():
     """Two layers at the real Llama-3.1-8B width (H=4096, I=14336, 32/8 heads, hd=128) with the full 128256-row LM
     head, Q8_0: full-width parity against the oracle without the full-depth CPU cost."""
     spec = E.synth_spec("8b", "Q8_0", layers=2)
-    path = "/tmp/_8b_l2_q8_0.gguf"
+    path = "/tmp/_8b_l2_q8_0_%d.gguf" % os.getpid()   # (per process: the directory is shared between users and runs)
     E.synth_write_gguf(path, spec)
     eng = E.Engine()
     eng.load(path, 256)
@@ -397,7 +397,7 @@ def _parity_at_config(tag, preset, mix, layers, n_prompt, n_decode, ctx=256, pat
     activations were made larger on purpose)."""
     import time
     spec = E.synth_spec(preset, mix, layers=layers)
-    path = os.path.join(_scratch_dir(), "_parity_%s.gguf" % tag)
+    path = os.path.join(_scratch_dir(), "_parity_%s_%d.gguf" % (tag, os.getpid()))   # (per process: the directory is shared between users and runs)
     E.synth_write_gguf(path, spec)
     if patch is not None: patch(path)
     try:

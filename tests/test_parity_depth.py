@@ -145,7 +145,7 @@ def _depth_parity(tag, preset, mix, layers, n_prompt, n_decode, ctx=256, patch=N
     attention logits of ~2e4 turn every near-tie of two keys into an O(1e-3) softmax error: profiles/r06_massive_activation_diagnosis.txt).  Part (a)
     keeps kv_scale."""
     spec = E.synth_spec(preset, mix, layers=layers)
-    path = os.path.join(_scratch_dir(), "_depth_%s.gguf" % tag)
+    path = os.path.join(_scratch_dir(), "_depth_%s_%d.gguf" % (tag, os.getpid()))   # (per process: the directory is shared between users and runs)
     E.synth_write_gguf(path, spec)
     if patch is not None: patch(path)   # edits the GGUF in place before anybody loads it
     rec = {"test": tag, "model": preset, "mix": mix, "layers": layers, "prompt_tokens": n_prompt, "decode_steps": n_decode,

@@ -122,7 +122,7 @@ def test_four_way_slices_of_a_70b_width_layer(world):
         assert not isinstance(out[0], Exception), out[0]
         return out[0]
     ref_logits, _, _ = single()
-    path = os.path.join("/dev/shm" if os.access("/dev/shm", os.W_OK) else "/tmp", "_tp_70b_l1.gguf")
+    path = os.path.join("/dev/shm" if os.access("/dev/shm", os.W_OK) else "/tmp", "_tp_70b_l1_%d.gguf" % os.getpid())   # (per process: shared directory)
     E.synth_write_gguf(path, spec)       # the same seeded tensors as load_synthetic (test_synthetic_loader_equals_file_loader)
     try:
         want = _oracle_logits(path, 128, prompt, fed)

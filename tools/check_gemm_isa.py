@@ -6,7 +6,7 @@ compiles the kernel to ISA and checks, per instantiation, that every VGPR writte
 than ring loads and the ds_write_b128 that consume them.
 usage: python tools/check_gemm_isa.py [--hipcc HIPCC] [--flags "HIPFLAGS"]   (exit code 1 on a violation)
 The Makefile runs it on the exact compiler and flags of every build of the library (shipping, trace, tuning, experiments)."""
-import argparse, hashlib, os, re, shlex, subprocess, sys, tempfile
+import argparse, os, re, shlex, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument("--hipcc", default="/opt/rocm/bin/hipcc")
@@ -14,9 +14,11 @@ ap.add_argument("--flags", default="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -
 a = ap.parse_args()
 src = os.path.join(ROOT, "ntransformer_amd", "csrc", "gemm_f16.hip")
 flags = [f for f in shlex.split(a.flags) if f not in ("-c",)]
-out = os.path.join(tempfile.gettempdir(), "gemm_f16_check_%s.s" % hashlib.sha1(a.flags.encode()).hexdigest()[:8])
-subprocess.check_call([a.hipcc] + flags + ["-S", "--cuda-device-only", src, "-o", out], cwd=tempfile.gettempdir(), stderr=subprocess.DEVNULL)
-txt = open(out).read()
+# a directory of this run's own: the temporary directory is shared between users and concurrent builds
+with tempfile.TemporaryDirectory(prefix="gemm_f16_check_") as tmp:
+    out = os.path.join(tmp, "gemm_f16.s")
+    subprocess.check_call([a.hipcc] + flags + ["-S", "--cuda-device-only", src, "-o", out], cwd=tmp, stderr=subprocess.DEVNULL)
+    txt = open(out).read()
 bad = 0
 def regs(tok):
     m = re.match(r"v\[(\d+):(\d+)\]", tok)

@@ -11,7 +11,7 @@ for rep in 1 2; do
     for v in merged two; do
       f=""; [ $v = merged ] && f="--attention-merge"
       echo "== prompt $pl $v (rep $rep)" >> $OUT/ab.txt
-      timeout 300 python bench.py --no-also --no-cpu-baseline --no-pmc-note --prompt-bench 0 --prompt-len $pl --ctx 4096 --steps 64 $f 2>/dev/null | tail -1 | cut -c1-200 >> $OUT/ab.txt
+      timeout 300 python bench.py --full --no-also --no-cpu-baseline --no-pmc-note --prompt-bench 0 --prompt-len $pl --ctx 4096 --steps 64 $f 2>/dev/null | tail -1 | cut -c1-200 >> $OUT/ab.txt
     done
   done
 done
