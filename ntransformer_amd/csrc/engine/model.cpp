@@ -26,6 +26,9 @@ static bool is_quant(int dt) {
     return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K;
 }
 
+// the three statuses with which a launcher says "nothing was launched: try the next form"
+static bool not_taken(int st) { return st == NTK_E_DTYPE || st == NTK_E_SHAPE || st == NTK_E_ALIGN; }
+
 Model::~Model() { free_all(); }
 
 void Model::free_all() {
@@ -623,6 +626,21 @@ float* Model::forward(const int* tokens, int T, int start_pos) {
     return logits_;
 }
 
+// The prompt pass's operand planes: the FP16 GEMM reads X split into FP16 planes, written into a workspace by its own pre-pass or by the launch that
+// produced X (ntk_*_prepare_x: the projection then needs no pre-pass launch at all).  Two workspaces are used alternately.  The invariant: a producer
+// never writes planes into the workspace whose partial sums it is reading -- a projection's deferred K splits lie in the workspace of its own planes, so
+// the producer that consumes them takes other().
+struct OperandPlanes {
+    void* ws[2];
+    int cur = 0;
+    const float* of = nullptr;   // the X whose planes lie in ws[cur] (Q, K, V and gate, up share one X)
+    void* current() const { return ws[cur]; }
+    bool hold(const float* X) const { return X == of; }
+    void* other() { cur ^= 1; of = nullptr; return ws[cur]; }                // a producer is about to write planes: the workspace the last projection did NOT use
+    void written(const float* X, bool split) { of = split ? X : nullptr; }   // X has new contents: planes are stale unless its producer just split it
+    void in_current(const float* X) { of = X; }                              // a projection's pre-pass (or such a producer) has left X's planes in ws[cur]
+};
+
 // layers [first, last) of the 1:1 path on hidden_[T][H] at positions start_pos.. (positions_ already on the device)
 int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
@@ -646,70 +664,68 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     };
     // Y[t] = W . X[t] for the T tokens: one pass over W per 16 tokens on the matrix cores, or the reference's loop
     const bool batched = batched_prefill_ && T > 1;
-    // (rounds 2-5: a prompt of <= 16 tokens was one pass of the F32-MFMA GEMM -- 2 217 tok/s against 1 727 through the 64-token form of the FP16 GEMM; round 6:
-    // prompts of <= 32 tokens take the FP16 GEMM's weight-streaming form, gemm_quant_f16_small_kernel)
+    // the FP16 GEMM takes every prompt of 2 tokens or more (its weight-streaming form up to 32); it also reads a matrix that exists only as its decode
+    // repack, where the F32-MFMA form (ntk_gemm_quant) would need the GGUF bytes unpacked first
     const bool bf16_now = bf16_prefill_ && gemm_ws_ && T > 1;
-    // ... but a matrix that exists ONLY as its decode repack goes through the FP16 GEMM (which reads the repack) from 2 tokens on: the F32-MFMA form would
-    // need the GGUF bytes unpacked first (a 16-token pass of the 8B Q4_K_M model: 9 ms this way, 11 ms with the unpack)
-    const bool bf16_rp = bf16_prefill_ && gemm_ws_ && T > 1;
-    const float* planes_of = nullptr;   // the x whose FP16 planes sit in the current workspace (Q, K, V and gate, up share one x)
-    // Two workspaces, used alternately: the launch that PRODUCES a projection's input also splits it into that projection's planes (ntk_*_prepare_x,
-    // round 6) -- into the workspace the previous projection did NOT use, whose partial sums it may still be reading.
-    void* cur_ws = gemm_ws_;
-    auto flip_ws = [&]() { cur_ws = cur_ws == gemm_ws_ ? gemm_ws2_ : gemm_ws_; return cur_ws; };
-    const float* planes_ready = nullptr;   // written by such a producer: becomes planes_of where the old contents are declared stale
-    // rm: the tokens' largest |X| when the kernel that produced X left them (ntk_rmsnorm_rowmax / ntk_silu_mul_rowmax): the FP16 GEMM's operand
-    // pre-pass then needs no pass of its own over X for the token scales
-    // the FP16 GEMM behind its descriptor (ntk_engine.h): matrices of one format sharing X
-    auto gemm_f16 = [&](const ntk_gemv_seg* segs, int nseg, const float* X, int in_f, const float* resid, int reuse_x, const float* rm, ntk_gemm_partials* pt,
-                        bool repacked) {
-        ntk_gemm_desc d{};
-        d.segs = segs; d.nseg = nseg; d.X = X; d.n_tokens = T; d.in_features = in_f; d.resid = resid;
-        d.workspace = cur_ws; d.workspace_bytes = gemm_ws_bytes_; d.reuse_x = reuse_x; d.row_max = rm; d.partials = pt;
-        d.weights_repacked = repacked ? 1 : 0;
-        return ntk_gemm_quant_f16(&d, s);
-    };
-    // RMSNorm / SiLU x up in front of an FP16-GEMM projection also leave the tokens' largest |x| (row_max_: [2][max_seq]; the second array is
-    // zeroed by the layer's first RMSNorm launch for the SiLU launch's atomic maxima)
+    OperandPlanes planes{{gemm_ws_, gemm_ws2_}};
+    // RMSNorm / SiLU x up in front of an FP16-GEMM projection also leave the tokens' largest |x|: the GEMM's operand pre-pass then needs no pass of its
+    // own over X for the token scales (row_max_: [2][max_seq]; the second array is zeroed by the layer's first RMSNorm launch for the SiLU launch's
+    // atomic maxima)
     const bool with_max = batched && bf16_now && row_max_ != nullptr && prefill_row_max_;
     float* rm_a = with_max ? row_max_ : nullptr;
     float* rm_b = with_max ? row_max_ + cfg_.max_seq_len : nullptr;
-    // (round 6) ... or split X themselves: the projection then needs no pre-pass launch at all
-    // (up to 64 tokens: a producer that owns a whole token per workgroup writes its planes in 16-byte pieces a kilobyte apart -- at 1024 tokens the pass
-    // measured 5 % SLOWER than with the GEMM's own pre-pass, 8B Q8_0 28 010 -> 26 460 tok/s; at 16 - 64 tokens it is 2 - 5 % faster)
-    const bool fuse_split = with_max && prefill_fused_split_ && gemm_ws2_ != nullptr && T <= 64;
     auto f16_ok = [&](const DevTensor& w) {   // the formats and shapes ntk_gemm_quant_f16 takes
         const bool kq = w.dtype == NTK_DT_Q4_0 || w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K;
         return (w.dtype == NTK_DT_Q8_0 || kq) && w.in_f % (kq ? 256 : 128) == 0 && w.out_f % 16 == 0 && (w.ptr || w.rp);
     };
-    auto prepare_x = [&](const float* X, const DevTensor& w) {   // X as it lies (the attention output): row maximum + split in one launch
-        if (!fuse_split || !f16_ok(w) || X == planes_of) return;
-        if (ntk_gemm_prepare_x(X, T, (int)w.in_f, flip_ws(), s) == NTK_OK) planes_of = X;
-        else planes_of = nullptr;
+    // The form the producer of X takes when X (`width` columns) feeds matrix next_w: it splits X into next_w's planes itself, leaves the tokens' maxima, or
+    // neither.  The split: up to 64 tokens (a producer that owns a whole token per workgroup writes its planes in 16-byte pieces a kilobyte apart:
+    // faster than the GEMM's own pre-pass at 16 - 64 tokens, slower at 1024), and not under tensor parallelism, where a rank's SiLU launch keeps its maxima
+    // in the array that only ntk_rmsnorm_rowmax zeroes.
+    enum class XForm { plain, row_max, split };
+    auto x_form = [&](int width, const DevTensor& next_w) {
+        if (with_max && prefill_fused_split_ && gemm_ws2_ != nullptr && T <= 64 && tp_world_ == 1 && f16_ok(next_w) && (int)next_w.in_f == width) return XForm::split;
+        return with_max ? XForm::row_max : XForm::plain;
     };
-    // One resident copy (round 6): a K-quant matrix whose GGUF bytes were freed after the load-time repack is read by the FP16 GEMM FROM THE REPACK
-    // (ntk_gemm_desc.weights_repacked: identical bits) -- no unpack in front of the prompt launches any more.  rp_only(w): that is the tensor's state.
+    // a K-quant matrix whose GGUF bytes were freed after the load-time repack (one resident copy): the FP16 GEMM reads it FROM THE REPACK
+    // (ntk_gemm_desc.weights_repacked: identical bits) -- no unpack in front of the prompt launches
     auto rp_only = [&](const DevTensor& w) {
         return !w.ptr && w.rp && (w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K) && w.out_f % 16 == 0;
     };
+    // The FP16 GEMM behind its descriptor (ntk_engine.h): 1..3 matrices of one format sharing X, ONE launch.  `raw`: the matrices' GGUF bytes where the
+    // caller has them already; without it a group whose every matrix is rp_only is read from the repack, any other group through raw_of() (one raw_begin()
+    // per group: its tensors lie side by side in the unpack scratch).  X's planes are reused when they lie in the current workspace, and lie there after
+    // the launch.  rm: the tokens' largest |X| where X's producer left them.
+    auto gemm_group = [&](float* const* Ys, const DevTensor* const* Ws, int n, const float* X, const float* resid, const float* rm, ntk_gemm_partials* pt,
+                          const void* const* raw) {
+        bool repacked = raw == nullptr;
+        for (int k = 0; k < n; ++k) repacked = repacked && rp_only(*Ws[k]);
+        if (!repacked && !raw) raw_begin();
+        ntk_gemv_seg segs[3];
+        for (int k = 0; k < n; ++k) segs[k] = {repacked ? Ws[k]->rp : raw ? raw[k] : raw_of(*Ws[k]), Ys[k], (int)Ws[k]->out_f, Ws[k]->dtype};
+        ntk_gemm_desc d{};
+        d.segs = segs; d.nseg = n; d.X = X; d.n_tokens = T; d.in_features = (int)Ws[0]->in_f; d.resid = resid;
+        d.workspace = planes.current(); d.workspace_bytes = gemm_ws_bytes_; d.reuse_x = planes.hold(X) ? 1 : 0; d.row_max = rm; d.partials = pt;
+        d.weights_repacked = repacked ? 1 : 0;
+        const int st = ntk_gemm_quant_f16(&d, s);
+        if (st == NTK_OK) planes.in_current(X);
+        return st;
+    };
+    auto gemm_one = [&](float* Y, const DevTensor& w, const float* X, const float* resid, const float* rm, ntk_gemm_partials* pt, const void* const* raw) {
+        const DevTensor* const wp = &w;
+        return gemm_group(&Y, &wp, 1, X, resid, rm, pt, raw);
+    };
     auto project = [&](float* Y, const DevTensor& w, const float* X, size_t ystride, size_t xstride, const float* rm) {
-        if (batched && bf16_rp && rp_only(w) && ystride == (size_t)w.out_f && xstride == (size_t)w.in_f) {   // straight from the repack
-            const ntk_gemv_seg sg{w.rp, Y, (int)w.out_f, w.dtype};
-            const int st = gemm_f16(&sg, 1, X, (int)w.in_f, nullptr, X == planes_of ? 1 : 0, rm, nullptr, true);
-            if (st == NTK_OK) { planes_of = X; return; }
-            if (st != NTK_E_DTYPE && st != NTK_E_SHAPE && st != NTK_E_ALIGN) { ok(st); return; }
+        const bool dense = ystride == (size_t)w.out_f && xstride == (size_t)w.in_f;
+        if (batched && bf16_now && rp_only(w) && dense) {   // straight from the repack
+            const int st = gemm_one(Y, w, X, nullptr, rm, nullptr, nullptr);
+            if (!not_taken(st)) { ok(st); return; }
         }
         raw_begin();
         const void* wp = raw_of(w);
-        if (batched && is_quant(w.dtype) && ystride == (size_t)w.out_f && xstride == (size_t)w.in_f) {
-            int st = NTK_E_DTYPE;
-            if (bf16_now) {   // FP16 matrix cores, up to 1024 tokens per pass (Q8_0 / Q4_K / Q5_K / Q6_K)
-                const ntk_gemv_seg sg{wp, Y, (int)w.out_f, w.dtype};
-                st = gemm_f16(&sg, 1, X, (int)w.in_f, nullptr, X == planes_of ? 1 : 0, rm, nullptr, false);
-            }
-            if (st == NTK_OK) planes_of = X;
-            if (st == NTK_E_DTYPE || st == NTK_E_SHAPE || st == NTK_E_ALIGN)
-                st = ntk_gemm_quant(Y, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, nullptr, s);
+        if (batched && is_quant(w.dtype) && dense) {
+            int st = bf16_now ? gemm_one(Y, w, X, nullptr, rm, nullptr, &wp) : NTK_E_DTYPE;   // FP16 matrix cores, up to 1024 tokens per pass
+            if (not_taken(st)) st = ntk_gemm_quant(Y, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, nullptr, s);
             if (st != NTK_E_ALIGN && st != NTK_E_SHAPE) { ok(st); return; }   // those two: shapes only the per-token loop takes
         }
         for (int t = 0; t < T; ++t) gemv(Y + (size_t)t * ystride, w, wp, X + (size_t)t * xstride);
@@ -717,101 +733,113 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     // matrices that share X (Q | K | V, gate | up): those of one format go out as ONE launch of the FP16 GEMM, the rest one by one
     auto project_many = [&](float* const* Ys, const DevTensor* const* Ws, int n, const float* X, const float* rm) {
         bool done[3] = {false, false, false};
-        if (batched && bf16_now) {
-            for (int a = 0; a < n; ++a) {
-                if (done[a]) continue;
-                ntk_gemv_seg segs[3];
-                int idx[3], m = 0;
-                for (int b = a; b < n; ++b)
-                    if (!done[b] && Ws[b]->dtype == Ws[a]->dtype && Ws[b]->in_f == Ws[a]->in_f) idx[m++] = b;
-                if (m < 2) continue;
-                bool all_rp = true;
-                for (int k = 0; k < m; ++k) all_rp = all_rp && rp_only(*Ws[idx[k]]);
-                if (!all_rp) raw_begin();   // (the group's tensors side by side in the unpack scratch when their GGUF bytes are not resident)
-                for (int k = 0; k < m; ++k) segs[k] = {all_rp ? Ws[idx[k]]->rp : raw_of(*Ws[idx[k]]), Ys[idx[k]], (int)Ws[idx[k]]->out_f, Ws[idx[k]]->dtype};
-                const int st = gemm_f16(segs, m, X, (int)Ws[a]->in_f, nullptr, X == planes_of ? 1 : 0, rm, nullptr, all_rp);
-                if (st == NTK_OK) { planes_of = X; for (int k = 0; k < m; ++k) done[idx[k]] = true; }
-                else if (st != NTK_E_DTYPE && st != NTK_E_SHAPE && st != NTK_E_ALIGN) { ok(st); return; }
-            }
+        for (int a = 0; a < n && batched && bf16_now; ++a) {
+            if (done[a]) continue;
+            float* ys[3];
+            const DevTensor* ws[3];
+            int idx[3], m = 0;
+            for (int b = a; b < n; ++b)
+                if (!done[b] && Ws[b]->dtype == Ws[a]->dtype && Ws[b]->in_f == Ws[a]->in_f) { ys[m] = Ys[b]; ws[m] = Ws[b]; idx[m++] = b; }
+            if (m < 2) continue;
+            const int st = gemm_group(ys, ws, m, X, nullptr, rm, nullptr, nullptr);
+            if (st == NTK_OK) for (int k = 0; k < m; ++k) done[idx[k]] = true;
+            else if (!not_taken(st)) { ok(st); return; }
         }
         for (int a = 0; a < n; ++a)
             if (!done[a]) project(Ys[a], *Ws[a], X, (size_t)Ws[a]->out_f, (size_t)Ws[a]->in_f, rm);
+    };
+    // X as it lies (the attention output) in front of matrix w: row maximum + split in one launch of its own
+    auto prepare_x = [&](const float* X, const DevTensor& w) {
+        if (x_form((int)w.in_f, w) != XForm::split || planes.hold(X)) return;
+        planes.written(X, ntk_gemm_prepare_x(X, T, (int)w.in_f, planes.other(), s) == NTK_OK);
     };
     // hidden += W . X (attention.cpp:207 + transformer.cpp:645, ffn.cpp:130 + transformer.cpp:652): the batched
     // projection adds the residual in its epilogue, the reference sequence goes through residual_ and launch_add_inplace
     auto project_add = [&](const DevTensor& w, const float* X, size_t xstride, const float* rm) {
         if (tp_world_ > 1) {   // this rank's columns give a PARTIAL sum: into the exchange slot, then hidden += sum over ranks
             project(tp_slot(), w, X, H, xstride, rm);
-            planes_of = nullptr;
             ok(tp_allreduce(hidden_, T * H));
             return;
         }
-        if (batched && bf16_now && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f) prepare_x(X, w);
-        if (batched && bf16_rp && rp_only(w) && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f) {   // straight from the repack
-            const ntk_gemv_seg sg{w.rp, hidden_, (int)w.out_f, w.dtype};
-            const int st = gemm_f16(&sg, 1, X, (int)w.in_f, hidden_, X == planes_of ? 1 : 0, rm, nullptr, true);
-            if (st != NTK_E_DTYPE && st != NTK_E_SHAPE && st != NTK_E_ALIGN) { planes_of = nullptr; ok(st); return; }
+        const bool dense = batched && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f;
+        if (dense && bf16_now) prepare_x(X, w);
+        if (dense && bf16_now && rp_only(w)) {   // straight from the repack
+            const int st = gemm_one(hidden_, w, X, hidden_, rm, nullptr, nullptr);
+            if (!not_taken(st)) { ok(st); return; }
         }
-        if (batched && is_quant(w.dtype) && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f) {
-            int st = NTK_E_DTYPE;
+        if (dense && is_quant(w.dtype)) {
             raw_begin();
             const void* wp = raw_of(w);
-            if (bf16_now) {
-                const ntk_gemv_seg sg{wp, hidden_, (int)w.out_f, w.dtype};
-                st = gemm_f16(&sg, 1, X, (int)w.in_f, hidden_, X == planes_of ? 1 : 0, rm, nullptr, false);
-            }
-            planes_of = nullptr;   // (this projection rewrites hidden_, and the next group has a new x)
-            if (st == NTK_E_DTYPE || st == NTK_E_SHAPE || st == NTK_E_ALIGN)
-                st = ntk_gemm_quant(hidden_, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, hidden_, s);
+            int st = bf16_now ? gemm_one(hidden_, w, X, hidden_, rm, nullptr, &wp) : NTK_E_DTYPE;
+            if (not_taken(st)) st = ntk_gemm_quant(hidden_, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, hidden_, s);
             if (st != NTK_E_ALIGN && st != NTK_E_SHAPE) { ok(st); return; }
         }
         project(residual_, w, X, H, xstride, rm);
         ok(ntk_add_inplace(hidden_, residual_, T * H, s));
     };
+    // residual_ = RMSNorm(hidden_) in the form its consumer next_w asks for
     auto norm = [&](const DevTensor& nw, bool zero_b, const DevTensor& next_w) {
-        if (fuse_split && f16_ok(next_w) && (int)next_w.in_f == H) {
-            ok(ntk_rmsnorm_prepare_x(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, flip_ws(), s));
-            planes_ready = residual_;
-        } else if (with_max) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, rm_a, zero_b ? rm_b : nullptr, s));
+        const XForm f = x_form(H, next_w);
+        if (f == XForm::split) ok(ntk_rmsnorm_prepare_x(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, planes.other(), s));
+        else if (f == XForm::row_max) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, rm_a, zero_b ? rm_b : nullptr, s));
         else ok(ntk_rmsnorm(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, s));
+        planes.written(residual_, f == XForm::split);
     };
-    // hidden += W . X followed by the NEXT RMSNorm (nw; into residual_, with the token maxima) as one consumer launch of the projection's K splits
-    // (ntk_gemm_quant_f16 with `partials` + ntk_reduce_rmsnorm_rowmax); false = not this shape / format: the caller runs project_add + norm
+    // hidden += W . X followed by the NEXT RMSNorm (nw; into residual_) as one consumer launch of the projection's K splits (ntk_gemm_quant_f16 with
+    // `partials` + ntk_reduce_rmsnorm_*); false = not this shape / format: the caller runs project_add + norm
     auto project_add_norm = [&](const DevTensor& w, const float* X, const float* rm, const DevTensor& nw, bool zero_b, const DevTensor& next_w) -> bool {
         if (!with_max || tp_world_ > 1 || !is_quant(w.dtype) || (size_t)w.out_f != (size_t)H) return false;
         ntk_gemm_partials pt;
-        int st = NTK_E_DTYPE;
         prepare_x(X, w);
-        if (rp_only(w)) {   // straight from the repack
-            const ntk_gemv_seg sg{w.rp, hidden_, (int)w.out_f, w.dtype};
-            st = gemm_f16(&sg, 1, X, (int)w.in_f, hidden_, X == planes_of ? 1 : 0, rm, &pt, true);
-        }
-        if (st == NTK_E_DTYPE || st == NTK_E_SHAPE || st == NTK_E_ALIGN) {
+        // (a launch that does not split K adds the residual in its own epilogue, in place, as project_add does: nothing is deferred then)
+        int st = rp_only(w) ? gemm_one(hidden_, w, X, hidden_, rm, &pt, nullptr) : NTK_E_DTYPE;   // straight from the repack
+        if (not_taken(st)) {
             raw_begin();
             const void* wp = raw_of(w);
-            // (a launch that does not split K adds the residual in its own epilogue, in place, as project_add does: nothing is deferred then)
-            const ntk_gemv_seg sg{wp, hidden_, (int)w.out_f, w.dtype};
-            st = gemm_f16(&sg, 1, X, (int)w.in_f, hidden_, X == planes_of ? 1 : 0, rm, &pt, false);
+            st = gemm_one(hidden_, w, X, hidden_, rm, &pt, &wp);
         }
-        if (st == NTK_E_DTYPE || st == NTK_E_SHAPE || st == NTK_E_ALIGN) return false;   // (nothing was launched)
-        planes_of = nullptr;
-        if (st == NTK_OK && fuse_split && f16_ok(next_w) && (int)next_w.in_f == H) {   // (the partial sums lie in cur_ws: the planes go to the other one)
-            st = ntk_reduce_rmsnorm_prepare_x(hidden_, &pt, (const float*)nw.ptr, cfg_.norm_eps, residual_, flip_ws(), s);
-            planes_ready = residual_;
-        } else
-        if (st == NTK_OK) st = ntk_reduce_rmsnorm_rowmax(hidden_, &pt, (const float*)nw.ptr, cfg_.norm_eps, residual_, rm_a, zero_b ? rm_b : nullptr, s);
+        if (not_taken(st)) return false;
+        const bool split = st == NTK_OK && x_form(H, next_w) == XForm::split;   // (the partial sums lie in the current workspace: the planes go to the other one)
+        if (split) st = ntk_reduce_rmsnorm_prepare_x(hidden_, &pt, (const float*)nw.ptr, cfg_.norm_eps, residual_, planes.other(), s);
+        else if (st == NTK_OK) st = ntk_reduce_rmsnorm_rowmax(hidden_, &pt, (const float*)nw.ptr, cfg_.norm_eps, residual_, rm_a, zero_b ? rm_b : nullptr, s);
+        planes.written(residual_, split);
         ok(st);
         return true;
     };
-    bool normed_ahead = false;   // residual_ / rm_a already hold this layer's normalised input (written with the previous layer's down projection)
+    // gate | up and SiLU x up (per token in the reference, ffn.cpp:127: the same elementwise op) with the gate | up launch's K splits summed by the SiLU
+    // launch itself (ntk_gemm_quant_f16 with `partials` + ntk_reduce_silu_mul_*); false = not this shape / format: the caller takes the separate launches
+    auto gate_up_silu = [&](const LayerWeights& L) -> bool {
+        if (!with_max || !rm_b || tp_world_ > 1 || L.w_gate.dtype != L.w_up.dtype || !is_quant(L.w_gate.dtype) || L.w_gate.in_f != L.w_up.in_f ||
+            (size_t)L.w_gate.out_f != (size_t)I || (size_t)L.w_up.out_f != (size_t)I || I % 4 != 0) return false;
+        float* const ys[2] = {gate_buf, up_buf};
+        const DevTensor* const ws[2] = {&L.w_gate, &L.w_up};
+        ntk_gemm_partials pt;
+        int st = gemm_group(ys, ws, 2, residual_, nullptr, rm_a, &pt, nullptr);
+        if (not_taken(st)) return false;
+        const bool split = st == NTK_OK && x_form(I, L.w_down) == XForm::split;
+        if (split) st = ntk_reduce_silu_mul_prepare_x(gate_buf, &pt, planes.other(), s);
+        else if (st == NTK_OK) st = ntk_reduce_silu_mul_rowmax(gate_buf, &pt, rm_b, s);
+        planes.written(gate_buf, split);
+        ok(st);
+        return true;
+    };
+    // gate_buf = SiLU(gate_buf) x up_buf in the form the down projection asks for
+    auto silu_mul = [&](const DevTensor& next_w) {
+        const XForm f = x_form(I, next_w);
+        int st = NTK_E_SHAPE;
+        if (f == XForm::split) st = ntk_silu_mul_prepare_x(gate_buf, gate_buf, up_buf, T, I, planes.other(), s);
+        else if (f == XForm::row_max && rm_b) st = ntk_silu_mul_rowmax(gate_buf, gate_buf, up_buf, T, I, rm_b, s);
+        planes.written(gate_buf, f == XForm::split && st == NTK_OK);
+        if (st == NTK_E_SHAPE || st == NTK_E_ALIGN) { st = ntk_silu_mul(gate_buf, gate_buf, up_buf, T * I, s); rm_b = nullptr; }   // (then for the rest of the pass)
+        ok(st);
+    };
+    bool normed_ahead = false;   // residual_ (with its maxima or planes) already holds this layer's normalised input, written with the previous layer's down projection
     for (int i = first; i < last_layer; ++i) {
         const LayerWeights& L = layers_[i];
         uint16_t* kc = k_cache_ + (size_t)i * kv_layer;
         uint16_t* vc = v_cache_ + (size_t)i * kv_layer;
         if (!normed_ahead) norm(L.attn_norm, true, L.wq);
         normed_ahead = false;
-        planes_of = planes_ready;   // residual_ has new contents (split already by the launch that wrote them, or not)
-        planes_ready = nullptr;
         {
             float* const ys[3] = {q_buf, k_buf, v_buf};
             const DevTensor* const ws[3] = {&L.wq, &L.wk, &L.wv};
@@ -830,43 +858,12 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
             project_add(L.wo, attn_out, qd, nullptr);
             norm(L.ffn_norm, false, L.w_gate);
         }
-        planes_of = planes_ready;
-        planes_ready = nullptr;
-        // gate | up and SiLU x up (per token in the reference, ffn.cpp:127: the same elementwise op): with the token maxima, the gate | up launch's K
-        // splits are summed by the SiLU launch itself (ntk_gemm_quant_f16 with `partials` + ntk_reduce_silu_mul_rowmax)
-        bool ffn_done = false;
-        if (with_max && rm_b && tp_world_ == 1 && L.w_gate.dtype == L.w_up.dtype && is_quant(L.w_gate.dtype) && L.w_gate.in_f == L.w_up.in_f &&
-            (size_t)L.w_gate.out_f == (size_t)I && (size_t)L.w_up.out_f == (size_t)I && I % 4 == 0) {
-            const bool both_rp = rp_only(L.w_gate) && rp_only(L.w_up);
-            if (!both_rp) raw_begin();
-            ntk_gemv_seg segs[2] = {{both_rp ? L.w_gate.rp : raw_of(L.w_gate), gate_buf, (int)I, L.w_gate.dtype},
-                                    {both_rp ? L.w_up.rp : raw_of(L.w_up), up_buf, (int)I, L.w_up.dtype}};
-            ntk_gemm_partials pt;
-            int st = gemm_f16(segs, 2, residual_, (int)L.w_gate.in_f, nullptr, residual_ == planes_of ? 1 : 0, rm_a, &pt, both_rp);
-            if (st != NTK_E_DTYPE && st != NTK_E_SHAPE && st != NTK_E_ALIGN) {   // (those three: nothing was launched)
-                if (st == NTK_OK && fuse_split && f16_ok(L.w_down) && (size_t)L.w_down.in_f == (size_t)I) {
-                    st = ntk_reduce_silu_mul_prepare_x(gate_buf, &pt, flip_ws(), s);
-                    planes_ready = gate_buf;
-                } else
-                if (st == NTK_OK) st = ntk_reduce_silu_mul_rowmax(gate_buf, &pt, rm_b, s);
-                ok(st);
-                ffn_done = true;
-            }
-        }
-        if (!ffn_done) {
+        if (!gate_up_silu(L)) {
             float* const ys[2] = {gate_buf, up_buf};
             const DevTensor* const ws[2] = {&L.w_gate, &L.w_up};
             project_many(ys, ws, 2, residual_, rm_a);
-            int st_silu = with_max && rm_b ? ntk_silu_mul_rowmax(gate_buf, gate_buf, up_buf, T, I, rm_b, s) : NTK_E_SHAPE;
-            if (fuse_split && f16_ok(L.w_down) && (size_t)L.w_down.in_f == (size_t)I && tp_world_ == 1) {
-                st_silu = ntk_silu_mul_prepare_x(gate_buf, gate_buf, up_buf, T, I, flip_ws(), s);
-                if (st_silu == NTK_OK) planes_ready = gate_buf;
-            }
-            if (st_silu == NTK_E_SHAPE || st_silu == NTK_E_ALIGN) { st_silu = ntk_silu_mul(gate_buf, gate_buf, up_buf, T * I, s); rm_b = nullptr; }   // (then for the rest of the pass)
-            ok(st_silu);
+            silu_mul(L.w_down);
         }
-        planes_of = planes_ready;
-        planes_ready = nullptr;
         // down projection + residual, and the NEXT layer's first RMSNorm in the same consumer launch when there is a next layer in this pass
         if (i + 1 < last_layer && project_add_norm(L.w_down, gate_buf, rm_b, layers_[i + 1].attn_norm, true, layers_[i + 1].wq)) normed_ahead = true;
         else project_add(L.w_down, gate_buf, I, rm_b);
@@ -977,7 +974,7 @@ int Model::enqueue_token(bool greedy) {
             if (repack_ && w.rp && (rp_mask() & 16)) {
                 ntk_gemv_seg rs = {w.rp, logits_, (int)w.out_f, w.dtype};
                 st = ntk_gemv_rp_fused(&rs, 1, hidden_, (int)w.in_f, (const float*)output_norm_.ptr, cfg_.norm_eps, nullptr, 0, s);
-                if (st != NTK_OK && st != NTK_E_DTYPE && st != NTK_E_SHAPE && st != NTK_E_ALIGN) return st;
+                if (st != NTK_OK && !not_taken(st)) return st;
             }
             if (st != NTK_OK) {
                 raw_begin();
@@ -1061,7 +1058,7 @@ int Model::enqueue_layers(int first, int last_layer) {
                 const int st = ntk_gemv_rp_fused(segs, n, x, (int)ws[0]->in_f, nw, cfg_.norm_eps, resid, 0, s);
                 mark(0, false);
                 if (st == NTK_OK) return NTK_OK;
-                if (st != NTK_E_DTYPE && st != NTK_E_ALIGN && st != NTK_E_SHAPE) return st;   // (those: the raw-GGUF launches below take over)
+                if (!not_taken(st)) return st;   // (those: the raw-GGUF launches below take over)
             }
         }
         if (n > 1 && !resid) {   // matrices in two K-quant formats (Q4_K_M's attn_v): still one launch when the library has the pair
@@ -1077,7 +1074,7 @@ int Model::enqueue_layers(int first, int last_layer) {
                 if (st == NTK_OK) return NTK_OK;
                 // formats / alignment / workgroup split / LDS size the optional one-launch form does not take: the per-format
                 // launches below do (the pair kernel is an optimisation, never the only way)
-                if (st != NTK_E_DTYPE && st != NTK_E_ALIGN && st != NTK_E_SHAPE) return st;
+                if (!not_taken(st)) return st;
             }
         }
         for (int a = 0; a < n; ++a) {
@@ -1136,7 +1133,7 @@ int Model::enqueue_layers(int first, int last_layer) {
                                                     attn_sync_, s);
             mark(0, false);
             if (st == NTK_OK) goto ffn;
-            if (st != NTK_E_ALIGN && st != NTK_E_SHAPE && st != NTK_E_DTYPE) return st;   // those: shapes only the two launches take
+            if (!not_taken(st)) return st;   // those: shapes only the two launches take
         }
 #endif
         mark(1, true);
@@ -1163,7 +1160,7 @@ int Model::enqueue_layers(int first, int last_layer) {
             if (repack_ && L.w_gate.rp && L.w_up.rp && (rp_mask() & 4)) {
                 ntk_gemv_seg rs[2] = {{L.w_gate.rp, gate_buf, I, L.w_gate.dtype}, {L.w_up.rp, up_buf, I, L.w_up.dtype}};
                 st = ntk_gemv_rp_fused(rs, 2, hidden_, H, (const float*)L.ffn_norm.ptr, cfg_.norm_eps, nullptr, 1, s);
-                if (st != NTK_OK && st != NTK_E_DTYPE && st != NTK_E_SHAPE && st != NTK_E_ALIGN) return st;
+                if (st != NTK_OK && !not_taken(st)) return st;
             }
             if (st != NTK_OK) {
                 raw_begin();

@@ -436,9 +436,13 @@ def synth_vocab(shape: LlamaShape, rng: np.random.Generator) -> Tuple[List[bytes
 
 
 def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: int = 20260925,
-                         with_scores: bool = False) -> Dict[str, int]:
-    """Write a seeded synthetic Llama-architecture GGUF; returns {tensor name: ggml type}."""
+                         with_scores: bool = False, overrides: Optional[Dict[str, str]] = None) -> Dict[str, int]:
+    """Write a seeded synthetic Llama-architecture GGUF; returns {tensor name: ggml type}.
+    overrides: per-matrix types on top of the mix, in every layer ({"ffn_up": "Q4_K"})."""
     types = tensor_types(shape, mix)
+    for m, t in (overrides or {}).items():
+        for i in range(shape.layers):
+            types["blk.%d.%s.weight" % (i, m)] = NAME_TO_GGML[t]
     hd = shape.hidden // shape.heads
     q_dim, kv_dim = shape.heads * hd, shape.kv_heads * hd
     dims = {"attn_q": (shape.hidden, q_dim), "attn_k": (shape.hidden, kv_dim), "attn_v": (shape.hidden, kv_dim),

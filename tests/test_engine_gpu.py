@@ -177,7 +177,7 @@ def test_prompt_pass_with_folded_launches_gives_the_same_bits(name, shape, mix, 
     path, z = golden_model(name, getattr(G, shape), mix, tmp_path)
     ctx = int(z["ctx"])
     r = np.random.Generator(np.random.Philox(key=[20260929, len(name)]))
-    for n in (40, 200, 700):
+    for n in (40, 200, 700, 16):   # (16: the weight-streaming form with its K slices, under the producers' split)
         if n + 8 > ctx: continue
         prompt = [int(z["prompt"][0])] + [int(t) for t in r.integers(0, 256, n - 1)]
         cont = [int(t) for t in r.integers(0, 256, 6)]
@@ -195,6 +195,36 @@ def test_prompt_pass_with_folded_launches_gives_the_same_bits(name, shape, mix, 
             outs.append(np.stack(lg))
         assert np.isfinite(outs[0]).all()
         assert np.array_equal(outs[0], outs[1]), (name, n, float(np.abs(outs[0] - outs[1]).max()))
+
+
+def test_gate_and_up_of_two_formats_take_one_silu_form(tmp_path):
+    """gate and up in different quantised formats go out as separate launches followed by a SiLU x up launch of its own, which
+    must take exactly ONE form: split its output into the down projection's operand planes ("prefill_fused_split" = 1, up to 64
+    tokens) or leave the token maxima (0).  The producers promise identical output: prompts of 8, 40 and 64 tokens and four
+    teacher-forced decode steps, logits equal BIT FOR BIT between the two settings.  (TINY, Q8_0 with ffn_up in Q4_K: ffn_down
+    stays in the FP16 GEMM's format set, which the MIXED file's F32 ffn_down is not.)"""
+    path = str(tmp_path / "tiny_q8_0_up_q4_k.gguf")
+    types = G.make_synthetic_llama(path, G.TINY, "Q8_0", seed=20260925, overrides={"ffn_up": "Q4_K"})
+    assert types["blk.0.ffn_gate.weight"] == G.GGML_Q8_0 and types["blk.0.ffn_up.weight"] == G.GGML_Q4_K
+    assert types["blk.0.ffn_down.weight"] == G.GGML_Q8_0
+    r = np.random.Generator(np.random.Philox(key=[20261016, 1]))
+    for n in (8, 40, 64):
+        prompt = [G.TINY.bos] + [int(t) for t in r.integers(0, 256, n - 1)]
+        cont = [int(t) for t in r.integers(0, 256, 4)]
+        outs = []
+        for split in (0, 1):
+            eng = E.Engine()
+            eng.load(path, G.TINY.ctx)
+            eng.set_option("prefill_fused_split", split)
+            lg = [eng.forward(prompt, 0)]
+            pos = len(prompt)
+            for t in cont:
+                lg.append(eng.decode_fused(t, pos, False))
+                pos += 1
+            eng.close()
+            outs.append(np.stack(lg))
+        assert np.isfinite(outs[0]).all()
+        assert np.array_equal(outs[0], outs[1]), (n, float(np.abs(outs[0] - outs[1]).max()))
 
 
 def test_long_context_decode_uses_split_attention_and_matches_the_oracle(tmp_path):

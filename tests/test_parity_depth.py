@@ -461,7 +461,7 @@ def test_depth_8b_q4_k_m_massive_activations():
     1.1e-4 under the same statistic over five equally valid evaluations (embeddings perturbed by one ulp), 25 x its value on the seeded model: queries and
     keys of magnitude ~140 make attention logits of ~2e4, where one F32 ulp is 2e-3 and every near-tie of two keys turns it into an O(1e-3) error of the
     softmax weights, which the next layers carry.  The statistic measures that amplifier, not an implementation -- so the end-to-end cache bar is taken
-    from the oracle's own draws (e2e_kv_from_oracle: 2 x the largest of three), like `free_bar`; the x 10 of round 5 is gone."""
+    from the oracle's own draws (e2e_kv_from_oracle: KV_E2E_FACTOR = 3 x the largest of five), like `free_bar`; the x 10 of round 5 is gone."""
     factors = {5: 1000.0, 1033: 1000.0, 2500: 1000.0, 4000: 1000.0, 3333: 4000.0}
 
     def patch(path):
