@@ -98,6 +98,37 @@ int ntk_attention_decode_split_merged(float* output, const float* q, const float
                                       int head_dim, int max_seq, float scale, float theta_base, float freq_scale, int nsplit,
                                       float* scratch, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The 8-bit (Q8_0) KV cache (csrc/attention_q8.hip; no reference counterpart).  A cache row holds Q8_0 values along head_dim: every 32
+ * consecutive elements of a head's row share one IEEE-half scale d and carry 32 int8 q -- ggml's quantize_row_q8_0_ref arithmetic in F32
+ * on the F32 post-RoPE k and the F32 v (amax, d = amax / 127, id = d ? 1 / d : 0, q = roundf(x * id), d stored RNE; where that arithmetic
+ * is undefined -- a subnormal amax makes id infinite -- x * id = NaN counts as 0 and the product is clamped to +-127).
+ * Device layout: ONE buffer per layer and side (K or V) of ntk_kv_q8_cache_bytes bytes, 16-byte aligned: int8 quants [max_seq][n_kv_heads *
+ * head_dim], then (at byte max_seq * n_kv_heads * head_dim) half scales [max_seq][n_kv_heads * head_dim / 32] -- 1.0625 bytes per element.
+ * head_dim % 32 == 0.  The decode kernel uses half(d) * q EXACTLY (int8 -> F16 is exact; scales are applied to F32 block sums / folded into
+ * the F32 softmax weights as an exact mantissa part, the exact power of two going onto the quants): nothing rounds d * q to half.
+ *   ntk_kv_store_q8          F32 rows k, v [seq_len][n_kv_heads * head_dim] (k already rotated) -> cache rows [start_pos, start_pos + seq_len)
+ *   ntk_rope_kv_store_q8     ntk_rope_kv_store with the 8-bit store: q and the cache bit-identical to ntk_rope + ntk_kv_store_q8 (seq_len >= 4)
+ *   ntk_attention_decode_q8  ntk_attention_decode_split over the 8-bit caches: RoPE of q and the new k, quantise + store the new row, GQA
+ *                            attention over rows 0 .. *d_pos (the new row included) on the F16 matrix cores, one workgroup per (KV head,
+ *                            split), partial states in `scratch` (ntk_attention_split_scratch_bytes) + the combine launch.  Any position
+ *                            from 0, any nsplit in 1 .. 1024; rows past *d_pos may hold any bytes.  head_dim 128 and <= 16 query heads per
+ *                            KV head (NTK_E_SHAPE otherwise).
+ *   ntk_kv_dequant_q8_f16    cache rows [0, n_rows) -> F16 K and V images [n_rows][n_kv_heads * head_dim] (the layout ntk_attention_prefill /
+ *                            ntk_attention_decode read): half_rne(half(d) * q)
+ * ------------------------------------------------------------------------------------------- */
+size_t ntk_kv_q8_cache_bytes(int max_seq, int n_kv_heads, int head_dim);
+int ntk_kv_store_q8(void* k_cache, void* v_cache, const float* k, const float* v, int seq_len, int n_kv_heads, int head_dim, int start_pos,
+                    int max_seq, void* stream);
+int ntk_rope_kv_store_q8(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
+                         float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
+                         void* stream);
+int ntk_attention_decode_q8(float* output, const float* q, const float* k, const float* v, void* k_cache, void* v_cache, const int* d_pos,
+                            const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq, float scale, float theta_base,
+                            float freq_scale, int nsplit, float* scratch, void* stream);
+int ntk_kv_dequant_q8_f16(void* k_f16, void* v_f16, const void* k_cache, const void* v_cache, int n_rows, int n_kv_heads, int head_dim,
+                          int max_seq, void* stream);
+
 /* Parity instrumentation: ntk_gemv_fused with the activation form of its Q4_K / Q6_K launches chosen by the CALL.  Those launches take,
  * from 48 MiB of weights on (a constant of the library: below it the conversion costs what the decode saves), the integer-activation
  * decoders of csrc/gemv_core.hip.h (three int8 digit planes per 32-column sub-block on v_dot4).  integer_activations = 1: whenever the

@@ -74,7 +74,13 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * bytes kept resident (K-quant weights twice in HBM) | "2" one resident copy: the GGUF bytes of a repacked matrix are freed and unpacked into a scratch
  * for the launches that read raw blocks (prompt GEMM, 1:1 sequence; a fixed cost per prompt pass) | "3" (default) "2" when both copies would leave less than
  * a fifth of the device's memory free, else "1"; "attention_merge" = "1" split-KV decode attention as one launch | "0" (default) with the separate merge
- * launch (identical results; the one-launch form measured slower) */
+ * launch (identical results; the one-launch form measured slower);
+ * "kv_cache" = "f16" (default) | "q8_0": the KV cache as GGUF Q8_0 values along head_dim (one half scale + 32 int8 per 32 elements of a head's row,
+ * quantised from the F32 post-RoPE k and the F32 v: 1.0625 bytes per element instead of 2, plus ONE layer's F16 image of max_context rows shared by all
+ * layers).  Set it BEFORE the load (afterwards: NTK_E_SHAPE + last_error); an nt_engine_load_shared sequence takes its own option.  Decode steps read
+ * the 8-bit rows on the matrix cores using half(d) * q exactly; prompt passes (and "fused" = "0") dequantise rows [0, start_pos + n) into the F16 image
+ * -- rounded to half, the chunk's own rows included -- and run the F16 attention kernels over it.  Refused at load (NTK_E_SHAPE + last_error): head_dim
+ * other than 128, more than 16 query heads per KV head, tensor parallelism, "fuse_attention". */
 int  nt_engine_set_option(nt_engine_t e, const char* key, const char* value);
 const char* nt_engine_last_error(nt_engine_t e);
 void nt_gen_params_default(nt_gen_params* p);
@@ -96,6 +102,7 @@ int  nt_engine_profile_token(nt_engine_t e, int token, int pos, int coarse, floa
 int  nt_engine_tokenize(nt_engine_t e, const char* text, int add_bos, int* out, int out_cap);   /* returns count */
 int  nt_engine_detokenize(nt_engine_t e, const int* ids, int n, char* out, int out_cap);       /* returns bytes */
 uint64_t nt_engine_bytes_per_token(nt_engine_t e, int pos);   /* algorithmic HBM bytes of one decode token */
+uint64_t nt_engine_kv_cache_bytes(nt_engine_t e);          /* resident KV cache of this sequence ("kv_cache" = "q8_0": the 8-bit caches + the one-layer F16 image) */
 uint64_t nt_engine_weight_bytes(nt_engine_t e);            /* the model's tensors in their GGUF encoding */
 uint64_t nt_engine_resident_weight_bytes(nt_engine_t e);   /* what they occupy in HBM now: GGUF bytes still resident + the decode repack + the unpack scratch */
 uint64_t nt_engine_repacked_bytes(nt_engine_t e);          /* of which the decode repack (tensors that did not fit stay on the raw path and are not counted) */
@@ -131,6 +138,14 @@ int  nt_engine_debug_run_layers(nt_engine_t e, const float* hidden_in, int n_tok
                                 int mode, float* hidden_out);
 int  nt_engine_debug_kv_read(nt_engine_t e, int layer, int pos0, int n, uint16_t* k_out, uint16_t* v_out);
 int  nt_engine_debug_kv_write(nt_engine_t e, int layer, int pos0, int n, const uint16_t* k, const uint16_t* v);
+/* ... of a "kv_cache" = "q8_0" engine: the rows as canonical 34-byte GGUF block_q8_0 {half d; int8 q[32]}, [n][n_kv_heads * head_dim / 32] blocks per
+ * side.  Each pair returns NTK_E_DTYPE on an engine of the other cache format. */
+int  nt_engine_debug_kv_read_q8(nt_engine_t e, int layer, int pos0, int n, void* k_blocks_out, void* v_blocks_out);
+int  nt_engine_debug_kv_write_q8(nt_engine_t e, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks);
+/* The F32 inputs of the KV store: after nt_engine_debug_kv_inputs_capture(layer) every prompt pass / 1:1 pass leaves that layer's k projection (BEFORE
+ * the rotation) and v projection aside; _read returns those of the last pass, [n][n_kv_heads * head_dim] floats each (n <= its token count).  layer < 0: off. */
+int  nt_engine_debug_kv_inputs_capture(nt_engine_t e, int layer);
+int  nt_engine_debug_kv_inputs_read(nt_engine_t e, int n, float* k_out, float* v_out);
 /* write a synthetic GGUF v3 file with the same generator (0 = ok) */
 int  nt_synth_write_gguf(const char* path, const nt_synth_spec* spec, int nthreads);
 /* fill one tensor of the synthetic plan into host memory (for CPU baselines); returns bytes or negative */

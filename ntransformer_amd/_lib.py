@@ -113,6 +113,11 @@ def lib() -> C.CDLL:
         "ntk_attention_split_scratch_init": (i, [vp, i, vp]),
         "ntk_attention_decode_split_merged": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_attention_decode_fused": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, vp]),
+        "ntk_kv_q8_cache_bytes": (C.c_size_t, [i, i, i]),
+        "ntk_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "ntk_rope_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp]),
+        "ntk_attention_decode_q8": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
+        "ntk_kv_dequant_q8_f16": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "ntk_embed_rows": (i, [vp, vp, vp, i, i, i, vp]),
         "ntk_argmax": (i, [vp, i, vp, vp, vp, vp]),
         "ntk_advance_pos": (i, [vp, vp]),

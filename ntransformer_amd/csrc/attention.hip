@@ -830,6 +830,12 @@ static int launch_attention(float* out, const float* Q, const void* kc, const vo
     return last_launch_status();
 }
 
+// the combine launch for partial states written by another translation unit (attention_q8.hip)
+int launch_attention_split_combine(float* output, const float* part, int n_heads, int hd, int nsplit, int n_kv_heads, hipStream_t st) {
+    hipLaunchKernelGGL(attention_split_combine_kernel, dim3(n_heads), dim3(128), 0, st, output, part, hd, nsplit, n_kv_heads);
+    return last_launch_status();
+}
+
 }  // namespace ntk
 
 extern "C" {

@@ -26,6 +26,7 @@ static void usage(const char* prog) {
             "  -h, --help               Show this help\n"
             "  --no-fuse / --no-graph   Use the 15-launch/layer sequence / launch eagerly\n"
             "  --no-batched-prefill     Prompt tokens one by one (the reference's GEMV loops) instead of 16 per weight pass\n"
+            "  --kv-cache <f16|q8_0>    KV cache format (default: f16; q8_0 = 8-bit Q8_0 blocks, 1.0625 bytes per element)\n"
             "  --synthetic <shape:mix>  8b|70b|tiny : Q8_0|Q4_K_M|Q6_K|...  seeded synthetic weights, no file\n"
             "Accepted for CLI compatibility, no effect on the output (weights are always resident in 288 GB HBM;\n"
             "speculative decoding only changes speed, and plain decode is what runs):\n"
@@ -72,6 +73,10 @@ int main(int argc, char** argv) {
         else if (a == "--no-batched-prefill") engine.options().batched_prefill = false;
         else if (a == "--no-graph") engine.options().graph = false;
         else if (a == "--synthetic") { if (auto v = val()) synthetic = v; }
+        else if (a == "--kv-cache") {
+            const char* v = val();
+            if (!v || engine.model().set_kv_cache(v) != NTK_OK) { fprintf(stderr, "Error: --kv-cache takes f16 or q8_0\n"); return 1; }
+        }
         else if (a == "--streaming") noop(a.c_str(), "weights are fully resident on MI355X");
         else if (a == "--self-spec") noop(a.c_str(), "plain decode runs (same tokens under greedy decoding, no draft pass)");
         else if (a == "--draft-model" || a == "--draft-k") { (void)val(); noop(a.c_str(), "plain decode runs (same tokens under greedy decoding, no draft model is loaded)"); }

@@ -59,7 +59,12 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
     else if (k == "batched_prefill") { E(e)->options().batched_prefill = on; E(e)->model().set_batched_prefill(on); }
     else if (k == "device_sampling") E(e)->options().device_sampling = on;
     else if (k == "f16_prefill" || k == "bf16_prefill") E(e)->model().set_bf16_prefill(on);   // (the round-2 name stays accepted)
-    else if (k == "fuse_attention") E(e)->model().set_fuse_attention(on);
+    else if (k == "fuse_attention") { const int rc = E(e)->model().set_fuse_attention(on); if (rc != NTK_OK) E(e)->set_error(E(e)->model().error()); return rc; }
+    else if (k == "kv_cache") {   // "f16" (default) | "q8_0": before the load only
+        const int rc = E(e)->loaded() ? (E(e)->set_error("kv_cache must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_kv_cache(value);
+        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
+        return rc;
+    }
     else if (k == "prefill_row_max") E(e)->model().set_prefill_row_max(on);   // 1 (default): see Model::prefill_row_max_
     else if (k == "prefill_fused_split") E(e)->model().set_prefill_fused_split(on);   // 1 (default): see Model::prefill_fused_split_
     else if (k == "attention_merge") return E(e)->model().set_attention_merge(on);   // 1: split-KV attention without the combine launch (default 0: measured slower)
@@ -158,6 +163,22 @@ int nt_engine_debug_kv_write(nt_engine_t e, int layer, int pos0, int n, const ui
     if (!e || !E(e)->loaded()) return NTK_E_NULL;
     return E(e)->model().debug_kv(layer, pos0, n, const_cast<uint16_t*>(k), const_cast<uint16_t*>(v), true);
 }
+int nt_engine_debug_kv_inputs_capture(nt_engine_t e, int layer) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_inputs_capture(layer);
+}
+int nt_engine_debug_kv_inputs_read(nt_engine_t e, int n, float* k_out, float* v_out) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_inputs_read(n, k_out, v_out);
+}
+int nt_engine_debug_kv_read_q8(nt_engine_t e, int layer, int pos0, int n, void* k_blocks, void* v_blocks) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_q8(layer, pos0, n, static_cast<uint8_t*>(k_blocks), static_cast<uint8_t*>(v_blocks), false);
+}
+int nt_engine_debug_kv_write_q8(nt_engine_t e, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_q8(layer, pos0, n, static_cast<uint8_t*>(const_cast<void*>(k_blocks)), static_cast<uint8_t*>(const_cast<void*>(v_blocks)), true);
+}
 
 void* nt_engine_persistent_plan(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().persistent_plan() : nullptr; }
 int nt_engine_persistent_kind(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().persistent_kind() : 0; }
@@ -212,6 +233,7 @@ int nt_engine_detokenize(nt_engine_t e, const int* ids, int n, char* out, int ca
 }
 
 uint64_t nt_engine_bytes_per_token(nt_engine_t e, int pos) { return e && E(e)->loaded() ? E(e)->model().bytes_per_token(pos) : 0; }
+uint64_t nt_engine_kv_cache_bytes(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().kv_cache_bytes() : 0; }
 uint64_t nt_engine_weight_bytes(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().weight_bytes() : 0; }
 uint64_t nt_engine_resident_weight_bytes(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().resident_weight_bytes() : 0; }
 uint64_t nt_engine_repacked_bytes(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().repack_bytes() : 0; }

@@ -63,6 +63,7 @@ public:
     const Stats& last_stats() const { return stats_; }
     EngineOptions& options() { return opt_; }
     const std::string& error() const { return err_; }
+    void set_error(const std::string& e) { err_ = e; }
     bool loaded() const { return loaded_; }
 
 private:

@@ -78,6 +78,8 @@ void Model::free_all() {
     host_pos_ = 0;
     attn_regime_ = 0;
     k_cache_ = v_cache_ = nullptr;
+    kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
+    k_cache_q8_ = v_cache_q8_ = nullptr; kv_f16_k_ = kv_f16_v_ = nullptr; kv_q8_layer_bytes_ = 0; kv_cache_bytes_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;
     positions_ = tokens_dev_ = d_pos_ = d_token_ = nullptr;
 }
@@ -521,8 +523,26 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     // 3.75 GiB is refused here, at load, rather than as NTK_E_SHAPE from the first decode step (8 KV heads of 128: 1.9 M positions)
     if (S * per * sizeof(uint16_t) >= 0xF0000000ull) { err_ = "context too long: one layer's K cache must stay below 3.75 GiB (32-bit row offsets)"; return NTK_E_SHAPE; }
     const size_t kvb = L * S * per * sizeof(uint16_t);
-    k_cache_ = (uint16_t*)dev(kvb, true);
-    v_cache_ = (uint16_t*)dev(kvb, true);
+    if (kv_q8_) {   // the 8-bit cache (csrc/attention_q8.hip) + ONE layer's F16 image for the prompt path
+        if (cfg_.head_dim != 128 || cfg_.n_kv_heads <= 0 || cfg_.n_heads % cfg_.n_kv_heads != 0 || cfg_.n_heads / cfg_.n_kv_heads > 16) {
+            err_ = "kv_cache=q8_0 needs head_dim 128 and at most 16 query heads per KV head (this model: head_dim " + std::to_string(cfg_.head_dim) +
+                   ", " + std::to_string(cfg_.n_kv_heads > 0 ? cfg_.n_heads / cfg_.n_kv_heads : 0) + " query heads per KV head)";
+            return NTK_E_SHAPE;
+        }
+        if (tp_world_ > 1) { err_ = "kv_cache=q8_0 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
+        if (fuse_attention_) { err_ = "kv_cache=q8_0 is not supported with the attention-inside-Wo launch (fuse_attention)"; return NTK_E_SHAPE; }
+        kv_q8_layer_bytes_ = ntk_kv_q8_cache_bytes((int)S, cfg_.n_kv_heads, cfg_.head_dim);
+        k_cache_q8_ = (uint8_t*)dev(L * kv_q8_layer_bytes_, true);
+        v_cache_q8_ = (uint8_t*)dev(L * kv_q8_layer_bytes_, true);
+        kv_f16_k_ = (uint16_t*)dev(S * per * sizeof(uint16_t), true);
+        kv_f16_v_ = (uint16_t*)dev(S * per * sizeof(uint16_t), true);
+        if (!k_cache_q8_ || !v_cache_q8_ || !kv_f16_k_ || !kv_f16_v_) { err_ = "buffer allocation failed (8-bit KV cache)"; return NTK_E_NOMEM; }
+        kv_cache_bytes_ = 2ull * L * kv_q8_layer_bytes_ + 2ull * S * per * sizeof(uint16_t);
+    } else {
+        k_cache_ = (uint16_t*)dev(kvb, true);
+        v_cache_ = (uint16_t*)dev(kvb, true);
+        kv_cache_bytes_ = 2ull * kvb;
+    }
     hidden_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
     residual_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
     logits_ = (float*)dev((size_t)cfg_.vocab_size * 4, false);
@@ -560,7 +580,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     }
     d_recent_ = (int*)dev(kRecentCap * 4, false);
     h_recent_ = (int*)nt_hip_malloc_host(kRecentCap * 4);
-    if (!k_cache_ || !v_cache_ || !hidden_ || !residual_ || !logits_ || !workspace_ || !positions_ || !tokens_dev_ ||
+    if ((!kv_q8_ && (!k_cache_ || !v_cache_)) || !hidden_ || !residual_ || !logits_ || !workspace_ || !positions_ || !tokens_dev_ ||
         !d_pos_ || !d_token_ || !argmax_scratch_ || !h_token_ || !h_ring_) {
         err_ = "buffer allocation failed";
         return NTK_E_NOMEM;
@@ -580,7 +600,8 @@ uint64_t Model::bytes_per_token(int pos) const {
         b += L.wq.nbytes + L.wk.nbytes + L.wv.nbytes + L.wo.nbytes + L.w_gate.nbytes + L.w_up.nbytes + L.w_down.nbytes;
     b += output_.nbytes;
     b += (uint64_t)(2 * cfg_.n_layers + 1) * cfg_.hidden_size * 4;
-    const uint64_t kv_row = (uint64_t)cfg_.n_kv_heads * cfg_.head_dim * 2;
+    const uint64_t kv_elems = (uint64_t)cfg_.n_kv_heads * cfg_.head_dim;
+    const uint64_t kv_row = kv_q8_ ? kv_elems + kv_elems / 16 : kv_elems * 2;   // q8_0: an int8 per element + a half per 32
     b += 2ull * cfg_.n_layers * kv_row * (uint64_t)(pos + 1) + 2ull * cfg_.n_layers * kv_row;
     b += ntk_row_bytes(token_embd_.dtype, cfg_.hidden_size);
     return b;
@@ -836,8 +857,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     bool normed_ahead = false;   // residual_ (with its maxima or planes) already holds this layer's normalised input, written with the previous layer's down projection
     for (int i = first; i < last_layer; ++i) {
         const LayerWeights& L = layers_[i];
-        uint16_t* kc = k_cache_ + (size_t)i * kv_layer;
-        uint16_t* vc = v_cache_ + (size_t)i * kv_layer;
+        uint16_t* kc = kv_q8_ ? nullptr : k_cache_ + (size_t)i * kv_layer;   // (q8_0: the one-layer F16 image, set below)
+        uint16_t* vc = kv_q8_ ? nullptr : v_cache_ + (size_t)i * kv_layer;
         if (!normed_ahead) norm(L.attn_norm, true, L.wq);
         normed_ahead = false;
         {
@@ -845,7 +866,24 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
             const DevTensor* const ws[3] = {&L.wq, &L.wk, &L.wv};
             project_many(ys, ws, 3, residual_, rm_a);
         }
-        if (with_max && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
+        if (i == kv_capture_layer_ && kv_capture_) {   // parity instrumentation: the F32 projections the store launches are about to read
+            ok(ntk_copy(kv_capture_, k_buf, T * kvd, s));
+            ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, v_buf, T * kvd, s));
+            kv_capture_T_ = T;
+        }
+        if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
+            uint8_t* kc8 = k_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
+            uint8_t* vc8 = v_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
+            if (T >= 4) {
+                ok(ntk_rope_kv_store_q8(q_buf, k_buf, v_buf, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
+                                        kc8, vc8, start_pos, cfg_.max_seq_len, s));
+            } else {
+                ok(ntk_rope(q_buf, k_buf, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, s));
+                ok(ntk_kv_store_q8(kc8, vc8, k_buf, v_buf, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
+            }
+            ok(ntk_kv_dequant_q8_f16(kv_f16_k_, kv_f16_v_, kc8, vc8, start_pos + T, nkv, hd, cfg_.max_seq_len, s));
+            kc = kv_f16_k_; vc = kv_f16_v_;
+        } else if (with_max && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
             ok(ntk_rope_kv_store(q_buf, k_buf, v_buf, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, kc, vc,
                                  start_pos, cfg_.max_seq_len, s));
         } else {
@@ -1115,15 +1153,15 @@ int Model::enqueue_layers(int first, int last_layer) {
 
     for (int i = first; i < last_layer; ++i) {
         const LayerWeights& L = layers_[i];
-        uint16_t* kc = k_cache_ + (size_t)i * kv_layer;
-        uint16_t* vc = v_cache_ + (size_t)i * kv_layer;
+        uint16_t* kc = kv_q8_ ? nullptr : k_cache_ + (size_t)i * kv_layer;   // (q8_0: the launch below takes the 8-bit caches)
+        uint16_t* vc = kv_q8_ ? nullptr : v_cache_ + (size_t)i * kv_layer;
         {
             const DevTensor* ws[3] = {&L.wq, &L.wk, &L.wv};
             float* ys[3] = {q_buf, k_buf, v_buf};
             NT_TRY(project(ws, ys, 3, hidden_, &L.attn_norm, nullptr, 1));
         }
 #ifdef NTK_EXPERIMENTS
-        if (attn_regime_ == 0 && fuse_attention_ && attn_sync_ && is_quant(L.wo.dtype) && tp_world_ == 1) {
+        if (attn_regime_ == 0 && fuse_attention_ && !kv_q8_ && attn_sync_ && is_quant(L.wo.dtype) && tp_world_ == 1) {
             // attention producers inside the Wo launch: one launch, one boundary and one first-byte latency less per layer
             raw_begin();
             ntk_gemv_seg wo = {raw_of(L.wo), hidden_, (int)L.wo.out_f, L.wo.dtype};
@@ -1137,7 +1175,11 @@ int Model::enqueue_layers(int first, int last_layer) {
         }
 #endif
         mark(1, true);
-        if (attn_regime_ == 0)
+        if (kv_q8_)
+            NT_TRY(ntk_attention_decode_q8(attn_out, q_buf, k_buf, v_buf, k_cache_q8_ + (size_t)i * kv_q8_layer_bytes_,
+                                           v_cache_q8_ + (size_t)i * kv_q8_layer_bytes_, d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
+                                           cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
+        else if (attn_regime_ == 0)
             NT_TRY(ntk_attention_decode_fused(attn_out, q_buf, k_buf, v_buf, kc, vc, d_pos_, rope_inv_freq_, nh, nkv, hd,
                                               cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, s));
         else
@@ -1233,6 +1275,7 @@ int Model::debug_run_layers(const float* hidden_in, int T, int start_pos, int fi
 // cache rows [pos0, pos0 + n) of one layer, [n][n_kv_heads * head_dim] halves each (reference layout, transformer.cpp:340-346)
 int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write) {
     if (!k || !v) return NTK_E_NULL;
+    if (kv_q8_) { err_ = "debug_kv: the KV cache is q8_0 (use the _q8 form)"; return NTK_E_DTYPE; }
     if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len) return NTK_E_SHAPE;
     const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim;
     const size_t off = ((size_t)layer * cfg_.max_seq_len + pos0) * per, bytes = (size_t)n * per * 2;
@@ -1245,6 +1288,82 @@ int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool w
         NT_TRY(ntk_memcpy_d2h_async(v, v_cache_ + off, bytes, s));
     }
     return ntk_stream_synchronize(s);
+}
+
+// ... of the 8-bit cache, as canonical 34-byte GGUF block_q8_0 {half d; int8 q[32]}: [n][n_kv_heads * head_dim / 32] blocks per side.  The device
+// keeps quants and scales in two planes (csrc/attention_q8.hip): the rows' slices of both are contiguous, the blocks are (de)interleaved here.
+int Model::debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write) {
+    if (!k_blocks || !v_blocks) return NTK_E_NULL;
+    if (!kv_q8_) { err_ = "debug_kv_q8: the KV cache is f16"; return NTK_E_DTYPE; }
+    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len) return NTK_E_SHAPE;
+    if (n == 0) return NTK_OK;
+    const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim, nb = per / 32;
+    const size_t qbytes = (size_t)n * per, sbytes = (size_t)n * nb * 2;
+    void* s = stream_;
+    std::vector<uint8_t> qh(qbytes), sh(sbytes);
+    for (int side = 0; side < 2; ++side) {
+        uint8_t* base = (side ? v_cache_q8_ : k_cache_q8_) + (size_t)layer * kv_q8_layer_bytes_;
+        uint8_t* qd = base + (size_t)pos0 * per;
+        uint8_t* sd = base + (size_t)cfg_.max_seq_len * per + (size_t)pos0 * nb * 2;
+        uint8_t* blocks = side ? v_blocks : k_blocks;
+        if (write) {
+            for (size_t b = 0; b < (size_t)n * nb; ++b) {
+                memcpy(&sh[2 * b], blocks + 34 * b, 2);
+                memcpy(&qh[32 * b], blocks + 34 * b + 2, 32);
+            }
+            NT_TRY(ntk_memcpy_h2d_async(qd, qh.data(), qbytes, s));
+            NT_TRY(ntk_memcpy_h2d_async(sd, sh.data(), sbytes, s));
+            NT_TRY(ntk_stream_synchronize(s));
+        } else {
+            NT_TRY(ntk_memcpy_d2h_async(qh.data(), qd, qbytes, s));
+            NT_TRY(ntk_memcpy_d2h_async(sh.data(), sd, sbytes, s));
+            NT_TRY(ntk_stream_synchronize(s));
+            for (size_t b = 0; b < (size_t)n * nb; ++b) {
+                memcpy(blocks + 34 * b, &sh[2 * b], 2);
+                memcpy(blocks + 34 * b + 2, &qh[32 * b], 32);
+            }
+        }
+    }
+    return NTK_OK;
+}
+
+// Parity instrumentation: from now on every 1:1 pass (forward / debug_run_layers mode 0) leaves the F32 k (BEFORE the rotation) and v projections of
+// `layer` in a capture buffer; debug_kv_inputs_read returns those of the last pass ([n][n_kv_heads * head_dim] floats each).  layer < 0: off.
+int Model::debug_kv_inputs_capture(int layer) {
+    if (layers_.empty()) return NTK_E_NULL;
+    if (layer >= cfg_.n_layers) return NTK_E_SHAPE;
+    kv_capture_layer_ = layer < 0 ? -1 : layer;
+    kv_capture_T_ = 0;
+    if (layer >= 0 && !kv_capture_) {
+        const size_t bytes = 2 * (size_t)cfg_.max_seq_len * cfg_.n_kv_heads * cfg_.head_dim * 4;
+        kv_capture_ = (float*)nt_hip_malloc(bytes);
+        if (!kv_capture_) { err_ = "debug_kv_inputs_capture: out of device memory"; return NTK_E_NOMEM; }
+        allocs_.push_back(kv_capture_);
+    }
+    return NTK_OK;
+}
+int Model::debug_kv_inputs_read(int n, float* k, float* v) {
+    if (!k || !v) return NTK_E_NULL;
+    if (!kv_capture_ || kv_capture_layer_ < 0 || n < 0 || n > kv_capture_T_) return NTK_E_SHAPE;
+    const size_t kvd = (size_t)cfg_.n_kv_heads * cfg_.head_dim;
+    NT_TRY(ntk_memcpy_d2h_async(k, kv_capture_, (size_t)n * kvd * 4, stream_));
+    NT_TRY(ntk_memcpy_d2h_async(v, kv_capture_ + (size_t)cfg_.max_seq_len * kvd, (size_t)n * kvd * 4, stream_));
+    return ntk_stream_synchronize(stream_);
+}
+
+int Model::set_kv_cache(const std::string& kind) {
+    if (kind != "f16" && kind != "q8_0") { err_ = "kv_cache: unknown format '" + kind + "' (f16 or q8_0)"; return NTK_E_DTYPE; }
+    if (!layers_.empty()) { err_ = "kv_cache must be set before the model is loaded"; return NTK_E_SHAPE; }
+    const bool q8 = kind == "q8_0";
+    if (q8 && fuse_attention_) { err_ = "kv_cache=q8_0 is not supported with the attention-inside-Wo launch (fuse_attention)"; return NTK_E_SHAPE; }
+    kv_q8_ = q8;
+    return NTK_OK;
+}
+
+int Model::set_fuse_attention(bool on) {
+    if (on && kv_q8_) { err_ = "fuse_attention (attention inside the Wo launch) is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
+    fuse_attention_ = on;
+    return NTK_OK;
 }
 
 // A tensor-parallel exchange whose bounded wait for a peer gave up has added garbage: surface it (and clear the sticky word)
@@ -1279,6 +1398,7 @@ void Model::set_persistent(int level) {   // 0 off, 1 the round-2 token kernel (
     }
 #endif
     if (!on || tp_world_ != 1 || layers_.empty()) return;
+    if (kv_q8_) { fprintf(stderr, "note: the persistent token kernels read the F16 KV cache; kv_cache=q8_0 decodes with fused launches\n"); return; }
     if (raw_freed_bytes_ > 0) (void)set_repack(1);   // the persistent kernels stream the GGUF bytes themselves: those must be resident
     if (!persistent_plan_) (void)build_persistent_plan(level == 2 ? 2 : 1);   // built on first use (EXPERIMENTS=1 builds only): it allocates device memory
     persistent_on_ = persistent_plan_ != nullptr;

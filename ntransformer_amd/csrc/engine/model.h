@@ -106,7 +106,20 @@ public:
     // longer ones keep the launch path.  Turned off for good if the kernel ever reports a bounded wait that gave up.
     void set_persistent(int level);   // 0 off, 1 decode_persistent.hip, 2 layer_engine.hip (round 5); EXPERIMENTS=1 builds only, otherwise stays off
     int persistent_kind() const { return persistent_plan_ ? persistent_kind_ : 0; }
-    void set_fuse_attention(bool on) { fuse_attention_ = on; }
+    int set_fuse_attention(bool on);   // (refused with the 8-bit KV cache)
+    // KV cache format: "f16" (default) or "q8_0" (csrc/attention_q8.hip: Q8_0 blocks along head_dim, 1.0625 bytes per element + ONE layer's F16
+    // scratch image for the prompt path).  Set BEFORE the load (load / load_synthetic / share_weights: a sharing sequence takes its own option);
+    // refused afterwards.  q8_0 needs head_dim 128, <= 16 query heads per KV head and no tensor parallelism: the load refuses otherwise.
+    // Decode: ntk_attention_decode_q8 + the combine launch in every regime (splits: kv_q8_splits).  Prompt pass / 1:1 sequence: 8-bit store, then
+    // rows [0, start_pos + T) dequantised (rounded to half) into the scratch that the unchanged F16 attention kernels read.
+    int set_kv_cache(const std::string& kind);
+    bool kv_q8() const { return kv_q8_; }
+    static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
+    uint64_t kv_cache_bytes() const { return kv_cache_bytes_; }   // resident KV bytes of this sequence, the q8_0 mode's F16 scratch included
+    // cache rows [pos0, pos0 + n) of a layer as canonical 34-byte GGUF block_q8_0, [n][n_kv_heads * head_dim / 32] blocks per side (q8_0 mode only)
+    int debug_kv_inputs_capture(int layer);
+    int debug_kv_inputs_read(int n, float* k, float* v);
+    int debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write);
     void set_prefill_row_max(bool on) { prefill_row_max_ = on; }
     void set_prefill_fused_split(bool on) { prefill_fused_split_ = on; }
     // Split-KV decode attention as ONE launch (the last workgroup of a head merges the partial states: attention_merge.hip.h) or -- the default --
@@ -198,6 +211,15 @@ private:
     // buffers (reference transformer.cpp:330-391)
     uint16_t* k_cache_ = nullptr;   // [L][max_seq][nkv][hd] half
     uint16_t* v_cache_ = nullptr;
+    bool kv_q8_ = false;            // the option (kept across loads)
+    uint8_t* k_cache_q8_ = nullptr; // [L] x kv_q8_layer_bytes_ (ntk_kv_q8_cache_bytes: int8 quants, then half scales)
+    uint8_t* v_cache_q8_ = nullptr;
+    size_t kv_q8_layer_bytes_ = 0;
+    uint16_t* kv_f16_k_ = nullptr;  // q8_0 mode: [max_seq][nkv][hd] half, ONE layer's dequantised image for the prompt path, shared by all layers
+    uint16_t* kv_f16_v_ = nullptr;
+    uint64_t kv_cache_bytes_ = 0;
+    float* kv_capture_ = nullptr;   // parity instrumentation (debug_kv_inputs_capture): [2][max_seq][nkv * hd] F32 k (unrotated) and v of one layer's last 1:1 pass
+    int kv_capture_layer_ = -1, kv_capture_T_ = 0;
     float* hidden_ = nullptr;       // [max_seq][H]
     float* residual_ = nullptr;     // [max_seq][H]
     float* workspace_ = nullptr;    // max(attention, ffn) floats, shared by all layers

@@ -91,6 +91,12 @@ def _bind():
     L.nt_engine_debug_run_layers.argtypes = [vp, vp, i, i, i, i, i, vp]
     L.nt_engine_debug_kv_read.argtypes = [vp, i, i, i, vp, vp]
     L.nt_engine_debug_kv_write.argtypes = [vp, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_read_q8.argtypes = [vp, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_write_q8.argtypes = [vp, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_inputs_capture.argtypes = [vp, i]
+    L.nt_engine_debug_kv_inputs_read.argtypes = [vp, i, vp, vp]
+    L.nt_engine_kv_cache_bytes.argtypes = [vp]
+    L.nt_engine_kv_cache_bytes.restype = C.c_uint64
     L._engine_bound = True
     return L
 
@@ -158,7 +164,8 @@ class Engine:
         return int(self.L.nt_engine_tp_error(self.h))
 
     def set_option(self, key: str, value) -> None:
-        self._check(self.L.nt_engine_set_option(self.h, key.encode(), str(int(value)).encode()), "set_option " + key)
+        text = value if isinstance(value, str) else str(int(value))   # ("kv_cache" takes "f16" / "q8_0")
+        self._check(self.L.nt_engine_set_option(self.h, key.encode(), text.encode()), "set_option " + key)
 
     @property
     def vocab_size(self): return self.L.nt_engine_vocab_size(self.h)
@@ -200,6 +207,31 @@ class Engine:
         k = np.ascontiguousarray(k, dtype=np.uint16)
         v = np.ascontiguousarray(v, dtype=np.uint16)
         self._check(self.L.nt_engine_debug_kv_write(self.h, layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "kv_write")
+
+    def kv_read_q8(self, layer: int, pos0: int, n: int, row_elems: int):
+        """(K, V) rows [pos0, pos0+n) of a kv_cache=q8_0 engine as canonical GGUF block_q8_0 bytes, uint8 [n, row_elems / 32, 34]"""
+        k = np.empty((n, row_elems // 32, 34), np.uint8)
+        v = np.empty((n, row_elems // 32, 34), np.uint8)
+        self._check(self.L.nt_engine_debug_kv_read_q8(self.h, layer, pos0, n, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "kv_read_q8")
+        return k, v
+
+    def kv_write_q8(self, layer: int, pos0: int, k_blocks: np.ndarray, v_blocks: np.ndarray) -> None:
+        k = np.ascontiguousarray(k_blocks, dtype=np.uint8)
+        v = np.ascontiguousarray(v_blocks, dtype=np.uint8)
+        self._check(self.L.nt_engine_debug_kv_write_q8(self.h, layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "kv_write_q8")
+
+    def kv_inputs_capture(self, layer: int) -> None:
+        self._check(self.L.nt_engine_debug_kv_inputs_capture(self.h, layer), "kv_inputs_capture")
+
+    def kv_inputs_read(self, n: int, row_elems: int):
+        """(k before the rotation, v) F32 [n, row_elems] that the captured layer's KV store read in the last prompt pass"""
+        k = np.empty((n, row_elems), np.float32)
+        v = np.empty((n, row_elems), np.float32)
+        self._check(self.L.nt_engine_debug_kv_inputs_read(self.h, n, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "kv_inputs_read")
+        return k, v
+
+    def kv_cache_bytes(self) -> int:
+        return int(self.L.nt_engine_kv_cache_bytes(self.h))
 
     def generate_tokens(self, prompt: Sequence[int], max_tokens: int, temperature: float = 0.0, top_k: int = 40,
                         top_p: float = 0.9, repeat_penalty: float = 1.0, repeat_window: int = 64, seed: int = 42,
