@@ -4,6 +4,7 @@
 // FFN::forward, RMSNorm::forward).  The reference's streaming / tiered / delta / speculative paths exist
 // to fit 24 GB of VRAM and are dropped: 288 GB of HBM holds every target model resident.
 #pragma once
+#include <array>
 #include <chrono>
 #include <cstdint>
 #include <string>
@@ -27,6 +28,11 @@ struct DevTensor {
 struct LayerWeights {
     DevTensor attn_norm, wq, wk, wv, wo, ffn_norm, w_gate, w_up, w_down;
 };
+// the seven projection matrices of a layer, for whoever visits them all: for (auto m : kLayerMatrices) use(L.*m);
+inline constexpr std::array<DevTensor LayerWeights::*, 7> kLayerMatrices = {&LayerWeights::wq, &LayerWeights::wk, &LayerWeights::wv, &LayerWeights::wo,
+                                                                            &LayerWeights::w_gate, &LayerWeights::w_up, &LayerWeights::w_down};
+
+enum Shard { WHOLE, ROWS, COLS };   // a tensor's part on a tensor-parallel rank: all of it, a block of rows, a block of columns
 
 class Model {
 public:
@@ -116,9 +122,9 @@ public:
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
     uint64_t kv_cache_bytes() const { return kv_cache_bytes_; }   // resident KV bytes of this sequence, the q8_0 mode's F16 scratch included
-    // cache rows [pos0, pos0 + n) of a layer as canonical 34-byte GGUF block_q8_0, [n][n_kv_heads * head_dim / 32] blocks per side (q8_0 mode only)
     int debug_kv_inputs_capture(int layer);
     int debug_kv_inputs_read(int n, float* k, float* v);
+    // cache rows [pos0, pos0 + n) of a layer as canonical 34-byte GGUF block_q8_0, [n][n_kv_heads * head_dim / 32] blocks per side (q8_0 mode only)
     int debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write);
     void set_prefill_row_max(bool on) { prefill_row_max_ = on; }
     void set_prefill_fused_split(bool on) { prefill_fused_split_ = on; }
@@ -173,12 +179,18 @@ public:
 
 private:
     int load_impl(const std::string& gguf_path, int max_context);
-    int finish_load(int max_context);
+    int finish_load();
+    int init_device();                // the GPU NTK_DEVICE names (default 0)
+    int own_stream();                 // a private non-blocking stream: sequences and ranks that share a process must not queue behind each other
     int alloc_buffers();
     int upload(DevTensor& dst, const void* host, int dtype, int64_t in_f, int64_t out_f, size_t nbytes);
-    enum Shard { WHOLE, ROWS, COLS };
     // upload this rank's part of a full host tensor [out_f][in_f]: everything, rows [rank * out/world ...), or the column slice
     int upload_shard(DevTensor& dst, const void* host_full, int dtype, int64_t in_f, int64_t out_f, size_t nbytes_full, Shard how);
+    // where the GGUF tensor `name` lands, how it is sharded over tensor-parallel ranks and its unsliced extents (false: no such tensor in this model)
+    struct TensorSlot { DevTensor* dst; Shard how; int64_t in_f, out_f; };
+    bool slot_of(const std::string& name, TensorSlot* slot);
+    // every projection matrix that can have a repacked form: the layers' seven, then the LM head
+    template <class F> void for_each_projection(F&& fn) { for (auto& L : layers_) for (auto m : kLayerMatrices) fn(L.*m); fn(output_); }
     int repack_all();                 // the repacked form of every K-quant projection (after the upload)
     int repack_one(DevTensor& t);
     int drop_raw_all();               // level 2: free the GGUF bytes of every repacked matrix, size the unpack scratch
@@ -191,12 +203,25 @@ private:
     int tp_allreduce(float* hidden, int n);   // hidden += sum over ranks of the partial vectors in the current slot
     float* tp_slot() const;           // where the next partial vector goes
     void free_all();
+    void drop_graphs(int slot = -1);  // destroy the captured tokens of one slot, or of all
+    // the activations of T tokens in workspace_: q | k | v | attn_out, and gate | up over the same floats once attention is done
+    struct Views { float *q, *k, *v, *attn_out, *gate, *up; };
+    Views views(int T) const;
     int enqueue_token(bool greedy);   // the fused launch sequence for one token
     int enqueue_layers(int first, int last);            // its layer loop
+    // y_k = W_k . f(x) for n <= 3 matrices sharing x, in as few fused launches as their formats allow (model_decode.cpp)
+    int decode_project(const DevTensor* const* ws, float* const* ys, int n, const float* x, const DevTensor* norm, const float* resid, int kind,
+                       int silu_pair = 0, bool timed = true);
     int layers_1to1(int T, int start_pos, int first, int last);   // the layer loop of forward()
     void prof_mark(int cls, bool begin);
     bool use_persistent_now() const;
+    // hooks of experiments/ (model_experiments.cpp); in the product they launch nothing: NTK_E_SHAPE = "not taken", no plan, no error to report
+    static bool experiments_built();
     int build_persistent_plan(int kind);   // the same operator sequence as a table for ntk_persistent_launch / ntk_layer_engine_launch (nullptr plan if unsupported)
+    void destroy_persistent_plan();                          // ... and the tokens captured with it
+    int launch_persistent();                                 // every layer and the LM head of a token in one launch
+    int attention_in_wo(const LayerWeights& L, int layer);   // attention producers inside the Wo launch
+    int check_experiments();                                 // the error words of those kernels' bounded waits
 
     ModelConfig cfg_;
     GgufVocab vocab_;

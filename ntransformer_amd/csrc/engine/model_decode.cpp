@@ -1,0 +1,223 @@
+// engine/model_decode.cpp -- the fused single-token pass: launch sequence, hipGraph capture, profiler hook (see model.h)
+#include "model_impl.h"
+
+namespace nt {
+
+// profiling hook (only inside profile_token(), never while capturing).  Fine mode: an event pair around every
+// launch.  Coarse mode: ONE event where the launch class changes -- a run of same-class launches is timed as a
+// whole (its kernels and the boundaries between them), so the cost of the events is paid once per run.
+void Model::prof_mark(int cls, bool begin) {
+    if (!prof_) return;
+    void* s = stream_;
+    if (prof_coarse_) {
+        if (!begin) return;
+        if (!prof_->empty() && prof_->back().cls == cls) { ++prof_->back().n; return; }
+        void* e = ntk_event_create();
+        ntk_event_record(e, s);
+        const bool shared = !prof_->empty();
+        if (shared) prof_->back().b = e;
+        prof_->push_back({cls, e, nullptr, 1, shared});
+        return;
+    }
+    void* e = ntk_event_create();
+    ntk_event_record(e, s);
+    if (begin) prof_->push_back({cls, e, nullptr, 1, false}); else prof_->back().b = e;
+}
+
+int Model::enqueue_token(bool greedy) {
+    const int H = cfg_.hidden_size;
+    void* s = stream_;
+    tp_call_ = 0;
+    prof_mark(2, true);
+    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, d_token_, 1, H, token_embd_.dtype, s);
+    prof_mark(2, false);
+    if (est != NTK_OK && est != NTK_E_DTYPE) return est;
+    if (use_persistent_now()) {   // (experiments builds) every layer and the LM head in one launch
+        NT_TRY(launch_persistent());
+    } else {
+        NT_TRY(enqueue_layers(0, cfg_.n_layers));
+        // final RMSNorm + LM head: one launch for a quantised output matrix (timed as one interval whichever form takes it), two 1:1 launches for a dense one
+        const DevTensor* const w = &output_;
+        const bool timed = is_quant(w->dtype);
+        if (timed) prof_mark(0, true);
+        NT_TRY(decode_project(&w, &logits_, 1, hidden_, &output_norm_, nullptr, 16, 0, false));
+        if (timed) prof_mark(0, false);
+    }
+    prof_mark(2, true);
+    // greedy: arg-max, token -> device word + pinned ring, position + 1 in ONE tail (ntk_argmax_advance); otherwise only the position
+    if (greedy) NT_TRY(ntk_argmax_advance(logits_, cfg_.vocab_size, d_token_, h_token_, h_ring_, d_pos_, argmax_scratch_, s));
+    else NT_TRY(ntk_advance_pos(d_pos_, s));
+    if (tp_world_ > 1) NT_TRY(ntk_tp_advance_epoch(tp_comm_, s));
+    prof_mark(2, false);
+    return NTK_OK;
+}
+
+// y_k = W_k . f(x) for n <= 3 matrices sharing x.  Matrices with one quantised dtype go out as one fused launch (RMSNorm prologue when `norm`, residual
+// epilogue when `resid`, n == 1; silu_pair: y_0 = SiLU(y_0) x y_1 in the epilogue, two matrices of one format); dense F16/F32 tensors take the 1:1
+// launchers.  Scratch: residual_[0,H) = dense output before the residual add, residual_[H,2H) = norm(x).  kind: the call site's rp_mask() bit.  timed: every
+// launch is a profiler interval of its own (false: the caller times the whole call as one).
+int Model::decode_project(const DevTensor* const* ws, float* const* ys, int n, const float* x, const DevTensor* norm, const float* resid, int kind,
+                          int silu_pair, bool timed) {
+    const int H = cfg_.hidden_size;
+    void* s = stream_;
+    auto mark = [&](bool begin) { if (timed) prof_mark(0, begin); };
+    const float* nw = norm ? (const float*)norm->ptr : nullptr;
+    // The two optional forms that take all n matrices in ONE launch, from the repack or from the GGUF blocks.  "Not taken" (formats / alignment / workgroup
+    // split / LDS size): the next form takes over -- the per-format launches below take everything.
+    auto one_launch = [&](bool rp, const float* r, int silu) {
+        ntk_gemv_seg segs[3];
+        if (!rp) raw_begin();
+        for (int a = 0; a < n; ++a) segs[a] = {rp ? ws[a]->rp : raw_of(*ws[a]), ys[a], (int)ws[a]->out_f, ws[a]->dtype};
+        mark(true);
+        const int st = (rp ? ntk_gemv_rp_fused : ntk_gemv_fused)(segs, n, x, (int)ws[0]->in_f, nw, cfg_.norm_eps, r, silu, s);
+        mark(false);
+        return st;
+    };
+    bool all_rp = repack_ && (rp_mask() & kind), all_quant = true, mixed = false;
+    for (int a = 0; a < n; ++a) {
+        all_rp = all_rp && ws[a]->rp != nullptr && ws[a]->in_f == ws[0]->in_f;
+        all_quant = all_quant && is_quant(ws[a]->dtype);
+        mixed = mixed || ws[a]->dtype != ws[0]->dtype;
+    }
+    if (all_rp) {   // every matrix has its repacked form: the matrix-core GEMV, whatever the mix of K-quant formats
+        const int st = one_launch(true, resid, silu_pair);
+        if (!not_taken(st)) return st;
+    }
+    if (n > 1 && !resid && all_quant && mixed) {   // matrices in two K-quant formats (Q4_K_M's attn_v): still one launch when the library has the pair
+        const int st = one_launch(false, nullptr, 0);
+        if (!not_taken(st)) return st;
+    }
+    bool done[3] = {false, false, false};
+    for (int a = 0; a < n; ++a) {
+        if (done[a]) continue;
+        const DevTensor& w = *ws[a];
+        if (!is_quant(w.dtype)) {
+            const float* xin = x;
+            if (nw) {
+                NT_TRY(ntk_rmsnorm(residual_ + H, x, nw, 1, (int)w.in_f, cfg_.norm_eps, s));
+                xin = residual_ + H;
+            }
+            float* y = resid ? residual_ : ys[a];
+            raw_begin();
+            NT_TRY(ntk_gemv(y, raw_of(w), xin, (int)w.out_f, (int)w.in_f, w.dtype, s));
+            if (resid) NT_TRY(ntk_add(ys[a], resid, residual_, (int)w.out_f, s));
+            done[a] = true;
+            continue;
+        }
+        ntk_gemv_seg segs[3];
+        int m = 0;
+        raw_begin();
+        for (int b = a; b < n; ++b) {
+            if (done[b] || ws[b]->dtype != w.dtype) continue;
+            segs[m++] = {raw_of(*ws[b]), ys[b], (int)ws[b]->out_f, ws[b]->dtype};
+            done[b] = true;
+        }
+        mark(true);
+        NT_TRY(ntk_gemv_fused(segs, m, x, (int)w.in_f, nw, cfg_.norm_eps, resid, silu_pair, s));
+        mark(false);
+    }
+    return NTK_OK;
+}
+
+// layers [first, last) of the fused single-token path on hidden_[H] (position in *d_pos_)
+int Model::enqueue_layers(int first, int last_layer) {
+    const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
+    void* s = stream_;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const size_t kv_layer = (size_t)cfg_.max_seq_len * nkv * hd;
+    const Views act = views(1);
+    auto project_add = [&](const DevTensor& w, const float* x, int kind) -> int {   // hidden += W . x
+        const DevTensor* const wp = &w;
+        float* y = tp_world_ > 1 ? tp_slot() : hidden_;   // tensor parallelism: this rank's partial sum -> exchange slot -> hidden += sum over ranks
+        NT_TRY(decode_project(&wp, &y, 1, x, nullptr, tp_world_ > 1 ? nullptr : hidden_, kind));
+        return tp_world_ > 1 ? tp_allreduce(hidden_, H) : (int)NTK_OK;
+    };
+
+    for (int i = first; i < last_layer; ++i) {
+        const LayerWeights& L = layers_[i];
+        const DevTensor* const qkv[3] = {&L.wq, &L.wk, &L.wv};
+        float* const qkv_out[3] = {act.q, act.k, act.v};
+        NT_TRY(decode_project(qkv, qkv_out, 3, hidden_, &L.attn_norm, nullptr, 1));
+        // (experiments builds: attention inside the Wo launch; not taken = shapes only the two launches take)
+        const int fused = fuse_attention_ ? attention_in_wo(L, i) : (int)NTK_E_SHAPE;
+        if (fused != NTK_OK) {
+            if (!not_taken(fused)) return fused;
+            uint16_t* kc = kv_q8_ ? nullptr : k_cache_ + (size_t)i * kv_layer;   // (q8_0: the launch takes the 8-bit caches)
+            uint16_t* vc = kv_q8_ ? nullptr : v_cache_ + (size_t)i * kv_layer;
+            prof_mark(1, true);
+            if (kv_q8_)
+                NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, k_cache_q8_ + (size_t)i * kv_q8_layer_bytes_,
+                                               v_cache_q8_ + (size_t)i * kv_q8_layer_bytes_, d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
+                                               cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
+            else if (attn_regime_ == 0)
+                NT_TRY(ntk_attention_decode_fused(act.attn_out, act.q, act.k, act.v, kc, vc, d_pos_, rope_inv_freq_, nh, nkv, hd,
+                                                  cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, s));
+            else
+                NT_TRY((attn_merge_ ? ntk_attention_decode_split_merged : ntk_attention_decode_split)(
+                    act.attn_out, act.q, act.k, act.v, kc, vc, d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale, cfg_.rope_theta,
+                    cfg_.rope_freq_scale, attention_splits(attn_regime_, hd), attn_scratch_, s));
+            prof_mark(1, false);
+            NT_TRY(project_add(L.wo, act.attn_out, 2));
+        }
+        const DevTensor* const ffn[2] = {&L.w_gate, &L.w_up};
+        float* const ffn_out[2] = {act.gate, act.up};
+        // one quantised format: SiLU x up in the launch's epilogue, one profiler interval whichever form takes it; otherwise a launch of its own
+        const bool pair = is_quant(L.w_gate.dtype) && L.w_gate.dtype == L.w_up.dtype;
+        if (pair) prof_mark(0, true);
+        NT_TRY(decode_project(ffn, ffn_out, 2, hidden_, &L.ffn_norm, nullptr, 4, pair, !pair));
+        if (pair) prof_mark(0, false);
+        else NT_TRY(ntk_silu_mul(act.gate, act.gate, act.up, I, s));
+        NT_TRY(project_add(L.w_down, act.gate, 8));
+    }
+    return NTK_OK;
+}
+
+void Model::pick_attention_regime() {
+    attn_regime_ = (attn_scratch_ && (cfg_.head_dim == 64 || cfg_.head_dim == 128 || cfg_.head_dim == 256))
+                       ? attention_regime(host_pos_, cfg_.head_dim) : 0;
+    ++host_pos_;   // every fused token ends with ntk_advance_pos on the device; set_device_pos() re-bases both
+}
+
+int Model::decode_step_fused(bool greedy, bool use_graph) {
+    pick_attention_regime();
+    if (!use_graph) return enqueue_token(greedy);
+    ihipGraphExec_t*& slot = graphs_[greedy ? 1 : 0][use_persistent_now() ? kPersistentSlot : attn_regime_];
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    if (!slot) {   // capture once: every per-token quantity (token id, position) lives in device memory
+        hipGraphExec_t ex = nullptr;
+        // (relaxed under tensor parallelism: ranks sharing a process run their own runtime calls on other threads meanwhile)
+        NT_TRY(capture_graph(st, tp_world_ > 1 ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal, [&] { return enqueue_token(greedy); }, &ex));
+        slot = reinterpret_cast<ihipGraphExec_t*>(ex);
+    }
+    return hipGraphLaunch(reinterpret_cast<hipGraphExec_t>(slot), st) == hipSuccess ? NTK_OK : NTK_E_LAUNCH;
+}
+
+int Model::profile_token(float ms[4], int calls[4], bool coarse) {
+    std::vector<Timed> rec;
+    rec.reserve(1024);
+    prof_ = &rec;
+    prof_coarse_ = coarse;
+    pick_attention_regime();
+    int rc = enqueue_token(true);
+    if (coarse && !rec.empty()) {   // close the last run
+        void* e = ntk_event_create();
+        ntk_event_record(e, stream_);
+        rec.back().b = e;
+    }
+    prof_ = nullptr;
+    prof_coarse_ = false;
+    if (rc == NTK_OK) rc = ntk_stream_synchronize(stream_);
+    for (int c = 0; c < 4; ++c) { ms[c] = 0.0f; calls[c] = 0; }
+    for (auto& t : rec) {
+        float m = 0.0f;
+        if (t.a && t.b && ntk_event_elapsed_ms(t.a, t.b, &m) == NTK_OK) { ms[t.cls] += m; calls[t.cls] += t.n; }
+        ++calls[3];   // timed intervals
+    }
+    for (auto& t : rec) {   // coarse: record i's `b` is record i+1's `a` -- destroy every event once
+        if (t.a && !t.shared_a) ntk_event_destroy(t.a);
+        if (t.b) ntk_event_destroy(t.b);
+    }
+    return rc;
+}
+
+}  // namespace nt

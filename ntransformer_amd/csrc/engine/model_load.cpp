@@ -1,0 +1,373 @@
+// engine/model_load.cpp -- weights into HBM: GGUF and synthetic loading, the decode repack and its one-resident-copy bookkeeping, buffers (see model.h)
+#include "model_impl.h"
+
+namespace nt {
+
+int Model::upload(DevTensor& dst, const void* host, int dtype, int64_t in_f, int64_t out_f, size_t nbytes) {
+    void* d = nt_hip_malloc(padded_bytes(nbytes));
+    if (!d) { err_ = "out of device memory"; return NTK_E_NOMEM; }
+    allocs_.push_back(d);
+    if (host && nbytes) {   // a failed upload must not leave silently garbage weights behind
+        if (hipMemcpy(d, host, nbytes, hipMemcpyHostToDevice) != hipSuccess) { err_ = "weight upload (H2D copy) failed"; return NTK_E_LAUNCH; }
+    }
+    dst.ptr = d; dst.dtype = dtype; dst.in_f = in_f; dst.out_f = out_f; dst.nbytes = nbytes;
+    weight_bytes_ += nbytes;
+    return NTK_OK;
+}
+
+int Model::slice_columns(void* dst, const void* src, int dtype, int64_t out_f, int64_t in_f, int rank, int world) {
+    if (!dst || !src) return NTK_E_NULL;
+    if (world < 1 || rank < 0 || rank >= world || in_f % world != 0) return NTK_E_SHAPE;
+    const int64_t in_l = in_f / world;
+    const size_t rb_full = ntk_row_bytes(dtype, in_f), rb_loc = ntk_row_bytes(dtype, in_l);
+    if (!rb_full || !rb_loc || rb_loc * (size_t)world != rb_full) return NTK_E_SHAPE;   // the slice must be whole blocks
+    const uint8_t* s8 = static_cast<const uint8_t*>(src);
+    uint8_t* d8 = static_cast<uint8_t*>(dst);
+    for (int64_t r = 0; r < out_f; ++r) memcpy(d8 + (size_t)r * rb_loc, s8 + (size_t)r * rb_full + (size_t)rank * rb_loc, rb_loc);
+    return NTK_OK;
+}
+
+int Model::upload_shard(DevTensor& dst, const void* host_full, int dtype, int64_t in_f, int64_t out_f, size_t nbytes_full, Shard how) {
+    if (tp_world_ == 1 || how == WHOLE) return upload(dst, host_full, dtype, in_f, out_f, nbytes_full);
+    if (how == ROWS) {   // rows are contiguous: a byte range
+        const int64_t rows = out_f / tp_world_;
+        const size_t rb = ntk_row_bytes(dtype, in_f);
+        if (out_f % tp_world_ != 0 || !rb) { err_ = "tensor rows do not divide over the tensor-parallel ranks"; return NTK_E_SHAPE; }
+        return upload(dst, static_cast<const uint8_t*>(host_full) + (size_t)tp_rank_ * rows * rb, dtype, in_f, rows, (size_t)rows * rb);
+    }
+    const int64_t in_l = in_f / tp_world_;
+    const size_t rb_loc = ntk_row_bytes(dtype, in_l);
+    std::vector<uint8_t> tmp((size_t)out_f * rb_loc);
+    const int st = slice_columns(tmp.data(), host_full, dtype, out_f, in_f, tp_rank_, tp_world_);
+    if (st != NTK_OK) { err_ = "tensor columns do not divide into whole blocks over the tensor-parallel ranks"; return st; }
+    return upload(dst, tmp.data(), dtype, in_l, out_f, tmp.size());
+}
+
+// a layer's tensors "blk.<i>.<name>": member, shard rule over tensor-parallel ranks, [out][in] extents (h hidden, q / k query / KV heads x head_dim, i FFN
+// width, 1 a vector) -- the one description both loaders go by
+static const struct { const char* name; DevTensor LayerWeights::* member; Shard how; char in, out; } kLayerTensors[] = {
+    {"attn_norm.weight", &LayerWeights::attn_norm, WHOLE, 'h', '1'},
+    {"attn_q.weight", &LayerWeights::wq, ROWS, 'h', 'q'},             // whole heads per rank
+    {"attn_k.weight", &LayerWeights::wk, ROWS, 'h', 'k'},
+    {"attn_v.weight", &LayerWeights::wv, ROWS, 'h', 'k'},
+    {"attn_output.weight", &LayerWeights::wo, COLS, 'q', 'h'},        // the columns of this rank's heads
+    {"ffn_norm.weight", &LayerWeights::ffn_norm, WHOLE, 'h', '1'},
+    {"ffn_gate.weight", &LayerWeights::w_gate, ROWS, 'h', 'i'},
+    {"ffn_up.weight", &LayerWeights::w_up, ROWS, 'h', 'i'},
+    {"ffn_down.weight", &LayerWeights::w_down, COLS, 'i', 'h'},
+};
+
+int Model::load(const std::string& path, int max_context) {
+    const int st = load_impl(path, max_context);
+    if (st != NTK_OK) free_all();   // nothing stays resident after a failed load
+    return st;
+}
+
+int Model::load_impl(const std::string& path, int max_context) {
+    free_all();
+    fprintf(stderr, "Loading model: %s\n", path.c_str());
+    GgufFile f;
+    int st = f.open(path);
+    if (st != NTK_OK) { err_ = f.error(); fprintf(stderr, "%s\n", err_.c_str()); return st; }
+    cfg_ = f.config();
+    vocab_ = f.vocab();
+    if (cfg_.max_seq_len > max_context) {   // transformer.cpp:70-74
+        fprintf(stderr, "Note: Capping context from %d to %d tokens (use --ctx-size to change)\n", cfg_.max_seq_len, max_context);
+        cfg_.max_seq_len = max_context;
+    }
+    cfg_.print();
+    f.print_info();
+    st = init_device();
+    if (st != NTK_OK) { fprintf(stderr, "%s\n", err_.c_str()); return st; }
+
+    NT_TRY(tp_check_shapes());
+    auto take = [&](const std::string& name) -> int {
+        const GgufTensor* t = f.find(name);
+        TensorSlot sl;
+        if (!t || !slot_of(name, &sl)) { err_ = "Tensor not found: " + name; return NTK_E_FORMAT; }
+        const int64_t in_f = sl.in_f, out_f = sl.out_f;
+        const bool vec = out_f == 1;
+        if (t->numel() != in_f * out_f || (!vec && (t->dims.size() != 2 || t->dims[0] != in_f))) {
+            err_ = "Unexpected shape for " + name;
+            return NTK_E_SHAPE;
+        }
+        if (vec && t->dtype != NTK_DT_F32) { err_ = name + " must be F32"; return NTK_E_DTYPE; }
+        if (t->nbytes == 0 || !t->known_type) { err_ = "Unsupported tensor type for " + name; return NTK_E_DTYPE; }
+        return upload_shard(*sl.dst, f.data(*t), t->dtype, in_f, out_f, t->nbytes, sl.how);
+    };
+    layers_.resize(cfg_.n_layers);
+    NT_TRY(take("token_embd.weight"));
+    if (f.find("output.weight")) {   // transformer.cpp:92-99
+        NT_TRY(take("output.weight"));
+    } else {
+        output_ = token_embd_;
+        output_tied_ = true;
+    }
+    NT_TRY(take("output_norm.weight"));
+    for (int i = 0; i < cfg_.n_layers; ++i)   // transformer.cpp:286-328
+        for (const auto& e : kLayerTensors) NT_TRY(take("blk." + std::to_string(i) + "." + e.name));
+    return finish_load();
+}
+
+bool Model::slot_of(const std::string& name, TensorSlot* sl) {
+    const int64_t H = cfg_.hidden_size, hd = cfg_.head_dim;
+    auto extent = [&](char c) -> int64_t { return c == 'h' ? H : c == 'q' ? cfg_.n_heads * hd : c == 'k' ? cfg_.n_kv_heads * hd : c == 'i' ? cfg_.intermediate_size : 1; };
+    if (name == "token_embd.weight") { *sl = {&token_embd_, WHOLE, H, cfg_.vocab_size}; return true; }
+    if (name == "output.weight") { *sl = {&output_, WHOLE, H, cfg_.vocab_size}; return true; }
+    if (name == "output_norm.weight") { *sl = {&output_norm_, WHOLE, H, 1}; return true; }
+    int li = -1, at = 0;
+    if (sscanf(name.c_str(), "blk.%d.%n", &li, &at) != 1 || at == 0 || li < 0 || li >= (int)layers_.size()) return false;
+    for (const auto& e : kLayerTensors)
+        if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), e.how, extent(e.in), extent(e.out)}; return true; }
+    return false;
+}
+
+int Model::load_synthetic(const SynthSpec& spec, int max_context, int nthreads) {
+    free_all();
+    std::vector<SynthTensor> plan;
+    if (!synth_plan(spec, plan)) { err_ = "bad synthetic spec"; return NTK_E_SHAPE; }
+    cfg_ = ModelConfig();
+    cfg_.model_name = "synthetic-" + spec.mix;
+    cfg_.vocab_size = spec.vocab; cfg_.hidden_size = spec.hidden; cfg_.intermediate_size = spec.inter;
+    cfg_.n_layers = spec.layers; cfg_.n_heads = spec.heads; cfg_.n_kv_heads = spec.kv_heads;
+    cfg_.head_dim = spec.hidden / spec.heads;
+    cfg_.norm_eps = spec.eps; cfg_.rope_theta = spec.theta;
+    cfg_.max_seq_len = std::min(spec.ctx, max_context);
+    cfg_.bos_token_id = spec.bos; cfg_.eos_token_id = spec.eos;
+    synth_vocab(spec, vocab_.tokens, vocab_.token_types);
+    NT_TRY(init_device());
+    NT_TRY(tp_check_shapes());
+
+    size_t biggest = 0;
+    for (const auto& t : plan) biggest = std::max(biggest, t.nbytes);
+    void* stage = nt_hip_malloc_host(biggest);
+    if (!stage) { err_ = "pinned staging allocation failed"; return NTK_E_NOMEM; }
+    layers_.resize(cfg_.n_layers);
+    int rc = NTK_OK;
+    for (const auto& t : plan) {
+        synth_fill(stage, t, spec.seed, nthreads);
+        TensorSlot sl;
+        if (!slot_of(t.name, &sl)) { rc = NTK_E_FORMAT; break; }
+        rc = upload_shard(*sl.dst, stage, ggml_type_to_dtype((uint32_t)t.ggml_type), t.in_f, t.out_f, t.nbytes, sl.how);
+        if (rc != NTK_OK) break;
+    }
+    nt_hip_free_host(stage);
+    if (rc == NTK_OK) rc = finish_load();
+    if (rc != NTK_OK) free_all();
+    return rc;
+}
+
+int Model::finish_load() {
+    cfg_full_ = cfg_;
+    if (tp_world_ > 1) {   // from here on this object IS a model with 1/W of the heads and of the FFN width (hidden size unchanged)
+        cfg_.n_heads /= tp_world_;
+        cfg_.n_kv_heads /= tp_world_;
+        cfg_.intermediate_size /= tp_world_;
+        NT_TRY(own_stream());   // ranks that share a process (tests) must not queue behind each other's waiting kernels
+    } else {
+        stream_ = ntk_stream(0);
+    }
+    if (!stream_) { err_ = "no compute stream"; return NTK_E_NODEVICE; }
+    NT_TRY(alloc_buffers());
+    repack_ = repack_wanted_;   // every load decides anew (a level-3 request that ended as 1 or 2 on the previous model must not stick)
+    if (repack_) {
+        // ADVICE (round 4): a repack that does not fit must not fail the load -- the raw path decodes every tensor that has no repacked form
+        const int st = repack_all();
+        if (st == NTK_E_NOMEM) {
+            int kept = 0;
+            for (auto& L : layers_) for (auto m : kLayerMatrices) kept += (L.*m).rp ? 0 : 1;
+            fprintf(stderr, "warning: not enough device memory for the decode repack of every matrix: %d projection tensors stay on the raw-GGUF path\n", kept);
+            err_.clear();
+        } else if (st != NTK_OK) {
+            return st;
+        }
+        if (repack_ == 3) repack_ = 2;   // round 6: the prompt GEMM reads the repack itself, so the second copy buys the batched paths nothing
+        if (repack_ == 2) NT_TRY(drop_raw_all());
+    }
+    if (persistent_wanted_) set_persistent(persistent_wanted_);
+    size_t fr = 0, tot = 0;
+    ntk_device_mem_info(&fr, &tot);
+    fprintf(stderr, "Model loaded successfully! (resident on MI355X: %.2f GB of weights%s)\nFree VRAM: %.1f GB\n",
+            (weight_bytes_ - raw_freed_bytes_) / 1073741824.0, repack_bytes_ ? (" + " + std::to_string(repack_bytes_ / 1073741824.0).substr(0, 5) + " GB repacked for decode").c_str() : "",
+            fr / 1073741824.0);
+    return NTK_OK;
+}
+
+// ---- engine-owned repack of the K-quant projections (csrc/gemv_rp.hip): made once, on the device, from the uploaded GGUF bytes, which
+//      stay resident for the 1:1 launchers and the prompt GEMM ----
+int Model::repack_one(DevTensor& t) {
+    if (t.rp || !t.ptr) return NTK_OK;
+    if (t.out_f <= 0 || t.out_f > 0x7FFFFFFF || t.in_f <= 0 || t.in_f > 32768) return NTK_OK;
+    const size_t n = ntk_rp_bytes(t.dtype, (int)t.out_f, (int)t.in_f);
+    if (n == 0 || n > 0xFFFFFFF0ull) return NTK_OK;   // formats / shapes the matrix-core GEMV does not take keep the raw path
+    void* d = nt_hip_malloc(n + 256);
+    if (!d) return NTK_E_NOMEM;   // (the caller keeps the tensors that did fit and lets the raw path take the rest)
+    allocs_.push_back(d);
+    const int st = ntk_rp_pack(d, t.ptr, (int)t.out_f, (int)t.in_f, t.dtype, stream_);
+    if (st != NTK_OK) { err_ = std::string("decode repack failed: ") + ntk_status_string(st); return st; }
+    t.rp = d;
+    t.rp_bytes = n;
+    repack_bytes_ += n;
+    return NTK_OK;
+}
+
+int Model::repack_all() {
+    int rc = NTK_OK;
+    auto one = [&](DevTensor& t) { const int st = repack_one(t); if (st != NTK_OK && rc == NTK_OK) rc = st; return st; };
+    for (auto& L : layers_) {
+        if (one(L.*kLayerMatrices[0]) == NTK_E_NOMEM) break;
+        for (size_t k = 1; k < kLayerMatrices.size(); ++k) one(L.*kLayerMatrices[k]);
+        if (rc == NTK_E_NOMEM) break;
+    }
+    if (rc != NTK_E_NOMEM) one(output_);
+    repack_done_ = true;
+    const int sy = ntk_stream_synchronize(stream_);
+    return rc != NTK_OK ? rc : sy;
+}
+
+// ---- one resident copy (level 2): the uploaded GGUF bytes of every repacked matrix go; raw_of() unpacks on demand ----
+int Model::drop_raw_all() {
+    size_t need = 0;
+    auto grp = [&](std::initializer_list<DevTensor*> ts) {
+        size_t g = 0;
+        for (DevTensor* t : ts) if (t->rp && !(output_tied_ && t->ptr == token_embd_.ptr)) g += padded_bytes(t->nbytes);
+        need = std::max(need, g);
+    };
+    for (auto& L : layers_) { grp({&L.wq, &L.wk, &L.wv}); grp({&L.wo}); grp({&L.w_gate, &L.w_up}); grp({&L.w_down}); }
+    grp({&output_});
+    if (need == 0) return NTK_OK;
+    if (!raw_scratch_ || raw_scratch_bytes_ < need) {
+        void* d = nt_hip_malloc(need);
+        if (!d) { fprintf(stderr, "warning: no device memory for the unpack scratch: the GGUF bytes stay resident beside the repack\n"); repack_ = 1; return NTK_OK; }
+        allocs_.push_back(d);
+        raw_scratch_ = d; raw_scratch_bytes_ = need;
+    }
+    auto drop = [&](DevTensor& t) {
+        if (!t.rp || !t.ptr || (output_tied_ && t.ptr == token_embd_.ptr)) return;
+        auto it = std::find(allocs_.begin(), allocs_.end(), t.ptr);
+        if (it != allocs_.end()) allocs_.erase(it);
+        nt_hip_free(t.ptr);
+        t.ptr = nullptr;
+        raw_freed_bytes_ += t.nbytes;
+    };
+    NT_TRY(ntk_stream_synchronize(stream_));
+    for_each_projection(drop);
+    return NTK_OK;
+}
+
+int Model::restore_raw_all() {
+    int rc = NTK_OK;
+    auto back = [&](DevTensor& t) {
+        if (t.ptr || !t.rp || rc != NTK_OK) return;
+        void* d = nt_hip_malloc(padded_bytes(t.nbytes));
+        if (!d) { rc = NTK_E_NOMEM; return; }
+        const int st = ntk_rp_unpack(d, t.rp, (int)t.out_f, (int)t.in_f, t.dtype, stream_);
+        if (st != NTK_OK) { nt_hip_free(d); rc = st; return; }
+        allocs_.push_back(d);
+        t.ptr = d;
+        raw_freed_bytes_ -= t.nbytes;
+    };
+    for_each_projection(back);
+    const int sy = ntk_stream_synchronize(stream_);
+    return rc != NTK_OK ? rc : sy;
+}
+
+const void* Model::raw_of(const DevTensor& t) {
+    if (t.ptr) return t.ptr;
+    if (!t.rp || !raw_scratch_) { raw_err_ = NTK_E_NULL; return nullptr; }
+    const size_t n = padded_bytes(t.nbytes);
+    if (raw_cursor_ + n > raw_scratch_bytes_) {   // a group never exceeds the scratch (sized for the largest in drop_raw_all): wrapping would overwrite a tensor the same launch still reads
+        if (!raw_err_) raw_err_ = NTK_E_NOMEM;
+        return nullptr;
+    }
+    void* d = static_cast<uint8_t*>(raw_scratch_) + raw_cursor_;
+    raw_cursor_ += n;
+    const int st = ntk_rp_unpack(d, t.rp, (int)t.out_f, (int)t.in_f, t.dtype, stream_);
+    if (st != NTK_OK) { raw_err_ = st; return nullptr; }
+    return d;
+}
+
+int Model::alloc_buffers() {   // transformer.cpp:330-391
+    const size_t S = (size_t)cfg_.max_seq_len, H = (size_t)cfg_.hidden_size, L = (size_t)cfg_.n_layers;
+    const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim;
+    auto dev = [&](size_t bytes, bool zero) -> void* {
+        void* p = nt_hip_malloc(bytes + 256);
+        if (p) { allocs_.push_back(p); if (zero) nt_hip_memset(p, 0, bytes); }
+        return p;
+    };
+    // the attention kernels address a layer's cache rows with 32-bit byte offsets (attention.hip): a context whose per-layer cache reaches
+    // 3.75 GiB is refused here, at load, rather than as NTK_E_SHAPE from the first decode step (8 KV heads of 128: 1.9 M positions)
+    if (S * per * sizeof(uint16_t) >= 0xF0000000ull) { err_ = "context too long: one layer's K cache must stay below 3.75 GiB (32-bit row offsets)"; return NTK_E_SHAPE; }
+    const size_t kvb = L * S * per * sizeof(uint16_t);
+    if (kv_q8_) {   // the 8-bit cache (csrc/attention_q8.hip) + ONE layer's F16 image for the prompt path
+        if (cfg_.head_dim != 128 || cfg_.n_kv_heads <= 0 || cfg_.n_heads % cfg_.n_kv_heads != 0 || cfg_.n_heads / cfg_.n_kv_heads > 16) {
+            err_ = "kv_cache=q8_0 needs head_dim 128 and at most 16 query heads per KV head (this model: head_dim " + std::to_string(cfg_.head_dim) +
+                   ", " + std::to_string(cfg_.n_kv_heads > 0 ? cfg_.n_heads / cfg_.n_kv_heads : 0) + " query heads per KV head)";
+            return NTK_E_SHAPE;
+        }
+        if (tp_world_ > 1) { err_ = "kv_cache=q8_0 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
+        if (fuse_attention_) { err_ = "kv_cache=q8_0 is not supported with the attention-inside-Wo launch (fuse_attention)"; return NTK_E_SHAPE; }
+        kv_q8_layer_bytes_ = ntk_kv_q8_cache_bytes((int)S, cfg_.n_kv_heads, cfg_.head_dim);
+        k_cache_q8_ = (uint8_t*)dev(L * kv_q8_layer_bytes_, true);
+        v_cache_q8_ = (uint8_t*)dev(L * kv_q8_layer_bytes_, true);
+        kv_f16_k_ = (uint16_t*)dev(S * per * sizeof(uint16_t), true);
+        kv_f16_v_ = (uint16_t*)dev(S * per * sizeof(uint16_t), true);
+        if (!k_cache_q8_ || !v_cache_q8_ || !kv_f16_k_ || !kv_f16_v_) { err_ = "buffer allocation failed (8-bit KV cache)"; return NTK_E_NOMEM; }
+        kv_cache_bytes_ = 2ull * L * kv_q8_layer_bytes_ + 2ull * S * per * sizeof(uint16_t);
+    } else {
+        k_cache_ = (uint16_t*)dev(kvb, true);
+        v_cache_ = (uint16_t*)dev(kvb, true);
+        kv_cache_bytes_ = 2ull * kvb;
+    }
+    hidden_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
+    residual_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
+    logits_ = (float*)dev((size_t)cfg_.vocab_size * 4, false);
+    const size_t attn_ws = S * (size_t)(2 * cfg_.n_heads + 2 * cfg_.n_kv_heads) * cfg_.head_dim;
+    const size_t ffn_ws = 2 * S * (size_t)cfg_.intermediate_size;
+    workspace_floats_ = std::max(attn_ws, ffn_ws);
+    workspace_ = (float*)dev(workspace_floats_ * 4, false);
+    positions_ = (int*)dev(S * 4, false);
+    tokens_dev_ = (int*)dev(S * 4, false);
+    d_pos_ = (int*)dev(64, true);
+    d_token_ = (int*)dev(64, true);
+    argmax_scratch_ = (float*)dev(2 * 1024 * 4, false);
+    rope_inv_freq_ = (float*)dev((size_t)cfg_.head_dim / 2 * 4 + 64, false);
+    row_max_ = (float*)dev((size_t)S * 2 * 4, true);
+    attn_scratch_ = (float*)dev(ntk_attention_split_scratch_bytes(cfg_.n_heads, cfg_.head_dim, kMaxAttnSplits), true);   // (zeroed: the arrival counters in front)
+    h_token_ = (int*)nt_hip_malloc_host(64);
+    h_ring_ = (unsigned long long*)nt_hip_malloc_host(64);
+    if (h_ring_) memset(h_ring_, 0, 64);
+    sample_scratch_ = dev(ntk_sample_scratch_bytes(cfg_.vocab_size), false);
+    attn_sync_ = (unsigned*)dev(4096, true);
+    {   // one workspace for every projection: the largest need over the launches the prompt pass makes (Q|K|V and gate|up go out as one)
+        const int H = cfg_.hidden_size, I = cfg_.intermediate_size, qkv = (cfg_.n_heads + 2 * cfg_.n_kv_heads) * cfg_.head_dim;
+        const int shapes[][2] = {{H, qkv}, {H, cfg_.n_heads * cfg_.head_dim}, {H, cfg_.n_kv_heads * cfg_.head_dim}, {cfg_.n_heads * cfg_.head_dim, H},
+                                 {H, 2 * I}, {H, I}, {I, H}};
+        gemm_ws_bytes_ = 0;
+        for (const auto& sh : shapes) gemm_ws_bytes_ = std::max(gemm_ws_bytes_, ntk_gemm_quant_workspace_bytes(sh[0], sh[1]));
+    }
+    gemm_ws_ = dev(gemm_ws_bytes_, false);
+    gemm_ws2_ = dev(gemm_ws_bytes_, false);
+    if (tp_world_ > 1) {   // communication buffer: flags + two slots of one prompt's worth of hidden vectors
+        tp_max_floats_ = S * H;
+        tp_comm_ = ntk_tp_comm_alloc(ntk_tp_comm_bytes(tp_max_floats_));   // fine-grained: csrc/tp.hip
+        if (tp_comm_) allocs_.push_back(tp_comm_);
+        if (!tp_comm_ || ntk_tp_comm_reset(tp_comm_, nullptr) != NTK_OK || ntk_device_synchronize() != NTK_OK) { err_ = "communication buffer allocation failed"; return NTK_E_NOMEM; }
+    }
+    d_recent_ = (int*)dev(kRecentCap * 4, false);
+    h_recent_ = (int*)nt_hip_malloc_host(kRecentCap * 4);
+    if ((!kv_q8_ && (!k_cache_ || !v_cache_)) || !hidden_ || !residual_ || !logits_ || !workspace_ || !positions_ || !tokens_dev_ ||
+        !d_pos_ || !d_token_ || !argmax_scratch_ || !h_token_ || !h_ring_) {
+        err_ = "buffer allocation failed";
+        return NTK_E_NOMEM;
+    }
+    *h_token_ = 0;
+    if (rope_inv_freq_) {
+        std::vector<float> f((size_t)cfg_.head_dim / 2);
+        for (int i = 0; i < cfg_.head_dim / 2; ++i) f[i] = 1.0f / powf(cfg_.rope_theta, (2.0f * i) / cfg_.head_dim);
+        nt_hip_memcpy_h2d(rope_inv_freq_, f.data(), f.size() * 4);
+    }
+    return NTK_OK;
+}
+
+}  // namespace nt

@@ -1,0 +1,296 @@
+// engine/model_prompt.cpp -- the prompt pass (see model.h)
+#include "model_impl.h"
+
+namespace nt {
+
+// ---------------------------------------------------------------------------------------------------
+// 1:1 path: the reference's own launcher sequence (transformer.cpp:604-669, attention.cpp:120-211,
+// ffn.cpp:85-134), through the same C ABI an external caller would use
+// ---------------------------------------------------------------------------------------------------
+float* Model::forward(const int* tokens, int T, int start_pos) {
+    if (T <= 0 || start_pos < 0 || start_pos + T > cfg_.max_seq_len) { err_ = "forward: sequence exceeds context"; return nullptr; }
+    for (int i = 0; i < T; ++i)   // the embedding gather indexes the table with these on the device
+        if (tokens[i] < 0 || tokens[i] >= cfg_.vocab_size) { err_ = "forward: token id out of range"; return nullptr; }
+    const int H = cfg_.hidden_size;
+    void* s = stream_;
+    tp_call_ = 0;
+    // embedding rows are dequantised on the device (the reference does it on the host and uploads, :419-599)
+    if (ntk_memcpy_h2d_async(tokens_dev_, tokens, (size_t)T * 4, s) != NTK_OK) return nullptr;
+    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, tokens_dev_, T, H, token_embd_.dtype, s);
+    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
+    else if (est != NTK_OK) return nullptr;
+    std::vector<int> pos(T);
+    for (int i = 0; i < T; ++i) pos[i] = start_pos + i;
+    if (ntk_memcpy_h2d_async(positions_, pos.data(), (size_t)T * 4, s) != NTK_OK) return nullptr;
+    if (ntk_stream_synchronize(s) != NTK_OK) return nullptr;   // `pos` / `tokens` are host temporaries
+
+    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers);
+    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
+    float* last = hidden_ + (size_t)(T - 1) * H;
+    ok(ntk_rmsnorm(last, last, (const float*)output_norm_.ptr, 1, H, cfg_.norm_eps, s));   // in place, :658-659
+    {
+        raw_begin();
+        const int st = ntk_gemv(logits_, raw_of(output_), last, (int)output_.out_f, (int)output_.in_f, output_.dtype, s);
+        if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(output_.dtype));   // gemm.cu:801-803
+        else ok(st);
+    }
+    if (tp_world_ > 1) ok(ntk_tp_advance_epoch(tp_comm_, s));
+    ok(ntk_stream_synchronize(s));
+    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
+    if (rc == NTK_OK) rc = check_tp();
+    if (rc != NTK_OK) { if (err_.empty() || rc != NTK_E_LAUNCH) err_ = std::string("forward failed: ") + ntk_status_string(rc); return nullptr; }
+    return logits_;
+}
+
+// The prompt pass's operand planes: the FP16 GEMM reads X split into FP16 planes, written into a workspace by its own pre-pass or by the launch that
+// produced X (ntk_*_prepare_x: the projection then needs no pre-pass launch at all).  Two workspaces are used alternately.  The invariant: a producer
+// never writes planes into the workspace whose partial sums it is reading -- a projection's deferred K splits lie in the workspace of its own planes, so
+// the producer that consumes them takes other().
+struct OperandPlanes {
+    void* ws[2];
+    int cur = 0;
+    const float* of = nullptr;   // the X whose planes lie in ws[cur] (Q, K, V and gate, up share one X)
+    void* current() const { return ws[cur]; }
+    bool hold(const float* X) const { return X == of; }
+    void* other() { cur ^= 1; of = nullptr; return ws[cur]; }                // a producer is about to write planes: the workspace the last projection did NOT use
+    void written(const float* X, bool split) { of = split ? X : nullptr; }   // X has new contents: planes are stale unless its producer just split it
+    void in_current(const float* X) { of = X; }                              // a projection's pre-pass (or such a producer) has left X's planes in ws[cur]
+};
+
+// layers [first, last) of the 1:1 path on hidden_[T][H] at positions start_pos.. (positions_ already on the device)
+int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
+    const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
+    const int qd = nh * hd, kvd = nkv * hd;
+    void* s = stream_;
+    const size_t kv_layer = (size_t)cfg_.max_seq_len * kvd;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const Views act = views(T);
+    int rc = NTK_OK;
+    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
+    // (wp: the tensor's raw GGUF blocks -- resident, or unpacked from the repack by raw_of() once per projection, not per token)
+    auto gemv = [&](float* y, const DevTensor& w, const void* wp, const float* x) {
+        const int st = ntk_gemv(y, wp, x, (int)w.out_f, (int)w.in_f, w.dtype, s);
+        if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
+        else ok(st);
+    };
+    // Y[t] = W . X[t] for the T tokens: one pass over W per 16 tokens on the matrix cores, or the reference's loop
+    const bool batched = batched_prefill_ && T > 1;
+    // the FP16 GEMM takes every prompt of 2 tokens or more (its weight-streaming form up to 32); it also reads a matrix that exists only as its decode
+    // repack, where the F32-MFMA form (ntk_gemm_quant) would need the GGUF bytes unpacked first
+    const bool bf16_now = bf16_prefill_ && gemm_ws_ && T > 1;
+    OperandPlanes planes{{gemm_ws_, gemm_ws2_}};
+    // RMSNorm / SiLU x up in front of an FP16-GEMM projection also leave the tokens' largest |x|: the GEMM's operand pre-pass then needs no pass of its
+    // own over X for the token scales (row_max_: [2][max_seq]; the second array is zeroed by the layer's first RMSNorm launch for the SiLU launch's
+    // atomic maxima)
+    const bool with_max = batched && bf16_now && row_max_ != nullptr && prefill_row_max_;
+    float* rm_a = with_max ? row_max_ : nullptr;
+    float* rm_b = with_max ? row_max_ + cfg_.max_seq_len : nullptr;
+    auto f16_ok = [&](const DevTensor& w) {   // the formats and shapes ntk_gemm_quant_f16 takes
+        const bool kq = w.dtype == NTK_DT_Q4_0 || w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K;
+        return (w.dtype == NTK_DT_Q8_0 || kq) && w.in_f % (kq ? 256 : 128) == 0 && w.out_f % 16 == 0 && (w.ptr || w.rp);
+    };
+    // The form the producer of X takes when X (`width` columns) feeds matrix next_w: it splits X into next_w's planes itself, leaves the tokens' maxima, or
+    // neither.  The split: up to 64 tokens (a producer that owns a whole token per workgroup writes its planes in 16-byte pieces a kilobyte apart:
+    // faster than the GEMM's own pre-pass at 16 - 64 tokens, slower at 1024), and not under tensor parallelism, where a rank's SiLU launch keeps its maxima
+    // in the array that only ntk_rmsnorm_rowmax zeroes.
+    enum class XForm { plain, row_max, split };
+    auto x_form = [&](int width, const DevTensor& next_w) {
+        if (with_max && prefill_fused_split_ && gemm_ws2_ != nullptr && T <= 64 && tp_world_ == 1 && f16_ok(next_w) && (int)next_w.in_f == width) return XForm::split;
+        return with_max ? XForm::row_max : XForm::plain;
+    };
+    // a K-quant matrix whose GGUF bytes were freed after the load-time repack (one resident copy): the FP16 GEMM reads it FROM THE REPACK
+    // (ntk_gemm_desc.weights_repacked: identical bits) -- no unpack in front of the prompt launches
+    auto rp_only = [&](const DevTensor& w) {
+        return !w.ptr && w.rp && (w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K) && w.out_f % 16 == 0;
+    };
+    // The FP16 GEMM behind its descriptor (ntk_engine.h): 1..3 matrices of one format sharing X, ONE launch.  `raw`: the matrices' GGUF bytes where the
+    // caller has them already; without it a group whose every matrix is rp_only is read from the repack, any other group through raw_of() (one raw_begin()
+    // per group: its tensors lie side by side in the unpack scratch).  X's planes are reused when they lie in the current workspace, and lie there after
+    // the launch.  rm: the tokens' largest |X| where X's producer left them.
+    auto gemm_group = [&](float* const* Ys, const DevTensor* const* Ws, int n, const float* X, const float* resid, const float* rm, ntk_gemm_partials* pt,
+                          const void* const* raw) {
+        bool repacked = raw == nullptr;
+        for (int k = 0; k < n; ++k) repacked = repacked && rp_only(*Ws[k]);
+        if (!repacked && !raw) raw_begin();
+        ntk_gemv_seg segs[3];
+        for (int k = 0; k < n; ++k) segs[k] = {repacked ? Ws[k]->rp : raw ? raw[k] : raw_of(*Ws[k]), Ys[k], (int)Ws[k]->out_f, Ws[k]->dtype};
+        ntk_gemm_desc d{};
+        d.segs = segs; d.nseg = n; d.X = X; d.n_tokens = T; d.in_features = (int)Ws[0]->in_f; d.resid = resid;
+        d.workspace = planes.current(); d.workspace_bytes = gemm_ws_bytes_; d.reuse_x = planes.hold(X) ? 1 : 0; d.row_max = rm; d.partials = pt;
+        d.weights_repacked = repacked ? 1 : 0;
+        const int st = ntk_gemm_quant_f16(&d, s);
+        if (st == NTK_OK) planes.in_current(X);
+        return st;
+    };
+    // One quantised matrix on the FP16 matrix cores (up to 1024 tokens per pass): straight from the repack where it exists only there; otherwise, or when that form
+    // is not taken, from its GGUF bytes -- *wp, obtained here for the caller's F32-MFMA / per-token fallbacks too (without the FP16 option: NTK_E_DTYPE, no launch).
+    auto gemm_f16 = [&](float* Y, const DevTensor& w, const float* X, const float* resid, const float* rm, ntk_gemm_partials* pt, const void** wp) {
+        const DevTensor* const one = &w;
+        if (bf16_now && rp_only(w)) {
+            const int st = gemm_group(&Y, &one, 1, X, resid, rm, pt, nullptr);
+            if (!not_taken(st)) return st;
+        }
+        raw_begin();
+        *wp = raw_of(w);
+        return bf16_now ? gemm_group(&Y, &one, 1, X, resid, rm, pt, wp) : (int)NTK_E_DTYPE;
+    };
+    auto project = [&](float* Y, const DevTensor& w, const float* X, size_t ystride, size_t xstride, const float* rm) {
+        const bool dense = ystride == (size_t)w.out_f && xstride == (size_t)w.in_f;
+        const void* wp = nullptr;
+        if (batched && is_quant(w.dtype) && dense) {
+            int st = gemm_f16(Y, w, X, nullptr, rm, nullptr, &wp);
+            if (not_taken(st)) st = ntk_gemm_quant(Y, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, nullptr, s);
+            if (st != NTK_E_ALIGN && st != NTK_E_SHAPE) { ok(st); return; }   // those two: shapes only the per-token loop takes
+        } else { raw_begin(); wp = raw_of(w); }
+        for (int t = 0; t < T; ++t) gemv(Y + (size_t)t * ystride, w, wp, X + (size_t)t * xstride);
+    };
+    // matrices that share X (Q | K | V, gate | up): those of one format go out as ONE launch of the FP16 GEMM, the rest one by one
+    auto project_many = [&](float* const* Ys, const DevTensor* const* Ws, int n, const float* X, const float* rm) {
+        bool done[3] = {false, false, false};
+        for (int a = 0; a < n && batched && bf16_now; ++a) {
+            if (done[a]) continue;
+            float* ys[3];
+            const DevTensor* ws[3];
+            int idx[3], m = 0;
+            for (int b = a; b < n; ++b)
+                if (!done[b] && Ws[b]->dtype == Ws[a]->dtype && Ws[b]->in_f == Ws[a]->in_f) { ys[m] = Ys[b]; ws[m] = Ws[b]; idx[m++] = b; }
+            if (m < 2) continue;
+            const int st = gemm_group(ys, ws, m, X, nullptr, rm, nullptr, nullptr);
+            if (st == NTK_OK) for (int k = 0; k < m; ++k) done[idx[k]] = true;
+            else if (!not_taken(st)) { ok(st); return; }
+        }
+        for (int a = 0; a < n; ++a)
+            if (!done[a]) project(Ys[a], *Ws[a], X, (size_t)Ws[a]->out_f, (size_t)Ws[a]->in_f, rm);
+    };
+    // X as it lies (the attention output) in front of matrix w: row maximum + split in one launch of its own
+    auto prepare_x = [&](const float* X, const DevTensor& w) {
+        if (x_form((int)w.in_f, w) != XForm::split || planes.hold(X)) return;
+        planes.written(X, ntk_gemm_prepare_x(X, T, (int)w.in_f, planes.other(), s) == NTK_OK);
+    };
+    // hidden += W . X (attention.cpp:207 + transformer.cpp:645, ffn.cpp:130 + transformer.cpp:652): the batched
+    // projection adds the residual in its epilogue, the reference sequence goes through residual_ and launch_add_inplace
+    auto project_add = [&](const DevTensor& w, const float* X, size_t xstride, const float* rm) {
+        if (tp_world_ > 1) {   // this rank's columns give a PARTIAL sum: into the exchange slot, then hidden += sum over ranks
+            project(tp_slot(), w, X, H, xstride, rm);
+            ok(tp_allreduce(hidden_, T * H));
+            return;
+        }
+        const bool dense = batched && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f;
+        if (dense && bf16_now) prepare_x(X, w);
+        if (dense && is_quant(w.dtype)) {
+            const void* wp = nullptr;
+            int st = gemm_f16(hidden_, w, X, hidden_, rm, nullptr, &wp);
+            if (not_taken(st)) st = ntk_gemm_quant(hidden_, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, hidden_, s);
+            if (st != NTK_E_ALIGN && st != NTK_E_SHAPE) { ok(st); return; }
+        }
+        project(residual_, w, X, H, xstride, rm);
+        ok(ntk_add_inplace(hidden_, residual_, T * H, s));
+    };
+    // residual_ = RMSNorm(hidden_) in the form its consumer next_w asks for
+    auto norm = [&](const DevTensor& nw, bool zero_b, const DevTensor& next_w) {
+        const XForm f = x_form(H, next_w);
+        if (f == XForm::split) ok(ntk_rmsnorm_prepare_x(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, planes.other(), s));
+        else if (f == XForm::row_max) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, rm_a, zero_b ? rm_b : nullptr, s));
+        else ok(ntk_rmsnorm(residual_, hidden_, (const float*)nw.ptr, T, H, cfg_.norm_eps, s));
+        planes.written(residual_, f == XForm::split);
+    };
+    // hidden += W . X followed by the NEXT RMSNorm (nw; into residual_) as one consumer launch of the projection's K splits (ntk_gemm_quant_f16 with
+    // `partials` + ntk_reduce_rmsnorm_*); false = not this shape / format: the caller runs project_add + norm
+    auto project_add_norm = [&](const DevTensor& w, const float* X, const float* rm, const DevTensor& nw, bool zero_b, const DevTensor& next_w) -> bool {
+        if (!with_max || tp_world_ > 1 || !is_quant(w.dtype) || (size_t)w.out_f != (size_t)H) return false;
+        ntk_gemm_partials pt;
+        prepare_x(X, w);
+        // (a launch that does not split K adds the residual in its own epilogue, in place, as project_add does: nothing is deferred then)
+        const void* wp = nullptr;
+        int st = gemm_f16(hidden_, w, X, hidden_, rm, &pt, &wp);
+        if (not_taken(st)) return false;
+        const bool split = st == NTK_OK && x_form(H, next_w) == XForm::split;   // (the partial sums lie in the current workspace: the planes go to the other one)
+        if (split) st = ntk_reduce_rmsnorm_prepare_x(hidden_, &pt, (const float*)nw.ptr, cfg_.norm_eps, residual_, planes.other(), s);
+        else if (st == NTK_OK) st = ntk_reduce_rmsnorm_rowmax(hidden_, &pt, (const float*)nw.ptr, cfg_.norm_eps, residual_, rm_a, zero_b ? rm_b : nullptr, s);
+        planes.written(residual_, split);
+        ok(st);
+        return true;
+    };
+    // gate | up and SiLU x up (per token in the reference, ffn.cpp:127: the same elementwise op) with the gate | up launch's K splits summed by the SiLU
+    // launch itself (ntk_gemm_quant_f16 with `partials` + ntk_reduce_silu_mul_*); false = not this shape / format: the caller takes the separate launches
+    auto gate_up_silu = [&](const LayerWeights& L) -> bool {
+        if (!with_max || !rm_b || tp_world_ > 1 || L.w_gate.dtype != L.w_up.dtype || !is_quant(L.w_gate.dtype) || L.w_gate.in_f != L.w_up.in_f ||
+            (size_t)L.w_gate.out_f != (size_t)I || (size_t)L.w_up.out_f != (size_t)I || I % 4 != 0) return false;
+        float* const ys[2] = {act.gate, act.up};
+        const DevTensor* const ws[2] = {&L.w_gate, &L.w_up};
+        ntk_gemm_partials pt;
+        int st = gemm_group(ys, ws, 2, residual_, nullptr, rm_a, &pt, nullptr);
+        if (not_taken(st)) return false;
+        const bool split = st == NTK_OK && x_form(I, L.w_down) == XForm::split;
+        if (split) st = ntk_reduce_silu_mul_prepare_x(act.gate, &pt, planes.other(), s);
+        else if (st == NTK_OK) st = ntk_reduce_silu_mul_rowmax(act.gate, &pt, rm_b, s);
+        planes.written(act.gate, split);
+        ok(st);
+        return true;
+    };
+    // gate = SiLU(gate) x up in the form the down projection asks for
+    auto silu_mul = [&](const DevTensor& next_w) {
+        const XForm f = x_form(I, next_w);
+        int st = NTK_E_SHAPE;
+        if (f == XForm::split) st = ntk_silu_mul_prepare_x(act.gate, act.gate, act.up, T, I, planes.other(), s);
+        else if (f == XForm::row_max && rm_b) st = ntk_silu_mul_rowmax(act.gate, act.gate, act.up, T, I, rm_b, s);
+        planes.written(act.gate, f == XForm::split && st == NTK_OK);
+        if (st == NTK_E_SHAPE || st == NTK_E_ALIGN) { st = ntk_silu_mul(act.gate, act.gate, act.up, T * I, s); rm_b = nullptr; }   // (then for the rest of the pass)
+        ok(st);
+    };
+    bool normed_ahead = false;   // residual_ (with its maxima or planes) already holds this layer's normalised input, written with the previous layer's down projection
+    for (int i = first; i < last_layer; ++i) {
+        const LayerWeights& L = layers_[i];
+        uint16_t* kc = kv_q8_ ? nullptr : k_cache_ + (size_t)i * kv_layer;   // (q8_0: the one-layer F16 image, set below)
+        uint16_t* vc = kv_q8_ ? nullptr : v_cache_ + (size_t)i * kv_layer;
+        if (!normed_ahead) norm(L.attn_norm, true, L.wq);
+        normed_ahead = false;
+        float* const qkv_out[3] = {act.q, act.k, act.v};
+        const DevTensor* const qkv[3] = {&L.wq, &L.wk, &L.wv};
+        project_many(qkv_out, qkv, 3, residual_, rm_a);
+        if (i == kv_capture_layer_ && kv_capture_) {   // parity instrumentation: the F32 projections the store launches are about to read
+            ok(ntk_copy(kv_capture_, act.k, T * kvd, s));
+            ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));
+            kv_capture_T_ = T;
+        }
+        if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
+            uint8_t* kc8 = k_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
+            uint8_t* vc8 = v_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
+            if (T >= 4) {
+                ok(ntk_rope_kv_store_q8(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
+                                        kc8, vc8, start_pos, cfg_.max_seq_len, s));
+            } else {
+                ok(ntk_rope(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, s));
+                ok(ntk_kv_store_q8(kc8, vc8, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
+            }
+            ok(ntk_kv_dequant_q8_f16(kv_f16_k_, kv_f16_v_, kc8, vc8, start_pos + T, nkv, hd, cfg_.max_seq_len, s));
+            kc = kv_f16_k_; vc = kv_f16_v_;
+        } else if (with_max && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
+            ok(ntk_rope_kv_store(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, kc, vc,
+                                 start_pos, cfg_.max_seq_len, s));
+        } else {
+            ok(ntk_rope(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, s));
+            ok(ntk_copy_to_kv_cache(kc, vc, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
+        }
+        if (T == 1) ok(ntk_attention_decode(act.attn_out, act.q, kc, vc, start_pos + T, nh, nkv, hd, cfg_.max_seq_len, scale, s));
+        else ok(ntk_attention_prefill(act.attn_out, act.q, kc, vc, T, start_pos, nh, nkv, hd, cfg_.max_seq_len, scale, s));
+        if (!project_add_norm(L.wo, act.attn_out, nullptr, L.ffn_norm, false, L.w_gate)) {
+            project_add(L.wo, act.attn_out, qd, nullptr);
+            norm(L.ffn_norm, false, L.w_gate);
+        }
+        if (!gate_up_silu(L)) {
+            float* const ys[2] = {act.gate, act.up};
+            const DevTensor* const ws[2] = {&L.w_gate, &L.w_up};
+            project_many(ys, ws, 2, residual_, rm_a);
+            silu_mul(L.w_down);
+        }
+        // down projection + residual, and the NEXT layer's first RMSNorm in the same consumer launch when there is a next layer in this pass
+        if (i + 1 < last_layer && project_add_norm(L.w_down, act.gate, rm_b, layers_[i + 1].attn_norm, true, layers_[i + 1].wq)) normed_ahead = true;
+        else project_add(L.w_down, act.gate, I, rm_b);
+        if (rc != NTK_OK) break;
+    }
+    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }   // what raw_of() could not report through its pointer (it precedes the consumer's NTK_E_NULL)
+    return rc;
+}
+
+}  // namespace nt

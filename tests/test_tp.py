@@ -1,4 +1,4 @@
-"""Tensor-parallel slices (csrc/tp.hip, engine/model.cpp): host-side checks that need no GPU.
+"""Tensor-parallel slices (csrc/tp.hip, engine/model_tp.cpp, engine/model_load.cpp): host-side checks that need no GPU.
 The column slice of a GGUF matrix is a re-packing of whole quantisation blocks; with it W . x = sum over ranks of
 W_r . x_r, which is what the exchange step adds up on the device."""
 import ctypes as C
