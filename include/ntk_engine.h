@@ -42,6 +42,15 @@ typedef struct ntk_gemv_seg {
 int ntk_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in_features, const float* norm_w,
                    float eps, const float* resid, int silu_pair, void* stream);
 
+/* Engine-owned load-time repack of a Q8_0 matrix, LANE-MAJOR (csrc/gemv.hip, layout: csrc/gemv_core.hip.h): a byte permutation of every row slice, the GGUF
+ * size, read by the row-per-wave decode GEMV with identical bits to ntk_gemv_fused over the GGUF blocks.  Taken when in_features % 256 == 0 and every column
+ * slice of the launch is a multiple of 256 columns: otherwise ntk_q8l_bytes == 0 / NTK_E_SHAPE.  The K-quant entry points below (ntk_rp_bytes / _pack /
+ * _unpack / ntk_gemv_rp) keep refusing Q8_0; the decode launch is ntk_gemv_rp_fused with ALL segments Q8_0 and segs[i].W pointing at ntk_q8l_pack output
+ * (Q8_0 beside a K-quant in one list: NTK_E_DTYPE).  pack: raw 4-byte aligned, dst 16-byte; unpack: the exact inverse.  Stream ordered. */
+size_t ntk_q8l_bytes(int rows, int in_features);
+int ntk_q8l_pack(void* dst, const void* raw, int rows, int in_features, void* stream);
+int ntk_q8l_unpack(void* raw, const void* packed, int rows, int in_features, void* stream);
+
 /* Engine-owned load-time repack of a K-quant matrix and the decode GEMV on the int8 matrix cores that reads it (csrc/gemv_rp.hip; SURVEY
  * 7.1 step 7 / 8(b) "Ownership": repack buffers belong to the engine object, the 1:1 ntk_gemv above keeps taking raw GGUF).  Q4_K, Q5_K,
  * Q6_K; in_features % 256 == 0 and <= 32768; rows padded to tiles of 16 inside the buffer.  Same integers, same scales (ntk_rp_dequant gives

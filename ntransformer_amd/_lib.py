@@ -99,6 +99,9 @@ def lib() -> C.CDLL:
         "ntk_cosine_similarity": (i, [vp, vp, vp, i, vp]),
         "ntk_gemv_fused": (i, [C.POINTER(GemvSeg), i, vp, i, vp, f, vp, i, vp]),
         "ntk_debug_gemv_fused_form": (i, [C.POINTER(GemvSeg), i, vp, i, vp, f, vp, i, i, vp]),
+        "ntk_q8l_bytes": (sz, [i, i]),
+        "ntk_q8l_pack": (i, [vp, vp, i, i, vp]),
+        "ntk_q8l_unpack": (i, [vp, vp, i, i, vp]),
         "ntk_rp_bytes": (sz, [i, i, i]),
         "ntk_rp_pack": (i, [vp, vp, i, i, i, vp]),
         "ntk_rp_dequant": (i, [vp, vp, i, i, i, vp]),

@@ -68,7 +68,7 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
     else if (k == "prefill_row_max") E(e)->model().set_prefill_row_max(on);   // 1 (default): see Model::prefill_row_max_
     else if (k == "prefill_fused_split") E(e)->model().set_prefill_fused_split(on);   // 1 (default): see Model::prefill_fused_split_
     else if (k == "attention_merge") return E(e)->model().set_attention_merge(on);   // 1: split-KV attention without the combine launch (default 0: measured slower)
-    else if (k == "repack") return E(e)->model().set_repack(atoi(value));   // 0 raw path, 1 repack + GGUF bytes resident, 2 one resident copy, 3 (default): 2 when device memory is short, else 1
+    else if (k == "repack") return E(e)->model().set_repack(atoi(value));   // 0 raw path, 1 repack + GGUF bytes resident, 2 one resident copy (Q8_0 matrices keep both: model.h), 3 (default): 2
     else if (k == "persistent") { E(e)->options().persistent = on; E(e)->model().set_persistent(atoi(value)); }   // 1: decode_persistent.hip, 2: layer_engine.hip
     else if (k == "synth_threads") E(e)->options().synth_threads = atoi(value);
     else return NTK_E_SHAPE;

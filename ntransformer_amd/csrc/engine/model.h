@@ -21,7 +21,7 @@ struct DevTensor {
     int dtype = 0;
     int64_t in_f = 0, out_f = 0;
     size_t nbytes = 0;
-    void* rp = nullptr;    // engine-owned repack for the matrix-core decode GEMV (csrc/gemv_rp.hip); nullptr: none
+    void* rp = nullptr;    // engine-owned repack for the decode GEMV (K-quants: csrc/gemv_rp.hip, matrix cores; Q8_0: lane-major rows, csrc/gemv.hip); nullptr: none
     size_t rp_bytes = 0;
 };
 
@@ -132,12 +132,15 @@ public:
     // with the separate combine launch of rounds 3-5; same bits either way, the one-launch form measured 0.1-0.6 us (walk) / 1.5-4 us (matrix-core
     // form) per layer slower (profiles/NEGATIVE_RESULTS.md 8).  Captured graphs are dropped when the setting changes.
     int set_attention_merge(bool on);
-    // Decode GEMVs of the K-quant matrices from the load-time repack (ntk_gemv_rp_fused) instead of the raw GGUF blocks (ntk_gemv_fused).
+    // Decode GEMVs of the K-quant and Q8_0 matrices from the load-time repack (ntk_gemv_rp_fused) instead of the raw GGUF blocks (ntk_gemv_fused).
+    // Q8_0 (lane-major rows: the same bytes permuted, csrc/gemv_core.hip.h) is repacked at every level > 0 and ALWAYS keeps its GGUF bytes resident beside
+    // the repack (the prompt GEMM, the 1:1 launchers and the embedding lookup read GGUF Q8_0 blocks): + the Q8_0 matrices' bytes of HBM.  The levels
+    // below are about the K-quant matrices.
     // level 0: no repack (raw path).  1: repack AND the uploaded GGUF bytes stay resident (K-quant weights x 2 in HBM; round 4's form).
     // 2: ONE resident copy (round 5) -- the GGUF bytes of every repacked matrix are freed after the repack; the launches that read raw blocks
     // (prompt GEMM, the 1:1 ntk_gemv sequence, fallbacks) get the tensor unpacked into a scratch right in front of them (ntk_rp_unpack:
     // byte-exact inverse; + 2 x the model's bytes of HBM traffic per PROMPT PASS whatever its length: 8B Q4_K_M +4 ms = -30 % on a 64-token
-    // prompt, -6 % on 1024 tokens; 70B -7 %; decode unchanged).  3 (default): round 5: 2 only when memory was short; ROUND 6: always 2 -- the FP16 prompt
+    // prompt, -6 % on 1024 tokens; 70B -7 %; decode unchanged).  3 (default): always 2 since round 6 -- the FP16 prompt
     // GEMM reads the repack itself (ntk_gemm_desc.weights_repacked: identical bits, no unpack), so the batched prompt path and the fused decode path need
     // no GGUF bytes of a repacked matrix; what still unpacks into the scratch: the 1:1 launcher sequence (--no-fuse / tests) and the prompt's LM-head GEMV.
     // The repack is made at load unless the option was switched off BEFORE the load; switching after the load works in every direction
@@ -193,7 +196,7 @@ private:
     template <class F> void for_each_projection(F&& fn) { for (auto& L : layers_) for (auto m : kLayerMatrices) fn(L.*m); fn(output_); }
     int repack_all();                 // the repacked form of every K-quant projection (after the upload)
     int repack_one(DevTensor& t);
-    int drop_raw_all();               // level 2: free the GGUF bytes of every repacked matrix, size the unpack scratch
+    int drop_raw_all();               // level 2: free the GGUF bytes of every repacked K-quant matrix (Q8_0 keeps them), size the unpack scratch
     int restore_raw_all();            // ... and back: the GGUF bytes re-materialised from the repack
     // the raw GGUF blocks of a projection for a launch that reads them: the resident bytes, or the tensor unpacked into the scratch (stream
     // ordered; raw_begin() starts a new group of tensors that must be valid together: Q | K | V, gate | up)
@@ -284,7 +287,7 @@ private:
     bool bf16_prefill_ = true;
     unsigned* attn_sync_ = nullptr;  // 3 words for ntk_attention_gemv_fused (attention producers inside the Wo launch)
     int repack_ = 3;                 // EFFECTIVE level: 0 raw path, 1 repack + raw resident, 2 repack only (one resident copy); 3 only before a load
-    int repack_wanted_ = 3;          // the level as ASKED (3 = "2 if memory is short else 1"): re-evaluated by every load
+    int repack_wanted_ = 3;          // the level as ASKED (3 = the default: resolves to 2 at load): re-evaluated by every load
     bool repack_done_ = false;       // repack_all() ran on the loaded tensors
     uint64_t repack_bytes_ = 0;
     uint64_t raw_freed_bytes_ = 0;   // GGUF bytes released after the repack (level 2)

@@ -79,7 +79,7 @@ int Model::decode_project(const DevTensor* const* ws, float* const* ys, int n, c
         all_quant = all_quant && is_quant(ws[a]->dtype);
         mixed = mixed || ws[a]->dtype != ws[0]->dtype;
     }
-    if (all_rp) {   // every matrix has its repacked form: the matrix-core GEMV, whatever the mix of K-quant formats
+    if (all_rp) {   // every matrix has its repacked form: the matrix-core GEMV, whatever the mix of K-quant formats; all-Q8_0: the lane-major rows
         const int st = one_launch(true, resid, silu_pair);
         if (!not_taken(st)) return st;
     }

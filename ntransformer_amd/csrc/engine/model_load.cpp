@@ -187,23 +187,27 @@ int Model::finish_load() {
     if (persistent_wanted_) set_persistent(persistent_wanted_);
     size_t fr = 0, tot = 0;
     ntk_device_mem_info(&fr, &tot);
-    fprintf(stderr, "Model loaded successfully! (resident on MI355X: %.2f GB of weights%s)\nFree VRAM: %.1f GB\n",
+    uint64_t q8_twice = 0;   // Q8_0 matrices resident in both forms (GGUF blocks for the prompt pass, lane-major rows for decode)
+    for_each_projection([&](DevTensor& t) { if (t.rp && t.ptr && t.dtype == NTK_DT_Q8_0) q8_twice += t.rp_bytes; });
+    fprintf(stderr, "Model loaded successfully! (resident on MI355X: %.2f GB of weights%s%s)\nFree VRAM: %.1f GB\n",
             (weight_bytes_ - raw_freed_bytes_) / 1073741824.0, repack_bytes_ ? (" + " + std::to_string(repack_bytes_ / 1073741824.0).substr(0, 5) + " GB repacked for decode").c_str() : "",
+            q8_twice ? (", of which " + std::to_string(q8_twice / 1073741824.0).substr(0, 5) + " GB extra: Q8_0 matrices keep their GGUF bytes beside the repack").c_str() : "",
             fr / 1073741824.0);
     return NTK_OK;
 }
 
-// ---- engine-owned repack of the K-quant projections (csrc/gemv_rp.hip): made once, on the device, from the uploaded GGUF bytes, which
+// ---- engine-owned repack of the K-quant projections (csrc/gemv_rp.hip) and of the Q8_0 ones (lane-major rows, csrc/gemv.hip): made once, on the device, from the uploaded GGUF bytes, which
 //      stay resident for the 1:1 launchers and the prompt GEMM ----
 int Model::repack_one(DevTensor& t) {
     if (t.rp || !t.ptr) return NTK_OK;
     if (t.out_f <= 0 || t.out_f > 0x7FFFFFFF || t.in_f <= 0 || t.in_f > 32768) return NTK_OK;
-    const size_t n = ntk_rp_bytes(t.dtype, (int)t.out_f, (int)t.in_f);
-    if (n == 0 || n > 0xFFFFFFF0ull) return NTK_OK;   // formats / shapes the matrix-core GEMV does not take keep the raw path
+    const bool q8 = t.dtype == NTK_DT_Q8_0;   // (its own form and entry points: the lane-major rows)
+    const size_t n = q8 ? ntk_q8l_bytes((int)t.out_f, (int)t.in_f) : ntk_rp_bytes(t.dtype, (int)t.out_f, (int)t.in_f);
+    if (n == 0 || n > 0xFFFFFFF0ull) return NTK_OK;   // formats / shapes without a repacked form keep the raw path
     void* d = nt_hip_malloc(n + 256);
     if (!d) return NTK_E_NOMEM;   // (the caller keeps the tensors that did fit and lets the raw path take the rest)
     allocs_.push_back(d);
-    const int st = ntk_rp_pack(d, t.ptr, (int)t.out_f, (int)t.in_f, t.dtype, stream_);
+    const int st = q8 ? ntk_q8l_pack(d, t.ptr, (int)t.out_f, (int)t.in_f, stream_) : ntk_rp_pack(d, t.ptr, (int)t.out_f, (int)t.in_f, t.dtype, stream_);
     if (st != NTK_OK) { err_ = std::string("decode repack failed: ") + ntk_status_string(st); return st; }
     t.rp = d;
     t.rp_bytes = n;
@@ -228,9 +232,11 @@ int Model::repack_all() {
 // ---- one resident copy (level 2): the uploaded GGUF bytes of every repacked matrix go; raw_of() unpacks on demand ----
 int Model::drop_raw_all() {
     size_t need = 0;
+    // (a Q8_0 matrix keeps its GGUF bytes beside the lane-major repack: the prompt GEMM, the 1:1 launchers and embed_rows read GGUF Q8_0 blocks)
+    auto goes = [&](const DevTensor& t) { return t.rp && t.dtype != NTK_DT_Q8_0 && !(output_tied_ && t.ptr == token_embd_.ptr); };
     auto grp = [&](std::initializer_list<DevTensor*> ts) {
         size_t g = 0;
-        for (DevTensor* t : ts) if (t->rp && !(output_tied_ && t->ptr == token_embd_.ptr)) g += padded_bytes(t->nbytes);
+        for (DevTensor* t : ts) if (goes(*t)) g += padded_bytes(t->nbytes);
         need = std::max(need, g);
     };
     for (auto& L : layers_) { grp({&L.wq, &L.wk, &L.wv}); grp({&L.wo}); grp({&L.w_gate, &L.w_up}); grp({&L.w_down}); }
@@ -243,7 +249,7 @@ int Model::drop_raw_all() {
         raw_scratch_ = d; raw_scratch_bytes_ = need;
     }
     auto drop = [&](DevTensor& t) {
-        if (!t.rp || !t.ptr || (output_tied_ && t.ptr == token_embd_.ptr)) return;
+        if (!t.ptr || !goes(t)) return;
         auto it = std::find(allocs_.begin(), allocs_.end(), t.ptr);
         if (it != allocs_.end()) allocs_.erase(it);
         nt_hip_free(t.ptr);

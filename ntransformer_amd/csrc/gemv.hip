@@ -47,11 +47,14 @@ namespace ntk {
 struct AttnFuse {};             // (the ATT instantiations exist in EXPERIMENTS=1 builds only)
 #endif
 
-template <int DT, bool NORM, bool XFAST, bool A16, bool ATT = false, bool XI = false>
+// LM: the lane-major Q8_0 repack (gemv_core.hip.h: q8l_layout) -- the same kernel with the row transport replaced: a lane loads its own 64 quants (four
+// coalesced 16-byte requests) and its two scales (one dword) straight into registers; no staging areas, no ds_write / read-back / realign.
+template <int DT, bool NORM, bool XFAST, bool A16, bool ATT = false, bool XI = false, bool LM = false>
 __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int bid, const int nblk, const AttnFuse* attp = nullptr) {   // workgroup bid of nblk
     using F = Fmt<DT>;
-    constexpr int NL = F::NL;
-    constexpr int STAGE = NL * 1024 + 64;
+    static_assert(!LM || (DT == NTK_DT_Q8_0 && !A16 && !ATT && !XI), "lane-major rows: Q8_0");
+    constexpr int NL = LM ? 4 : F::NL;
+    constexpr int STAGE = LM ? 0 : NL * 1024 + 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 #ifdef NTK_GEMV_TRACE
     unsigned long long gv_t[GT_EV] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -145,7 +148,10 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
         }
     };
 
-    u32x4 pf[NL];
+    u32x4 pf[NL], pf2[LM ? NL : 1];   // (LM: two register sets, rows alternate between them -- the prefetch of row q + 1 must not land on row q)
+    uint32_t pf_sc = 0u, pf2_sc = 0u;   // LM: the lane's two FP16 scales
+    // LM: lanes past the slice's end repeat its last lane (their activations are zero)
+    const int lm_nl = my_len >> 6, lm_lane = min(lane, max(lm_nl - 1, 0));
     // rows that start 16-byte aligned (A16) cover the same 16-byte chunks row after row: the clamped chunk offsets are lane constants
     unsigned pre_off[NL];
     if constexpr (A16) {
@@ -162,6 +168,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
             asm volatile("" : "+v"(idx));   // a vector load: a scalar one would sit in lgkmcnt in front of the LDS reads
             pf_res = p.resid[idx];
         }
+        if constexpr (LM) return;   // (rows go through issue_lm)
         const unsigned rel = (unsigned)p.seg[cu_seg].delta + (unsigned)cu_row * p.row_bytes + slice_byte0;
         pf_shift = (int)(rel & 15u);
         const unsigned nbytes = (rel & 15u) + slice_bytes;
@@ -174,6 +181,14 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
             pf[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a + off));
         }
     };
+    auto issue_lm = [&](u32x4 (&c)[NL], uint32_t& sc) {   // LM: the same item into the register set (c, sc); host: W 16-byte aligned (delta == 0)
+        const uint8_t* a = p.seg[cu_seg].W + ((unsigned)cu_row * p.row_bytes + slice_byte0);
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+            c[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a + 16u * (unsigned)(j * lm_nl + lm_lane)));
+        sc = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(a + 64u * (unsigned)lm_nl + 4u * (unsigned)lm_lane));
+    };
+    auto issue_first = [&]() { issue(); if constexpr (LM) issue_lm(pf, pf_sc); };
     if (n_my <= 0) { cu_seg = 0; cu_row = 0; }   // a wave without rows still prefetches (row 0): keeps the prologue branch-free
 
     // ---- prologue: this lane's 64 activations into registers (through a padded LDS image: coalesced
@@ -221,7 +236,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 #ifdef NTK_EXPERIMENTS
                 // x is produced INSIDE this launch: weights first (they depend on nothing), then the attention heads and the
                 // grid-wide hand-off, then x through cache-bypassing loads (the first weight row has landed long before)
-                issue();
+                issue_first();
                 att_wait(*attp);
 #pragma unroll
                 for (int i = 0; i < XIT; ++i) xv[i] = asm_load16_sc1(p.x, 4u * (unsigned)min(tid * 4 + i * step, p.in - 4));
@@ -241,7 +256,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
             asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7]));
             if constexpr (NORM) asm volatile("" : "+v"(wv[0]), "+v"(wv[1]), "+v"(wv[2]), "+v"(wv[3]));
 #endif
-            issue();   // unconditional (a wave without rows re-reads row 0)
+            issue_first();   // unconditional (a wave without rows re-reads row 0)
             GV_STAMP(8);   // first weight row requested
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -383,7 +398,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
                 if (s >= g0 && s < g0 + GS) read_own_row(g0);
             }
         } else {   // unaligned / odd sizes (and the NTK_GEMV_ABLATE=1 experiment): plain loops
-            issue();
+            issue_first();
             float rms_inv = 1.0f;
             if (NORM && !(kAblate & 1)) {
                 float ssq = 0.0f;
@@ -410,7 +425,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 #pragma unroll
             for (int j = 0; j < 32; ++j) x2[j] = f32x2{1.0f, 1.0f};
         }
-        if (p.ns > 1) __syncthreads();   // the image becomes the staging area
+        if (p.ns > 1 && !LM) __syncthreads();   // the image becomes the staging area
         GV_STAMP(2);   // activations in registers
     }
     float sx16[4], sx32[2];
@@ -481,25 +496,38 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
     // Every wave walks its own list of (segment,row) items; the valid ones are a prefix of length n_my.
     // All loads / LDS writes are unpredicated (lanes past the slice end re-read its last chunk) so the loop
     // body is straight-line code: hipcc then waits for the prefetch exactly once, right before the ds_writes.
-    for (int q = 0; q < n_my; ++q) {
+    // One row: `cur` (LM) holds its bytes, the next row's go to `nxt`.
+    auto row_step = [&](const int q, u32x4 (&cur)[NL], uint32_t& cur_sc, u32x4 (&nxt)[LM ? NL : 1], uint32_t& nxt_sc) __attribute__((always_inline)) {
         const int seg = pf_seg, row = pf_row, shift = A16 ? 0 : pf_shift;
         const float res = pf_res;
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            if (kAblate & 4) { asm volatile("" ::"v"(pf[j])); continue; }
-            *reinterpret_cast<u32x4*>(stage + 16 * (lane + 64 * j)) = pf[j];
-        }
-        __builtin_amdgcn_wave_barrier();   // DS ops of one wave execute in order: the image is visible below
-#ifdef NTK_GEMV_TRACE
-        if (q == 0) GV_STAMP(3);            // first row has landed
-        if (q == n_my - 1) GV_STAMP(5);     // last row has landed
-#endif
-        if (q + 1 < n_my) { cursor_advance(); issue(); }   // next row's bytes fly while this one is decoded
         float acc;
-        if constexpr (XI && DT == NTK_DT_Q6_K) acc = DotI<DT>::run(stage, shift, lane, ncols, xi);
-        else if constexpr (XI) acc = DotI<DT>::run(stage, lane, ncols, xi);
-        else acc = (kAblate & 2) ? x2[0].x + (float)q : Dot<DT, A16>::run(stage, shift, lane, ncols, x2, sx16, sx32);
-        __builtin_amdgcn_wave_barrier();   // all reads of the image precede the next overwrite
+        if constexpr (LM) {
+            // the row's registers are "used" here, so the wait for them stands in front of the next row's requests (as the ds_writes of the staged form)
+            asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur_sc));
+#ifdef NTK_GEMV_TRACE
+            if (q == 0) GV_STAMP(3);            // first row has landed
+            if (q == n_my - 1) GV_STAMP(5);     // last row has landed
+#endif
+            if (q + 1 < n_my) { cursor_advance(); issue(); issue_lm(nxt, nxt_sc); }   // next row's bytes fly while this one is decoded
+            __builtin_amdgcn_sched_barrier(0);   // ... requested BEFORE the decode, not where the scheduler finds room
+            acc = dot_q8_regs(cur, cur_sc, ncols, x2);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NL; ++j) {
+                if (kAblate & 4) { asm volatile("" ::"v"(pf[j])); continue; }
+                *reinterpret_cast<u32x4*>(stage + 16 * (lane + 64 * j)) = pf[j];
+            }
+            __builtin_amdgcn_wave_barrier();   // DS ops of one wave execute in order: the image is visible below
+#ifdef NTK_GEMV_TRACE
+            if (q == 0) GV_STAMP(3);            // first row has landed
+            if (q == n_my - 1) GV_STAMP(5);     // last row has landed
+#endif
+            if (q + 1 < n_my) { cursor_advance(); issue(); }   // next row's bytes fly while this one is decoded
+            if constexpr (XI && DT == NTK_DT_Q6_K) acc = DotI<DT>::run(stage, shift, lane, ncols, xi);
+            else if constexpr (XI) acc = DotI<DT>::run(stage, lane, ncols, xi);
+            else acc = (kAblate & 2) ? x2[0].x + (float)q : Dot<DT, A16>::run(stage, shift, lane, ncols, x2, sx16, sx32);
+            __builtin_amdgcn_wave_barrier();   // all reads of the image precede the next overwrite
+        }
         const float tot = wave_sum_lane63(acc);   // valid in lane 63
 #ifdef NTK_GEMV_TRACE
         if (q == 0) { asm volatile("" :: "v"(tot)); GV_STAMP(4); }   // first row decoded and reduced
@@ -527,6 +555,10 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
                 combine(b, RB);
             }
         }
+    };
+    for (int q = 0; q < n_my; ++q) {
+        row_step(q, pf, pf_sc, pf2, pf2_sc);
+        if constexpr (LM) { if (++q < n_my) row_step(q, pf2, pf2_sc, pf, pf_sc); }
     }
     if (p.ns > 1) {   // close a partial batch, then keep barrier counts equal across the workgroup
         int done = n_my / RB;
@@ -547,6 +579,53 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
         for (int e = 0; e < GT_EV; ++e) g_gemv_trace[p.trace_slot & (GT_SLOTS - 1)][bid][e] = gv_t[e];
     }
 #endif
+}
+
+// Q8_0 rows in the lane-major layout of the engine's repack (LM above)
+template <bool NORM, bool XFAST>
+__global__ __launch_bounds__(512, Fmt<NTK_DT_Q8_0>::MINW) void gemv_q8l_kernel(const GemvParams p) {
+    gemv_quant_body<NTK_DT_Q8_0, NORM, XFAST, false, false, false, true>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+// GGUF Q8_0 rows -> lane-major rows (UNPACK: back).  One thread per (row, 64-column lane): its two blocks are 17 dwords
+// [d0 | 32 quants | d1 | 32 quants] in the file (4-byte aligned: the tensor is, and a row is a multiple of 272 bytes), 16 quant dwords + 1 scale dword packed.
+template <bool UNPACK>
+__global__ __launch_bounds__(256) void q8l_pack_kernel(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, const int rows, const int in,
+                                                       const int slice_cols) {
+    const int lanes_row = in >> 6;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)rows * lanes_row) return;
+    const int row = (int)(t / lanes_row), gl = (int)(t % lanes_row);       // gl: the lane's 64-column group in the row
+    const int lanes_slice = slice_cols >> 6, sl = gl / lanes_slice, l = gl - sl * lanes_slice;
+    const int nl = min(lanes_slice, lanes_row - sl * lanes_slice);          // lanes of this slice (the last one may be shorter)
+    const size_t row0 = (size_t)row * lanes_row * 68;
+    uint32_t* file = reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(UNPACK ? dst : src) + row0 + (size_t)gl * 68);
+    uint8_t* slice = const_cast<uint8_t*>(UNPACK ? src : dst) + row0 + (size_t)sl * lanes_slice * 68;
+    uint32_t w[17], q[16], sc;
+    if constexpr (!UNPACK) {
+#pragma unroll
+        for (int k = 0; k < 17; ++k) w[k] = file[k];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { q[k] = (w[k] >> 16) | (w[k + 1] << 16); q[8 + k] = w[9 + k]; }
+        sc = (w[0] & 0xFFFFu) | (w[8] & 0xFFFF0000u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<u32x4*>(slice + (size_t)(j * nl + l) * 16) = u32x4{q[4 * j], q[4 * j + 1], q[4 * j + 2], q[4 * j + 3]};
+        *reinterpret_cast<uint32_t*>(slice + (size_t)64 * nl + 4 * l) = sc;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const u32x4 v = *reinterpret_cast<const u32x4*>(slice + (size_t)(j * nl + l) * 16);
+            q[4 * j] = v.x; q[4 * j + 1] = v.y; q[4 * j + 2] = v.z; q[4 * j + 3] = v.w;
+        }
+        sc = *reinterpret_cast<const uint32_t*>(slice + (size_t)64 * nl + 4 * l);
+        w[0] = (sc & 0xFFFFu) | (q[0] << 16);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) w[k] = (q[k - 1] >> 16) | (q[k] << 16);
+        w[8] = (q[7] >> 16) | (sc & 0xFFFF0000u);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[9 + k] = q[8 + k];
+#pragma unroll
+        for (int k = 0; k < 17; ++k) file[k] = w[k];
+    }
 }
 
 #ifdef NTK_EXPERIMENTS
@@ -650,7 +729,7 @@ static bool raise_lds_limit(const void* fn) {
 // argument checks + geometry of one single-format launch (max_wg workgroups at most)
 template <int DT>
 static int prepare_quant(const ntk_gemv_seg* segs, int nseg, const float* x, int in, const float* norm_w, float eps,
-                         const float* resid, int silu_pair, int max_wg, GemvLaunch& L) {
+                         const float* resid, int silu_pair, int max_wg, GemvLaunch& L, bool lm = false) {
     using F = Fmt<DT>;
     if (in <= 0 || in % F::BW != 0) return NTK_E_SHAPE;
     GemvParams& p = L.p;
@@ -677,10 +756,7 @@ static int prepare_quant(const ntk_gemv_seg* segs, int nseg, const float* x, int
     p.total_rows = (int)total;
     p.x = x;
     p.in = in;
-    const int align = F::BW == 256 ? 256 : 64;
-    p.ns = (in + 4095) / 4096;
-    p.slice_cols = ((in + p.ns - 1) / p.ns + align - 1) / align * align;
-    if (p.ns > 8 || (long)(p.ns - 1) * p.slice_cols >= in) return NTK_E_SHAPE;   // in_features > 32768 not supported
+    if (!gemv_slices(in, F::BW == 256 ? 256 : 64, p.ns, p.slice_cols)) return NTK_E_SHAPE;
     // waves per workgroup = ns * rw ~ 8: one x prologue feeds eight row streams
     static const int env_waves = std::max(1, NTK_TUNE_ENV_INT("NTK_GEMV_WAVES", 8));   // (tuning builds only)
     p.rw = std::max(1, env_waves / p.ns);   // (6-wave workgroups for the 3-waves/SIMD formats measured 30 % slower)
@@ -700,7 +776,7 @@ static int prepare_quant(const ntk_gemv_seg* segs, int nseg, const float* x, int
     const long ngroups = (long)grid * p.rw;
     const long rows_per_group = (total + ngroups - 1) / ngroups;
     p.nbatch = (int)((rows_per_group * mats + RB - 1) / RB);
-    constexpr int STAGE = F::NL * 1024 + 64;
+    const int STAGE = lm ? 0 : F::NL * 1024 + 64;   // (lane-major rows go to registers: no staging areas)
     const size_t image_bytes = (size_t)std::min(p.ns, 4) * 64 * XPITCH * 4;   // same layout as gemv_quant_body
     const size_t regionA = p.ns == 1 ? image_bytes + (size_t)L.nwaves * STAGE : std::max((size_t)L.nwaves * STAGE, image_bytes);
     L.lds = regionA + (size_t)(2 * p.rw * p.ns * RB + 16 + 16) * sizeof(float);
@@ -800,6 +876,53 @@ static int launch_quant(const ntk_gemv_seg* segs, int nseg, const float* x, int 
     return last_launch_status();
 }
 
+// ---- lane-major Q8_0: size, pack / unpack (ntk_q8l_bytes / ntk_q8l_pack / ntk_q8l_unpack), launch (the all-Q8_0 side of ntk_gemv_rp_fused) ----
+static size_t q8l_bytes(int rows, int in) {
+    int ns, sc;
+    return rows > 0 && q8l_layout(in, ns, sc) ? (size_t)rows * (size_t)(in / 32 * 34) : 0;
+}
+
+static int q8l_pack(void* dst, const void* raw, int rows, int in, bool unpack, hipStream_t st) {
+    int ns, sc;
+    if (rows <= 0 || !q8l_layout(in, ns, sc)) return NTK_E_SHAPE;
+    // (dst: the packed side when packing, the GGUF side when unpacking)
+    if ((reinterpret_cast<uintptr_t>(unpack ? raw : dst) & 15) || (reinterpret_cast<uintptr_t>(unpack ? dst : raw) & 3)) return NTK_E_ALIGN;
+    const size_t n = (size_t)rows * (in / 64);
+    if ((n + 255) / 256 > 0x7FFFFFFFull) return NTK_E_SHAPE;
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    uint8_t* d = static_cast<uint8_t*>(dst);
+    const uint8_t* r = static_cast<const uint8_t*>(raw);
+    if (unpack) hipLaunchKernelGGL(q8l_pack_kernel<true>, g, b, 0, st, d, r, rows, in, sc);
+    else hipLaunchKernelGGL(q8l_pack_kernel<false>, g, b, 0, st, d, r, rows, in, sc);
+    return last_launch_status();
+}
+
+int q8l_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in, const float* norm_w, float eps, const float* resid,
+                   int silu_pair, hipStream_t st) {
+    int ns, sc;
+    if (!q8l_layout(in, ns, sc)) return NTK_E_SHAPE;
+    for (int i = 0; i < nseg; ++i)
+        if (reinterpret_cast<uintptr_t>(segs[i].W) & 15) return NTK_E_ALIGN;   // rows are read with 16-byte requests from the tensor's own start
+    GemvLaunch L;
+    const int rc = prepare_quant<NTK_DT_Q8_0>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, max_workgroups(), L, true);
+    if (rc != NTK_OK) return rc;
+    if (L.p.total_rows == 0) return NTK_OK;
+    using KernelFn = void (*)(const GemvParams);
+    static const KernelFn table[2][2] = {{gemv_q8l_kernel<false, false>, gemv_q8l_kernel<false, true>},
+                                         {gemv_q8l_kernel<true, false>, gemv_q8l_kernel<true, true>}};
+    if (L.lds > 64 * 1024) {   // 28672-wide rows: the activation image of four slices, 68 KiB
+        static const bool once = raise_lds_limit((const void*)table[0][0]) && raise_lds_limit((const void*)table[0][1]) &&
+                                 raise_lds_limit((const void*)table[1][0]) && raise_lds_limit((const void*)table[1][1]);
+        if (!once || L.lds > 160 * 1024) return NTK_E_SHAPE;
+    }
+#ifdef NTK_GEMV_TRACE
+    static int trace_counter = 0;
+    L.p.trace_slot = trace_counter++;
+#endif
+    hipLaunchKernelGGL(table[norm_w ? 1 : 0][L.xfast ? 1 : 0], dim3(L.grid), dim3(64 * L.nwaves), L.lds, st, L.p);
+    return last_launch_status();
+}
+
 #ifdef NTK_EXPERIMENTS
 template <int DT>
 static int launch_att(const AttnFuse& att, const ntk_gemv_seg* seg, int in, const float* resid, hipStream_t st) {
@@ -882,6 +1005,16 @@ NTK_EXTRA_API int ntk_debug_gemv_trace(unsigned long long* out, size_t n) {   //
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(ntk::g_gemv_trace), n * sizeof(unsigned long long)) == hipSuccess ? 0 : -3;
 }
 #endif
+
+size_t ntk_q8l_bytes(int rows, int in_features) { return ntk::q8l_bytes(rows, in_features); }
+int ntk_q8l_pack(void* dst, const void* raw, int rows, int in_features, void* stream) {
+    if (!dst || !raw) return NTK_E_NULL;
+    return ntk::q8l_pack(dst, raw, rows, in_features, false, ntk::resolve_stream(stream));
+}
+int ntk_q8l_unpack(void* raw, const void* packed, int rows, int in_features, void* stream) {
+    if (!raw || !packed) return NTK_E_NULL;
+    return ntk::q8l_pack(raw, packed, rows, in_features, true, ntk::resolve_stream(stream));
+}
 
 int ntk_gemv(float* y, const void* W, const float* x, int out_features, int in_features, int weight_dtype, void* stream) {
     if (!y || !W || !x) return NTK_E_NULL;

@@ -90,6 +90,23 @@ __device__ __forceinline__ void wait_vm(unsigned n) {   // wave-uniform
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- how a row is cut into column slices (host): ns slices of slice_cols columns, the last one possibly shorter.  ONE rule for the launcher
+// (prepare_quant, gemv.hip) and for the lane-major Q8_0 packer below: the packed layout follows the launch's slices.
+inline bool gemv_slices(int in, int align, int& ns, int& slice_cols) {
+    ns = (in + 4095) / 4096;
+    slice_cols = ((in + ns - 1) / ns + align - 1) / align * align;
+    return ns <= 8 && (long)(ns - 1) * slice_cols < in;   // in_features > 32768 not supported
+}
+// Lane-major Q8_0 (the engine's load-time repack of a Q8_0 matrix): a byte permutation of every row slice that lets lane l load
+// its 64 columns -- GGUF blocks 2l and 2l+1 of the slice -- straight into registers.  A slice of nl = width / 64 lanes is stored as
+//   16-byte chunk j (j = 0..3: quant bytes [16j, 16j+16) of the lane's 64) of lane l at byte (j nl + l) 16,
+//   one dword per lane at 64 nl + 4 l: the FP16 scale of block 2l (low half) and of block 2l+1 (high half),
+// 68 nl bytes, the slice's GGUF size: row_bytes and the bytes a launch streams are unchanged.  Taken when every slice width is a
+// multiple of 256 columns (every slice and row then starts 16-byte aligned: 4096, 14336 = 4 x 3584, 8192, 28672 = 7 x 4096).
+inline bool q8l_layout(int in, int& ns, int& slice_cols) {
+    if (in <= 0 || in % 256 != 0 || !gemv_slices(in, 64, ns, slice_cols)) return false;
+    return slice_cols % 256 == 0 && (in - (ns - 1) * slice_cols) % 256 == 0;
+}
 // formats that have a 16-byte-aligned fast decoder (others instantiate only the general one)
 template <int DT> constexpr bool A16_OK = (DT == NTK_DT_Q4_K || DT == NTK_DT_Q5_K);
 
@@ -166,6 +183,27 @@ template <bool A16> struct Dot<NTK_DT_Q8_0, A16> {   // reference gemm.cu:129-14
         return acc;
     }
 };
+
+// the same sums from REGISTERS (lane-major Q8_0): q = the lane's 16 quant dwords (chunks 0,1: block 2l; 2,3: block 2l+1), sc = its two FP16
+// scales.  The same dwords in the same order through the same packed FMAs as above: identical bits.  ncols is 0 or 64 here.
+__device__ __forceinline__ float dot_q8_regs(const u32x4 (&c)[4], const uint32_t sc, const int ncols, const f32x2 (&x2)[32]) {
+    float acc = 0.0f;
+    if (ncols > 0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float d = h2f((uint16_t)(h ? sc >> 16 : sc & 0xFFFFu));
+            const uint32_t q[8] = {c[2 * h].x, c[2 * h].y, c[2 * h].z, c[2 * h].w, c[2 * h + 1].x, c[2 * h + 1].y, c[2 * h + 1].z, c[2 * h + 1].w};
+            f32x2 a0 = {0.0f, 0.0f}, a1 = {0.0f, 0.0f};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                a0 = pkfma(f32x2{sb2f(q[i], 0), sb2f(q[i], 1)}, x2[16 * h + 2 * i], a0);
+                a1 = pkfma(f32x2{sb2f(q[i], 2), sb2f(q[i], 3)}, x2[16 * h + 2 * i + 1], a1);
+            }
+            acc = fmaf(d, hsum(a0, a1), acc);
+        }
+    }
+    return acc;
+}
 
 template <bool A16> struct Dot<NTK_DT_Q4_0, A16> {   // reference gemm.cu:60-75: w_j = d (lo-8), w_{j+16} = d (hi-8)
     __device__ static float run(const uint8_t* st, int shift, int lane, int ncols, const f32x2 (&x2)[32],

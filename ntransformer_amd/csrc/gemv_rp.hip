@@ -927,6 +927,17 @@ int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in
     if (in_features <= 0 || in_features % 256 != 0 || in_features > 32768) return NTK_E_SHAPE;
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (norm_w && (reinterpret_cast<uintptr_t>(norm_w) & 15))) return NTK_E_ALIGN;
     if (silu_pair && (nseg != 2 || segs[0].rows != segs[1].rows || segs[0].dtype != segs[1].dtype || resid)) return NTK_E_SHAPE;
+    {   // all-Q8_0 segment lists: W = the lane-major rows of ntk_q8l_pack, csrc/gemv.hip (Q8_0 beside a K-quant: not taken, NTK_E_DTYPE below)
+        bool q8 = true;
+        for (int i = 0; i < nseg; ++i) q8 = q8 && segs[i].dtype == NTK_DT_Q8_0;
+        if (q8) {
+            for (int i = 0; i < nseg; ++i) {
+                if (segs[i].rows <= 0) return NTK_E_SHAPE;
+                if (!segs[i].W || !segs[i].y) return NTK_E_NULL;
+            }
+            return q8l_gemv_fused(segs, nseg, x, in_features, norm_w, eps, resid, silu_pair, resolve_stream(stream));
+        }
+    }
     // order: format A first (the first segment's), then the rest (one other format at most)
     ntk_gemv_seg ord[3];
     int na = 0, nb = 0, dtb = -1;
@@ -990,6 +1001,7 @@ int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in
 }
 
 int ntk_gemv_rp(float* y, const void* rp, const float* x, int out_features, int in_features, int weight_dtype, void* stream) {
+    if (!ntk::rp_supported(weight_dtype)) return NTK_E_DTYPE;   // the 1:1 form is the matrix-core GEMV: K-quants (Q8_0 rows go through the fused entry point)
     ntk_gemv_seg seg{rp, y, out_features, weight_dtype};
     return ntk_gemv_rp_fused(&seg, 1, x, in_features, nullptr, 0.0f, nullptr, 0, stream);
 }

@@ -172,6 +172,29 @@ def gemv_fused(segs: Sequence[tuple], x, in_features, norm_w=None, eps=0.0, resi
                                                    1 if integer_activations else 0, stream), "gemv_fused_form")
 
 
+def q8l_bytes(rows, in_features) -> int:
+    return int(_lib.lib().ntk_q8l_bytes(rows, in_features))
+
+
+def q8l_pack(raw, rows, in_features, stream=None) -> "DeviceBuffer":
+    """ntk_q8l_pack: the lane-major repack of a raw GGUF Q8_0 matrix (device buffer in, new device buffer out); read by gemv_rp_fused"""
+    n = q8l_bytes(rows, in_features)
+    if n == 0:
+        raise _lib.NtkError(-2, "q8l_pack: shape without a lane-major form")
+    dst = DeviceBuffer(n + 256)
+    check(_lib.lib().ntk_q8l_pack(_p(dst), _p(raw), rows, in_features, stream), "q8l_pack")
+    synchronize(stream)
+    return dst
+
+
+def q8l_unpack(packed, rows, in_features, nbytes, stream=None) -> "DeviceBuffer":
+    """ntk_q8l_unpack: the GGUF Q8_0 blocks back from the lane-major form"""
+    dst = DeviceBuffer(nbytes + 256)
+    check(_lib.lib().ntk_q8l_unpack(_p(dst), _p(packed), rows, in_features, stream), "q8l_unpack")
+    synchronize(stream)
+    return dst
+
+
 def rp_bytes(dtype, rows, in_features) -> int:
     return int(_lib.lib().ntk_rp_bytes(int(dtype), rows, in_features))
 
