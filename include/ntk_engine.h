@@ -205,6 +205,9 @@ int ntk_gemm_quant(float* Y, const void* W, const float* X, int n_tokens, int ou
  *   weights_repacked  != 0: segs[i].W point at the engine's DECODE REPACK of the matrices (ntk_rp_pack: tiles of 16 rows x 256-column super-blocks) instead
  *                 of raw GGUF blocks -- Q4_K / Q5_K / Q6_K (NTK_E_DTYPE otherwise).  Round 6: with one resident copy of a K-quant matrix the prompt pass
  *                 needs no unpack any more.  The same integers and scale products in the same order: IDENTICAL bits to the raw form.
+ *   full_form     != 0: the launch takes the form, K split and chunk pairing of a FULL pass (1024 tokens) whatever n_tokens is, never the short-prompt
+ *                 forms: a token's outputs are then the same bits however the caller cuts its tokens into calls (Model::score: the LM head over
+ *                 "score_rows" rows at a time).  0 (every other caller): the form is chosen for n_tokens, as before.
  * Stream ordered, no allocation, no synchronisation. */
 typedef struct ntk_gemm_partials {
     const float* part[3];   /* per matrix: [nsplit][n_tokens][rows] partial sums (NULL when nsplit == 1) */
@@ -224,6 +227,7 @@ typedef struct ntk_gemm_desc {
     const float*        row_max;
     ntk_gemm_partials*  partials;
     int                 weights_repacked;   /* != 0: segs[i].W are tensors of the decode repack (ntk_rp_pack; Q4_K / Q5_K / Q6_K), read as they lie */
+    int                 full_form;          /* != 0: the form of a full 1024-token pass whatever n_tokens is (chunking-independent bits) */
 } ntk_gemm_desc;
 size_t ntk_gemm_quant_workspace_bytes(int in_features, int out_features);
 int ntk_gemm_quant_f16(const ntk_gemm_desc* desc, void* stream);
@@ -259,6 +263,14 @@ int ntk_embed_rows(float* out, const void* table, const int* tokens, int n_token
  * Writes the index to *d_out_token (device) -- and to *h_mirror if it is a pinned host pointer (may be NULL).
  * scratch: device buffer of >= 2*1024 floats. */
 int ntk_argmax(const float* logits, int n, int* d_out_token, int* h_mirror, float* scratch, void* stream);
+
+/* Scoring (csrc/logprob.hip; no reference counterpart): per row of logits the log-probability of one target token and, optionally, the greedy token.
+ * logits [n_rows][ld] F32 (ld >= vocab, row pitch in floats; any 4-byte aligned address), targets DEVICE int [n_rows].
+ * logprob[r] = logits[r][targets[r]] - log(sum_j exp(logits[r][j]))   (natural log; targets[r] < 0: logprob[r] = 0, and the row is not read unless top1 is asked for)
+ * top1[r] (optional, may be NULL) = first index of the row's maximum (strict >, as ntk_argmax: NaN never wins, a row without a finite or +inf entry gives 0)
+ * One pass over the row (online softmax), accurate expf / logf, a fixed reduction order: the same bits on every launch.  -inf logits add 0 to the sum; a row of
+ * -inf only, or one that holds a NaN, gives NaN for that row alone.  The caller validates targets[r] < vocab (the kernel clamps: it never leaves the row). */
+int ntk_logprob_rows(const float* logits, int n_rows, int vocab, int ld, const int* targets, float* logprob, int* top1, void* stream);
 
 /* The reference's sampler on the device (reference src/inference/sampler.cpp:30-117), for temperature > 0 and
  * 0 < top_k <= 64 (NTK_E_SHAPE otherwise: the caller samples on the host): repeat penalty over d_recent[n_recent] (DEVICE

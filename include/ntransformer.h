@@ -80,7 +80,9 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * layers).  Set it BEFORE the load (afterwards: NTK_E_SHAPE + last_error); an nt_engine_load_shared sequence takes its own option.  Decode steps read
  * the 8-bit rows on the matrix cores using half(d) * q exactly; prompt passes (and "fused" = "0") dequantise rows [0, start_pos + n) into the F16 image
  * -- rounded to half, the chunk's own rows included -- and run the F16 attention kernels over it.  Refused at load (NTK_E_SHAPE + last_error): head_dim
- * other than 128, more than 16 query heads per KV head, tensor parallelism, "fuse_attention". */
+ * other than 128, more than 16 query heads per KV head, tensor parallelism, "fuse_attention";
+ * "score_rows" = "1" .. "1024" (default "256"): rows of logits nt_engine_score_tokens computes per pass over the LM head (score_rows x vocab floats of device
+ * memory from the first scoring call on; any time). */
 int  nt_engine_set_option(nt_engine_t e, const char* key, const char* value);
 const char* nt_engine_last_error(nt_engine_t e);
 void nt_gen_params_default(nt_gen_params* p);
@@ -89,6 +91,11 @@ int  nt_engine_generate_tokens(nt_engine_t e, const int* prompt, int n_prompt, c
 int  nt_engine_last_stats(nt_engine_t e, nt_stats* out);
 /* Transformer::forward: tokens [n] at start_pos -> logits of the last position copied to host (vocab floats) */
 int  nt_engine_forward(nt_engine_t e, const int* tokens, int n, int start_pos, float* logits_out);
+/* Scoring: logprob_out[i] = log P(targets[i] | tokens[0..i]) (natural log) for targets[i] >= 0, 0 where targets[i] < 0; top1_out (optional, may be NULL):
+ * the greedy token behind tokens[0..i] for every i.  Runs the prompt pass over tokens at start_pos (the KV cache afterwards = nt_engine_forward's), then
+ * the LM head over "score_rows" positions at a time; returns the number of scored positions or a negative NTK_E_* (+ nt_engine_last_error: an id out of
+ * range, n + start_pos beyond the context, a tensor-parallel engine, no device memory for the first call's buffers -- the engine stays usable). */
+int  nt_engine_score_tokens(nt_engine_t e, const int* tokens, const int* targets, int n, int start_pos, float* logprob_out, int* top1_out);
 /* one fused decode step for `token` at position `pos` (device-resident state), logits copied to host */
 int  nt_engine_decode_fused(nt_engine_t e, int token, int pos, int use_graph, float* logits_out);
 /* n greedy decode steps from (token, pos): exactly the timed inner loop of generate (device argmax, one host

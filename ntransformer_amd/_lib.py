@@ -37,7 +37,7 @@ class GemmPartials(C.Structure):   # ntk_gemm_partials (include/ntk_engine.h)
 class GemmDesc(C.Structure):   # ntk_gemm_desc (include/ntk_engine.h)
     _fields_ = [("segs", C.POINTER(GemvSeg)), ("nseg", C.c_int), ("X", C.c_void_p), ("n_tokens", C.c_int), ("in_features", C.c_int), ("resid", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("reuse_x", C.c_int), ("row_max", C.c_void_p),
-                ("partials", C.POINTER(GemmPartials)), ("weights_repacked", C.c_int)]
+                ("partials", C.POINTER(GemmPartials)), ("weights_repacked", C.c_int), ("full_form", C.c_int)]
 
 
 _lib = None
@@ -123,6 +123,7 @@ def lib() -> C.CDLL:
         "ntk_kv_dequant_q8_f16": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "ntk_embed_rows": (i, [vp, vp, vp, i, i, i, vp]),
         "ntk_argmax": (i, [vp, i, vp, vp, vp, vp]),
+        "ntk_logprob_rows": (i, [vp, i, i, i, vp, vp, vp, vp]),
         "ntk_advance_pos": (i, [vp, vp]),
         "ntk_debug_sclk": (i, [vp, vp]),
         "ntk_debug_sclk_begin": (i, [vp, vp, vp]),

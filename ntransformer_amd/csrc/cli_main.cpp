@@ -1,9 +1,15 @@
 // cli_main.cpp -- the `ntransformer` command line, flag for flag the reference's (reference src/main.cpp:8-174).
 // Streaming-family flags exist to fit 24 GB of VRAM; on MI355X every target model is resident, so they are
 // accepted for compatibility and reported as no-ops.  Added: --synthetic <preset>:<mix> to run without a file.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <fstream>
+#include <iterator>
 #include <string>
+#include <vector>
 #include "engine/engine.h"
 #include "../../include/ntk_engine.h"
 
@@ -22,6 +28,7 @@ static void usage(const char* prog) {
             "  --seed <int>             Random seed (default: 42)\n"
             "  --benchmark              Run benchmark mode\n"
             "  --chat                   Interactive chat mode\n"
+            "  --perplexity <file>      Score the file's text in windows of the context size (BOS in front of each) and print its perplexity\n"
             "  -v, --verbose            Verbose output\n"
             "  -h, --help               Show this help\n"
             "  --no-fuse / --no-graph   Use the 15-launch/layer sequence / launch eagerly\n"
@@ -36,12 +43,51 @@ static void usage(const char* prog) {
             prog);
 }
 
+// --perplexity: the file's tokens in windows of ctx - 1, BOS in front of each, every window scored from position 0 (Engine::score); the first token
+// of a window is context only.  exp(-mean log P) over all scored tokens, summed in double.
+static int run_perplexity(nt::Engine& engine, const std::string& path, bool verbose) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) { fprintf(stderr, "Error: cannot read %s\n", path.c_str()); return 1; }
+    const std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    const std::vector<int> ids = engine.tokenizer().encode(text, false);
+    if (ids.empty()) { fprintf(stderr, "Error: %s holds no text to score\n", path.c_str()); return 1; }
+    const int ctx = engine.model().config().max_seq_len;
+    if (ctx < 2) { fprintf(stderr, "Error: a context of %d tokens leaves nothing to score\n", ctx); return 1; }
+    const size_t per = (size_t)ctx - 1;
+    double sum = 0.0;
+    size_t scored = 0;
+    std::vector<int> window, targets;
+    std::vector<float> lp;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t w0 = 0, k = 0; w0 < ids.size(); w0 += per, ++k) {
+        const size_t n = std::min(per, ids.size() - w0);
+        window.assign(1, engine.tokenizer().bos_id());
+        window.insert(window.end(), ids.begin() + (long)w0, ids.begin() + (long)(w0 + n));
+        targets.assign(window.begin() + 1, window.end());
+        targets.push_back(-1);
+        lp.assign(window.size(), 0.0f);
+        if (engine.score(window.data(), targets.data(), (int)window.size(), 0, lp.data(), nullptr) != NTK_OK) {
+            fprintf(stderr, "Error: scoring failed: %s\n", engine.error().c_str());
+            return 1;
+        }
+        double ws = 0.0;
+        for (size_t i = 0; i < n; ++i) ws += (double)lp[i];
+        sum += ws;
+        scored += n;
+        if (verbose) fprintf(stdout, "window %zu: %zu tokens, perplexity %.4f\n", k, n, std::exp(-ws / (double)n));
+    }
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stdout, "Perplexity: %.4f over %zu tokens (%.1f tok/s)\n", std::exp(-sum / (double)scored), scored, secs > 0 ? (double)scored / secs : 0.0);
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    std::string model_path, prompt, synthetic;
+    std::string model_path, prompt, synthetic, perplexity_file;
     int max_context = 4096;
     bool benchmark = false, chat = false;
     nt::GenerateConfig cfg;
     cfg.verbose = true;
+    bool verbose_flag = false;
     nt::Engine engine;
     // reference main.cpp:52-103.  Streaming and speculative decoding change HOW tokens are produced, not WHICH tokens
     // (greedy speculative decoding verifies every draft token against the full model); they are accepted and plain resident
@@ -68,7 +114,8 @@ int main(int argc, char** argv) {
         else if (a == "-c" || a == "--ctx-size") { if (auto v = val()) max_context = std::stoi(v); }
         else if (a == "--benchmark") benchmark = true;
         else if (a == "--chat") chat = true;
-        else if (a == "-v" || a == "--verbose") cfg.verbose = true;
+        else if (a == "-v" || a == "--verbose") { cfg.verbose = true; verbose_flag = true; }
+        else if (a == "--perplexity") { const char* v = val(); if (!v) { fprintf(stderr, "Error: --perplexity takes a file\n"); return 1; } perplexity_file = v; }
         else if (a == "--no-fuse") { engine.options().fused = false; engine.options().batched_prefill = false; }
         else if (a == "--no-batched-prefill") engine.options().batched_prefill = false;
         else if (a == "--no-graph") engine.options().graph = false;
@@ -101,6 +148,7 @@ int main(int argc, char** argv) {
     }
     if (st != NTK_OK) { fprintf(stderr, "Failed to load model: %s (%s)\n", model_path.c_str(), engine.error().c_str()); return 1; }
 
+    if (!perplexity_file.empty()) return run_perplexity(engine, perplexity_file, verbose_flag);
     if (benchmark) engine.benchmark(prompt.empty() ? "The meaning of life is" : prompt, cfg.max_tokens);
     else if (chat || prompt.empty()) engine.chat(cfg);
     else engine.generate(prompt, cfg);

@@ -70,6 +70,11 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
     else if (k == "attention_merge") return E(e)->model().set_attention_merge(on);   // 1: split-KV attention without the combine launch (default 0: measured slower)
     else if (k == "repack") return E(e)->model().set_repack(atoi(value));   // 0 raw path, 1 repack + GGUF bytes resident, 2 one resident copy (Q8_0 matrices keep both: model.h), 3 (default): 2
     else if (k == "persistent") { E(e)->options().persistent = on; E(e)->model().set_persistent(atoi(value)); }   // 1: decode_persistent.hip, 2: layer_engine.hip
+    else if (k == "score_rows") {   // rows of logits per LM-head chunk of nt_engine_score_tokens, 1 .. 1024 (default 256)
+        const int rc = E(e)->model().set_score_rows(atoi(value));
+        if (rc != NTK_OK) E(e)->set_error(E(e)->model().error());
+        return rc;
+    }
     else if (k == "synth_threads") E(e)->options().synth_threads = atoi(value);
     else return NTK_E_SHAPE;
     return NTK_OK;
@@ -134,6 +139,17 @@ int nt_engine_forward(nt_engine_t e, const int* tokens, int n, int start_pos, fl
     float* d = E(e)->model().forward(tokens, n, start_pos);
     if (!d) return NTK_E_LAUNCH;
     return E(e)->model().copy_logits(logits_out);
+}
+
+int nt_engine_score_tokens(nt_engine_t e, const int* tokens, const int* targets, int n, int start_pos, float* logprob_out, int* top1_out) {
+    if (!e || !tokens || !targets || !logprob_out) return NTK_E_NULL;
+    try {
+        const int rc = E(e)->score(tokens, targets, n, start_pos, logprob_out, top1_out);
+        if (rc != NTK_OK) return rc;
+        int scored = 0;
+        for (int i = 0; i < n; ++i) scored += targets[i] >= 0;
+        return scored;
+    } catch (...) { return NTK_E_NOMEM; }
 }
 
 int nt_engine_decode_fused(nt_engine_t e, int token, int pos, int use_graph, float* logits_out) {

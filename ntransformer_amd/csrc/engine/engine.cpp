@@ -181,6 +181,14 @@ int Engine::decode_greedy_steps(int token, int pos, int n, int* out) {
     return NTK_OK;
 }
 
+int Engine::score(const int* tokens, const int* targets, int n, int start_pos, float* logprob_out, int* top1_out) {
+    if (!loaded_) { err_ = "model not loaded"; return NTK_E_NULL; }
+    model_.set_batched_prefill(opt_.batched_prefill);
+    const int rc = model_.score(tokens, targets, n, start_pos, logprob_out, top1_out);
+    if (rc != NTK_OK) err_ = model_.error();
+    return rc;
+}
+
 std::string Engine::generate(const std::string& prompt, const GenerateConfig& cfg, TokenCallback cb) {
     std::vector<int> tokens = tok_.encode(prompt, true);
     std::string out;

@@ -54,6 +54,8 @@ public:
     int generate_tokens(const std::vector<int>& prompt, const GenerateConfig& cfg, std::vector<int>& out, bool stop_at_eos);
     // n greedy decode steps continuing from (token, pos): the timed inner loop of run(), nothing else.
     int decode_greedy_steps(int token, int pos, int n, int* out);
+    // log P(targets[i] | tokens[0..i]) for every position of a prompt pass at start_pos (Model::score; top1_out may be null)
+    int score(const int* tokens, const int* targets, int n, int start_pos, float* logprob_out, int* top1_out);
     void chat(const GenerateConfig& cfg);
     void benchmark(const std::string& prompt, int n_tokens);
     void print_stats(const Stats& st) const;

@@ -50,6 +50,8 @@ void Model::free_all() {
     k_cache_q8_ = v_cache_q8_ = nullptr; kv_f16_k_ = kv_f16_v_ = nullptr; kv_q8_layer_bytes_ = 0; kv_cache_bytes_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;
     positions_ = tokens_dev_ = d_pos_ = d_token_ = nullptr;
+    score_logits_ = score_logprob_ = nullptr; score_targets_ = score_top1_ = nullptr; score_cap_ = 0;   // (they were in allocs_)
+    score_ws_ = nullptr; score_ws_bytes_ = 0;
 }
 
 int Model::share_weights(const Model& src, int max_context) {

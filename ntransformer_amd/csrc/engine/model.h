@@ -56,6 +56,16 @@ public:
     // any seq_len (prefill = per-token GEMV loops like the reference).  Returns device logits [vocab].
     float* forward(const int* tokens, int seq_len, int start_pos);
 
+    // Scoring (csrc/logprob.hip): the prompt pass over `tokens` at start_pos exactly as forward() runs it -- the KV cache afterwards is forward's, bit for bit --
+    // and then, instead of the last position's logits: the final RMSNorm of ALL rows (into residual_), the LM head over score_rows rows at a time into a
+    // [score_rows][vocab] F32 buffer (the FP16 GEMM where forward's projections take it, read from the repack when the head lies only there; otherwise the
+    // F32-MFMA form or the per-row GEMV) and ntk_logprob_rows on each chunk.  logprob_out[i] = log P(targets[i] | tokens[0..i]) (natural log; 0 where
+    // targets[i] < 0), top1_out[i] (optional) = the greedy token behind tokens[0..i].  One D2H copy and one synchronisation per call.  The chunk buffer and the
+    // device target / result arrays are allocated by the FIRST call (NTK_E_NOMEM + error(): the model stays usable) and freed with the model.  Refused
+    // (NTK_E_SHAPE + error()): ids out of range, a sequence beyond the context, tensor parallelism.
+    int score(const int* tokens, const int* targets, int seq_len, int start_pos, float* logprob_out, int* top1_out);
+    int set_score_rows(int rows);   // rows of logits per LM-head chunk, 1 .. 1024 (default 256: 131 MB at a vocabulary of 128 256); any time
+
     // Fused single-token step: 5 launches per layer, position and token id stay on the device so the whole
     // token is one hipGraph replay.  Token comes from d_token_ (set_device_token / previous argmax).
     // If greedy: also runs the device argmax and advances the position.
@@ -215,7 +225,8 @@ private:
     // y_k = W_k . f(x) for n <= 3 matrices sharing x, in as few fused launches as their formats allow (model_decode.cpp)
     int decode_project(const DevTensor* const* ws, float* const* ys, int n, const float* x, const DevTensor* norm, const float* resid, int kind,
                        int silu_pair = 0, bool timed = true);
-    int layers_1to1(int T, int start_pos, int first, int last);   // the layer loop of forward()
+    int layers_1to1(int T, int start_pos, int first, int last);   // the layer loop of forward() and score()
+    int score_buffers();              // the buffers of score(), on its first call (and again when score_rows grew)
     void prof_mark(int cls, bool begin);
     bool use_persistent_now() const;
     // hooks of experiments/ (model_experiments.cpp); in the product they launch nothing: NTK_E_SHAPE = "not taken", no plan, no error to report
@@ -253,6 +264,14 @@ private:
     float* workspace_ = nullptr;    // max(attention, ffn) floats, shared by all layers
     size_t workspace_floats_ = 0;
     float* logits_ = nullptr;       // [V]
+    int score_rows_ = 256;          // the option (kept across loads)
+    float* score_logits_ = nullptr; // [score_cap_][V]: one chunk of score()'s logits
+    int score_cap_ = 0;
+    int* score_targets_ = nullptr;  // [max_seq] each: score()'s targets, log-probabilities and greedy tokens
+    float* score_logprob_ = nullptr;
+    int* score_top1_ = nullptr;
+    void* score_ws_ = nullptr;      // the FP16 GEMM's workspace for the LM head where gemm_ws_ is too small for vocab rows
+    size_t score_ws_bytes_ = 0;
     int* positions_ = nullptr;      // [max_seq]
     int* tokens_dev_ = nullptr;     // [max_seq]
     int* d_pos_ = nullptr;          // device scalar: position of the token being decoded

@@ -57,6 +57,17 @@ struct OperandPlanes {
     void in_current(const float* X) { of = X; }                              // a projection's pre-pass (or such a producer) has left X's planes in ws[cur]
 };
 
+// the formats and shapes ntk_gemm_quant_f16 takes
+static bool f16_ok(const DevTensor& w) {
+    const bool kq = w.dtype == NTK_DT_Q4_0 || w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K;
+    return (w.dtype == NTK_DT_Q8_0 || kq) && w.in_f % (kq ? 256 : 128) == 0 && w.out_f % 16 == 0 && (w.ptr || w.rp);
+}
+// a K-quant matrix whose GGUF bytes were freed after the load-time repack (one resident copy): the FP16 GEMM reads it FROM THE REPACK
+// (ntk_gemm_desc.weights_repacked: identical bits) -- no unpack in front of the prompt launches
+static bool rp_only(const DevTensor& w) {
+    return !w.ptr && w.rp && (w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K) && w.out_f % 16 == 0;
+}
+
 // layers [first, last) of the 1:1 path on hidden_[T][H] at positions start_pos.. (positions_ already on the device)
 int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
@@ -85,10 +96,6 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     const bool with_max = batched && bf16_now && row_max_ != nullptr && prefill_row_max_;
     float* rm_a = with_max ? row_max_ : nullptr;
     float* rm_b = with_max ? row_max_ + cfg_.max_seq_len : nullptr;
-    auto f16_ok = [&](const DevTensor& w) {   // the formats and shapes ntk_gemm_quant_f16 takes
-        const bool kq = w.dtype == NTK_DT_Q4_0 || w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K;
-        return (w.dtype == NTK_DT_Q8_0 || kq) && w.in_f % (kq ? 256 : 128) == 0 && w.out_f % 16 == 0 && (w.ptr || w.rp);
-    };
     // The form the producer of X takes when X (`width` columns) feeds matrix next_w: it splits X into next_w's planes itself, leaves the tokens' maxima, or
     // neither.  The split: up to 64 tokens (a producer that owns a whole token per workgroup writes its planes in 16-byte pieces a kilobyte apart:
     // faster than the GEMM's own pre-pass at 16 - 64 tokens, slower at 1024), and not under tensor parallelism, where a rank's SiLU launch keeps its maxima
@@ -97,11 +104,6 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     auto x_form = [&](int width, const DevTensor& next_w) {
         if (with_max && prefill_fused_split_ && gemm_ws2_ != nullptr && T <= 64 && tp_world_ == 1 && f16_ok(next_w) && (int)next_w.in_f == width) return XForm::split;
         return with_max ? XForm::row_max : XForm::plain;
-    };
-    // a K-quant matrix whose GGUF bytes were freed after the load-time repack (one resident copy): the FP16 GEMM reads it FROM THE REPACK
-    // (ntk_gemm_desc.weights_repacked: identical bits) -- no unpack in front of the prompt launches
-    auto rp_only = [&](const DevTensor& w) {
-        return !w.ptr && w.rp && (w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K) && w.out_f % 16 == 0;
     };
     // The FP16 GEMM behind its descriptor (ntk_engine.h): 1..3 matrices of one format sharing X, ONE launch.  `raw`: the matrices' GGUF bytes where the
     // caller has them already; without it a group whose every matrix is rp_only is read from the repack, any other group through raw_of() (one raw_begin()
@@ -290,6 +292,122 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
         if (rc != NTK_OK) break;
     }
     if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }   // what raw_of() could not report through its pointer (it precedes the consumer's NTK_E_NULL)
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Scoring: the same prompt pass, then every position's logits in chunks of score_rows_ rows (see model.h)
+// ---------------------------------------------------------------------------------------------------
+int Model::set_score_rows(int rows) {
+    if (rows < 1 || rows > 1024) { err_ = "score_rows must lie in 1 .. 1024"; return NTK_E_SHAPE; }
+    score_rows_ = rows;
+    return NTK_OK;
+}
+
+int Model::score_buffers() {
+    const size_t S = (size_t)cfg_.max_seq_len, V = (size_t)cfg_.vocab_size;
+    auto dev = [&](size_t bytes) -> void* {
+        void* p = nt_hip_malloc(bytes + 256);
+        if (p) allocs_.push_back(p);
+        return p;
+    };
+    auto release = [&](auto*& p) {
+        if (!p) return;
+        allocs_.erase(std::remove(allocs_.begin(), allocs_.end(), (void*)p), allocs_.end());
+        nt_hip_free(p);
+        p = nullptr;
+    };
+    auto fail = [&](const char* what) { err_ = std::string("score: no device memory for ") + what; return NTK_E_NOMEM; };
+    if (!score_targets_ && !(score_targets_ = (int*)dev(S * 4))) return fail("the targets");
+    if (!score_logprob_ && !(score_logprob_ = (float*)dev(S * 4))) return fail("the results");
+    if (!score_top1_ && !(score_top1_ = (int*)dev(S * 4))) return fail("the results");
+    if (score_cap_ < score_rows_) {
+        NT_TRY(sync());   // (an earlier call's launches may still read the smaller buffer)
+        release(score_logits_);
+        score_cap_ = 0;
+        if (!(score_logits_ = (float*)dev((size_t)score_rows_ * V * 4))) return fail("the chunk of logits (score_rows x vocab floats)");
+        score_cap_ = score_rows_;
+    }
+    // the FP16 GEMM sizes its workspace by the matrix's rows: the load-time one covers the layers' projections, not always a vocabulary
+    const size_t need = ntk_gemm_quant_workspace_bytes(cfg_.hidden_size, cfg_.vocab_size);
+    if (gemm_ws_ && bf16_prefill_ && f16_ok(output_) && need > gemm_ws_bytes_ && need > score_ws_bytes_) {
+        release(score_ws_);
+        score_ws_bytes_ = 0;
+        if (!(score_ws_ = dev(need))) return fail("the LM head's GEMM workspace");
+        score_ws_bytes_ = need;
+    }
+    return NTK_OK;
+}
+
+int Model::score(const int* tokens, const int* targets, int T, int start_pos, float* logprob_out, int* top1_out) {
+    if (!tokens || !targets || !logprob_out) { err_ = "score: null argument"; return NTK_E_NULL; }
+    if (tp_world_ > 1) { err_ = "score: not available under tensor parallelism"; return NTK_E_SHAPE; }
+    if (T <= 0) { err_ = "score: no tokens to score"; return NTK_E_SHAPE; }
+    if (start_pos < 0 || start_pos + T > cfg_.max_seq_len) { err_ = "score: sequence exceeds context"; return NTK_E_SHAPE; }
+    const int H = cfg_.hidden_size, V = cfg_.vocab_size;
+    for (int i = 0; i < T; ++i) {   // the embedding gather and the target gather index with these on the device
+        if (tokens[i] < 0 || tokens[i] >= V) { err_ = "score: token id out of range"; return NTK_E_SHAPE; }
+        if (targets[i] >= V) { err_ = "score: target id out of range"; return NTK_E_SHAPE; }
+    }
+    NT_TRY(score_buffers());
+    void* s = stream_;
+    tp_call_ = 0;
+    // embedding and positions as forward() has them
+    NT_TRY(ntk_memcpy_h2d_async(tokens_dev_, tokens, (size_t)T * 4, s));
+    NT_TRY(ntk_memcpy_h2d_async(score_targets_, targets, (size_t)T * 4, s));
+    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, tokens_dev_, T, H, token_embd_.dtype, s);
+    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
+    else if (est != NTK_OK) return est;
+    std::vector<int> pos(T);
+    for (int i = 0; i < T; ++i) pos[i] = start_pos + i;
+    NT_TRY(ntk_memcpy_h2d_async(positions_, pos.data(), (size_t)T * 4, s));
+    NT_TRY(ntk_stream_synchronize(s));   // `pos` / `tokens` / `targets` are host memory of the caller
+
+    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers);
+    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
+    // the final RMSNorm of every row, beside hidden_ (with the rows' largest |x| where the FP16 GEMM reads the head)
+    const DevTensor& w = output_;
+    const bool batched = batched_prefill_ && is_quant(w.dtype);
+    const bool f16 = batched && bf16_prefill_ && gemm_ws_ && f16_ok(w);
+    const float* rm = f16 && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
+    if (rm) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)output_norm_.ptr, T, H, cfg_.norm_eps, row_max_, nullptr, s));
+    else ok(ntk_rmsnorm(residual_, hidden_, (const float*)output_norm_.ptr, T, H, cfg_.norm_eps, s));
+    void* const ws = score_ws_ ? score_ws_ : gemm_ws_;
+    const size_t ws_bytes = score_ws_ ? score_ws_bytes_ : gemm_ws_bytes_;
+    // logits of rows [t0, t0 + n): one pass over the head per chunk
+    auto head = [&](const float* X, int n, const float* chunk_max) -> int {
+        int st = NTK_E_DTYPE;
+        if (f16) {
+            const bool repacked = rp_only(w);
+            if (!repacked) raw_begin();
+            const ntk_gemv_seg seg{repacked ? w.rp : raw_of(w), score_logits_, V, w.dtype};
+            ntk_gemm_desc d{};
+            d.segs = &seg; d.nseg = 1; d.X = X; d.n_tokens = n; d.in_features = H;
+            d.workspace = ws; d.workspace_bytes = ws_bytes; d.row_max = chunk_max; d.weights_repacked = repacked ? 1 : 0;
+            d.full_form = 1;   // the same bits whatever score_rows cuts the rows into (the form is otherwise chosen by the call's token count)
+            st = ntk_gemm_quant_f16(&d, s);
+        }
+        if (batched && not_taken(st)) { raw_begin(); st = ntk_gemm_quant(score_logits_, raw_of(w), X, n, V, H, w.dtype, nullptr, s); }
+        if (batched && !not_taken(st)) return st;
+        raw_begin();   // dense heads and shapes the matrix-core forms do not take: the reference's GEMV, row by row
+        const void* wp = raw_of(w);
+        for (int t = 0; t < n; ++t) {
+            st = ntk_gemv(score_logits_ + (size_t)t * V, wp, X + (size_t)t * H, V, H, w.dtype, s);
+            if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
+            if (st != NTK_OK) return st;
+        }
+        return NTK_OK;
+    };
+    for (int t0 = 0; t0 < T && rc == NTK_OK; t0 += score_rows_) {
+        const int n = std::min(score_rows_, T - t0);
+        ok(head(residual_ + (size_t)t0 * H, n, rm ? rm + t0 : nullptr));
+        ok(ntk_logprob_rows(score_logits_, n, V, V, score_targets_ + t0, score_logprob_ + t0, top1_out ? score_top1_ + t0 : nullptr, s));
+    }
+    if (rc == NTK_OK) ok(ntk_memcpy_d2h_async(logprob_out, score_logprob_, (size_t)T * 4, s));
+    if (rc == NTK_OK && top1_out) ok(ntk_memcpy_d2h_async(top1_out, score_top1_, (size_t)T * 4, s));
+    ok(ntk_stream_synchronize(s));
+    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
+    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("score failed: ") + ntk_status_string(rc);
     return rc;
 }
 

@@ -1984,7 +1984,9 @@ struct HostSeg { float* Y; const void* W; int out; };
 // T <= GB_MAX_CHUNKS * 64 = 1024 tokens in one launch; nseg matrices [out_s][in] of one format sharing X
 template <int DT>
 static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T, int in, const float* resid, void* ws, int reuse_x,
-                            const float* row_max, ntk_gemm_partials* defer, hipStream_t st) {
+                            const float* row_max, ntk_gemm_partials* defer, bool full_form, hipStream_t st) {
+    // (full_form: the form, K split and chunk pairing of a full pass -- GB_MAX_CHUNKS chunks -- whatever T is, never the short-prompt forms: a token's
+    // sums then run in the same order however the caller cuts its tokens into calls -- ntk_gemm_desc.full_form)
     using D = DeqI<DT>;
     constexpr int TRIP = GB_UPT * D::SPU;   // steps per loop trip: K ranges are whole trips
     // whole units only (Q8_0: in a multiple of 128, Q4_0 and the K-quants: of 256): a partial last unit would decode the next row's bytes as
@@ -2032,7 +2034,7 @@ static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T,
     // (Q8_0: -DNTK_GK_Q8_BLOCKS=16 or 8 runs this form in wide units, DeqI<NTK_DT_Q8_0 + GB_WIDE> -- measured slower: see there; the default keeps KDT = DT)
     constexpr int KDT = (DT == NTK_DT_Q8_0 && NTK_GK_Q8_BLOCKS > 4) ? NTK_DT_Q8_0 + GB_WIDE : DT;
     using KD = DeqI<KDT>;
-    if (T <= kslice_max && T <= 32 && in % (32 * KD::SPU) == 0) {
+    if (!full_form && T <= kslice_max && T <= 32 && in % (32 * KD::SPU) == 0) {
         const int ntb = T <= 16 ? 1 : 2;
         const int units = in / (32 * KD::SPU);
         static const int c0 = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_C0", 32), force_krt = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_RT", 0),
@@ -2142,7 +2144,7 @@ static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T,
     // weights in flight per wave changed nothing -- the next step up needs the planes resident in LDS, i.e. the large kernel's structure.
     static const int small_env = NTK_TUNE_ENV_INT("NTK_GEMM_SMALL", -1);   // (tuning builds only: 0 = never, n = up to n tokens)
     const int small_max = small_env >= 0 ? small_env : ((D::HAS_MIN || D::SPLIT16) ? 32 : 16);
-    if (T <= small_max && T <= 32) {
+    if (!full_form && T <= small_max && T <= 32) {
         GemmSParams sp{};
         sp.nseg = nseg; sp.T = T; sp.in = in; sp.steps = in / 32; sp.row_bytes = (unsigned)row_bytes;
         sp.xb = wsb; sp.aux = reinterpret_cast<const uint8_t*>(p.aux); sp.inv = scales; sp.resid = resid;
@@ -2203,7 +2205,8 @@ static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T,
     // sums of many splits cost more than the idle half buys (same box, 8B Q8_0: 256 tokens 16 370 -> 17 000 tok/s, 512 19 830 -> 20 950;
     // 64 tokens 8 090 -> 7 570 with the same rule, which is why it stops there)
     static const int want_env = NTK_TUNE_ENV_INT("NTK_GEMM_WGS", 0);   // (tuning builds only)
-    const int want_wgs = want_env ? want_env : (p.chunks >= 4 ? 512 : 256);
+    const int plan_chunks = full_form ? GB_MAX_CHUNKS : p.chunks;   // the chunk count the plan below is made for
+    const int want_wgs = want_env ? want_env : (plan_chunks >= 4 ? 512 : 256);
     int rt = out_total >= 2048 ? 2 : 1;
     if (force_rt == 1 || force_rt == 2) rt = force_rt;
     int tiles = 0;
@@ -2228,7 +2231,7 @@ static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T,
     constexpr bool PFD = DeqI<DT>::PF, CW2_OK = !DeqI<DT>::SPLIT16 && DT != NTK_DT_Q5_K && DT != NTK_DT_Q5_K + GB_RP;   // (Q5_K: 15 registers over the budget in that form)
     // K splits of a plan with `groups` workgroup columns: doubled while the grid is short of `want_wgs`, whole trips, and
     // splits x 64-token chunks within the partial-sum area (gb_split_rows)
-    const int chunks64 = p.chunks, max_rows = gb_split_rows((int)out_total);
+    const int chunks64 = plan_chunks, max_rows = gb_split_rows((int)out_total);
     auto splits_for = [&](int groups) {
         int n = 1;
         while (n * 2 * chunks64 <= max_rows && (long)p.row_wgs * groups * n < want_wgs && trips / (n * 2) >= 1) n *= 2;
@@ -2240,7 +2243,7 @@ static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T,
     bool cw2 = false;
     if (CW2_OK && al && rt == 2 && chunks64 >= 2 && force_cw != 1) {
         const int pairs = (chunks64 + 1) / 2, n2 = splits_for(pairs);
-        if ((n2 <= 2 && (long)p.row_wgs * pairs * n2 >= 512) || force_cw == 2) { cw2 = true; nsplit = n2; p.chunks = pairs; }
+        if ((n2 <= 2 && (long)p.row_wgs * pairs * n2 >= 512) || force_cw == 2) { cw2 = true; nsplit = n2; p.chunks = (p.chunks + 1) / 2; }
     }
     const int tps = (trips + nsplit - 1) / nsplit;   // trips per split
     nsplit = (trips + tps - 1) / tps;                // no empty split
@@ -2315,7 +2318,7 @@ size_t ntk_gemm_quant_workspace_bytes(int in_features, int out_features) {
 }
 
 static int gemm_ws_dispatch(const ntk::HostSeg* segs, int nseg, const float* X, int n_tokens, int in_features, int weight_dtype, const float* resid,
-                            void* workspace, int reuse_x, const float* row_max, ntk_gemm_partials* defer, hipStream_t st) {
+                            void* workspace, int reuse_x, const float* row_max, ntk_gemm_partials* defer, int full_form, hipStream_t st) {
     // (weight_dtype + ntk::GB_RP: the matrices are tensors of the engine's decode repack)
     constexpr int PASS = ntk::GB_MAX_CHUNKS * ntk::GB_TOK;
     if (n_tokens > PASS) reuse_x = 0;   // the planes hold one pass (1024 tokens) at a time
@@ -2333,14 +2336,14 @@ static int gemm_ws_dispatch(const ntk::HostSeg* segs, int nseg, const float* X, 
         const float* rm = row_max ? row_max + t0 : nullptr;
         int rc;
         switch (weight_dtype) {
-            case NTK_DT_Q8_0: rc = ntk::launch_gemm_f16<NTK_DT_Q8_0>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
-            case NTK_DT_Q4_0: rc = ntk::launch_gemm_f16<NTK_DT_Q4_0>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
-            case NTK_DT_Q4_K: rc = ntk::launch_gemm_f16<NTK_DT_Q4_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
-            case NTK_DT_Q5_K: rc = ntk::launch_gemm_f16<NTK_DT_Q5_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
-            case NTK_DT_Q4_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q4_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
-            case NTK_DT_Q5_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q5_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
-            case NTK_DT_Q6_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q6_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
-            default: rc = ntk::launch_gemm_f16<NTK_DT_Q6_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, st); break;
+            case NTK_DT_Q8_0: rc = ntk::launch_gemm_f16<NTK_DT_Q8_0>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
+            case NTK_DT_Q4_0: rc = ntk::launch_gemm_f16<NTK_DT_Q4_0>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
+            case NTK_DT_Q4_K: rc = ntk::launch_gemm_f16<NTK_DT_Q4_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
+            case NTK_DT_Q5_K: rc = ntk::launch_gemm_f16<NTK_DT_Q5_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
+            case NTK_DT_Q4_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q4_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
+            case NTK_DT_Q5_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q5_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
+            case NTK_DT_Q6_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q6_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
+            default: rc = ntk::launch_gemm_f16<NTK_DT_Q6_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
         }
         if (rc != NTK_OK) return rc;
     }
@@ -2375,7 +2378,7 @@ int ntk_gemm_quant_f16(const ntk_gemm_desc* d, void* stream) {
     }
     if (n_tokens == 0 || total == 0) return NTK_OK;
     // (resid with partials: added by the launch's own epilogue when it does not split K -- nothing is deferred then; left to the consumer when it does)
-    return gemm_ws_dispatch(sg, nseg, d->X, n_tokens, in_features, dt, d->resid, d->workspace, d->reuse_x, d->row_max, defer, ntk::resolve_stream(stream));
+    return gemm_ws_dispatch(sg, nseg, d->X, n_tokens, in_features, dt, d->resid, d->workspace, d->reuse_x, d->row_max, defer, d->full_form, ntk::resolve_stream(stream));
 }
 
 // hidden[t] += W . X[t] (the projection's splits summed here, residual last) and x_out[t] = rmsnorm(hidden[t]) with its largest |x|

@@ -67,6 +67,7 @@ def _bind():
     L.nt_engine_last_stats.argtypes = [vp, C.POINTER(CStats)]
     L.nt_engine_forward.argtypes = [vp, C.POINTER(i), i, i, vp]
     L.nt_engine_decode_fused.argtypes = [vp, i, i, i, vp]
+    L.nt_engine_score_tokens.argtypes = [vp, C.POINTER(i), C.POINTER(i), i, i, vp, vp]
     L.nt_engine_tokenize.argtypes = [vp, C.c_char_p, i, C.POINTER(i), i]
     L.nt_engine_detokenize.argtypes = [vp, C.POINTER(i), i, C.c_char_p, i]
     L.nt_engine_bytes_per_token.argtypes = [vp, i]
@@ -184,6 +185,48 @@ class Engine:
         out = np.empty(self.vocab_size, np.float32)
         self._check(self.L.nt_engine_decode_fused(self.h, int(token), pos, int(graph), out.ctypes.data_as(C.c_void_p)), "decode_fused")
         return out
+
+    @property
+    def max_context(self): return self.L.nt_engine_max_context(self.h)
+
+    def score(self, tokens: Sequence[int], start_pos: int = 0, targets: Optional[Sequence[int]] = None, top1: bool = False):
+        """log P(targets[i] | tokens[0..i]) (natural log) as float32 [len(tokens)], 0 where targets[i] < 0 -- one prompt pass at start_pos
+        (nt_engine_score_tokens; the KV cache afterwards is forward's).  targets default to the next token: tokens[1:] + [-1].
+        top1=True: (logprobs, int32 greedy token behind every prefix)."""
+        n = len(tokens)
+        tg = (list(tokens[1:]) + [-1])[:n] if targets is None else list(targets)
+        if len(tg) != n:
+            raise ValueError("score: %d targets for %d tokens" % (len(tg), n))
+        arr = (C.c_int * n)(*[int(t) for t in tokens])
+        tarr = (C.c_int * n)(*[int(t) for t in tg])
+        lp = np.empty(n, np.float32)
+        ids = np.empty(n, np.int32) if top1 else None
+        st = self.L.nt_engine_score_tokens(self.h, arr, tarr, n, start_pos, lp.ctypes.data_as(C.c_void_p),
+                                           ids.ctypes.data_as(C.c_void_p) if top1 else None)
+        if st < 0:
+            self._check(st, "score")
+        return (lp, ids) if top1 else lp
+
+    def perplexity(self, tokens: Sequence[int], window: Optional[int] = None, bos: Optional[int] = None):
+        """(exp(-mean log P), number of scored tokens) over windows of at most `window` tokens (default and at most the context), each scored from
+        position 0, the sum kept in float64.
+        bos=None: the windows are cut from `tokens` as they are; a window's first token is context only and is not scored (n_scored = len(tokens)
+        - the number of windows), and a last window of ONE token has nothing to score.
+        bos=<id>: what `ntransformer --perplexity` computes on text tokenised WITHOUT a BOS -- windows of window - 1 tokens with `bos` put in front of
+        each, every token of `tokens` scored (n_scored = len(tokens))."""
+        ctx = self.max_context
+        window = ctx if window is None else max(2, min(int(window), ctx))
+        per = window if bos is None else window - 1
+        total, count = 0.0, 0
+        for w0 in range(0, len(tokens), per):
+            chunk = ([] if bos is None else [int(bos)]) + list(tokens[w0:w0 + per])
+            if len(chunk) < 2:
+                break
+            total += float(self.score(chunk)[:-1].astype(np.float64).sum())
+            count += len(chunk) - 1
+        if count == 0:
+            raise ValueError("perplexity: nothing to score (fewer than two tokens in a window)")
+        return float(np.exp(-total / count)), count
 
     # ---- parity instrumentation (include/ntransformer.h: nt_engine_debug_*) ----
     def debug_run_layers(self, hidden_in: np.ndarray, start_pos: int, first: int, count: int = 1, mode: int = 0) -> np.ndarray:

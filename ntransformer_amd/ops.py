@@ -228,7 +228,7 @@ def gemv_rp_fused(segs: Sequence[tuple], x, in_features, norm_w=None, eps=0.0, r
 
 
 def _gemm_quant_f16(segs, X, n_tokens, in_features, resid=None, row_max=None, partials=None, stream=None, keep=None, repacked=False, workspace=None,
-                    reuse_x=0):
+                    reuse_x=0, full_form=False):
     """ntk_gemm_quant_f16 behind its descriptor (include/ntk_engine.h: ntk_gemm_desc); segs = [(W, Y, rows, dtype), ...] of one format sharing X.  The
     workspace is allocated here (and kept alive in `keep` when the caller's next launch reads the deferred partial sums)."""
     L = _lib.lib()
@@ -243,6 +243,7 @@ def _gemm_quant_f16(segs, X, n_tokens, in_features, resid=None, row_max=None, pa
     d.workspace, d.workspace_bytes, d.reuse_x, d.row_max = ws.ptr, n, int(reuse_x), _p(row_max)
     d.partials = C.pointer(partials) if partials is not None else None
     d.weights_repacked = 1 if repacked else 0
+    d.full_form = 1 if full_form else 0   # the form of a full 1024-token pass whatever n_tokens is: chunking-independent bits
     L.ntk_gemm_quant_f16.argtypes = [C.POINTER(_lib.GemmDesc), C.c_void_p]
     st = L.ntk_gemm_quant_f16(C.byref(d), stream)
     if keep is not None:
@@ -419,6 +420,12 @@ def embed_rows(out, table, tokens, n_tokens, hidden, dtype, stream=None, allow_u
 
 def argmax(logits, n, d_out_token, scratch, h_mirror=None, stream=None):
     check(_lib.lib().ntk_argmax(_p(logits), n, _p(d_out_token), _p(h_mirror), _p(scratch), stream), "argmax")
+
+
+def logprob_rows(logits, n_rows, vocab, ld, targets, logprob, top1=None, stream=None):
+    """ntk_logprob_rows: logprob[r] = log softmax(logits[r, :vocab])[targets[r]] (0 where targets[r] < 0), top1[r] (optional) = the row's first maximum;
+    logits: device F32 [n_rows][ld], targets / top1: device int32 [n_rows]"""
+    check(_lib.lib().ntk_logprob_rows(_p(logits), n_rows, vocab, ld, _p(targets), _p(logprob), _p(top1), stream), "logprob_rows")
 
 
 def advance_pos(d_pos, stream=None):
