@@ -107,6 +107,26 @@ int ntk_attention_decode_split_merged(float* output, const float* q, const float
                                       int head_dim, int max_seq, float scale, float theta_base, float freq_scale, int nsplit,
                                       float* scratch, void* stream);
 
+/* Decode attention for a BATCH of sequences (csrc/attention_batch.hip; no reference counterpart): for each of n_rows rows, 1 <= n_rows <=
+ * NTK_ATTN_BATCH_MAX, what ntk_attention_decode_fused (nsplit == 1) / ntk_attention_decode_split (nsplit > 1: + ONE combine launch for all rows) do for
+ * one row, in one launch -- the same device functions, the same bits as the single-row launch of the same form, and a row's result depends on nothing
+ * but that row (permuting the rows permutes the outputs).  q [n_rows][n_heads * head_dim], k, v [n_rows][n_kv_heads * head_dim] F32, unrotated, only
+ * read; positions DEVICE int [n_rows]; caches: HOST struct with the rows' K and V cache base pointers for this layer ([max_seq][n_kv_heads][head_dim]
+ * half each; entries past n_rows are ignored), copied BY VALUE into the launch -- no device table.  Row b: RoPE of q and k at positions[b] (inv_freq as
+ * in the single-row kernels), k and v stored as F16 (RNE) into row positions[b] of cache b -- the ONLY cache rows written -- and attention over rows
+ * 0 .. positions[b] of cache b into output[b]; rows past positions[b] may hold anything.  A split that lies wholly past a row's position contributes
+ * nothing.  nsplit >= 16 at head_dim 128 with <= 16 query heads per KV head: the matrix-core form.  scratch (nsplit > 1): n_rows x
+ * ntk_attention_split_scratch_bytes(n_heads, head_dim, nsplit).  Two rows must not name the same cache (unchecked; every position must lie in
+ * [0, max_seq): the caller validates).  NTK_E_SHAPE: n_rows outside 1 .. 16, head sizes / split counts the single-row kernels refuse; NTK_E_NULL. */
+#define NTK_ATTN_BATCH_MAX 16
+typedef struct ntk_kv_batch {
+    void* k[NTK_ATTN_BATCH_MAX];
+    void* v[NTK_ATTN_BATCH_MAX];
+} ntk_kv_batch;
+int ntk_attention_decode_batch(float* output, const float* q, const float* k, const float* v, const ntk_kv_batch* caches, const int* positions,
+                               int n_rows, const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq, float scale,
+                               float theta_base, float freq_scale, int nsplit, float* scratch, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The 8-bit (Q8_0) KV cache (csrc/attention_q8.hip; no reference counterpart).  A cache row holds Q8_0 values along head_dim: every 32
  * consecutive elements of a head's row share one IEEE-half scale d and carry 32 int8 q -- ggml's quantize_row_q8_0_ref arithmetic in F32

@@ -81,6 +81,10 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * the 8-bit rows on the matrix cores using half(d) * q exactly; prompt passes (and "fused" = "0") dequantise rows [0, start_pos + n) into the F16 image
  * -- rounded to half, the chunk's own rows included -- and run the F16 attention kernels over it.  Refused at load (NTK_E_SHAPE + last_error): head_dim
  * other than 128, more than 16 query heads per KV head, tensor parallelism, "fuse_attention";
+ * "sequences" = "1" .. "16" (default "1"): sequence slots of this engine for the batched decode step below.  Slot 0 is the KV cache every other entry point
+ * uses, exactly as without the option; slots 1 .. N - 1 are extra F16 caches of the same layout, allocated at load (counted in nt_engine_kv_cache_bytes)
+ * beside a [16][vocab] F32 logits buffer.  Set it BEFORE the load (afterwards: NTK_E_SHAPE + last_error); an nt_engine_load_shared sequence takes its own.
+ * Refused at load (NTK_E_SHAPE + last_error) when > 1 together with "kv_cache" = "q8_0", tensor parallelism or a context of fewer than N positions;
  * "score_rows" = "1" .. "1024" (default "256"): rows of logits nt_engine_score_tokens computes per pass over the LM head (score_rows x vocab floats of device
  * memory from the first scoring call on; any time). */
 int  nt_engine_set_option(nt_engine_t e, const char* key, const char* value);
@@ -91,6 +95,27 @@ int  nt_engine_generate_tokens(nt_engine_t e, const int* prompt, int n_prompt, c
 int  nt_engine_last_stats(nt_engine_t e, nt_stats* out);
 /* Transformer::forward: tokens [n] at start_pos -> logits of the last position copied to host (vocab floats) */
 int  nt_engine_forward(nt_engine_t e, const int* tokens, int n, int start_pos, float* logits_out);
+/* ---- sequence slots: several requests per pass over the weights ("sequences" option) -------------------------------------------------------
+ * ARITHMETIC CONTRACT of the batched step: every row is computed with the PROMPT PASS's arithmetic -- projections on the FP16 matrix cores with two FP16
+ * pieces per activation -- and the decode kernels' attention; NOT the decode GEMV's arithmetic.  A sequence's logits therefore agree with its solo
+ * nt_engine_decode_fused run to the project's 1e-3 bar, not bit for bit, and its greedy stream may differ at a near tie.  Within one batch size a row's
+ * result depends on nothing but that row (every output element of the GEMM is accumulated on its own, the launch form is chosen by the row count alone):
+ * companions, their order and their slots do not matter.  No bit claim across batch sizes.
+ * nt_engine_seq_forward: nt_engine_forward into the KV cache of sequence slot `slot` (slot 0: the same call as nt_engine_forward, bit for bit).
+ * nt_engine_decode_batch: ONE decode step of n sequences: row i = token tokens[i] of the sequence in slots[i] at position positions[i] (its K / V row is
+ * stored there, attention runs over rows 0 .. positions[i] of that slot).  logits_out [n][vocab] and next_out [n] (each row's greedy token: first maximum)
+ * may each be NULL.  Eager, one synchronisation; leaves the fused path's slot-0 state (device position / token, captured graphs) alone.  Refused
+ * (NTK_E_SHAPE + last_error; the engine stays usable): n outside 1 .. "sequences", a slot out of range or named twice, a position outside the context,
+ * a token id out of range.
+ * nt_engine_generate_batch: n prompts (prompts[i][0 .. prompt_lens[i])) generated in lockstep, GREEDY: prompt i is prefilled into slot i, then all live
+ * sequences step together; a sequence leaves the batch at EOS (stop_at_eos; the EOS token is written) or at max_tokens.  out [n][out_stride] receives the
+ * generated ids, out_counts [n] how many.  Returns n or a negative NTK_E_*; temperature > 0 or repeat_penalty != 1: NTK_E_SHAPE + last_error (sample from
+ * nt_engine_decode_batch's logits instead).  nt_engine_last_stats: prompt and generated tokens summed over the sequences (as nt_engine_generate_tokens
+ * counts them: without each sequence's first token), the aggregate decode rate. */
+int  nt_engine_seq_forward(nt_engine_t e, int slot, const int* tokens, int n, int start_pos, float* logits_out);
+int  nt_engine_decode_batch(nt_engine_t e, const int* slots, const int* tokens, const int* positions, int n, float* logits_out, int* next_out);
+int  nt_engine_generate_batch(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* p, int* out, int out_stride,
+                              int* out_counts);
 /* Scoring: logprob_out[i] = log P(targets[i] | tokens[0..i]) (natural log) for targets[i] >= 0, 0 where targets[i] < 0; top1_out (optional, may be NULL):
  * the greedy token behind tokens[0..i] for every i.  Runs the prompt pass over tokens at start_pos (the KV cache afterwards = nt_engine_forward's), then
  * the LM head over "score_rows" positions at a time; returns the number of scored positions or a negative NTK_E_* (+ nt_engine_last_error: an id out of
@@ -145,6 +170,10 @@ int  nt_engine_debug_run_layers(nt_engine_t e, const float* hidden_in, int n_tok
                                 int mode, float* hidden_out);
 int  nt_engine_debug_kv_read(nt_engine_t e, int layer, int pos0, int n, uint16_t* k_out, uint16_t* v_out);
 int  nt_engine_debug_kv_write(nt_engine_t e, int layer, int pos0, int n, const uint16_t* k, const uint16_t* v);
+/* TEST SUPPORT, host only (no engine, no device): the argument checks of nt_engine_decode_batch for an engine of `sequences` slots, `max_seq` positions and
+ * `vocab` ids -- NTK_OK, NTK_E_NULL or NTK_E_SHAPE (tests/test_batch_validate_cpu.py) */
+int  nt_batch_validate(const int* slots, const int* tokens, const int* positions, int n, int sequences, int max_seq, int vocab);
+int  nt_engine_debug_kv_read_slot(nt_engine_t e, int slot, int layer, int pos0, int n, uint16_t* k_out, uint16_t* v_out);   /* ... of sequence slot `slot` */
 /* ... of a "kv_cache" = "q8_0" engine: the rows as canonical 34-byte GGUF block_q8_0 {half d; int8 q[32]}, [n][n_kv_heads * head_dim / 32] blocks per
  * side.  Each pair returns NTK_E_DTYPE on an engine of the other cache format. */
 int  nt_engine_debug_kv_read_q8(nt_engine_t e, int layer, int pos0, int n, void* k_blocks_out, void* v_blocks_out);

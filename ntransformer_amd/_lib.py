@@ -26,6 +26,10 @@ def check(status: int, what: str = "") -> None:
         raise NtkError(status, what)
 
 
+class KvBatch(C.Structure):   # ntk_kv_batch: the rows' cache base pointers of one layer
+    _fields_ = [("k", C.c_void_p * 16), ("v", C.c_void_p * 16)]
+
+
 class GemvSeg(C.Structure):
     _fields_ = [("W", C.c_void_p), ("y", C.c_void_p), ("rows", C.c_int), ("dtype", C.c_int)]
 
@@ -116,6 +120,7 @@ def lib() -> C.CDLL:
         "ntk_attention_split_scratch_init": (i, [vp, i, vp]),
         "ntk_attention_decode_split_merged": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_attention_decode_fused": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, vp]),
+        "ntk_attention_decode_batch": (i, [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_kv_q8_cache_bytes": (C.c_size_t, [i, i, i]),
         "ntk_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, i, vp]),
         "ntk_rope_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp]),

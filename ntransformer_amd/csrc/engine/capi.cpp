@@ -65,6 +65,11 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
         return rc;
     }
+    else if (k == "sequences") {   // "1" .. "16" sequence slots: before the load only
+        const int rc = E(e)->loaded() ? (E(e)->set_error("sequences must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_sequences(atoi(value));
+        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
+        return rc;
+    }
     else if (k == "prefill_row_max") E(e)->model().set_prefill_row_max(on);   // 1 (default): see Model::prefill_row_max_
     else if (k == "prefill_fused_split") E(e)->model().set_prefill_fused_split(on);   // 1 (default): see Model::prefill_fused_split_
     else if (k == "attention_merge") return E(e)->model().set_attention_merge(on);   // 1: split-KV attention without the combine launch (default 0: measured slower)
@@ -141,6 +146,34 @@ int nt_engine_forward(nt_engine_t e, const int* tokens, int n, int start_pos, fl
     return E(e)->model().copy_logits(logits_out);
 }
 
+int nt_engine_seq_forward(nt_engine_t e, int slot, const int* tokens, int n, int start_pos, float* logits_out) {
+    if (!e || !tokens || !logits_out) return NTK_E_NULL;
+    if (!E(e)->loaded()) return NTK_E_NULL;
+    if (slot < 0 || slot >= E(e)->model().sequences()) { E(e)->set_error("seq_forward: no such sequence slot"); return NTK_E_SHAPE; }
+    float* d = E(e)->model().forward(tokens, n, start_pos, slot);
+    if (!d) { E(e)->set_error(E(e)->model().error()); return NTK_E_LAUNCH; }
+    return E(e)->model().copy_logits(logits_out);
+}
+
+int nt_engine_decode_batch(nt_engine_t e, const int* slots, const int* tokens, const int* positions, int n, float* logits_out, int* next_out) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    try {
+        const int rc = E(e)->model().decode_batch(slots, tokens, positions, n, logits_out, next_out);
+        if (rc != NTK_OK) E(e)->set_error(E(e)->model().error());
+        return rc;
+    } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_engine_generate_batch(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* p, int* out, int out_stride,
+                             int* out_counts) {
+    if (!e || !prompts || !prompt_lens || !p || !out || !out_counts) return NTK_E_NULL;
+    try { return E(e)->generate_batch(prompts, prompt_lens, n, *p, out, out_stride, out_counts); } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_batch_validate(const int* slots, const int* tokens, const int* positions, int n, int sequences, int max_seq, int vocab) {
+    return nt::Model::validate_batch(slots, tokens, positions, n, sequences, max_seq, vocab, nullptr);   // host only
+}
+
 int nt_engine_score_tokens(nt_engine_t e, const int* tokens, const int* targets, int n, int start_pos, float* logprob_out, int* top1_out) {
     if (!e || !tokens || !targets || !logprob_out) return NTK_E_NULL;
     try {
@@ -174,6 +207,10 @@ int nt_engine_debug_run_layers(nt_engine_t e, const float* hidden_in, int n_toke
 int nt_engine_debug_kv_read(nt_engine_t e, int layer, int pos0, int n, uint16_t* k_out, uint16_t* v_out) {
     if (!e || !E(e)->loaded()) return NTK_E_NULL;
     return E(e)->model().debug_kv(layer, pos0, n, k_out, v_out, false);
+}
+int nt_engine_debug_kv_read_slot(nt_engine_t e, int slot, int layer, int pos0, int n, uint16_t* k_out, uint16_t* v_out) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv(layer, pos0, n, k_out, v_out, false, slot);
 }
 int nt_engine_debug_kv_write(nt_engine_t e, int layer, int pos0, int n, const uint16_t* k, const uint16_t* v) {
     if (!e || !E(e)->loaded()) return NTK_E_NULL;

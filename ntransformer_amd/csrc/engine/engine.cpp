@@ -41,6 +41,59 @@ int Engine::load_shared(Engine& src, int max_context) {
     return NTK_OK;
 }
 
+int Engine::generate_batch(const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params& p, int* out, int out_stride, int* out_counts) {
+    stats_ = Stats();
+    if (!loaded_) { err_ = "model not loaded"; return NTK_E_NULL; }
+    if (n < 1 || n > model_.sequences()) { err_ = "generate_batch: the batch must hold 1 .. `sequences` prompts"; return NTK_E_SHAPE; }
+    if (p.temperature > 0.0f || p.repeat_penalty != 1.0f) {
+        err_ = "generate_batch: greedy only (temperature <= 0, repeat_penalty 1); sample from nt_engine_decode_batch's logits";
+        return NTK_E_SHAPE;
+    }
+    if (p.max_tokens < 1 || out_stride < p.max_tokens) { err_ = "generate_batch: out_stride must hold max_tokens >= 1 ids per sequence"; return NTK_E_SHAPE; }
+    const int V = model_.config().vocab_size, max_pos = model_.config().max_seq_len, eos = tok_.eos_id();
+    for (int i = 0; i < n; ++i) {
+        if (!prompts[i]) { err_ = "generate_batch: null prompt"; return NTK_E_NULL; }
+        if (prompt_lens[i] < 1 || prompt_lens[i] > max_pos) { err_ = "generate_batch: a prompt is empty or exceeds the context"; return NTK_E_SHAPE; }
+    }
+    // prefill, slot by slot; the first token of each sequence is the first maximum of its prompt's logits (Sampler::argmax)
+    std::vector<float> host(V);
+    std::vector<int> last(n), pos(n);
+    std::vector<char> live(n, 1);
+    model_.set_batched_prefill(opt_.batched_prefill);
+    auto t0 = Clock::now();
+    for (int i = 0; i < n; ++i) {
+        if (!model_.forward(prompts[i], prompt_lens[i], 0, i)) { err_ = model_.error(); return NTK_E_LAUNCH; }
+        if (model_.copy_logits(host.data()) != NTK_OK) return NTK_E_LAUNCH;
+        int best = 0;
+        for (int j = 1; j < V; ++j) if (host[j] > host[best]) best = j;
+        out[(size_t)i * out_stride] = last[i] = best;
+        out_counts[i] = 1;
+        pos[i] = prompt_lens[i];
+        stats_.prompt_tokens += prompt_lens[i];
+    }
+    stats_.prefill_ms = ms_since(t0);
+    int slots[Model::kMaxSequences], toks[Model::kMaxSequences], poss[Model::kMaxSequences], next[Model::kMaxSequences];
+    auto d0 = Clock::now();
+    int rc = NTK_OK;
+    for (;;) {
+        int B = 0;
+        for (int i = 0; i < n; ++i) {   // who is still in: not at EOS, below max_tokens, inside the context
+            if (live[i] && ((p.stop_at_eos && last[i] == eos) || out_counts[i] >= p.max_tokens || pos[i] >= max_pos)) live[i] = 0;
+            if (live[i]) { slots[B] = i; toks[B] = last[i]; poss[B] = pos[i]; ++B; }
+        }
+        if (B == 0) break;
+        if ((rc = model_.decode_batch(slots, toks, poss, B, nullptr, next)) != NTK_OK) { err_ = model_.error(); break; }
+        for (int b = 0; b < B; ++b) {
+            const int i = slots[b];
+            out[(size_t)i * out_stride + out_counts[i]++] = last[i] = next[b];
+            ++pos[i];
+            ++stats_.gen_tokens;
+        }
+    }
+    stats_.decode_ms = ms_since(d0);
+    return rc == NTK_OK ? n : rc;
+}
+
 // One generation, reference engine.cpp:40-145 step for step:
 //   prefill (timed) -> logits -> repeat penalty -> sample first token -> decode loop (timed as a whole;
 //   gen_tokens counts loop iterations, so the first sampled token is not counted) -> stop at EOS.

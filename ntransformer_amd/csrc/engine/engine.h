@@ -6,6 +6,7 @@
 #include <functional>
 #include <string>
 #include <vector>
+#include "../../../include/ntransformer.h"
 #include "model.h"
 #include "sampler.h"
 #include "tokenizer.h"
@@ -56,6 +57,9 @@ public:
     int decode_greedy_steps(int token, int pos, int n, int* out);
     // log P(targets[i] | tokens[0..i]) for every position of a prompt pass at start_pos (Model::score; top1_out may be null)
     int score(const int* tokens, const int* targets, int n, int start_pos, float* logprob_out, int* top1_out);
+    // n prompts generated in lockstep over the sequence slots ("sequences" option), greedy: prompt i prefilled into slot i, then one Model::decode_batch
+    // per step over the sequences still alive (include/ntransformer.h: nt_engine_generate_batch)
+    int generate_batch(const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params& p, int* out, int out_stride, int* out_counts);
     void chat(const GenerateConfig& cfg);
     void benchmark(const std::string& prompt, int n_tokens);
     void print_stats(const Stats& st) const;

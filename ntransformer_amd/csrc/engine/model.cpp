@@ -46,6 +46,8 @@ void Model::free_all() {
     repack_done_ = output_tied_ = false;
     host_pos_ = attn_regime_ = 0;
     k_cache_ = v_cache_ = nullptr;
+    slot_k_.clear(); slot_v_.clear();
+    batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = nullptr;
     kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
     k_cache_q8_ = v_cache_q8_ = nullptr; kv_f16_k_ = kv_f16_v_ = nullptr; kv_q8_layer_bytes_ = 0; kv_cache_bytes_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;
@@ -202,6 +204,12 @@ int Model::wait_token(int pos, int* token) {
     const unsigned long long v = *slot;
     if ((unsigned)(v >> 32) != want) { err_ = "decode step finished without publishing its token"; return NTK_E_LAUNCH; }
     *token = (int)(unsigned)v;
+    return NTK_OK;
+}
+
+int Model::set_sequences(int n) {
+    if (n < 1 || n > kMaxSequences) { err_ = "sequences must lie in 1 .. " + std::to_string(kMaxSequences); return NTK_E_SHAPE; }
+    sequences_ = n;
     return NTK_OK;
 }
 

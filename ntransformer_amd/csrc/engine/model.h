@@ -54,7 +54,8 @@ public:
 
     // reference Transformer::forward (transformer.cpp:604-669): the reference's launcher sequence, 1:1,
     // any seq_len (prefill = per-token GEMV loops like the reference).  Returns device logits [vocab].
-    float* forward(const int* tokens, int seq_len, int start_pos);
+    // slot: the sequence slot whose KV cache the pass reads and writes (0 .. sequences() - 1; slot 0 is the cache every other entry point uses)
+    float* forward(const int* tokens, int seq_len, int start_pos, int slot = 0);
 
     // Scoring (csrc/logprob.hip): the prompt pass over `tokens` at start_pos exactly as forward() runs it -- the KV cache afterwards is forward's, bit for bit --
     // and then, instead of the last position's logits: the final RMSNorm of ALL rows (into residual_), the LM head over score_rows rows at a time into a
@@ -63,7 +64,28 @@ public:
     // targets[i] < 0), top1_out[i] (optional) = the greedy token behind tokens[0..i].  One D2H copy and one synchronisation per call.  The chunk buffer and the
     // device target / result arrays are allocated by the FIRST call (NTK_E_NOMEM + error(): the model stays usable) and freed with the model.  Refused
     // (NTK_E_SHAPE + error()): ids out of range, a sequence beyond the context, tensor parallelism.
-    int score(const int* tokens, const int* targets, int seq_len, int start_pos, float* logprob_out, int* top1_out);
+    int score(const int* tokens, const int* targets, int seq_len, int start_pos, float* logprob_out, int* top1_out, int slot = 0);
+
+    // ---- sequence slots and the batched decode step ---------------------------------------------------------------------------------
+    // "sequences" = N (1 .. kMaxSequences, default 1; BEFORE the load, kept across loads; a sharing sequence takes its own): slots 1 .. N - 1 are extra F16
+    // caches of slot 0's [L][max_seq][n_kv][hd] layout, allocated at load and counted in kv_cache_bytes(), beside a [16][vocab] F32 logits buffer, the batch
+    // attention's scratch and -- where score_buffers() would need one -- an LM-head GEMM workspace.  N = 1 allocates nothing (decode_batch with one row
+    // on slot 0 allocates the logits buffers on its first call, as score() does).  Refused at load with kv_cache = q8_0, tensor parallelism or a context of fewer than N positions (a step is a pass of up to N rows
+    // through the max_seq-row activation buffers).
+    static constexpr int kMaxSequences = 16;
+    int set_sequences(int n);
+    int sequences() const { return sequences_; }
+    // One decode step of B sequences in ONE pass over the weights: row b = token tokens[b] of the sequence in slot slots[b] at positions[b].  Eager and
+    // host-driven: one H2D copy of tokens | positions, embedding, the layer loop as for a prompt of B tokens (layers_1to1 in batch mode: rope / store /
+    // attention are one ntk_attention_decode_batch over the rows' own caches; B = 1: the projections of a 1-token forward), the final RMSNorm and the LM head
+    // over the B rows (lm_head: score()'s, full_form), ntk_logprob_rows for each row's first maximum, one D2H copy of whichever of logits_out [B][vocab] /
+    // next_out [B] is non-null, one synchronisation.  ARITHMETIC: the prompt pass's (FP16 matrix cores, two FP16 pieces per activation) with the decode
+    // kernels' attention -- within the 1e-3 bar of the fused decode path, not its bits; within one batch size a row depends on nothing but that row.
+    // Touches nothing of the fused path's slot-0 state (d_pos_, d_token_, graphs).  Refused (NTK_E_SHAPE + error()): see validate_batch.
+    int decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out);
+    // the host-side checks of decode_batch (no device): B in 1 .. sequences, every slot in range and named once, positions in [0, max_seq), token ids in
+    // [0, vocab); NTK_OK or NTK_E_NULL / NTK_E_SHAPE with the reason in *why (optional)
+    static int validate_batch(const int* slots, const int* tokens, const int* positions, int B, int sequences, int max_seq, int vocab, std::string* why);
     int set_score_rows(int rows);   // rows of logits per LM-head chunk, 1 .. 1024 (default 256: 131 MB at a vocabulary of 128 256); any time
 
     // Fused single-token step: 5 launches per layer, position and token id stay on the device so the whole
@@ -169,7 +191,7 @@ public:
     int check_tp();           // the tensor-parallel part of it: error word of the exchange kernel, surfaced and cleared
     // parity instrumentation (tests): layers [first, first+count) on caller-supplied hidden states; KV cache rows in / out
     int debug_run_layers(const float* hidden_in, int T, int start_pos, int first, int count, int mode, float* hidden_out);
-    int debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write);
+    int debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write, int slot = 0);
     // One fused token launched eagerly and timed with HIP events on the compute stream.
     // ms[c] / calls[c] per class c: 0 quant GEMV, 1 attention, 2 everything else (embed, argmax, pos); calls[3] = timed
     // intervals.  fine (coarse = false): an event pair around every launch.  coarse: one event per change of class, so
@@ -225,7 +247,15 @@ private:
     // y_k = W_k . f(x) for n <= 3 matrices sharing x, in as few fused launches as their formats allow (model_decode.cpp)
     int decode_project(const DevTensor* const* ws, float* const* ys, int n, const float* x, const DevTensor* norm, const float* resid, int kind,
                        int silu_pair = 0, bool timed = true);
-    int layers_1to1(int T, int start_pos, int first, int last);   // the layer loop of forward() and score()
+    // where the T rows of a layer pass keep their K / V: one slot's cache at rows start_pos .. (forward, score), or -- slots != nullptr -- row t in the cache
+    // of slot slots[t] at its own position positions_[t] (decode_batch; max_pos: the largest of them, which picks the attention regime)
+    struct KvTarget { int slot; const int* slots; int max_pos; };
+    int layers_1to1(int T, int start_pos, int first, int last, const KvTarget& kv = KvTarget{0, nullptr, 0});   // the layer loop of forward(), score() and decode_batch()
+    // logits [n][vocab] of the final-normed rows X [n][H] (row_max: their largest |x| or null): one pass over the LM head, in the form score() takes
+    int lm_head(float* logits, const float* X, int n, const float* row_max);
+    bool lm_head_f16() const;         // ... is the FP16 GEMM
+    int lm_head_workspace(const char* who);   // the LM head's own GEMM workspace where gemm_ws_ is too small for vocab rows (score_ws_)
+    int batch_buffers();              // the buffers of decode_batch(): at load when sequences > 1, else on its first call
     int score_buffers();              // the buffers of score(), on its first call (and again when score_rows grew)
     void prof_mark(int cls, bool begin);
     bool use_persistent_now() const;
@@ -251,6 +281,14 @@ private:
     uint16_t* k_cache_ = nullptr;   // [L][max_seq][nkv][hd] half
     uint16_t* v_cache_ = nullptr;
     bool kv_q8_ = false;            // the option (kept across loads)
+    int sequences_ = 1;             // the option (kept across loads)
+    std::vector<uint16_t*> slot_k_, slot_v_;   // [sequences_] caches by slot; [0] = k_cache_ / v_cache_
+    float* batch_logits_ = nullptr; // [kMaxSequences][V]: decode_batch's logits
+    int* batch_in_ = nullptr;       // [3][kMaxSequences] device ints: tokens | positions | -1 (ntk_logprob_rows' "no target")
+    int batch_host_[3 * 16] = {};   // ... and their host image
+    float* batch_logprob_ = nullptr;   // [kMaxSequences] (unused result of ntk_logprob_rows)
+    int* batch_next_ = nullptr;     // [kMaxSequences] first maxima
+    float* batch_attn_scratch_ = nullptr;   // kMaxSequences x the single-row split scratch
     uint8_t* k_cache_q8_ = nullptr; // [L] x kv_q8_layer_bytes_ (ntk_kv_q8_cache_bytes: int8 quants, then half scales)
     uint8_t* v_cache_q8_ = nullptr;
     size_t kv_q8_layer_bytes_ = 0;

@@ -44,15 +44,17 @@ int Model::debug_run_layers(const float* hidden_in, int T, int start_pos, int fi
 }
 
 // cache rows [pos0, pos0 + n) of one layer, [n][n_kv_heads * head_dim] halves each (reference layout, transformer.cpp:340-346)
-int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write) {
+int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write, int slot) {
     if (!k || !v) return NTK_E_NULL;
     if (kv_q8_) { err_ = "debug_kv: the KV cache is q8_0 (use the _q8 form)"; return NTK_E_DTYPE; }
-    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len) return NTK_E_SHAPE;
+    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= (int)slot_k_.size()) return NTK_E_SHAPE;
     const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim;
+    uint16_t* const kcache = slot_k_[slot];
+    uint16_t* const vcache = slot_v_[slot];
     const size_t off = ((size_t)layer * cfg_.max_seq_len + pos0) * per, bytes = (size_t)n * per * 2;
     void* s = stream_;
-    NT_TRY(write ? ntk_memcpy_h2d_async(k_cache_ + off, k, bytes, s) : ntk_memcpy_d2h_async(k, k_cache_ + off, bytes, s));
-    NT_TRY(write ? ntk_memcpy_h2d_async(v_cache_ + off, v, bytes, s) : ntk_memcpy_d2h_async(v, v_cache_ + off, bytes, s));
+    NT_TRY(write ? ntk_memcpy_h2d_async(kcache + off, k, bytes, s) : ntk_memcpy_d2h_async(k, kcache + off, bytes, s));
+    NT_TRY(write ? ntk_memcpy_h2d_async(vcache + off, v, bytes, s) : ntk_memcpy_d2h_async(v, vcache + off, bytes, s));
     return ntk_stream_synchronize(s);
 }
 

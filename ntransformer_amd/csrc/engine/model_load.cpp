@@ -325,6 +325,20 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         v_cache_ = (uint16_t*)dev(kvb, true);
         kv_cache_bytes_ = 2ull * kvb;
     }
+    slot_k_.assign(1, k_cache_);
+    slot_v_.assign(1, v_cache_);
+    if (sequences_ > 1) {   // the extra sequence slots: F16 caches of slot 0's layout
+        if (kv_q8_) { err_ = "sequences > 1 is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
+        if (tp_world_ > 1) { err_ = "sequences > 1 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
+        // a batched step is a prompt pass of up to `sequences` rows through buffers of max_seq rows (hidden_, residual_, workspace_, row_max_, kv_capture_)
+        if ((size_t)sequences_ > S) { err_ = "sequences = " + std::to_string(sequences_) + " needs a context of at least as many positions (this load: " + std::to_string(S) + ")"; return NTK_E_SHAPE; }
+        for (int i = 1; i < sequences_; ++i) {
+            slot_k_.push_back((uint16_t*)dev(kvb, true));
+            slot_v_.push_back((uint16_t*)dev(kvb, true));
+            if (!slot_k_.back() || !slot_v_.back()) { err_ = "buffer allocation failed (KV cache of sequence slot " + std::to_string(i) + ")"; return NTK_E_NOMEM; }
+            kv_cache_bytes_ += 2ull * kvb;
+        }
+    }
     hidden_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
     residual_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
     logits_ = (float*)dev((size_t)cfg_.vocab_size * 4, false);
@@ -373,6 +387,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         for (int i = 0; i < cfg_.head_dim / 2; ++i) f[i] = 1.0f / powf(cfg_.rope_theta, (2.0f * i) / cfg_.head_dim);
         nt_hip_memcpy_h2d(rope_inv_freq_, f.data(), f.size() * 4);
     }
+    if (sequences_ > 1) NT_TRY(batch_buffers());
     return NTK_OK;
 }
 

@@ -1,5 +1,6 @@
 // engine/model_prompt.cpp -- the prompt pass (see model.h)
 #include "model_impl.h"
+#include <type_traits>
 
 namespace nt {
 
@@ -7,8 +8,9 @@ namespace nt {
 // 1:1 path: the reference's own launcher sequence (transformer.cpp:604-669, attention.cpp:120-211,
 // ffn.cpp:85-134), through the same C ABI an external caller would use
 // ---------------------------------------------------------------------------------------------------
-float* Model::forward(const int* tokens, int T, int start_pos) {
+float* Model::forward(const int* tokens, int T, int start_pos, int slot) {
     if (T <= 0 || start_pos < 0 || start_pos + T > cfg_.max_seq_len) { err_ = "forward: sequence exceeds context"; return nullptr; }
+    if (slot < 0 || slot >= sequences_) { err_ = "forward: no such sequence slot"; return nullptr; }
     for (int i = 0; i < T; ++i)   // the embedding gather indexes the table with these on the device
         if (tokens[i] < 0 || tokens[i] >= cfg_.vocab_size) { err_ = "forward: token id out of range"; return nullptr; }
     const int H = cfg_.hidden_size;
@@ -24,7 +26,8 @@ float* Model::forward(const int* tokens, int T, int start_pos) {
     if (ntk_memcpy_h2d_async(positions_, pos.data(), (size_t)T * 4, s) != NTK_OK) return nullptr;
     if (ntk_stream_synchronize(s) != NTK_OK) return nullptr;   // `pos` / `tokens` are host temporaries
 
-    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers);
+    const KvTarget kv{slot, nullptr, 0};
+    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers, kv);
     auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
     float* last = hidden_ + (size_t)(T - 1) * H;
     ok(ntk_rmsnorm(last, last, (const float*)output_norm_.ptr, 1, H, cfg_.norm_eps, s));   // in place, :658-659
@@ -69,7 +72,7 @@ static bool rp_only(const DevTensor& w) {
 }
 
 // layers [first, last) of the 1:1 path on hidden_[T][H] at positions start_pos.. (positions_ already on the device)
-int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
+int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const KvTarget& kv) {
     const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
     const int qd = nh * hd, kvd = nkv * hd;
     void* s = stream_;
@@ -243,8 +246,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
     bool normed_ahead = false;   // residual_ (with its maxima or planes) already holds this layer's normalised input, written with the previous layer's down projection
     for (int i = first; i < last_layer; ++i) {
         const LayerWeights& L = layers_[i];
-        uint16_t* kc = kv_q8_ ? nullptr : k_cache_ + (size_t)i * kv_layer;   // (q8_0: the one-layer F16 image, set below)
-        uint16_t* vc = kv_q8_ ? nullptr : v_cache_ + (size_t)i * kv_layer;
+        uint16_t* kc = kv_q8_ ? nullptr : slot_k_[kv.slot] + (size_t)i * kv_layer;   // (q8_0: the one-layer F16 image, set below)
+        uint16_t* vc = kv_q8_ ? nullptr : slot_v_[kv.slot] + (size_t)i * kv_layer;
         if (!normed_ahead) norm(L.attn_norm, true, L.wq);
         normed_ahead = false;
         float* const qkv_out[3] = {act.q, act.k, act.v};
@@ -255,7 +258,17 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
             ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));
             kv_capture_T_ = T;
         }
-        if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
+        if (kv.slots) {   // a batch of sequences: rope / store / attention of every row on its own cache at its own position, one launch
+            ntk_kv_batch caches{};
+            for (int t = 0; t < T; ++t) {
+                caches.k[t] = slot_k_[kv.slots[t]] + (size_t)i * kv_layer;
+                caches.v[t] = slot_v_[kv.slots[t]] + (size_t)i * kv_layer;
+            }
+            const bool splits_ok = batch_attn_scratch_ && (hd == 64 || hd == 128 || hd == 256);   // (pick_attention_regime's rule)
+            const int regime = splits_ok ? attention_regime(kv.max_pos, hd) : 0;
+            ok(ntk_attention_decode_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
+                                          cfg_.rope_theta, cfg_.rope_freq_scale, regime == 0 ? 1 : attention_splits(regime, hd), batch_attn_scratch_, s));
+        } else if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
             uint8_t* kc8 = k_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
             uint8_t* vc8 = v_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
             if (T >= 4) {
@@ -274,7 +287,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer) {
             ok(ntk_rope(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, s));
             ok(ntk_copy_to_kv_cache(kc, vc, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
         }
-        if (T == 1) ok(ntk_attention_decode(act.attn_out, act.q, kc, vc, start_pos + T, nh, nkv, hd, cfg_.max_seq_len, scale, s));
+        if (kv.slots) {}   // (attended above)
+        else if (T == 1) ok(ntk_attention_decode(act.attn_out, act.q, kc, vc, start_pos + T, nh, nkv, hd, cfg_.max_seq_len, scale, s));
         else ok(ntk_attention_prefill(act.attn_out, act.q, kc, vc, T, start_pos, nh, nkv, hd, cfg_.max_seq_len, scale, s));
         if (!project_add_norm(L.wo, act.attn_out, nullptr, L.ffn_norm, false, L.w_gate)) {
             project_add(L.wo, act.attn_out, qd, nullptr);
@@ -328,22 +342,65 @@ int Model::score_buffers() {
         if (!(score_logits_ = (float*)dev((size_t)score_rows_ * V * 4))) return fail("the chunk of logits (score_rows x vocab floats)");
         score_cap_ = score_rows_;
     }
-    // the FP16 GEMM sizes its workspace by the matrix's rows: the load-time one covers the layers' projections, not always a vocabulary
+    return lm_head_workspace("score");
+}
+
+// the FP16 GEMM sizes its workspace by the matrix's rows: the load-time one covers the layers' projections, not always a vocabulary
+int Model::lm_head_workspace(const char* who) {
     const size_t need = ntk_gemm_quant_workspace_bytes(cfg_.hidden_size, cfg_.vocab_size);
-    if (gemm_ws_ && bf16_prefill_ && f16_ok(output_) && need > gemm_ws_bytes_ && need > score_ws_bytes_) {
-        release(score_ws_);
-        score_ws_bytes_ = 0;
-        if (!(score_ws_ = dev(need))) return fail("the LM head's GEMM workspace");
-        score_ws_bytes_ = need;
+    if (!(gemm_ws_ && bf16_prefill_ && f16_ok(output_) && need > gemm_ws_bytes_ && need > score_ws_bytes_)) return NTK_OK;
+    if (score_ws_) {
+        NT_TRY(sync());
+        allocs_.erase(std::remove(allocs_.begin(), allocs_.end(), score_ws_), allocs_.end());
+        nt_hip_free(score_ws_);
+        score_ws_ = nullptr;
+    }
+    score_ws_bytes_ = 0;
+    if (!(score_ws_ = nt_hip_malloc(need + 256))) { err_ = std::string(who) + ": no device memory for the LM head's GEMM workspace"; return NTK_E_NOMEM; }
+    allocs_.push_back(score_ws_);
+    score_ws_bytes_ = need;
+    return NTK_OK;
+}
+
+bool Model::lm_head_f16() const { return batched_prefill_ && is_quant(output_.dtype) && bf16_prefill_ && gemm_ws_ && f16_ok(output_); }
+
+// logits of n final-normed rows: one pass over the head (see model.h)
+int Model::lm_head(float* logits, const float* X, int n, const float* chunk_max) {
+    const DevTensor& w = output_;
+    const int H = cfg_.hidden_size, V = cfg_.vocab_size;
+    void* s = stream_;
+    const bool batched = batched_prefill_ && is_quant(w.dtype);
+    void* const ws = score_ws_ ? score_ws_ : gemm_ws_;
+    const size_t ws_bytes = score_ws_ ? score_ws_bytes_ : gemm_ws_bytes_;
+    int st = NTK_E_DTYPE;
+    if (lm_head_f16()) {
+        const bool repacked = rp_only(w);
+        if (!repacked) raw_begin();
+        const ntk_gemv_seg seg{repacked ? w.rp : raw_of(w), logits, V, w.dtype};
+        ntk_gemm_desc d{};
+        d.segs = &seg; d.nseg = 1; d.X = X; d.n_tokens = n; d.in_features = H;
+        d.workspace = ws; d.workspace_bytes = ws_bytes; d.row_max = chunk_max; d.weights_repacked = repacked ? 1 : 0;
+        d.full_form = 1;   // the same bits whatever the caller cuts the rows into (the form is otherwise chosen by the call's token count)
+        st = ntk_gemm_quant_f16(&d, s);
+    }
+    if (batched && not_taken(st)) { raw_begin(); st = ntk_gemm_quant(logits, raw_of(w), X, n, V, H, w.dtype, nullptr, s); }
+    if (batched && !not_taken(st)) return st;
+    raw_begin();   // dense heads and shapes the matrix-core forms do not take: the reference's GEMV, row by row
+    const void* wp = raw_of(w);
+    for (int t = 0; t < n; ++t) {
+        st = ntk_gemv(logits + (size_t)t * V, wp, X + (size_t)t * H, V, H, w.dtype, s);
+        if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
+        if (st != NTK_OK) return st;
     }
     return NTK_OK;
 }
 
-int Model::score(const int* tokens, const int* targets, int T, int start_pos, float* logprob_out, int* top1_out) {
+int Model::score(const int* tokens, const int* targets, int T, int start_pos, float* logprob_out, int* top1_out, int slot) {
     if (!tokens || !targets || !logprob_out) { err_ = "score: null argument"; return NTK_E_NULL; }
     if (tp_world_ > 1) { err_ = "score: not available under tensor parallelism"; return NTK_E_SHAPE; }
     if (T <= 0) { err_ = "score: no tokens to score"; return NTK_E_SHAPE; }
     if (start_pos < 0 || start_pos + T > cfg_.max_seq_len) { err_ = "score: sequence exceeds context"; return NTK_E_SHAPE; }
+    if (slot < 0 || slot >= sequences_) { err_ = "score: no such sequence slot"; return NTK_E_SHAPE; }
     const int H = cfg_.hidden_size, V = cfg_.vocab_size;
     for (int i = 0; i < T; ++i) {   // the embedding gather and the target gather index with these on the device
         if (tokens[i] < 0 || tokens[i] >= V) { err_ = "score: token id out of range"; return NTK_E_SHAPE; }
@@ -363,44 +420,16 @@ int Model::score(const int* tokens, const int* targets, int T, int start_pos, fl
     NT_TRY(ntk_memcpy_h2d_async(positions_, pos.data(), (size_t)T * 4, s));
     NT_TRY(ntk_stream_synchronize(s));   // `pos` / `tokens` / `targets` are host memory of the caller
 
-    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers);
+    const KvTarget kv{slot, nullptr, 0};
+    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers, kv);
     auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
     // the final RMSNorm of every row, beside hidden_ (with the rows' largest |x| where the FP16 GEMM reads the head)
-    const DevTensor& w = output_;
-    const bool batched = batched_prefill_ && is_quant(w.dtype);
-    const bool f16 = batched && bf16_prefill_ && gemm_ws_ && f16_ok(w);
-    const float* rm = f16 && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
+    const float* rm = lm_head_f16() && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
     if (rm) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)output_norm_.ptr, T, H, cfg_.norm_eps, row_max_, nullptr, s));
     else ok(ntk_rmsnorm(residual_, hidden_, (const float*)output_norm_.ptr, T, H, cfg_.norm_eps, s));
-    void* const ws = score_ws_ ? score_ws_ : gemm_ws_;
-    const size_t ws_bytes = score_ws_ ? score_ws_bytes_ : gemm_ws_bytes_;
-    // logits of rows [t0, t0 + n): one pass over the head per chunk
-    auto head = [&](const float* X, int n, const float* chunk_max) -> int {
-        int st = NTK_E_DTYPE;
-        if (f16) {
-            const bool repacked = rp_only(w);
-            if (!repacked) raw_begin();
-            const ntk_gemv_seg seg{repacked ? w.rp : raw_of(w), score_logits_, V, w.dtype};
-            ntk_gemm_desc d{};
-            d.segs = &seg; d.nseg = 1; d.X = X; d.n_tokens = n; d.in_features = H;
-            d.workspace = ws; d.workspace_bytes = ws_bytes; d.row_max = chunk_max; d.weights_repacked = repacked ? 1 : 0;
-            d.full_form = 1;   // the same bits whatever score_rows cuts the rows into (the form is otherwise chosen by the call's token count)
-            st = ntk_gemm_quant_f16(&d, s);
-        }
-        if (batched && not_taken(st)) { raw_begin(); st = ntk_gemm_quant(score_logits_, raw_of(w), X, n, V, H, w.dtype, nullptr, s); }
-        if (batched && !not_taken(st)) return st;
-        raw_begin();   // dense heads and shapes the matrix-core forms do not take: the reference's GEMV, row by row
-        const void* wp = raw_of(w);
-        for (int t = 0; t < n; ++t) {
-            st = ntk_gemv(score_logits_ + (size_t)t * V, wp, X + (size_t)t * H, V, H, w.dtype, s);
-            if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
-            if (st != NTK_OK) return st;
-        }
-        return NTK_OK;
-    };
     for (int t0 = 0; t0 < T && rc == NTK_OK; t0 += score_rows_) {
         const int n = std::min(score_rows_, T - t0);
-        ok(head(residual_ + (size_t)t0 * H, n, rm ? rm + t0 : nullptr));
+        ok(lm_head(score_logits_, residual_ + (size_t)t0 * H, n, rm ? rm + t0 : nullptr));
         ok(ntk_logprob_rows(score_logits_, n, V, V, score_targets_ + t0, score_logprob_ + t0, top1_out ? score_top1_ + t0 : nullptr, s));
     }
     if (rc == NTK_OK) ok(ntk_memcpy_d2h_async(logprob_out, score_logprob_, (size_t)T * 4, s));
@@ -408,6 +437,79 @@ int Model::score(const int* tokens, const int* targets, int T, int start_pos, fl
     ok(ntk_stream_synchronize(s));
     if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
     if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("score failed: ") + ntk_status_string(rc);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Sequence slots: one decode step of B sequences in one pass over the weights (see model.h)
+// ---------------------------------------------------------------------------------------------------
+int Model::batch_buffers() {
+    const size_t V = (size_t)cfg_.vocab_size, N = kMaxSequences;
+    // (a buffer an earlier, failed call obtained is kept: only what is missing is allocated)
+    auto need = [&](auto*& p, size_t bytes) {
+        if (p) return true;
+        void* d = nt_hip_malloc(bytes + 256);
+        if (!d) return false;
+        allocs_.push_back(d);
+        nt_hip_memset(d, 0, bytes);
+        p = static_cast<std::remove_reference_t<decltype(p)>>(d);
+        return true;
+    };
+    if (!need(batch_in_, 3 * N * 4) || !need(batch_logprob_, N * 4) || !need(batch_next_, N * 4) ||
+        !need(batch_attn_scratch_, N * ntk_attention_split_scratch_bytes(cfg_.n_heads, cfg_.head_dim, kMaxAttnSplits)) || !need(batch_logits_, N * V * 4)) {
+        err_ = "decode_batch: no device memory for the batch buffers (16 x vocab floats of logits)";
+        return NTK_E_NOMEM;
+    }
+    return lm_head_workspace("decode_batch");   // (nothing to do once the workspace is large enough)
+}
+
+int Model::validate_batch(const int* slots, const int* tokens, const int* positions, int B, int sequences, int max_seq, int vocab, std::string* why) {
+    auto fail = [&](int rc, const char* msg) { if (why) *why = msg; return rc; };
+    if (!slots || !tokens || !positions) return fail(NTK_E_NULL, "decode_batch: null argument");
+    if (B < 1 || B > sequences || B > kMaxSequences) return fail(NTK_E_SHAPE, "decode_batch: the batch must hold 1 .. `sequences` rows");
+    unsigned seen = 0;
+    for (int b = 0; b < B; ++b) {
+        if (slots[b] < 0 || slots[b] >= sequences || slots[b] >= kMaxSequences) return fail(NTK_E_SHAPE, "decode_batch: no such sequence slot");
+        if (seen & (1u << slots[b])) return fail(NTK_E_SHAPE, "decode_batch: the same sequence slot twice in one batch");
+        seen |= 1u << slots[b];
+        if (positions[b] < 0 || positions[b] >= max_seq) return fail(NTK_E_SHAPE, "decode_batch: position outside the context");
+        if (tokens[b] < 0 || tokens[b] >= vocab) return fail(NTK_E_SHAPE, "decode_batch: token id out of range");
+    }
+    return NTK_OK;
+}
+
+int Model::decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out) {
+    NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
+    if (kv_q8_ || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    NT_TRY(batch_buffers());
+    const int H = cfg_.hidden_size, V = cfg_.vocab_size, N = kMaxSequences;
+    void* s = stream_;
+    tp_call_ = 0;
+    int* const host = batch_host_;   // tokens | positions | "no target": ONE copy (a member: the copy may read it until the synchronisation below)
+    KvTarget kv{0, slots, 0};
+    for (int b = 0; b < N; ++b) {
+        host[b] = b < B ? tokens[b] : 0;
+        host[N + b] = b < B ? positions[b] : 0;
+        host[2 * N + b] = -1;
+        if (b < B) kv.max_pos = std::max(kv.max_pos, positions[b]);
+    }
+    NT_TRY(ntk_memcpy_h2d_async(batch_in_, host, sizeof batch_host_, s));
+    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, batch_in_, B, H, token_embd_.dtype, s);
+    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
+    else if (est != NTK_OK) return est;
+
+    int rc = layers_1to1(B, 0, 0, cfg_.n_layers, kv);
+    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
+    const float* rm = lm_head_f16() && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
+    if (rm) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)output_norm_.ptr, B, H, cfg_.norm_eps, row_max_, nullptr, s));
+    else ok(ntk_rmsnorm(residual_, hidden_, (const float*)output_norm_.ptr, B, H, cfg_.norm_eps, s));
+    ok(lm_head(batch_logits_, residual_, B, rm));
+    if (next_out) ok(ntk_logprob_rows(batch_logits_, B, V, V, batch_in_ + 2 * N, batch_logprob_, batch_next_, s));
+    if (rc == NTK_OK && logits_out) ok(ntk_memcpy_d2h_async(logits_out, batch_logits_, (size_t)B * V * 4, s));
+    if (rc == NTK_OK && next_out) ok(ntk_memcpy_d2h_async(next_out, batch_next_, (size_t)B * 4, s));
+    ok(ntk_stream_synchronize(s));
+    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
+    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("decode_batch failed: ") + ntk_status_string(rc);
     return rc;
 }
 

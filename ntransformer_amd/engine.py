@@ -67,6 +67,11 @@ def _bind():
     L.nt_engine_last_stats.argtypes = [vp, C.POINTER(CStats)]
     L.nt_engine_forward.argtypes = [vp, C.POINTER(i), i, i, vp]
     L.nt_engine_decode_fused.argtypes = [vp, i, i, i, vp]
+    L.nt_engine_seq_forward.argtypes = [vp, i, C.POINTER(i), i, i, vp]
+    L.nt_engine_decode_batch.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), i, vp, vp]
+    L.nt_engine_generate_batch.argtypes = [vp, C.POINTER(C.POINTER(i)), C.POINTER(i), i, C.POINTER(GenParams), C.POINTER(i), i, C.POINTER(i)]
+    L.nt_batch_validate.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, i, i]
+    L.nt_engine_debug_kv_read_slot.argtypes = [vp, i, i, i, i, vp, vp]
     L.nt_engine_score_tokens.argtypes = [vp, C.POINTER(i), C.POINTER(i), i, i, vp, vp]
     L.nt_engine_tokenize.argtypes = [vp, C.c_char_p, i, C.POINTER(i), i]
     L.nt_engine_detokenize.argtypes = [vp, C.POINTER(i), i, C.c_char_p, i]
@@ -185,6 +190,48 @@ class Engine:
         out = np.empty(self.vocab_size, np.float32)
         self._check(self.L.nt_engine_decode_fused(self.h, int(token), pos, int(graph), out.ctypes.data_as(C.c_void_p)), "decode_fused")
         return out
+
+    # ---- sequence slots ("sequences" option; include/ntransformer.h) ----
+    def seq_forward(self, slot: int, tokens: Sequence[int], start_pos: int) -> np.ndarray:
+        """forward() into the KV cache of sequence slot `slot`"""
+        out = np.empty(self.vocab_size, np.float32)
+        arr = (C.c_int * len(tokens))(*[int(t) for t in tokens])
+        self._check(self.L.nt_engine_seq_forward(self.h, int(slot), arr, len(tokens), start_pos, out.ctypes.data_as(C.c_void_p)), "seq_forward")
+        return out
+
+    def decode_batch(self, slots: Sequence[int], tokens: Sequence[int], positions: Sequence[int], logits: bool = True):
+        """One decode step of len(slots) sequences in one pass over the weights: (logits [n, vocab] or None, greedy tokens [n])."""
+        n = len(slots)
+        ia = lambda xs: (C.c_int * max(len(xs), 1))(*[int(x) for x in xs])
+        out = np.empty((n, self.vocab_size), np.float32) if logits else None
+        nxt = (C.c_int * max(n, 1))()
+        self._check(self.L.nt_engine_decode_batch(self.h, ia(slots), ia(tokens), ia(positions), n,
+                                                  out.ctypes.data_as(C.c_void_p) if logits else None, C.cast(nxt, C.c_void_p)), "decode_batch")
+        return out, list(nxt[:n])
+
+    def generate_batch(self, prompts: Sequence[Sequence[int]], max_tokens: int, stop_at_eos: bool = True, temperature: float = 0.0,
+                       repeat_penalty: float = 1.0) -> List[List[int]]:
+        """Greedy generation of len(prompts) sequences in lockstep (prompt i in slot i): the generated ids per sequence."""
+        n = len(prompts)
+        p = GenParams(max_tokens, temperature, 40, 0.9, repeat_penalty, 64, 42, int(stop_at_eos))
+        rows = [(C.c_int * max(len(q), 1))(*[int(t) for t in q]) for q in prompts]
+        ptrs = (C.POINTER(C.c_int) * max(n, 1))(*[C.cast(r, C.POINTER(C.c_int)) for r in rows])
+        lens = (C.c_int * max(n, 1))(*[len(q) for q in prompts])
+        stride = max(max_tokens, 1)
+        out = (C.c_int * (max(n, 1) * stride))()
+        counts = (C.c_int * max(n, 1))()
+        st = self.L.nt_engine_generate_batch(self.h, ptrs, lens, n, C.byref(p), out, stride, counts)
+        if st < 0:
+            self._check(st, "generate_batch")
+        return [list(out[i * stride: i * stride + counts[i]]) for i in range(n)]
+
+    def kv_read_slot(self, slot: int, layer: int, pos0: int, n: int, row_halves: int):
+        """kv_read of sequence slot `slot`"""
+        k = np.empty((n, row_halves), np.uint16)
+        v = np.empty((n, row_halves), np.uint16)
+        self._check(self.L.nt_engine_debug_kv_read_slot(self.h, int(slot), layer, pos0, n, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)),
+                    "kv_read_slot")
+        return k, v
 
     @property
     def max_context(self): return self.L.nt_engine_max_context(self.h)

@@ -411,6 +411,22 @@ def attention_decode_split_merged(output, q, k, v, k_cache, v_cache, d_pos, n_he
     return None
 
 
+def attention_decode_batch(output, q, k, v, k_caches, v_caches, positions, n_rows, n_heads, n_kv_heads, head_dim, max_seq, scale,
+                           theta_base, nsplit=1, freq_scale=1.0, inv_freq=None, stream=None, table=True):
+    """Decode attention of n_rows sequences, each with its own caches (k_caches / v_caches: lists of DeviceBuffers) and its own position
+    (positions: device int [n_rows]): ntk_attention_decode_batch.  table=False passes a NULL cache table (the refusal)."""
+    L = _lib.lib()
+    kv = _lib.KvBatch()
+    for b, (kc, vc) in enumerate(zip(k_caches, v_caches)):
+        kv.k[b], kv.v[b] = _p(kc), _p(vc)
+    scratch = DeviceBuffer(max(n_rows, 1) * int(L.ntk_attention_split_scratch_bytes(n_heads, head_dim, nsplit)))
+    check(L.ntk_attention_decode_batch(_p(output), _p(q), _p(k), _p(v), C.addressof(kv) if table else None, _p(positions), n_rows, _p(inv_freq),
+                                       n_heads, n_kv_heads, head_dim, max_seq, scale, theta_base, freq_scale, nsplit, _p(scratch), stream),
+          "attention_decode_batch")
+    synchronize()   # `scratch` is released when this returns
+    return None
+
+
 def embed_rows(out, table, tokens, n_tokens, hidden, dtype, stream=None, allow_unsupported=False):
     st = _lib.lib().ntk_embed_rows(_p(out), _p(table), _p(tokens), n_tokens, hidden, int(dtype), stream)
     if not (allow_unsupported and st == -1):
