@@ -174,6 +174,7 @@ int  nt_engine_debug_kv_write(nt_engine_t e, int layer, int pos0, int n, const u
  * `vocab` ids -- NTK_OK, NTK_E_NULL or NTK_E_SHAPE (tests/test_batch_validate_cpu.py) */
 int  nt_batch_validate(const int* slots, const int* tokens, const int* positions, int n, int sequences, int max_seq, int vocab);
 int  nt_engine_debug_kv_read_slot(nt_engine_t e, int slot, int layer, int pos0, int n, uint16_t* k_out, uint16_t* v_out);   /* ... of sequence slot `slot` */
+int  nt_engine_debug_kv_write_slot(nt_engine_t e, int slot, int layer, int pos0, int n, const uint16_t* k, const uint16_t* v);   /* _write into slot `slot`, the same checks */
 /* ... of a "kv_cache" = "q8_0" engine: the rows as canonical 34-byte GGUF block_q8_0 {half d; int8 q[32]}, [n][n_kv_heads * head_dim / 32] blocks per
  * side.  Each pair returns NTK_E_DTYPE on an engine of the other cache format. */
 int  nt_engine_debug_kv_read_q8(nt_engine_t e, int layer, int pos0, int n, void* k_blocks_out, void* v_blocks_out);

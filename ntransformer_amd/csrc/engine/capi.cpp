@@ -216,6 +216,10 @@ int nt_engine_debug_kv_write(nt_engine_t e, int layer, int pos0, int n, const ui
     if (!e || !E(e)->loaded()) return NTK_E_NULL;
     return E(e)->model().debug_kv(layer, pos0, n, const_cast<uint16_t*>(k), const_cast<uint16_t*>(v), true);
 }
+int nt_engine_debug_kv_write_slot(nt_engine_t e, int slot, int layer, int pos0, int n, const uint16_t* k, const uint16_t* v) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv(layer, pos0, n, const_cast<uint16_t*>(k), const_cast<uint16_t*>(v), true, slot);
+}
 int nt_engine_debug_kv_inputs_capture(nt_engine_t e, int layer) {
     if (!e || !E(e)->loaded()) return NTK_E_NULL;
     return E(e)->model().debug_kv_inputs_capture(layer);

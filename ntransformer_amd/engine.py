@@ -72,6 +72,7 @@ def _bind():
     L.nt_engine_generate_batch.argtypes = [vp, C.POINTER(C.POINTER(i)), C.POINTER(i), i, C.POINTER(GenParams), C.POINTER(i), i, C.POINTER(i)]
     L.nt_batch_validate.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, i, i]
     L.nt_engine_debug_kv_read_slot.argtypes = [vp, i, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_write_slot.argtypes = [vp, i, i, i, i, vp, vp]
     L.nt_engine_score_tokens.argtypes = [vp, C.POINTER(i), C.POINTER(i), i, i, vp, vp]
     L.nt_engine_tokenize.argtypes = [vp, C.c_char_p, i, C.POINTER(i), i]
     L.nt_engine_detokenize.argtypes = [vp, C.POINTER(i), i, C.c_char_p, i]
@@ -232,6 +233,13 @@ class Engine:
         self._check(self.L.nt_engine_debug_kv_read_slot(self.h, int(slot), layer, pos0, n, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)),
                     "kv_read_slot")
         return k, v
+
+    def kv_write_slot(self, slot: int, layer: int, pos0: int, k: np.ndarray, v: np.ndarray) -> None:
+        """kv_write into sequence slot `slot`"""
+        k = np.ascontiguousarray(k, dtype=np.uint16)
+        v = np.ascontiguousarray(v, dtype=np.uint16)
+        self._check(self.L.nt_engine_debug_kv_write_slot(self.h, int(slot), layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p),
+                                                         v.ctypes.data_as(C.c_void_p)), "kv_write_slot")
 
     @property
     def max_context(self): return self.L.nt_engine_max_context(self.h)
