@@ -304,6 +304,28 @@ int ntk_sample_top_k(float* logits, int n, const int* d_recent, int n_recent, fl
 /* the repeat penalty alone (greedy decoding with a penalty = this + ntk_argmax) */
 int ntk_repeat_penalty(float* logits, int n, const int* d_recent, int n_recent, float repeat_penalty, void* stream);
 
+/* The sampler over the rows of a batched decode step, every row with its own settings (csrc/sampling_batch.hip): at most three launches whatever n_rows
+ * is -- the penalty (one thread per row), stage 1 over a (chunk, row) grid, stage 2 with one workgroup per row.
+ * logits [n_rows][ld] F32, ld >= vocab: only [b][0 .. vocab) is read or written.  d_recent: DEVICE int [n_rows][recent_ld], row b uses its first
+ * n_recent[b] entries (may be NULL when no row has a penalty to apply).  d_out: device int [n_rows]; h_mirror: pinned int [n_rows], may be NULL.
+ * `rows` is a HOST struct, copied by value into the launches (as ntk_kv_batch is): the caller may reuse it as soon as the call returns.
+ * Row b with temperature[b] > 0: exactly ntk_sample_top_k on logits + b * ld with row b's settings and draw r[b] -- the same device code, the same bits.
+ * Row b with temperature[b] <= 0: the penalty (if repeat_penalty[b] > 1 and n_recent[b] > 0), then the FIRST maximum of the row (Sampler::argmax:
+ * it starts at id 0 and moves on a strict >, so -0 and +0 tie, a NaN above id 0 never wins and a NaN AT id 0 gives 0); no division, r[b] / top_k[b] /
+ * top_p[b] ignored.
+ * A row's penalty touches that row only; rows are independent: the same bits whatever the companions and the row order.
+ * scratch: ntk_sample_rows_scratch_bytes(n_rows, vocab) device bytes.
+ * Refused before any launch -- NTK_E_NULL: logits / rows / d_out / scratch, or d_recent where a penalty needs it; NTK_E_SHAPE: n_rows outside 1 .. 16,
+ * ld < vocab, vocab beyond 131 072, a sampled row's top_k outside 1 .. 64, an n_recent[b] negative or beyond recent_ld. */
+#define NTK_SAMPLE_ROWS_MAX 16
+typedef struct ntk_sample_rows {
+    float temperature[NTK_SAMPLE_ROWS_MAX], top_p[NTK_SAMPLE_ROWS_MAX], repeat_penalty[NTK_SAMPLE_ROWS_MAX], r[NTK_SAMPLE_ROWS_MAX];
+    int   top_k[NTK_SAMPLE_ROWS_MAX], n_recent[NTK_SAMPLE_ROWS_MAX];
+} ntk_sample_rows;
+size_t ntk_sample_rows_scratch_bytes(int n_rows, int vocab);
+int ntk_sample_rows_top_k(float* logits, int n_rows, int vocab, int ld, const int* d_recent, int recent_ld, const ntk_sample_rows* rows, int* d_out,
+                          int* h_mirror, void* scratch, void* stream);
+
 /* The greedy tail of a decode token in two launches instead of three: ntk_argmax, then -- in the same final launch -- the token id to the
  * pinned host ring h_ring4 (4 x 8 bytes, may be NULL): slot (*d_pos & 3) receives ONE 8-byte store {token, *d_pos + 1 in the high
  * word}, and *d_pos += 1.  The ring lets a host loop keep the NEXT token's launches queued while it polls for this one (a token that

@@ -83,7 +83,8 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * other than 128, more than 16 query heads per KV head, tensor parallelism, "fuse_attention";
  * "sequences" = "1" .. "16" (default "1"): sequence slots of this engine for the batched decode step below.  Slot 0 is the KV cache every other entry point
  * uses, exactly as without the option; slots 1 .. N - 1 are extra F16 caches of the same layout, allocated at load (counted in nt_engine_kv_cache_bytes)
- * beside a [16][vocab] F32 logits buffer.  Set it BEFORE the load (afterwards: NTK_E_SHAPE + last_error); an nt_engine_load_shared sequence takes its own.
+ * beside a [16][vocab] F32 logits buffer and the batched sampler's buffers (under 1 MB; neither is counted there).  Set it BEFORE the load (afterwards:
+ * NTK_E_SHAPE + last_error); an nt_engine_load_shared sequence takes its own.
  * Refused at load (NTK_E_SHAPE + last_error) when > 1 together with "kv_cache" = "q8_0", tensor parallelism or a context of fewer than N positions;
  * "score_rows" = "1" .. "1024" (default "256"): rows of logits nt_engine_score_tokens computes per pass over the LM head (score_rows x vocab floats of device
  * memory from the first scoring call on; any time). */
@@ -111,11 +112,32 @@ int  nt_engine_forward(nt_engine_t e, const int* tokens, int n, int start_pos, f
  * sequences step together; a sequence leaves the batch at EOS (stop_at_eos; the EOS token is written) or at max_tokens.  out [n][out_stride] receives the
  * generated ids, out_counts [n] how many.  Returns n or a negative NTK_E_*; temperature > 0 or repeat_penalty != 1: NTK_E_SHAPE + last_error (sample from
  * nt_engine_decode_batch's logits instead).  nt_engine_last_stats: prompt and generated tokens summed over the sequences (as nt_engine_generate_tokens
- * counts them: without each sequence's first token), the aggregate decode rate. */
+ * counts them: without each sequence's first token), the aggregate decode rate.
+ * SAMPLED batches, every sequence with its own settings.  CONTRACT: the sampled stream = the host sampler (reference src/inference/sampler.cpp) on the
+ * batched step's logits -- ntk_sample_rows_top_k runs the single-sequence device sampler's code on every row, the uniform draws come from one
+ * std::mt19937 per sequence on the host.
+ * nt_engine_decode_batch_sample: ONE step, caller-driven: nt_engine_decode_batch with row i sampled on the device by params[i] (temperature, top_k, top_p,
+ * repeat_penalty; max_tokens / stop_at_eos / seed / repeat_window ignored) over the window recent[i][0 .. n_recent[i]) -- the caller passes the window it
+ * wants applied, the last repeat_window tokens (recent / n_recent may be NULL: no windows) -- with the uniform draw r[i] (ignored where temperature <= 0:
+ * that row gets the first maximum of its penalised logits; r may be NULL when no row is sampled).  logits_out [n][vocab] (may be NULL) receives the logits
+ * BEFORE any penalty: nt_engine_decode_batch's bits.  next_out [n]: the tokens.  One synchronisation, no logits download unless asked for.  Refused
+ * (NTK_E_SHAPE + last_error; the engine stays usable) as nt_engine_decode_batch, and: a sampled row with top_k outside 1 .. 64 or top_k >= vocab, a
+ * vocabulary beyond 131 072, an n_recent[i] outside 0 .. 4096.
+ * nt_engine_generate_batch_ex: nt_engine_generate_batch with params[i] = sequence i's temperature, top_k, top_p, repeat_penalty, repeat_window, seed,
+ * max_tokens and stop_at_eos.  Sequence i has its own sampler seeded with params[i].seed; its first token is sampled on the host from the prefill logits
+ * (penalty over the prompt, then the draw), every further one on the device in the lockstep step, with the window = the last min(have, repeat_window) ids
+ * of prompt + generated -- the stream nt_engine_generate_tokens' sampler would produce on those logits.  A sequence whose settings the device sampler
+ * does not take (top_k <= 0, > 64 or >= vocab; repeat_window > 4096) is sampled by its host sampler from its own row of logits (vocab floats per step).
+ * A sequence leaves at its own max_tokens, at EOS if its own stop_at_eos is set, or at the end of the context; out_stride must hold the largest
+ * max_tokens.  Returns n or a negative NTK_E_*; stats as nt_engine_generate_batch. */
 int  nt_engine_seq_forward(nt_engine_t e, int slot, const int* tokens, int n, int start_pos, float* logits_out);
 int  nt_engine_decode_batch(nt_engine_t e, const int* slots, const int* tokens, const int* positions, int n, float* logits_out, int* next_out);
 int  nt_engine_generate_batch(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* p, int* out, int out_stride,
                               int* out_counts);
+int  nt_engine_decode_batch_sample(nt_engine_t e, const int* slots, const int* tokens, const int* positions, int n, const nt_gen_params* params,
+                                   const int* const* recent, const int* n_recent, const float* r, float* logits_out, int* next_out);
+int  nt_engine_generate_batch_ex(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* params, int* out,
+                                 int out_stride, int* out_counts);
 /* Scoring: logprob_out[i] = log P(targets[i] | tokens[0..i]) (natural log) for targets[i] >= 0, 0 where targets[i] < 0; top1_out (optional, may be NULL):
  * the greedy token behind tokens[0..i] for every i.  Runs the prompt pass over tokens at start_pos (the KV cache afterwards = nt_engine_forward's), then
  * the LM head over "score_rows" positions at a time; returns the number of scored positions or a negative NTK_E_* (+ nt_engine_last_error: an id out of
@@ -203,6 +225,9 @@ int   nt_tokenizer_is_gpt2(nt_tokenizer_t t);
 /* n_draws successive Sampler::sample calls on the same logits (penalty applied once per draw over `recent`) */
 int   nt_sampler_draw(const float* logits, int n, const nt_gen_params* p, const int* recent, int n_recent,
                       int n_draws, int* out);
+/* TEST SUPPORT, host only: a sampler seeded with p->seed, `skip` draws discarded, then ONE repeat penalty over recent[0 .. n_recent) (its last
+ * repeat_window entries) + one sample on a copy of `logits`: draw number `skip` of nt_sampler_draw's stream, given the window it had then */
+int   nt_sampler_draw_nth(const float* logits, int n, const nt_gen_params* p, const int* recent, int n_recent, int skip, int* out);
 /* the first n uniform draws a sampler seeded with `seed` consumes (one per sampled token) */
 int   nt_sampler_uniforms(uint64_t seed, int n, float* out);
 

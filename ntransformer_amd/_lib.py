@@ -30,6 +30,11 @@ class KvBatch(C.Structure):   # ntk_kv_batch: the rows' cache base pointers of o
     _fields_ = [("k", C.c_void_p * 16), ("v", C.c_void_p * 16)]
 
 
+class SampleRows(C.Structure):   # ntk_sample_rows: the per-row settings of ntk_sample_rows_top_k
+    _fields_ = [("temperature", C.c_float * 16), ("top_p", C.c_float * 16), ("repeat_penalty", C.c_float * 16), ("r", C.c_float * 16),
+                ("top_k", C.c_int * 16), ("n_recent", C.c_int * 16)]
+
+
 class GemvSeg(C.Structure):
     _fields_ = [("W", C.c_void_p), ("y", C.c_void_p), ("rows", C.c_int), ("dtype", C.c_int)]
 
@@ -129,6 +134,8 @@ def lib() -> C.CDLL:
         "ntk_embed_rows": (i, [vp, vp, vp, i, i, i, vp]),
         "ntk_argmax": (i, [vp, i, vp, vp, vp, vp]),
         "ntk_logprob_rows": (i, [vp, i, i, i, vp, vp, vp, vp]),
+        "ntk_sample_rows_scratch_bytes": (C.c_size_t, [i, i]),
+        "ntk_sample_rows_top_k": (i, [vp, i, i, i, vp, i, C.POINTER(SampleRows), vp, vp, vp, vp]),
         "ntk_advance_pos": (i, [vp, vp]),
         "ntk_debug_sclk": (i, [vp, vp]),
         "ntk_debug_sclk_begin": (i, [vp, vp, vp]),

@@ -170,6 +170,18 @@ int nt_engine_generate_batch(nt_engine_t e, const int* const* prompts, const int
     try { return E(e)->generate_batch(prompts, prompt_lens, n, *p, out, out_stride, out_counts); } catch (...) { return NTK_E_NOMEM; }
 }
 
+int nt_engine_decode_batch_sample(nt_engine_t e, const int* slots, const int* tokens, const int* positions, int n, const nt_gen_params* params,
+                                  const int* const* recent, const int* n_recent, const float* r, float* logits_out, int* next_out) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    try { return E(e)->decode_batch_sample(slots, tokens, positions, n, params, recent, n_recent, r, logits_out, next_out); } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_engine_generate_batch_ex(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* params, int* out, int out_stride,
+                                int* out_counts) {
+    if (!e || !prompts || !prompt_lens || !params || !out || !out_counts) return NTK_E_NULL;
+    try { return E(e)->generate_batch_ex(prompts, prompt_lens, n, params, out, out_stride, out_counts); } catch (...) { return NTK_E_NOMEM; }
+}
+
 int nt_batch_validate(const int* slots, const int* tokens, const int* positions, int n, int sequences, int max_seq, int vocab) {
     return nt::Model::validate_batch(slots, tokens, positions, n, sequences, max_seq, vocab, nullptr);   // host only
 }
@@ -395,10 +407,7 @@ int nt_tokenizer_is_gpt2(nt_tokenizer_t t) { return t && static_cast<nt::Tokeniz
 int nt_sampler_draw(const float* logits, int n, const nt_gen_params* p, const int* recent, int n_recent, int n_draws, int* out) {
     if (!logits || !p || !out || n <= 0) return NTK_E_NULL;
     nt::Sampler s;
-    nt::SamplerConfig c;
-    c.temperature = p->temperature; c.top_k = p->top_k; c.top_p = p->top_p; c.repeat_penalty = p->repeat_penalty;
-    c.repeat_window = p->repeat_window; c.seed = p->seed;
-    s.init(c);
+    s.init(nt::sampler_config(*p));
     std::vector<int> rec(recent ? recent : nullptr, recent ? recent + n_recent : nullptr);
     std::vector<float> l(n);
     for (int d = 0; d < n_draws; ++d) {
@@ -408,6 +417,20 @@ int nt_sampler_draw(const float* logits, int n, const nt_gen_params* p, const in
         rec.push_back(out[d]);
     }
     return n_draws;
+}
+
+// draw number `skip` of that stream on its own: the generator advanced past `skip` draws, then one penalty + sample on the caller's window
+int nt_sampler_draw_nth(const float* logits, int n, const nt_gen_params* p, const int* recent, int n_recent, int skip, int* out) {
+    if (!logits || !p || !out || n <= 0 || (n_recent > 0 && !recent)) return NTK_E_NULL;
+    if (skip < 0 || n_recent < 0) return NTK_E_SHAPE;
+    nt::Sampler s;
+    s.init(nt::sampler_config(*p));
+    for (int d = 0; d < skip; ++d) (void)s.draw();
+    const std::vector<int> rec(recent, recent + n_recent);
+    std::vector<float> l(logits, logits + n);
+    s.apply_repeat_penalty(l.data(), n, rec);
+    *out = s.sample(l.data(), n);
+    return NTK_OK;
 }
 
 // the uniform draws Sampler::sample takes from std::mt19937(seed), in order (one per sampled token): lets a test (or an embedder

@@ -94,6 +94,114 @@ int Engine::generate_batch(const int* const* prompts, const int* prompt_lens, in
     return rc == NTK_OK ? n : rc;
 }
 
+int Engine::decode_batch_sample(const int* slots, const int* tokens, const int* positions, int n, const nt_gen_params* params, const int* const* recent,
+                                const int* n_recent, const float* r, float* logits_out, int* next_out) {
+    if (!loaded_) { err_ = "model not loaded"; return NTK_E_NULL; }
+    if (!params || !next_out) { err_ = "decode_batch_sample: null argument"; return NTK_E_NULL; }
+    int rc = Model::validate_batch(slots, tokens, positions, n, model_.sequences(), model_.config().max_seq_len, model_.config().vocab_size, &err_);
+    if (rc != NTK_OK) return rc;
+    ntk_sample_rows rows{};
+    for (int i = 0; i < n; ++i) {
+        const bool sampled = params[i].temperature > 0.0f;
+        if (sampled && !r) { err_ = "decode_batch_sample: a sampled row needs its uniform draw"; return NTK_E_NULL; }
+        rows.temperature[i] = params[i].temperature; rows.top_k[i] = params[i].top_k; rows.top_p[i] = params[i].top_p;
+        rows.repeat_penalty[i] = params[i].repeat_penalty;
+        rows.r[i] = sampled ? r[i] : 0.0f;
+        rows.n_recent[i] = recent && n_recent ? n_recent[i] : 0;
+    }
+    rc = model_.decode_batch_sample(slots, tokens, positions, n, rows, recent, logits_out, nullptr, next_out);
+    if (rc != NTK_OK) err_ = model_.error();
+    return rc;
+}
+
+int Engine::generate_batch_ex(const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* params, int* out, int out_stride, int* out_counts) {
+    stats_ = Stats();
+    if (!loaded_) { err_ = "model not loaded"; return NTK_E_NULL; }
+    if (n < 1 || n > model_.sequences()) { err_ = "generate_batch_ex: the batch must hold 1 .. `sequences` prompts"; return NTK_E_SHAPE; }
+    const int V = model_.config().vocab_size, max_pos = model_.config().max_seq_len, eos = tok_.eos_id();
+    for (int i = 0; i < n; ++i) {
+        if (params[i].max_tokens < 1 || out_stride < params[i].max_tokens) {
+            err_ = "generate_batch_ex: out_stride must hold every sequence's max_tokens >= 1 ids";
+            return NTK_E_SHAPE;
+        }
+        if (!prompts[i]) { err_ = "generate_batch_ex: null prompt"; return NTK_E_NULL; }
+        if (prompt_lens[i] < 1 || prompt_lens[i] > max_pos) { err_ = "generate_batch_ex: a prompt is empty or exceeds the context"; return NTK_E_SHAPE; }
+    }
+    // prefill, slot by slot; the first token of each sequence is sampled on the host from its prompt's logits, as Engine::run does
+    std::vector<float> host(V), host_rows;
+    std::vector<Sampler> sampler(n);
+    std::vector<std::vector<int>> seq(n);   // prompt + generated ids: the repeat-penalty windows are cut from these
+    std::vector<int> pos(n);
+    std::vector<char> live(n, 1), on_host(n, 0);
+    model_.set_batched_prefill(opt_.batched_prefill);
+    auto t0 = Clock::now();
+    for (int i = 0; i < n; ++i) {
+        sampler[i].init(sampler_config(params[i]));
+        // what the device sampler does not take stays with this sequence's host Sampler (its row's logits alone are downloaded)
+        on_host[i] = !Model::device_sampler_supports(params[i].temperature, params[i].top_k, V) || params[i].repeat_window > Model::kMaxRecent;
+        seq[i].assign(prompts[i], prompts[i] + prompt_lens[i]);
+        if (!model_.forward(prompts[i], prompt_lens[i], 0, i)) { err_ = model_.error(); return NTK_E_LAUNCH; }
+        if (model_.copy_logits(host.data()) != NTK_OK) return NTK_E_LAUNCH;
+        sampler[i].apply_repeat_penalty(host.data(), V, seq[i]);
+        const int first = sampler[i].sample(host.data(), V);
+        seq[i].push_back(first);
+        out[(size_t)i * out_stride] = first;
+        out_counts[i] = 1;
+        pos[i] = prompt_lens[i];
+        stats_.prompt_tokens += prompt_lens[i];
+    }
+    stats_.prefill_ms = ms_since(t0);
+    int slots[Model::kMaxSequences], toks[Model::kMaxSequences], poss[Model::kMaxSequences], next[Model::kMaxSequences];
+    const int* recent[Model::kMaxSequences];
+    float* row_logits[Model::kMaxSequences];
+    auto d0 = Clock::now();
+    int rc = NTK_OK;
+    for (;;) {
+        int B = 0;
+        bool any_host = false;
+        ntk_sample_rows rows{};
+        for (int i = 0; i < n; ++i) {   // who is still in: not at EOS, below its max_tokens, inside the context
+            const nt_gen_params& p = params[i];
+            if (live[i] && ((p.stop_at_eos && seq[i].back() == eos) || out_counts[i] >= p.max_tokens || pos[i] >= max_pos)) live[i] = 0;
+            if (!live[i]) continue;
+            slots[B] = i; toks[B] = seq[i].back(); poss[B] = pos[i];
+            recent[B] = nullptr; row_logits[B] = nullptr;
+            if (on_host[i]) {   // to the device as a greedy row without a penalty (its result is ignored)
+                rows.repeat_penalty[B] = 1.0f;
+                any_host = true;
+            } else {
+                const int have = (int)seq[i].size(), win = std::max(0, std::min(have, p.repeat_window));   // sampler.cpp:34
+                rows.temperature[B] = p.temperature; rows.top_k[B] = p.top_k; rows.top_p[B] = p.top_p; rows.repeat_penalty[B] = p.repeat_penalty;
+                rows.n_recent[B] = win;
+                recent[B] = seq[i].data() + have - win;
+                rows.r[B] = p.temperature > 0.0f ? sampler[i].draw() : 0.0f;   // one draw per sampled token, none for a greedy row
+            }
+            ++B;
+        }
+        if (B == 0) break;
+        if (any_host) {   // V floats for each row the host samples
+            host_rows.resize((size_t)B * V);
+            for (int b = 0; b < B; ++b) if (on_host[slots[b]]) row_logits[b] = host_rows.data() + (size_t)b * V;
+        }
+        rc = model_.decode_batch_sample(slots, toks, poss, B, rows, recent, nullptr, any_host ? row_logits : nullptr, next);
+        if (rc != NTK_OK) { err_ = model_.error(); break; }
+        for (int b = 0; b < B; ++b) {
+            const int i = slots[b];
+            int tok = next[b];
+            if (on_host[i]) {
+                sampler[i].apply_repeat_penalty(row_logits[b], V, seq[i]);
+                tok = sampler[i].sample(row_logits[b], V);
+            }
+            seq[i].push_back(tok);
+            out[(size_t)i * out_stride + out_counts[i]++] = tok;
+            ++pos[i];
+            ++stats_.gen_tokens;
+        }
+    }
+    stats_.decode_ms = ms_since(d0);
+    return rc == NTK_OK ? n : rc;
+}
+
 // One generation, reference engine.cpp:40-145 step for step:
 //   prefill (timed) -> logits -> repeat penalty -> sample first token -> decode loop (timed as a whole;
 //   gen_tokens counts loop iterations, so the first sampled token is not counted) -> stop at EOS.

@@ -33,7 +33,15 @@ struct Stats {            // reference engine.h:76-84
     float decode_tok_s() const { return decode_ms > 0 ? gen_tokens / (decode_ms / 1000.0f) : 0.0f; }
 };
 
-using TokenCallback = std::function<bool(const std::string& piece, int token_id)>;
+// the sampler settings of a C-API request (max_tokens / stop_at_eos are the generator's, not the sampler's)
+inline SamplerConfig sampler_config(const nt_gen_params& p) {
+    SamplerConfig c;
+    c.temperature = p.temperature; c.top_k = p.top_k; c.top_p = p.top_p;
+    c.repeat_penalty = p.repeat_penalty; c.repeat_window = p.repeat_window; c.seed = p.seed;
+    return c;
+}
+
+using TokenCallback =std::function<bool(const std::string& piece, int token_id)>;
 
 struct EngineOptions {
     bool fused = true;            // fused 5-launch/layer decode path (false: the reference's 15-launch sequence)
@@ -60,6 +68,12 @@ public:
     // n prompts generated in lockstep over the sequence slots ("sequences" option), greedy: prompt i prefilled into slot i, then one Model::decode_batch
     // per step over the sequences still alive (include/ntransformer.h: nt_engine_generate_batch)
     int generate_batch(const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params& p, int* out, int out_stride, int* out_counts);
+    // one batched step with every row sampled on the device by its own params[i] (include/ntransformer.h: nt_engine_decode_batch_sample)
+    int decode_batch_sample(const int* slots, const int* tokens, const int* positions, int n, const nt_gen_params* params, const int* const* recent,
+                            const int* n_recent, const float* r, float* logits_out, int* next_out);
+    // generate_batch with per-sequence settings, sampled: one Sampler per sequence, the first token from the prefill logits on the host, then
+    // Model::decode_batch_sample per step (include/ntransformer.h: nt_engine_generate_batch_ex)
+    int generate_batch_ex(const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* params, int* out, int out_stride, int* out_counts);
     void chat(const GenerateConfig& cfg);
     void benchmark(const std::string& prompt, int n_tokens);
     void print_stats(const Stats& st) const;

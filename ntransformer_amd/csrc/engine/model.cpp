@@ -33,7 +33,7 @@ void Model::free_all() {
     for (void* p : allocs_) nt_hip_free(p);
     allocs_.clear();
     auto free_host = [](auto*& p) { if (p) nt_hip_free_host(p); p = nullptr; };
-    free_host(h_token_); free_host(h_ring_); free_host(h_recent_);
+    free_host(h_token_); free_host(h_ring_); free_host(h_recent_); free_host(h_batch_recent_); free_host(h_batch_next_);
     sample_scratch_ = gemm_ws_ = gemm_ws2_ = nullptr;
     d_recent_ = nullptr;
     attn_sync_ = nullptr;
@@ -47,7 +47,7 @@ void Model::free_all() {
     host_pos_ = attn_regime_ = 0;
     k_cache_ = v_cache_ = nullptr;
     slot_k_.clear(); slot_v_.clear();
-    batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = nullptr;
+    batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = batch_recent_ = nullptr; batch_sample_scratch_ = nullptr;
     kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
     k_cache_q8_ = v_cache_q8_ = nullptr; kv_f16_k_ = kv_f16_v_ = nullptr; kv_q8_layer_bytes_ = 0; kv_cache_bytes_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;

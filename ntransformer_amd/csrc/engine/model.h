@@ -12,6 +12,8 @@
 #include "gguf.h"
 #include "synth.h"
 
+struct ntk_sample_rows;   // include/ntk_engine.h
+
 struct ihipGraphExec_t;   // hipGraphExec_t
 
 namespace nt {
@@ -69,9 +71,10 @@ public:
     // ---- sequence slots and the batched decode step ---------------------------------------------------------------------------------
     // "sequences" = N (1 .. kMaxSequences, default 1; BEFORE the load, kept across loads; a sharing sequence takes its own): slots 1 .. N - 1 are extra F16
     // caches of slot 0's [L][max_seq][n_kv][hd] layout, allocated at load and counted in kv_cache_bytes(), beside a [16][vocab] F32 logits buffer, the batch
-    // attention's scratch and -- where score_buffers() would need one -- an LM-head GEMM workspace.  N = 1 allocates nothing (decode_batch with one row
-    // on slot 0 allocates the logits buffers on its first call, as score() does).  Refused at load with kv_cache = q8_0, tensor parallelism or a context of fewer than N positions (a step is a pass of up to N rows
-    // through the max_seq-row activation buffers).
+    // attention's scratch, the batched sampler's windows / scratch / pinned mirrors (batch_sample_buffers: about 0.9 MB, not counted) and -- where
+    // score_buffers() would need one -- an LM-head GEMM workspace.  N = 1 allocates nothing (decode_batch with one row on slot 0 allocates the logits
+    // buffers on its first call, as score() does).  Refused at load with kv_cache = q8_0, tensor parallelism or a context of fewer than N positions (a
+    // step is a pass of up to N rows through the max_seq-row activation buffers).
     static constexpr int kMaxSequences = 16;
     int set_sequences(int n);
     int sequences() const { return sequences_; }
@@ -83,6 +86,16 @@ public:
     // kernels' attention -- within the 1e-3 bar of the fused decode path, not its bits; within one batch size a row depends on nothing but that row.
     // Touches nothing of the fused path's slot-0 state (d_pos_, d_token_, graphs).  Refused (NTK_E_SHAPE + error()): see validate_batch.
     int decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out);
+    // The same step with the rows SAMPLED on the device: ntk_sample_rows_top_k over the step's logits in place of the greedy pass -- row b with rows'
+    // settings [b], draw rows.r[b] and the window recent[b][0 .. rows.n_recent[b]) (host ints; read only where the row has a penalty to apply; each
+    // n_recent at most kMaxRecent).  The windows go up in ONE further host-to-device copy, packed at the step's own pitch; next_out [B] comes back through a
+    // pinned mirror; one synchronisation.  logits_out [B][vocab] (optional) and row_logits[b] (optional per row, vocab floats each: a caller that samples
+    // some rows on the host downloads those alone) receive the logits BEFORE any penalty: their copies are queued ahead of the sampler.  The sampled stream
+    // is the host Sampler's on this step's logits (csrc/sampling_core.hip.h).  Refused as decode_batch, and NTK_E_SHAPE for a row the device sampler does
+    // not take (device_sampler_supports) or a window beyond kMaxRecent.
+    static constexpr int kMaxRecent = 4096;
+    int decode_batch_sample(const int* slots, const int* tokens, const int* positions, int B, const ntk_sample_rows& rows, const int* const* recent,
+                            float* logits_out, float* const* row_logits, int* next_out);
     // the host-side checks of decode_batch (no device): B in 1 .. sequences, every slot in range and named once, positions in [0, max_seq), token ids in
     // [0, vocab); NTK_OK or NTK_E_NULL / NTK_E_SHAPE with the reason in *why (optional)
     static int validate_batch(const int* slots, const int* tokens, const int* positions, int B, int sequences, int max_seq, int vocab, std::string* why);
@@ -256,6 +269,8 @@ private:
     bool lm_head_f16() const;         // ... is the FP16 GEMM
     int lm_head_workspace(const char* who);   // the LM head's own GEMM workspace where gemm_ws_ is too small for vocab rows (score_ws_)
     int batch_buffers();              // the buffers of decode_batch(): at load when sequences > 1, else on its first call
+    int batch_logits(const int* slots, const int* tokens, const int* positions, int B);   // decode_batch / _sample up to batch_logits_ (queued)
+    int batch_sample_buffers();       // ... and what decode_batch_sample() needs beside them (windows, sampler scratch, pinned mirrors): the same rule
     int score_buffers();              // the buffers of score(), on its first call (and again when score_rows grew)
     void prof_mark(int cls, bool begin);
     bool use_persistent_now() const;
@@ -289,6 +304,10 @@ private:
     float* batch_logprob_ = nullptr;   // [kMaxSequences] (unused result of ntk_logprob_rows)
     int* batch_next_ = nullptr;     // [kMaxSequences] first maxima
     float* batch_attn_scratch_ = nullptr;   // kMaxSequences x the single-row split scratch
+    int* batch_recent_ = nullptr;   // [kMaxSequences][kRecentCap] device ints: the rows' repeat-penalty windows (decode_batch_sample)
+    int* h_batch_recent_ = nullptr; // pinned staging of it (a step packs its windows at the step's own pitch)
+    void* batch_sample_scratch_ = nullptr;   // ntk_sample_rows_scratch_bytes(kMaxSequences, V)
+    int* h_batch_next_ = nullptr;   // pinned [kMaxSequences]: the sampled tokens (ntk_sample_rows_top_k's mirror)
     uint8_t* k_cache_q8_ = nullptr; // [L] x kv_q8_layer_bytes_ (ntk_kv_q8_cache_bytes: int8 quants, then half scales)
     uint8_t* v_cache_q8_ = nullptr;
     size_t kv_q8_layer_bytes_ = 0;
@@ -321,7 +340,7 @@ private:
     void* sample_scratch_ = nullptr;
     int* d_recent_ = nullptr;       // device copy of the repeat-penalty window
     int* h_recent_ = nullptr;       // pinned staging of it
-    static constexpr int kRecentCap = 4096;
+    static constexpr int kRecentCap = kMaxRecent;
     float* rope_inv_freq_ = nullptr; // [hd/2] 1/powf(theta, 2i/hd), computed once on the host (rotary.cu:47)
     void* stream_ = nullptr;
     bool batched_prefill_ = true;

@@ -387,7 +387,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         for (int i = 0; i < cfg_.head_dim / 2; ++i) f[i] = 1.0f / powf(cfg_.rope_theta, (2.0f * i) / cfg_.head_dim);
         nt_hip_memcpy_h2d(rope_inv_freq_, f.data(), f.size() * 4);
     }
-    if (sequences_ > 1) NT_TRY(batch_buffers());
+    if (sequences_ > 1) { NT_TRY(batch_buffers()); NT_TRY(batch_sample_buffers()); }   // (none of it counted in kv_cache_bytes_)
     return NTK_OK;
 }
 

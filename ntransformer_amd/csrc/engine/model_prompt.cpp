@@ -478,14 +478,12 @@ int Model::validate_batch(const int* slots, const int* tokens, const int* positi
     return NTK_OK;
 }
 
-int Model::decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out) {
-    NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
-    if (kv_q8_ || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
-    NT_TRY(batch_buffers());
-    const int H = cfg_.hidden_size, V = cfg_.vocab_size, N = kMaxSequences;
+// the step up to its logits: tokens | positions up, embedding, the layer loop in batch mode, final RMSNorm, LM head into batch_logits_ (all queued, no wait)
+int Model::batch_logits(const int* slots, const int* tokens, const int* positions, int B) {
+    const int H = cfg_.hidden_size, N = kMaxSequences;
     void* s = stream_;
     tp_call_ = 0;
-    int* const host = batch_host_;   // tokens | positions | "no target": ONE copy (a member: the copy may read it until the synchronisation below)
+    int* const host = batch_host_;   // tokens | positions | "no target": ONE copy (a member: the copy may read it until the caller's synchronisation)
     KvTarget kv{0, slots, 0};
     for (int b = 0; b < N; ++b) {
         host[b] = b < B ? tokens[b] : 0;
@@ -504,12 +502,85 @@ int Model::decode_batch(const int* slots, const int* tokens, const int* position
     if (rm) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)output_norm_.ptr, B, H, cfg_.norm_eps, row_max_, nullptr, s));
     else ok(ntk_rmsnorm(residual_, hidden_, (const float*)output_norm_.ptr, B, H, cfg_.norm_eps, s));
     ok(lm_head(batch_logits_, residual_, B, rm));
+    return rc;
+}
+
+int Model::decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out) {
+    NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
+    if (kv_q8_ || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    NT_TRY(batch_buffers());
+    const int V = cfg_.vocab_size, N = kMaxSequences;
+    void* s = stream_;
+    int rc = batch_logits(slots, tokens, positions, B);
+    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
     if (next_out) ok(ntk_logprob_rows(batch_logits_, B, V, V, batch_in_ + 2 * N, batch_logprob_, batch_next_, s));
     if (rc == NTK_OK && logits_out) ok(ntk_memcpy_d2h_async(logits_out, batch_logits_, (size_t)B * V * 4, s));
     if (rc == NTK_OK && next_out) ok(ntk_memcpy_d2h_async(next_out, batch_next_, (size_t)B * 4, s));
     ok(ntk_stream_synchronize(s));
     if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
     if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("decode_batch failed: ") + ntk_status_string(rc);
+    return rc;
+}
+
+int Model::batch_sample_buffers() {
+    const size_t N = kMaxSequences;
+    auto need = [&](auto*& p, size_t bytes) {
+        if (p) return true;
+        void* d = nt_hip_malloc(bytes + 256);
+        if (!d) return false;
+        allocs_.push_back(d);
+        p = static_cast<std::remove_reference_t<decltype(p)>>(d);
+        return true;
+    };
+    if (!need(batch_recent_, N * kRecentCap * 4) || !need(batch_sample_scratch_, ntk_sample_rows_scratch_bytes((int)N, cfg_.vocab_size))) {
+        err_ = "decode_batch_sample: no device memory for the rows' windows and the sampler's scratch";
+        return NTK_E_NOMEM;
+    }
+    if (!h_batch_recent_) h_batch_recent_ = (int*)nt_hip_malloc_host(N * kRecentCap * 4);
+    if (!h_batch_next_) h_batch_next_ = (int*)nt_hip_malloc_host(N * 4);
+    if (!h_batch_recent_ || !h_batch_next_) { err_ = "decode_batch_sample: no pinned host memory for the windows and the sampled tokens"; return NTK_E_NOMEM; }
+    return NTK_OK;
+}
+
+int Model::decode_batch_sample(const int* slots, const int* tokens, const int* positions, int B, const ntk_sample_rows& rows, const int* const* recent,
+                               float* logits_out, float* const* row_logits, int* next_out) {
+    NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
+    if (kv_q8_ || tp_world_ > 1) { err_ = "decode_batch_sample: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if (!next_out) { err_ = "decode_batch_sample: null argument"; return NTK_E_NULL; }
+    const int V = cfg_.vocab_size;
+    int pitch = 0;   // of this step's windows: the longest one a penalty reads
+    for (int b = 0; b < B; ++b) {
+        if (V > 131072 || !device_sampler_supports(rows.temperature[b], rows.top_k[b], V)) {
+            err_ = "decode_batch_sample: a row the device sampler does not take (temperature > 0 needs 0 < top_k <= 64, top_k < vocab <= 131072)";
+            return NTK_E_SHAPE;
+        }
+        if (rows.n_recent[b] < 0 || rows.n_recent[b] > kMaxRecent) { err_ = "decode_batch_sample: a window of 0 .. 4096 tokens per row"; return NTK_E_SHAPE; }
+        if (rows.repeat_penalty[b] > 1.0f && rows.n_recent[b] > 0) {
+            if (!recent || !recent[b]) { err_ = "decode_batch_sample: null window"; return NTK_E_NULL; }
+            pitch = std::max(pitch, rows.n_recent[b]);
+        }
+    }
+    NT_TRY(batch_buffers());
+    NT_TRY(batch_sample_buffers());
+    void* s = stream_;
+    ntk_sample_rows dev = rows;   // rows without a penalty to apply read no window
+    for (int b = 0; b < B; ++b) {
+        if (rows.repeat_penalty[b] > 1.0f && rows.n_recent[b] > 0) memcpy(h_batch_recent_ + (size_t)b * pitch, recent[b], (size_t)rows.n_recent[b] * 4);
+        else dev.n_recent[b] = 0;
+    }
+    // (the previous step's copy out of the pinned staging has completed: that step synchronised)
+    if (pitch > 0) NT_TRY(ntk_memcpy_h2d_async(batch_recent_, h_batch_recent_, (size_t)B * pitch * 4, s));
+    int rc = batch_logits(slots, tokens, positions, B);
+    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
+    // the logits as the step computed them: queued AHEAD of the sampler, whose penalty rewrites batch_logits_ in place
+    if (rc == NTK_OK && logits_out) ok(ntk_memcpy_d2h_async(logits_out, batch_logits_, (size_t)B * V * 4, s));
+    for (int b = 0; b < B && rc == NTK_OK && row_logits; ++b)
+        if (row_logits[b]) ok(ntk_memcpy_d2h_async(row_logits[b], batch_logits_ + (size_t)b * V, (size_t)V * 4, s));
+    if (rc == NTK_OK) ok(ntk_sample_rows_top_k(batch_logits_, B, V, V, batch_recent_, pitch, &dev, batch_next_, h_batch_next_, batch_sample_scratch_, s));
+    ok(ntk_stream_synchronize(s));
+    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
+    if (rc == NTK_OK) for (int b = 0; b < B; ++b) next_out[b] = h_batch_next_[b];
+    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("decode_batch_sample failed: ") + ntk_status_string(rc);
     return rc;
 }
 

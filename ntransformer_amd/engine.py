@@ -70,6 +70,11 @@ def _bind():
     L.nt_engine_seq_forward.argtypes = [vp, i, C.POINTER(i), i, i, vp]
     L.nt_engine_decode_batch.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), i, vp, vp]
     L.nt_engine_generate_batch.argtypes = [vp, C.POINTER(C.POINTER(i)), C.POINTER(i), i, C.POINTER(GenParams), C.POINTER(i), i, C.POINTER(i)]
+    L.nt_engine_decode_batch_sample.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), i, C.POINTER(GenParams), C.POINTER(C.POINTER(i)), C.POINTER(i),
+                                                C.POINTER(f), vp, vp]
+    L.nt_engine_generate_batch_ex.argtypes = [vp, C.POINTER(C.POINTER(i)), C.POINTER(i), i, C.POINTER(GenParams), C.POINTER(i), i, C.POINTER(i)]
+    L.nt_sampler_draw_nth.argtypes = [vp, i, C.POINTER(GenParams), C.POINTER(i), i, i, C.POINTER(i)]
+    L.nt_sampler_uniforms.argtypes = [C.c_uint64, i, vp]
     L.nt_batch_validate.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, i, i]
     L.nt_engine_debug_kv_read_slot.argtypes = [vp, i, i, i, i, vp, vp]
     L.nt_engine_debug_kv_write_slot.argtypes = [vp, i, i, i, i, vp, vp]
@@ -224,6 +229,38 @@ class Engine:
         st = self.L.nt_engine_generate_batch(self.h, ptrs, lens, n, C.byref(p), out, stride, counts)
         if st < 0:
             self._check(st, "generate_batch")
+        return [list(out[i * stride: i * stride + counts[i]]) for i in range(n)]
+
+    def decode_batch_sample(self, slots: Sequence[int], tokens: Sequence[int], positions: Sequence[int], params: Sequence[GenParams],
+                            recent: Sequence[Sequence[int]], r: Sequence[float], logits: bool = True):
+        """decode_batch with every row sampled on the device: row i by params[i] over the window recent[i] (the caller cuts it: the last repeat_window
+        tokens) with the uniform draw r[i] (ignored where temperature <= 0).  (logits [n, vocab] BEFORE any penalty or None, tokens [n])."""
+        n = len(slots)
+        ia = lambda xs: (C.c_int * max(len(xs), 1))(*[int(x) for x in xs])
+        pa = (GenParams * max(n, 1))(*params)
+        wins = [ia(w) for w in recent]
+        ptrs = (C.POINTER(C.c_int) * max(n, 1))(*[C.cast(w, C.POINTER(C.c_int)) for w in wins])
+        ra = (C.c_float * max(n, 1))(*[float(x) for x in r])
+        out = np.empty((n, self.vocab_size), np.float32) if logits else None
+        nxt = (C.c_int * max(n, 1))()
+        self._check(self.L.nt_engine_decode_batch_sample(self.h, ia(slots), ia(tokens), ia(positions), n, pa, ptrs, ia([len(w) for w in recent]), ra,
+                                                         out.ctypes.data_as(C.c_void_p) if logits else None, C.cast(nxt, C.c_void_p)), "decode_batch_sample")
+        return out, list(nxt[:n])
+
+    def generate_batch_ex(self, prompts: Sequence[Sequence[int]], params: Sequence[GenParams]) -> List[List[int]]:
+        """Generation of len(prompts) sequences in lockstep (prompt i in slot i), sequence i sampled with params[i] -- its own temperature, top_k, top_p,
+        repeat penalty and window, seed, max_tokens and stop_at_eos: the generated ids per sequence."""
+        n = len(prompts)
+        pa = (GenParams * max(n, 1))(*params)
+        rows = [(C.c_int * max(len(q), 1))(*[int(t) for t in q]) for q in prompts]
+        ptrs = (C.POINTER(C.c_int) * max(n, 1))(*[C.cast(r, C.POINTER(C.c_int)) for r in rows])
+        lens = (C.c_int * max(n, 1))(*[len(q) for q in prompts])
+        stride = max([int(p.max_tokens) for p in params] + [1])
+        out = (C.c_int * (max(n, 1) * stride))()
+        counts = (C.c_int * max(n, 1))()
+        st = self.L.nt_engine_generate_batch_ex(self.h, ptrs, lens, n, pa, out, stride, counts)
+        if st < 0:
+            self._check(st, "generate_batch_ex")
         return [list(out[i * stride: i * stride + counts[i]]) for i in range(n)]
 
     def kv_read_slot(self, slot: int, layer: int, pos0: int, n: int, row_halves: int):
@@ -394,6 +431,25 @@ class Engine:
         out = (C.c_int * 4096)()
         n = self.L.nt_engine_tokenize(self.h, text.encode(), int(add_bos), out, 4096)
         return list(out[:n])
+
+
+def sampler_draw_nth(logits: np.ndarray, params: GenParams, recent: Sequence[int], skip: int) -> int:
+    """Host only (nt_sampler_draw_nth): the token a Sampler seeded with params.seed returns for its draw number `skip` -- one repeat penalty over `recent`
+    (its last repeat_window entries), then one sample -- on `logits`."""
+    x = np.ascontiguousarray(logits, dtype=np.float32)
+    rec = (C.c_int * max(len(recent), 1))(*[int(t) for t in recent])
+    out = C.c_int()
+    check(_bind().nt_sampler_draw_nth(x.ctypes.data_as(C.c_void_p), x.size, C.byref(params), rec, len(recent), int(skip), C.byref(out)), "sampler_draw_nth")
+    return int(out.value)
+
+
+def sampler_uniforms(seed: int, n: int) -> np.ndarray:
+    """Host only (nt_sampler_uniforms): the first n uniform draws of a sampler seeded with `seed`, float32."""
+    out = np.zeros(max(n, 1), np.float32)
+    got = _bind().nt_sampler_uniforms(int(seed), n, out.ctypes.data_as(C.c_void_p))
+    if got != n:
+        raise _lib.NtkError(int(got), "sampler_uniforms")
+    return out[:n]
 
 
 def synth_write_gguf(path: str, spec: SynthSpec, nthreads: int = 0) -> None:

@@ -373,6 +373,24 @@ def sample_top_k(logits, n, recent, n_recent, repeat_penalty, temperature, top_k
     return st
 
 
+def sample_rows_top_k(logits, n_rows, vocab, ld, recent, recent_ld, rows, d_out, stream=None, null=()):
+    """ntk_sample_rows_top_k: the sampler over the rows of a batched step, each with its own settings.  logits: device F32 [n_rows][ld], penalised in
+    place; recent: device int32 [n_rows][recent_ld]; rows: a list of (temperature, top_k, top_p, repeat_penalty, r, n_recent) per row, or a ready
+    _lib.SampleRows; token ids to d_out (device int32 [n_rows]).  Returns the status.  null: names of pointer arguments to pass as NULL (the refusals)."""
+    L = _lib.lib()
+    if not isinstance(rows, _lib.SampleRows):
+        sr = _lib.SampleRows()
+        for b, (temperature, top_k, top_p, repeat_penalty, r, n_recent) in enumerate(rows):
+            sr.temperature[b], sr.top_k[b], sr.top_p[b], sr.repeat_penalty[b], sr.r[b], sr.n_recent[b] = temperature, top_k, top_p, repeat_penalty, r, n_recent
+        rows = sr
+    scratch = DeviceBuffer(int(L.ntk_sample_rows_scratch_bytes(min(max(n_rows, 1), 16), min(max(vocab, 1), 1 << 20))))
+    arg = lambda name, v: None if name in null else v
+    st = L.ntk_sample_rows_top_k(arg("logits", _p(logits)), n_rows, vocab, ld, _p(recent), recent_ld, arg("rows", C.pointer(rows)), arg("d_out", _p(d_out)), None,
+                                 arg("scratch", _p(scratch)), stream)
+    synchronize()   # `scratch` is released when this returns
+    return st
+
+
 def gemm_quant(Y, W, X, n_tokens, out_features, in_features, dtype, resid=None, stream=None):
     """Y[t,:] = W . X[t,:] (+ resid[t,:]) for a chunk of prompt tokens: one pass over W per 16 tokens (ntk_gemm_quant)."""
     check(_lib.lib().ntk_gemm_quant(_p(Y), _p(W), _p(X), n_tokens, out_features, in_features, int(dtype), _p(resid),
