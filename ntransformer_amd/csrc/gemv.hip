@@ -49,10 +49,18 @@ struct AttnFuse {};             // (the ATT instantiations exist in EXPERIMENTS=
 
 // LM: the lane-major Q8_0 repack (gemv_core.hip.h: q8l_layout) -- the same kernel with the row transport replaced: a lane loads its own 64 quants (four
 // coalesced 16-byte requests) and its two scales (one dword) straight into registers; no staging areas, no ds_write / read-back / realign.
-template <int DT, bool NORM, bool XFAST, bool A16, bool ATT = false, bool XI = false, bool LM = false>
+//
+// NSF: whether a row is one slice, as a compile-time choice for the lane-major kernels -- each instantiation carries only its own row loop and
+// epilogue (one kernel for both held 128 VGPRs with 3-4 of them spilled to scratch: a private segment on the headline's hottest launches)
+//   NS_ANY    decided at run time from p.ns (the kernels over GGUF blocks)
+//   NS_ONE    rows of one slice: a wave owns whole rows
+//   NS_SPLIT  rows of several slices, one wave per slice, partial sums combined through LDS
+enum { NS_ANY = 0, NS_ONE = 1, NS_SPLIT = 2 };
+template <int DT, bool NORM, bool XFAST, bool A16, bool ATT = false, bool XI = false, bool LM = false, int NSF = NS_ANY>
 __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int bid, const int nblk, const AttnFuse* attp = nullptr) {   // workgroup bid of nblk
     using F = Fmt<DT>;
     static_assert(!LM || (DT == NTK_DT_Q8_0 && !A16 && !ATT && !XI), "lane-major rows: Q8_0");
+    static_assert(NSF == NS_ANY || LM, "compile-time slice forms: the lane-major kernels");
     constexpr int NL = LM ? 4 : F::NL;
     constexpr int STAGE = LM ? 0 : NL * 1024 + 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -98,20 +106,22 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
     }
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwaves = p.ns * p.rw;
-    const int s = wave % p.ns;        // column slice of this wave
-    const int g = wave / p.ns;        // row group of this wave
+    const int ns = NSF == NS_ONE ? 1 : p.ns;
+    const bool single = NSF == NS_ANY ? p.ns == 1 : NSF == NS_ONE;   // rows of one slice
+    const int nwaves = ns * p.rw;
+    const int s = wave % ns;        // column slice of this wave
+    const int g = wave / ns;        // row group of this wave
     constexpr bool norm = NORM;   // compile-time: the norm-weight loads/stores must not sit behind a runtime branch
 
     // LDS: [activation image][per-wave staging of row bytes][partials].  Single-slice rows (<= 4096 columns) keep the image and
     // the staging areas apart, so a wave enters the row loop as soon as it has read its own activations; wider rows (image 35-70 KB)
     // reuse the image as staging area behind one more barrier.
-    const size_t image_bytes = (size_t)std::min(p.ns, 4) * 64 * XPITCH * 4;
-    const size_t stage0 = p.ns == 1 ? image_bytes : 0;
-    const size_t regionA = p.ns == 1 ? image_bytes + (size_t)nwaves * STAGE : std::max((size_t)nwaves * STAGE, image_bytes);
+    const size_t image_bytes = (size_t)std::min(ns, 4) * 64 * XPITCH * 4;
+    const size_t stage0 = single ? image_bytes : 0;
+    const size_t regionA = single ? image_bytes + (size_t)nwaves * STAGE : std::max((size_t)nwaves * STAGE, image_bytes);
     float* part = reinterpret_cast<float*>(smem + regionA);
-    float* red = part + 2 * p.rw * p.ns * RB;
-    const size_t lds_floats_total = regionA / 4 + (size_t)(2 * p.rw * p.ns * RB + 16 + 16);   // ... + red[16] + 16 spare
+    float* red = part + 2 * p.rw * ns * RB;
+    const size_t lds_floats_total = regionA / 4 + (size_t)(2 * p.rw * ns * RB + 16 + 16);   // ... + red[16] + 16 spare
 
     // ---- item bookkeeping + first prefetch (issued before the prologue so HBM latency overlaps it) ----
     uint8_t* stage = smem + stage0 + (size_t)wave * STAGE;
@@ -125,13 +135,24 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
     const int n_my = (p.total_rows > group) ? ((p.total_rows - 1 - group) / ngroups + 1) * mats : 0;
 
     // item q of this wave -> (segment, row inside the segment); q < n_my  (per-lane form, used by the combine step)
+    // The segment table of that step lives in scalar registers (MAX_SEG = 3: two row counts, three y pointers): a lane-indexed p.seg[seg] is a
+    // dependent memory round trip at the end of every batch.  One segment: the target is segment 0, nothing to search.
+    static_assert(MAX_SEG == 3, "locate / seg_y: unrolled for three segments");
+    const int seg_rows0 = p.seg[0].rows, seg_rows1 = p.seg[1].rows;
+    float* const seg_y0 = p.seg[0].y;
+    float* const seg_y1 = p.seg[1].y;
+    float* const seg_y2 = p.seg[2].y;
     auto locate = [&](int q, int& seg, int& row) {
         int r = group + (q >> (mats - 1)) * ngroups;   // mats is 1 or 2
         if (p.silu_pair) { seg = q & 1; row = r; return; }
         seg = 0;
-        while (seg + 1 < p.nseg && r >= p.seg[seg].rows) { r -= p.seg[seg].rows; ++seg; }
+        if (p.nseg > 1 && r >= seg_rows0) {
+            r -= seg_rows0; seg = 1;
+            if (p.nseg > 2 && r >= seg_rows1) { r -= seg_rows1; seg = 2; }
+        }
         row = r;
     };
+    auto seg_y = [&](int seg) { return seg == 0 ? seg_y0 : seg == 1 ? seg_y1 : seg_y2; };
     // The wave walks its items in order, so the location is kept as a cursor (scalar registers) and advanced
     // incrementally: one add and one compare per row instead of a search through the segment table.
     int cu_seg = 0, cu_row = group, cu_rows = p.silu_pair ? 0x7fffffff : p.seg[0].rows;   // cursor = next item to issue
@@ -163,7 +184,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
     float pf_res = 0.0f;                         // residual of that row (ns == 1): fetched a row ahead, not in the epilogue
     auto issue = [&]() {   // prefetch the item under the cursor (rows * row_bytes < 4 GiB: checked on the host)
         pf_seg = cu_seg; pf_row = cu_row;
-        if (p.resid != nullptr && p.ns == 1) {
+        if (p.resid != nullptr && single) {
             int idx = cu_row;
             asm volatile("" : "+v"(idx));   // a vector load: a scalar one would sit in lgkmcnt in front of the LDS reads
             pf_res = p.resid[idx];
@@ -207,7 +228,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
         float* ximg = reinterpret_cast<float*>(smem);
         constexpr int GS = 4;   // slices per image pass: 28672-wide rows (7 slices) take two passes, keeping LDS at 68 KB
         auto img_index = [&](int c, int g0) {
-            if (p.ns == 1) return (c >> 6) * XPITCH + (c & 63);   // (uniform; spares the division)
+            if (single) return (c >> 6) * XPITCH + (c & 63);   // (uniform; spares the division)
             const int sp = c / p.slice_cols, cc = c - sp * p.slice_cols;
             return ((sp - g0) * 64 + (cc >> 6)) * XPITCH + (cc & 63);
         };
@@ -389,7 +410,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 #endif
             }
             if constexpr (!XI)
-            for (int g0 = GS; g0 < p.ns; g0 += GS) {   // 28672-wide rows: slices 4..6 in a second pass (weights already in flight)
+            for (int g0 = GS; g0 < ns; g0 += GS) {   // 28672-wide rows: slices 4..6 in a second pass (weights already in flight)
                 const int cbeg = g0 * p.slice_cols, cend = min(p.in, (g0 + GS) * p.slice_cols);
                 __syncthreads();   // the previous pass has been read
                 for (int c = cbeg + tid * 4; c < cend; c += step)
@@ -410,7 +431,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
                 for (int w = 0; w < nwaves; ++w) tot += red[w];
                 rms_inv = 1.0f / sqrtf(tot / (float)p.in + p.eps);
             }
-            for (int g0 = 0; g0 < p.ns; g0 += GS) {
+            for (int g0 = 0; g0 < ns; g0 += GS) {
                 const int cbeg = g0 * p.slice_cols, cend = min(p.in, (g0 + GS) * p.slice_cols);
                 if (g0 > 0) __syncthreads();
                 if (!(kAblate & 1)) {
@@ -425,7 +446,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 #pragma unroll
             for (int j = 0; j < 32; ++j) x2[j] = f32x2{1.0f, 1.0f};
         }
-        if (p.ns > 1 && !LM) __syncthreads();   // the image becomes the staging area
+        if (!single && !LM) __syncthreads();   // the image becomes the staging area
         GV_STAMP(2);   // activations in registers
     }
     float sx16[4], sx32[2];
@@ -470,23 +491,23 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
         locate(b * RB + lane, seg, row);
         res_pf = p.resid[row];
     };
-    if (p.ns > 1) prefetch_resid(0);
+    if (!single) prefetch_resid(0);
     auto combine = [&](int b, int cnt) {
         if (s != 0) return;
-        const float* pg = part + (size_t)(b & 1) * p.rw * p.ns * RB + (size_t)(g * p.ns) * RB;
+        const float* pg = part + (size_t)(b & 1) * p.rw * ns * RB + (size_t)(g * ns) * RB;
         float t = 0.0f;
         if (lane < cnt)
-            for (int ss = 0; ss < p.ns; ++ss) t += pg[ss * RB + lane];
+            for (int ss = 0; ss < ns; ++ss) t += pg[ss * RB + lane];
         const float nxt = __shfl_down(t, 1, 64);
         if (lane < cnt) {
             int seg, row;
             locate(b * RB + lane, seg, row);
             if (p.silu_pair) {
-                if ((lane & 1) == 0) p.seg[0].y[row] = t / (1.0f + expf(-t)) * nxt;
+                if ((lane & 1) == 0) seg_y0[row] = t / (1.0f + expf(-t)) * nxt;
             } else {
                 float v = t;
                 if (p.resid != nullptr && seg == 0) v = res_pf + v;
-                p.seg[seg].y[row] = v;
+                seg_y(seg)[row] = v;
             }
         }
         prefetch_resid(b + 1);
@@ -533,7 +554,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
         if (q == 0) { asm volatile("" :: "v"(tot)); GV_STAMP(4); }   // first row decoded and reduced
 #endif
 
-        if (p.ns == 1) {
+        if (single) {
             if (p.silu_pair) {
                 const float t63 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 63));
                 const int pi = (q >> 1) & 63;
@@ -549,7 +570,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
             }
         } else {
             const int b = q / RB, i = q % RB;
-            if (lane == 63) part[(size_t)(b & 1) * p.rw * p.ns * RB + (size_t)(g * p.ns + s) * RB + i] = tot;
+            if (lane == 63) part[(size_t)(b & 1) * p.rw * ns * RB + (size_t)(g * ns + s) * RB + i] = tot;
             if (i == RB - 1) {
                 __syncthreads();
                 combine(b, RB);
@@ -560,7 +581,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
         row_step(q, pf, pf_sc, pf2, pf2_sc);
         if constexpr (LM) { if (++q < n_my) row_step(q, pf2, pf2_sc, pf, pf_sc); }
     }
-    if (p.ns > 1) {   // close a partial batch, then keep barrier counts equal across the workgroup
+    if (!single) {   // close a partial batch, then keep barrier counts equal across the workgroup
         int done = n_my / RB;
         if (n_my % RB) {
             __syncthreads();
@@ -582,9 +603,9 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 }
 
 // Q8_0 rows in the lane-major layout of the engine's repack (LM above)
-template <bool NORM, bool XFAST>
+template <bool NORM, bool XFAST, int NSF>
 __global__ __launch_bounds__(512, Fmt<NTK_DT_Q8_0>::MINW) void gemv_q8l_kernel(const GemvParams p) {
-    gemv_quant_body<NTK_DT_Q8_0, NORM, XFAST, false, false, false, true>(p, (int)blockIdx.x, (int)gridDim.x);
+    gemv_quant_body<NTK_DT_Q8_0, NORM, XFAST, false, false, false, true, NSF>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 // GGUF Q8_0 rows -> lane-major rows (UNPACK: back).  One thread per (row, 64-column lane): its two blocks are 17 dwords
 // [d0 | 32 quants | d1 | 32 quants] in the file (4-byte aligned: the tensor is, and a row is a multiple of 272 bytes), 16 quant dwords + 1 scale dword packed.
@@ -908,18 +929,24 @@ int q8l_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in, c
     if (rc != NTK_OK) return rc;
     if (L.p.total_rows == 0) return NTK_OK;
     using KernelFn = void (*)(const GemvParams);
-    static const KernelFn table[2][2] = {{gemv_q8l_kernel<false, false>, gemv_q8l_kernel<false, true>},
-                                         {gemv_q8l_kernel<true, false>, gemv_q8l_kernel<true, true>}};
+#define Q8L_FORMS(NORM, XFAST) {gemv_q8l_kernel<NORM, XFAST, NS_ONE>, gemv_q8l_kernel<NORM, XFAST, NS_SPLIT>}
+    static const KernelFn table[2][2][2] = {{Q8L_FORMS(false, false), Q8L_FORMS(false, true)}, {Q8L_FORMS(true, false), Q8L_FORMS(true, true)}};
+#undef Q8L_FORMS
     if (L.lds > 64 * 1024) {   // 28672-wide rows: the activation image of four slices, 68 KiB
-        static const bool once = raise_lds_limit((const void*)table[0][0]) && raise_lds_limit((const void*)table[0][1]) &&
-                                 raise_lds_limit((const void*)table[1][0]) && raise_lds_limit((const void*)table[1][1]);
+        static const bool once = [] {
+            bool ok = true;
+            for (int a = 0; a < 2; ++a)
+                for (int b = 0; b < 2; ++b)
+                    for (int c = 0; c < 2; ++c) ok = ok && raise_lds_limit((const void*)table[a][b][c]);
+            return ok;
+        }();
         if (!once || L.lds > 160 * 1024) return NTK_E_SHAPE;
     }
 #ifdef NTK_GEMV_TRACE
     static int trace_counter = 0;
     L.p.trace_slot = trace_counter++;
 #endif
-    hipLaunchKernelGGL(table[norm_w ? 1 : 0][L.xfast ? 1 : 0], dim3(L.grid), dim3(64 * L.nwaves), L.lds, st, L.p);
+    hipLaunchKernelGGL(table[norm_w ? 1 : 0][L.xfast ? 1 : 0][L.p.ns == 1 ? 0 : 1], dim3(L.grid), dim3(64 * L.nwaves), L.lds, st, L.p);
     return last_launch_status();
 }
 

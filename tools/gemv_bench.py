@@ -32,9 +32,13 @@ def main():
     ap.add_argument("--pool-mb", type=int, default=1536)
     ap.add_argument("--json", default=None)
     ap.add_argument("--rp", action="store_true", help="the matrix-core GEMV over repacked tensors (ntk_gemv_rp_fused); GB/s still counts GGUF bytes")
+    ap.add_argument("--lm", action="store_true", help="Q8_0 over lane-major rows (ntk_gemv_rp_fused -> the q8l kernels of csrc/gemv.hip): the pool's bytes read as packed rows")
     ap.add_argument("--nw", type=int, default=0, help="--rp with a tuning build (make tune, NTK_LIB_PATH): waves per workgroup, 0 = planner")
     ap.add_argument("--sweep", action="store_true", help="--rp with a tuning build: every (waves per workgroup, workgroups per CU) the planner could take, per shape")
     a = ap.parse_args()
+    if a.lm:
+        a.dtypes = "Q8_0"
+    fused = ops.gemv_rp_fused if a.lm else ops.gemv_fused
     ops.init(0)
     L = _lib.lib()
     global HIP
@@ -78,18 +82,20 @@ def main():
                     ops.gemv_rp_fused(segs, x, in_f, norm_w=nw if kind in ("qkv", "silu") else None, eps=1e-5,
                                       resid=ys[0] if kind == "resid" else None, silu_pair=kind == "silu")
                     return
-                if kind == "plain":
+                if kind == "plain" and a.lm:
+                    fused([(base, ys[0], rlist[0], dt)], x, in_f)
+                elif kind == "plain":
                     ops.launch_gemv(ys[0], base, x, rlist[0], in_f, dt)
                 elif kind == "resid":
-                    ops.gemv_fused([(base, ys[0], rlist[0], dt)], x, in_f, resid=ys[0])
+                    fused([(base, ys[0], rlist[0], dt)], x, in_f, resid=ys[0])
                 elif kind == "qkv":
                     segs, off = [], 0
                     for i, r in enumerate(rlist):
                         segs.append((base + off, ys[i], r, dt))
                         off += r * rb
-                    ops.gemv_fused(segs, x, in_f, norm_w=nw, eps=1e-5)
+                    fused(segs, x, in_f, norm_w=nw, eps=1e-5)
                 else:
-                    ops.gemv_fused([(base, ys[0], rlist[0], dt), (base + rlist[0] * rb, ys[1], rlist[0], dt)], x, in_f,
+                    fused([(base, ys[0], rlist[0], dt), (base + rlist[0] * rb, ys[1], rlist[0], dt)], x, in_f,
                                    norm_w=nw, eps=1e-5, silu_pair=True)
             def measure():
                 for s in range(min(nslots, 4)):

@@ -5,6 +5,8 @@ first row decoded, last row landed, end.  For each shape a hipGraph of back-to-b
 replayed; for the launches in the middle of the chain the tool prints the gap to the previous launch's last workgroup and the
 spread (min / median / max over workgroups) of every stamp relative to the launch's first entry.
 usage: python tools/gemv_trace.py [--dtypes Q8_0] [--shapes ...]
+       python tools/gemv_trace.py --lm                         (Q8_0 over lane-major rows, ntk_gemv_rp_fused: the kernel the engine launches;
+                                                                the pool's bytes are read as packed rows -- timing only)
        python tools/gemv_trace.py --rp --dtypes Q4_K,Q6_K     (the matrix-core GEMV over the engine's repack, csrc/gemv_rp.hip: its own stamps)"""
 import argparse
 import ctypes as C
@@ -37,7 +39,11 @@ def main():
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--pool-mb", type=int, default=1536, help="weight pool the launches rotate over (small = Infinity-Cache resident)")
     ap.add_argument("--rp", action="store_true", help="ntk_gemv_rp_fused over repacked copies of the pool's matrices (Q4_K / Q5_K / Q6_K)")
+    ap.add_argument("--lm", action="store_true", help="Q8_0: the lane-major kernel (ntk_gemv_rp_fused) over the same pool")
     a = ap.parse_args()
+    if a.lm:
+        a.dtypes = "Q8_0"
+    fused = ops.gemv_rp_fused if a.lm else ops.gemv_fused   # (each has its own trace slot counter, starting at 0 in this process)
     ops.init(0)
     L = _lib.lib()
     L.ntk_debug_gemv_trace.argtypes = [C.POINTER(C.c_ulonglong), C.c_size_t]
@@ -69,15 +75,15 @@ def main():
             def launch(slot):
                 base = pool.ptr + slot * per_al
                 if kind == "resid":
-                    ops.gemv_fused([(base, ys[0], rlist[0], dt)], x, in_f, resid=ys[0])
+                    fused([(base, ys[0], rlist[0], dt)], x, in_f, resid=ys[0])
                 elif kind == "qkv":
                     segs, off = [], 0
                     for i, r in enumerate(rlist):
                         segs.append((base + off, ys[i], r, dt))
                         off += r * rb
-                    ops.gemv_fused(segs, x, in_f, norm_w=nw, eps=1e-5)
+                    fused(segs, x, in_f, norm_w=nw, eps=1e-5)
                 else:
-                    ops.gemv_fused([(base, ys[0], rlist[0], dt), (base + rlist[0] * rb, ys[1], rlist[0], dt)], x, in_f,
+                    fused([(base, ys[0], rlist[0], dt), (base + rlist[0] * rb, ys[1], rlist[0], dt)], x, in_f,
                                    norm_w=nw, eps=1e-5, silu_pair=True)
 
             n = 24
@@ -96,7 +102,7 @@ def main():
             assert L.ntk_debug_gemv_trace(buf, SLOTS * WG * EV) == 0
             t = np.frombuffer(buf, dtype=np.uint64).astype(np.int64).reshape(SLOTS, WG, EV)
             HIP.hipGraphExecDestroy(gexec); HIP.hipGraphDestroy(graph)
-            print("== %s %s: %.2f MB per launch, chain of %d (10 ns clock; us relative to the launch's first workgroup entry)" % (dname, sname, per_launch / 1e6, n))
+            print("== %s%s %s: %.2f MB per launch, chain of %d (10 ns clock; us relative to the launch's first workgroup entry)" % (dname, " lane-major" if a.lm else "", sname, per_launch / 1e6, n))
             gaps, totals, rows_ = [], [], []
             agg = {k: [] for k in range(1, 12)}
             for j in range(8, n - 2):   # middle of the chain

@@ -40,12 +40,13 @@ def main():
     print("%-48s %8s %12s %10s %7s" % ("kernel", "calls", "total_us", "avg_us", "share"))
     for k, (c, t, shapes) in sorted(stats.items(), key=lambda kv: -kv[1][1]):
         print("%-48s %8d %12.1f %10.2f %6.1f%%" % (k, c, t, t / c, 100 * t / busy))
-    is_gemv = lambda k: "gemv_quant_" in k or "rp_gemv_kernel" in k   # every form: plain, integer-activation (xi), two-format (pair), matrix-core (rp)
+    # every form: plain, integer-activation (xi), two-format (pair), matrix-core (rp), lane-major Q8_0 (q8l)
+    is_gemv = lambda k: "gemv_quant_" in k or "rp_gemv_kernel" in k or "gemv_q8l_kernel" in k
     g = [v for k, v in stats.items() if is_gemv(k)]
     if g and n_tokens:
         c, t = sum(v[0] for v in g), sum(v[1] for v in g)
         per_launch = a.gemv_bytes_per_token * n_tokens / c
-        print("\ngemv launches (gemv_quant_* + rp_gemv_kernel) pooled: %.1f launches/token, avg %.2f us, algorithmic %.1f MB/launch -> %.1f GB/s = %.1f%% of 8 TB/s"
+        print("\ngemv launches (gemv_quant_* + rp_gemv_kernel + gemv_q8l_kernel) pooled: %.1f launches/token, avg %.2f us, algorithmic %.1f MB/launch -> %.1f GB/s = %.1f%% of 8 TB/s"
               % (c / n_tokens, t / c, per_launch / 1e6, per_launch / (t / c * 1e-6) / 1e9, per_launch / (t / c * 1e-6) / 8e12 * 100))
         print("kernel time per token: %.1f us all kernels, %.1f us GEMV launches" % (busy / n_tokens, t / n_tokens))
         # the GEMV launches of a token by KIND, from their order inside the token (fused path: Q|K|V, Wo, gate|up, down per layer, the LM head last):
