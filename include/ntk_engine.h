@@ -145,6 +145,15 @@ int ntk_attention_decode_batch(float* output, const float* q, const float* k, co
  *                            KV head (NTK_E_SHAPE otherwise).
  *   ntk_kv_dequant_q8_f16    cache rows [0, n_rows) -> F16 K and V images [n_rows][n_kv_heads * head_dim] (the layout ntk_attention_prefill /
  *                            ntk_attention_decode read): half_rne(half(d) * q)
+ *   ntk_attention_decode_q8_batch  ntk_attention_decode_q8 for n_rows sequences (1 .. NTK_ATTN_BATCH_MAX) in ONE launch + ONE combine launch for all
+ *                            rows: the same device function (csrc/attention_q8_decode.hip.h), so row b has the bits of the single-row launch with
+ *                            the same nsplit, and depends on nothing but row b.  q [n_rows][n_heads * head_dim], k, v [n_rows][n_kv_heads *
+ *                            head_dim] F32, unrotated, only read; positions DEVICE int [n_rows], each in [0, max_seq) (the caller validates);
+ *                            caches: HOST struct with the rows' 8-bit K and V buffers of this layer (ntk_kv_q8_cache_bytes each), copied BY VALUE
+ *                            into the launch; entries past n_rows are ignored.  The only cache bytes written are row positions[b] of caches b.
+ *                            Two rows must not name the same cache (unchecked).  A split that lies wholly past a row's position contributes
+ *                            nothing.  scratch: n_rows x ntk_attention_split_scratch_bytes(n_heads, head_dim, nsplit).  Refusals: those of
+ *                            ntk_attention_decode_q8, NTK_E_SHAPE for n_rows outside 1 .. 16, NTK_E_NULL for a NULL cache among the first n_rows.
  * ------------------------------------------------------------------------------------------- */
 size_t ntk_kv_q8_cache_bytes(int max_seq, int n_kv_heads, int head_dim);
 int ntk_kv_store_q8(void* k_cache, void* v_cache, const float* k, const float* v, int seq_len, int n_kv_heads, int head_dim, int start_pos,
@@ -157,6 +166,9 @@ int ntk_attention_decode_q8(float* output, const float* q, const float* k, const
                             float freq_scale, int nsplit, float* scratch, void* stream);
 int ntk_kv_dequant_q8_f16(void* k_f16, void* v_f16, const void* k_cache, const void* v_cache, int n_rows, int n_kv_heads, int head_dim,
                           int max_seq, void* stream);
+int ntk_attention_decode_q8_batch(float* output, const float* q, const float* k, const float* v, const ntk_kv_batch* caches, const int* positions,
+                                  int n_rows, const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq, float scale,
+                                  float theta_base, float freq_scale, int nsplit, float* scratch, void* stream);
 
 /* Parity instrumentation: ntk_gemv_fused with the activation form of its Q4_K / Q6_K launches chosen by the CALL.  Those launches take,
  * from 48 MiB of weights on (a constant of the library: below it the conversion costs what the decode saves), the integer-activation

@@ -85,7 +85,17 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * uses, exactly as without the option; slots 1 .. N - 1 are extra F16 caches of the same layout, allocated at load (counted in nt_engine_kv_cache_bytes)
  * beside a [16][vocab] F32 logits buffer and the batched sampler's buffers (under 1 MB; neither is counted there).  Set it BEFORE the load (afterwards:
  * NTK_E_SHAPE + last_error); an nt_engine_load_shared sequence takes its own.
- * Refused at load (NTK_E_SHAPE + last_error) when > 1 together with "kv_cache" = "q8_0", tensor parallelism or a context of fewer than N positions;
+ * Refused at load (NTK_E_SHAPE + last_error) when > 1 together with "kv_cache" = "q8_0" (unless "batch_kv_q8"), tensor parallelism or a context of fewer
+ * than N positions;
+ * "batch_kv_q8" = "0" (default) | "1" (any other value: NTK_E_SHAPE + last_error): sequence slots and the batched decode step over the 8-bit KV cache.
+ * Set it BEFORE the load (afterwards: NTK_E_SHAPE + last_error); it is kept across loads; an nt_engine_load_shared sequence takes its own.  With "1" and
+ * "kv_cache" = "q8_0", "sequences" = "1" .. "16" loads -- slot 0 is the 8-bit cache every other entry point uses, slots 1 .. N - 1 are further 8-bit caches
+ * of the same layout, zeroed at load; the one-layer F16 image stays ONE per engine, rebuilt by every prompt pass for the slot it runs on, so
+ * nt_engine_kv_cache_bytes = sequences x the 8-bit caches + one image -- and nt_engine_decode_batch / _decode_batch_sample / _generate_batch / _generate_batch_ex
+ * run (one row on a one-slot engine included): each row's attention is the single-sequence 8-bit decode kernel's, bit for bit at the same split count.
+ * With "kv_cache" = "f16" the option is accepted and changes nothing.  With "0" every refusal and message is what it was before the option existed.
+ * (The option exists ONLY because the default refusal of "sequences" > 1 with "q8_0" is pinned by a test; a later change that may touch that test can
+ * fold the option away and make this the behaviour of "sequences" + "q8_0".);
  * "score_rows" = "1" .. "1024" (default "256"): rows of logits nt_engine_score_tokens computes per pass over the LM head (score_rows x vocab floats of device
  * memory from the first scoring call on; any time). */
 int  nt_engine_set_option(nt_engine_t e, const char* key, const char* value);
@@ -156,7 +166,7 @@ int  nt_engine_profile_token(nt_engine_t e, int token, int pos, int coarse, floa
 int  nt_engine_tokenize(nt_engine_t e, const char* text, int add_bos, int* out, int out_cap);   /* returns count */
 int  nt_engine_detokenize(nt_engine_t e, const int* ids, int n, char* out, int out_cap);       /* returns bytes */
 uint64_t nt_engine_bytes_per_token(nt_engine_t e, int pos);   /* algorithmic HBM bytes of one decode token */
-uint64_t nt_engine_kv_cache_bytes(nt_engine_t e);          /* resident KV cache of this sequence ("kv_cache" = "q8_0": the 8-bit caches + the one-layer F16 image) */
+uint64_t nt_engine_kv_cache_bytes(nt_engine_t e);          /* resident KV cache of this sequence, all its slots ("kv_cache" = "q8_0": the slots' 8-bit caches + the ONE one-layer F16 image) */
 uint64_t nt_engine_weight_bytes(nt_engine_t e);            /* the model's tensors in their GGUF encoding */
 uint64_t nt_engine_resident_weight_bytes(nt_engine_t e);   /* what they occupy in HBM now: GGUF bytes still resident + the decode repack + the unpack scratch */
 uint64_t nt_engine_repacked_bytes(nt_engine_t e);          /* of which the decode repack (tensors that did not fit stay on the raw path and are not counted) */
@@ -201,6 +211,10 @@ int  nt_engine_debug_kv_write_slot(nt_engine_t e, int slot, int layer, int pos0,
  * side.  Each pair returns NTK_E_DTYPE on an engine of the other cache format. */
 int  nt_engine_debug_kv_read_q8(nt_engine_t e, int layer, int pos0, int n, void* k_blocks_out, void* v_blocks_out);
 int  nt_engine_debug_kv_write_q8(nt_engine_t e, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks);
+/* ... of sequence slot `slot` of a q8_0 engine ("batch_kv_q8"; slot 0: the calls above): the checks of the F16 slot pair -- a slot outside
+ * 0 .. "sequences" - 1: NTK_E_SHAPE -- and NTK_E_DTYPE on an F16 engine */
+int  nt_engine_debug_kv_read_q8_slot(nt_engine_t e, int slot, int layer, int pos0, int n, void* k_blocks_out, void* v_blocks_out);
+int  nt_engine_debug_kv_write_q8_slot(nt_engine_t e, int slot, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks);
 /* The F32 inputs of the KV store: after nt_engine_debug_kv_inputs_capture(layer) every prompt pass / 1:1 pass leaves that layer's k projection (BEFORE
  * the rotation) and v projection aside; _read returns those of the last pass, [n][n_kv_heads * head_dim] floats each (n <= its token count).  layer < 0: off. */
 int  nt_engine_debug_kv_inputs_capture(nt_engine_t e, int layer);

@@ -131,6 +131,7 @@ def lib() -> C.CDLL:
         "ntk_rope_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp]),
         "ntk_attention_decode_q8": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_kv_dequant_q8_f16": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
+        "ntk_attention_decode_q8_batch": (i, [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_embed_rows": (i, [vp, vp, vp, i, i, i, vp]),
         "ntk_argmax": (i, [vp, i, vp, vp, vp, vp]),
         "ntk_logprob_rows": (i, [vp, i, i, i, vp, vp, vp, vp]),

@@ -88,6 +88,13 @@ __global__ __launch_bounds__(128) void attention_batch_combine_kernel(float* __r
                                  (int)blockIdx.x, (int)gridDim.x);
 }
 
+// ... and its launcher, for the batched launch over the 8-bit caches too (attention_q8.hip), as attention.hip exposes launch_attention_split_combine
+int launch_attention_batch_combine(float* output, const float* part, size_t part_row, int n_heads, int n_rows, int hd, int nsplit, int n_kv_heads,
+                                   hipStream_t st) {
+    hipLaunchKernelGGL(attention_batch_combine_kernel, dim3(n_heads, n_rows), dim3(128), 0, st, output, part, part_row, hd, nsplit, n_kv_heads);
+    return last_launch_status();
+}
+
 }  // namespace ntk
 
 extern "C" int ntk_attention_decode_batch(float* output, const float* q, const float* k, const float* v, const ntk_kv_batch* caches,
@@ -148,6 +155,5 @@ extern "C" int ntk_attention_decode_batch(float* output, const float* q, const f
 #undef NTK_ATTB
     }
     if (ntk::last_launch_status() != NTK_OK) return NTK_E_LAUNCH;
-    hipLaunchKernelGGL(ntk::attention_batch_combine_kernel, dim3(n_heads, n_rows), dim3(128), 0, st, output, part, part_row, head_dim, nsplit, n_kv_heads);
-    return ntk::last_launch_status();
+    return ntk::launch_attention_batch_combine(output, part, part_row, n_heads, n_rows, head_dim, nsplit, n_kv_heads, st);
 }

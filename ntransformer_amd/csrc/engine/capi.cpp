@@ -70,6 +70,13 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
         return rc;
     }
+    else if (k == "batch_kv_q8") {   // "0" (default) | "1": sequence slots and the batched step over the 8-bit cache; before the load only (model.h)
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("batch_kv_q8 must be 0 or 1"); return NTK_E_SHAPE; }
+        const int rc = E(e)->loaded() ? (E(e)->set_error("batch_kv_q8 must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_batch_kv_q8(on);
+        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
+        return rc;
+    }
     else if (k == "prefill_row_max") E(e)->model().set_prefill_row_max(on);   // 1 (default): see Model::prefill_row_max_
     else if (k == "prefill_fused_split") E(e)->model().set_prefill_fused_split(on);   // 1 (default): see Model::prefill_fused_split_
     else if (k == "attention_merge") return E(e)->model().set_attention_merge(on);   // 1: split-KV attention without the combine launch (default 0: measured slower)
@@ -247,6 +254,14 @@ int nt_engine_debug_kv_read_q8(nt_engine_t e, int layer, int pos0, int n, void* 
 int nt_engine_debug_kv_write_q8(nt_engine_t e, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks) {
     if (!e || !E(e)->loaded()) return NTK_E_NULL;
     return E(e)->model().debug_kv_q8(layer, pos0, n, static_cast<uint8_t*>(const_cast<void*>(k_blocks)), static_cast<uint8_t*>(const_cast<void*>(v_blocks)), true);
+}
+int nt_engine_debug_kv_read_q8_slot(nt_engine_t e, int slot, int layer, int pos0, int n, void* k_blocks, void* v_blocks) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_q8(layer, pos0, n, static_cast<uint8_t*>(k_blocks), static_cast<uint8_t*>(v_blocks), false, slot);
+}
+int nt_engine_debug_kv_write_q8_slot(nt_engine_t e, int slot, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_q8(layer, pos0, n, static_cast<uint8_t*>(const_cast<void*>(k_blocks)), static_cast<uint8_t*>(const_cast<void*>(v_blocks)), true, slot);
 }
 
 void* nt_engine_persistent_plan(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().persistent_plan() : nullptr; }

@@ -46,7 +46,7 @@ void Model::free_all() {
     repack_done_ = output_tied_ = false;
     host_pos_ = attn_regime_ = 0;
     k_cache_ = v_cache_ = nullptr;
-    slot_k_.clear(); slot_v_.clear();
+    slot_k_.clear(); slot_v_.clear(); slot_k_q8_.clear(); slot_v_q8_.clear();
     batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = batch_recent_ = nullptr; batch_sample_scratch_ = nullptr;
     kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
     k_cache_q8_ = v_cache_q8_ = nullptr; kv_f16_k_ = kv_f16_v_ = nullptr; kv_q8_layer_bytes_ = 0; kv_cache_bytes_ = 0;
@@ -210,6 +210,12 @@ int Model::wait_token(int pos, int* token) {
 int Model::set_sequences(int n) {
     if (n < 1 || n > kMaxSequences) { err_ = "sequences must lie in 1 .. " + std::to_string(kMaxSequences); return NTK_E_SHAPE; }
     sequences_ = n;
+    return NTK_OK;
+}
+
+int Model::set_batch_kv_q8(bool on) {
+    if (!layers_.empty()) { err_ = "batch_kv_q8 must be set before the model is loaded"; return NTK_E_SHAPE; }
+    batch_kv_q8_ = on;
     return NTK_OK;
 }
 

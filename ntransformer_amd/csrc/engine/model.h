@@ -73,11 +73,21 @@ public:
     // caches of slot 0's [L][max_seq][n_kv][hd] layout, allocated at load and counted in kv_cache_bytes(), beside a [16][vocab] F32 logits buffer, the batch
     // attention's scratch, the batched sampler's windows / scratch / pinned mirrors (batch_sample_buffers: about 0.9 MB, not counted) and -- where
     // score_buffers() would need one -- an LM-head GEMM workspace.  N = 1 allocates nothing (decode_batch with one row on slot 0 allocates the logits
-    // buffers on its first call, as score() does).  Refused at load with kv_cache = q8_0, tensor parallelism or a context of fewer than N positions (a
+    // buffers on its first call, as score() does).  Refused at load with kv_cache = q8_0 (unless "batch_kv_q8", below), tensor parallelism or a context of fewer than N positions (a
     // step is a pass of up to N rows through the max_seq-row activation buffers).
     static constexpr int kMaxSequences = 16;
     int set_sequences(int n);
     int sequences() const { return sequences_; }
+    // "batch_kv_q8" = 1 (default 0; BEFORE the load, kept across loads; a sharing sequence takes its own): sequence slots and the batched step over the
+    // 8-bit cache.  With kv_cache = q8_0 the load then takes sequences = 1 .. 16 -- slot 0 is k_cache_q8_ / v_cache_q8_, slots 1 .. N - 1 are further
+    // L x kv_q8_layer_bytes_ buffers (zeroed), the one-layer F16 image of the prompt path stays ONE per engine (every prompt pass rebuilds rows
+    // [0, start_pos + T) of it per layer before reading it, on one stream, so it carries nothing from one pass or slot to the next) -- and decode_batch /
+    // decode_batch_sample run: their attention is ntk_attention_decode_q8_batch with kv_q8_splits(attention_regime(largest position)) splits.
+    // kv_cache = f16: accepted, changes nothing.  The option exists ONLY because the default refusals (sequences > 1 at load, decode_batch on a q8_0
+    // engine) are pinned by tests/test_batch_decode_gpu.py::test_refusals_leave_the_engine_usable: with it off every refusal and message is unchanged.
+    // A later change that may touch that test can fold the option away.
+    int set_batch_kv_q8(bool on);
+    bool batch_kv_q8() const { return batch_kv_q8_; }
     // One decode step of B sequences in ONE pass over the weights: row b = token tokens[b] of the sequence in slot slots[b] at positions[b].  Eager and
     // host-driven: one H2D copy of tokens | positions, embedding, the layer loop as for a prompt of B tokens (layers_1to1 in batch mode: rope / store /
     // attention are one ntk_attention_decode_batch over the rows' own caches; B = 1: the projections of a 1-token forward), the final RMSNorm and the LM head
@@ -169,8 +179,9 @@ public:
     uint64_t kv_cache_bytes() const { return kv_cache_bytes_; }   // resident KV bytes of this sequence, the q8_0 mode's F16 scratch included
     int debug_kv_inputs_capture(int layer);
     int debug_kv_inputs_read(int n, float* k, float* v);
-    // cache rows [pos0, pos0 + n) of a layer as canonical 34-byte GGUF block_q8_0, [n][n_kv_heads * head_dim / 32] blocks per side (q8_0 mode only)
-    int debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write);
+    // cache rows [pos0, pos0 + n) of a layer of sequence slot `slot` as canonical 34-byte GGUF block_q8_0, [n][n_kv_heads * head_dim / 32] blocks per
+    // side (q8_0 mode only: NTK_E_DTYPE otherwise; a slot out of range: NTK_E_SHAPE)
+    int debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write, int slot = 0);
     void set_prefill_row_max(bool on) { prefill_row_max_ = on; }
     void set_prefill_fused_split(bool on) { prefill_fused_split_ = on; }
     // Split-KV decode attention as ONE launch (the last workgroup of a head merges the partial states: attention_merge.hip.h) or -- the default --
@@ -311,6 +322,8 @@ private:
     uint8_t* k_cache_q8_ = nullptr; // [L] x kv_q8_layer_bytes_ (ntk_kv_q8_cache_bytes: int8 quants, then half scales)
     uint8_t* v_cache_q8_ = nullptr;
     size_t kv_q8_layer_bytes_ = 0;
+    bool batch_kv_q8_ = false;      // the option (kept across loads): sequence slots / the batched step over the 8-bit cache
+    std::vector<uint8_t*> slot_k_q8_, slot_v_q8_;   // q8_0 mode: [sequences_] 8-bit caches by slot; [0] = k_cache_q8_ / v_cache_q8_
     uint16_t* kv_f16_k_ = nullptr;  // q8_0 mode: [max_seq][nkv][hd] half, ONE layer's dequantised image for the prompt path, shared by all layers
     uint16_t* kv_f16_v_ = nullptr;
     uint64_t kv_cache_bytes_ = 0;

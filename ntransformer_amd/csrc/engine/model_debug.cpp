@@ -60,17 +60,17 @@ int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool w
 
 // ... of the 8-bit cache, as canonical 34-byte GGUF block_q8_0 {half d; int8 q[32]}: [n][n_kv_heads * head_dim / 32] blocks per side.  The device
 // keeps quants and scales in two planes (csrc/attention_q8.hip): the rows' slices of both are contiguous, the blocks are (de)interleaved here.
-int Model::debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write) {
+int Model::debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write, int slot) {
     if (!k_blocks || !v_blocks) return NTK_E_NULL;
     if (!kv_q8_) { err_ = "debug_kv_q8: the KV cache is f16"; return NTK_E_DTYPE; }
-    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len) return NTK_E_SHAPE;
+    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= (int)slot_k_q8_.size()) return NTK_E_SHAPE;
     if (n == 0) return NTK_OK;
     const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim, nb = per / 32;
     const size_t qbytes = (size_t)n * per, sbytes = (size_t)n * nb * 2;
     void* s = stream_;
     std::vector<uint8_t> qh(qbytes), sh(sbytes);
     for (int side = 0; side < 2; ++side) {
-        uint8_t* base = (side ? v_cache_q8_ : k_cache_q8_) + (size_t)layer * kv_q8_layer_bytes_;
+        uint8_t* base = (side ? slot_v_q8_[slot] : slot_k_q8_[slot]) + (size_t)layer * kv_q8_layer_bytes_;
         uint8_t* qd = base + (size_t)pos0 * per;
         uint8_t* sd = base + (size_t)cfg_.max_seq_len * per + (size_t)pos0 * nb * 2;
         uint8_t* blocks = side ? v_blocks : k_blocks;

@@ -327,12 +327,20 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     }
     slot_k_.assign(1, k_cache_);
     slot_v_.assign(1, v_cache_);
-    if (sequences_ > 1) {   // the extra sequence slots: F16 caches of slot 0's layout
-        if (kv_q8_) { err_ = "sequences > 1 is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
+    slot_k_q8_.assign(1, k_cache_q8_);
+    slot_v_q8_.assign(1, v_cache_q8_);
+    if (sequences_ > 1) {   // the extra sequence slots: caches of slot 0's layout
+        if (kv_q8_ && !batch_kv_q8_) { err_ = "sequences > 1 is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
         if (tp_world_ > 1) { err_ = "sequences > 1 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
         // a batched step is a prompt pass of up to `sequences` rows through buffers of max_seq rows (hidden_, residual_, workspace_, row_max_, kv_capture_)
         if ((size_t)sequences_ > S) { err_ = "sequences = " + std::to_string(sequences_) + " needs a context of at least as many positions (this load: " + std::to_string(S) + ")"; return NTK_E_SHAPE; }
-        for (int i = 1; i < sequences_; ++i) {
+        for (int i = 1; i < sequences_ && kv_q8_; ++i) {   // ("batch_kv_q8": 8-bit caches; the one-layer F16 image stays one per engine)
+            slot_k_q8_.push_back((uint8_t*)dev(L * kv_q8_layer_bytes_, true));
+            slot_v_q8_.push_back((uint8_t*)dev(L * kv_q8_layer_bytes_, true));
+            if (!slot_k_q8_.back() || !slot_v_q8_.back()) { err_ = "buffer allocation failed (8-bit KV cache of sequence slot " + std::to_string(i) + ")"; return NTK_E_NOMEM; }
+            kv_cache_bytes_ += 2ull * L * kv_q8_layer_bytes_;
+        }
+        for (int i = 1; i < sequences_ && !kv_q8_; ++i) {
             slot_k_.push_back((uint16_t*)dev(kvb, true));
             slot_v_.push_back((uint16_t*)dev(kvb, true));
             if (!slot_k_.back() || !slot_v_.back()) { err_ = "buffer allocation failed (KV cache of sequence slot " + std::to_string(i) + ")"; return NTK_E_NOMEM; }

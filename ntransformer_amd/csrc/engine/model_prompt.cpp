@@ -258,7 +258,15 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));
             kv_capture_T_ = T;
         }
-        if (kv.slots) {   // a batch of sequences: rope / store / attention of every row on its own cache at its own position, one launch
+        if (kv.slots && kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
+            ntk_kv_batch caches{};
+            for (int t = 0; t < T; ++t) {
+                caches.k[t] = slot_k_q8_[kv.slots[t]] + (size_t)i * kv_q8_layer_bytes_;
+                caches.v[t] = slot_v_q8_[kv.slots[t]] + (size_t)i * kv_q8_layer_bytes_;
+            }
+            ok(ntk_attention_decode_q8_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len,
+                                             scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attention_regime(kv.max_pos, hd)), batch_attn_scratch_, s));
+        } else if (kv.slots) {   // a batch of sequences: rope / store / attention of every row on its own cache at its own position, one launch
             ntk_kv_batch caches{};
             for (int t = 0; t < T; ++t) {
                 caches.k[t] = slot_k_[kv.slots[t]] + (size_t)i * kv_layer;
@@ -269,8 +277,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             ok(ntk_attention_decode_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
                                           cfg_.rope_theta, cfg_.rope_freq_scale, regime == 0 ? 1 : attention_splits(regime, hd), batch_attn_scratch_, s));
         } else if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
-            uint8_t* kc8 = k_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
-            uint8_t* vc8 = v_cache_q8_ + (size_t)i * kv_q8_layer_bytes_;
+            uint8_t* kc8 = slot_k_q8_[kv.slot] + (size_t)i * kv_q8_layer_bytes_;   // (the image is shared by all slots: rebuilt here, for this slot, every pass)
+            uint8_t* vc8 = slot_v_q8_[kv.slot] + (size_t)i * kv_q8_layer_bytes_;
             if (T >= 4) {
                 ok(ntk_rope_kv_store_q8(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
                                         kc8, vc8, start_pos, cfg_.max_seq_len, s));
@@ -507,7 +515,7 @@ int Model::batch_logits(const int* slots, const int* tokens, const int* position
 
 int Model::decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out) {
     NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
-    if (kv_q8_ || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if ((kv_q8_ && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
     NT_TRY(batch_buffers());
     const int V = cfg_.vocab_size, N = kMaxSequences;
     void* s = stream_;
@@ -545,7 +553,7 @@ int Model::batch_sample_buffers() {
 int Model::decode_batch_sample(const int* slots, const int* tokens, const int* positions, int B, const ntk_sample_rows& rows, const int* const* recent,
                                float* logits_out, float* const* row_logits, int* next_out) {
     NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
-    if (kv_q8_ || tp_world_ > 1) { err_ = "decode_batch_sample: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if ((kv_q8_ && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch_sample: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
     if (!next_out) { err_ = "decode_batch_sample: null argument"; return NTK_E_NULL; }
     const int V = cfg_.vocab_size;
     int pitch = 0;   // of this step's windows: the longest one a penalty reads

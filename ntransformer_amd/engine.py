@@ -105,6 +105,8 @@ def _bind():
     L.nt_engine_debug_kv_write.argtypes = [vp, i, i, i, vp, vp]
     L.nt_engine_debug_kv_read_q8.argtypes = [vp, i, i, i, vp, vp]
     L.nt_engine_debug_kv_write_q8.argtypes = [vp, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_read_q8_slot.argtypes = [vp, i, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_write_q8_slot.argtypes = [vp, i, i, i, i, vp, vp]
     L.nt_engine_debug_kv_inputs_capture.argtypes = [vp, i]
     L.nt_engine_debug_kv_inputs_read.argtypes = [vp, i, vp, vp]
     L.nt_engine_kv_cache_bytes.argtypes = [vp]
@@ -354,6 +356,20 @@ class Engine:
         k = np.ascontiguousarray(k_blocks, dtype=np.uint8)
         v = np.ascontiguousarray(v_blocks, dtype=np.uint8)
         self._check(self.L.nt_engine_debug_kv_write_q8(self.h, layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "kv_write_q8")
+
+    def kv_read_q8_slot(self, slot: int, layer: int, pos0: int, n: int, row_elems: int):
+        """kv_read_q8 of sequence slot `slot` ("batch_kv_q8" option)"""
+        k = np.empty((n, row_elems // 32, 34), np.uint8)
+        v = np.empty((n, row_elems // 32, 34), np.uint8)
+        self._check(self.L.nt_engine_debug_kv_read_q8_slot(self.h, int(slot), layer, pos0, n, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)),
+                    "kv_read_q8_slot")
+        return k, v
+
+    def kv_write_q8_slot(self, slot: int, layer: int, pos0: int, k_blocks: np.ndarray, v_blocks: np.ndarray) -> None:
+        k = np.ascontiguousarray(k_blocks, dtype=np.uint8)
+        v = np.ascontiguousarray(v_blocks, dtype=np.uint8)
+        self._check(self.L.nt_engine_debug_kv_write_q8_slot(self.h, int(slot), layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p),
+                                                            v.ctypes.data_as(C.c_void_p)), "kv_write_q8_slot")
 
     def kv_inputs_capture(self, layer: int) -> None:
         self._check(self.L.nt_engine_debug_kv_inputs_capture(self.h, layer), "kv_inputs_capture")

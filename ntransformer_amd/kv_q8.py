@@ -144,3 +144,23 @@ def attention_decode_q8_status(output, q, k, v, k_cache, v_cache, d_pos, n_heads
 
 def attention_decode_q8(*args, **kw) -> None:
     check(attention_decode_q8_status(*args, **kw), "attention_decode_q8")
+
+
+def attention_decode_q8_batch_status(output, q, k, v, caches, positions, n_rows, n_heads, n_kv_heads, head_dim, max_seq, scale, theta_base, nsplit,
+                                     freq_scale=1.0, inv_freq=None, stream=None, table=True, scratch=True) -> int:
+    """ntk_attention_decode_q8_batch: the decode attention of n_rows sequences over their own 8-bit caches.  caches: a list of (K, V) Q8Cache pairs, one
+    per row (None for a NULL entry); positions: device int [n_rows].  table=False passes a NULL table, scratch=False a NULL scratch (the refusals).
+    Returns the status."""
+    L = _lib.lib()
+    kv = _lib.KvBatch()
+    for b, pair in enumerate(caches):
+        kv.k[b], kv.v[b] = (_p(pair[0]), _p(pair[1])) if pair is not None else (None, None)
+    buf = DeviceBuffer(max(n_rows, 1) * int(L.ntk_attention_split_scratch_bytes(n_heads, head_dim, nsplit))) if scratch else None
+    st = L.ntk_attention_decode_q8_batch(_p(output), _p(q), _p(k), _p(v), C.addressof(kv) if table else None, _p(positions), n_rows, _p(inv_freq),
+                                         n_heads, n_kv_heads, head_dim, max_seq, scale, theta_base, freq_scale, nsplit, _p(buf), stream)
+    synchronize()   # `buf` is released when this returns
+    return int(st)
+
+
+def attention_decode_q8_batch(*args, **kw) -> None:
+    check(attention_decode_q8_batch_status(*args, **kw), "attention_decode_q8_batch")
