@@ -170,6 +170,30 @@ int ntk_attention_decode_q8_batch(float* output, const float* q, const float* k,
                                   int n_rows, const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq, float scale,
                                   float theta_base, float freq_scale, int nsplit, float* scratch, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * KV cache sequence operations (csrc/kv_ops.hip; no reference counterpart): the CONTEXT SHIFT.  In every one of n_layers layers, rows
+ * [src0, src0 + n_rows) of both caches move to [dst0, dst0 + n_rows), 0 <= dst0 < src0, src0 + n_rows <= max_seq.  V rows move byte for byte (Q8:
+ * quants and scales).  K rows -- cached AFTER RoPE -- are rotated by delta = dst0 - src0 positions, which makes them the keys the model would have
+ * cached at the new positions.  Every byte of both caches outside the destination rows keeps its value.
+ * Layouts: ntk_kv_shift      F16 [n_layers][max_seq][n_kv_heads][head_dim] halves, head_dim 64 / 80 / 128;
+ *          ntk_kv_shift_q8   n_layers consecutive layer buffers of ntk_kv_q8_cache_bytes(max_seq, n_kv_heads, head_dim) bytes each (int8 quants
+ *                            [max_seq][row], then half scales [max_seq][row / 32]); head_dim 128 only, as the 8-bit store.
+ * Rotation: the frequency of pair i is inv_freq[i] (DEVICE table [head_dim / 2]) or, inv_freq == NULL, 1 / (float)pow((double)theta_base,
+ * (double)((2.0f * i) / head_dim)); angle = (float)delta * freq * freq_scale in F32, left to right (the forward kernels' pos * freq * fscale);
+ * c, s = cosf, sinf; a' = a c - b s, b' = a s + b c in F32, each operation rounded on its own; the pair is (i, i + head_dim / 2), or (2 i, 2 i + 1)
+ * when `interleaved`.  F16: the result rounded to nearest even.  Q8: the head dequantised as half(d) * q (exact in F32), rotated as a whole (a pair
+ * spans two 32-blocks), every block requantised by the store's rule (ggml quantize_row_q8_0_ref) -- so an 8-bit K row loses up to half a
+ * quantisation step per shift, an F16 row half an ulp of half.
+ * Overlapping ranges (n_rows > src0 - dst0) are moved correctly for every src0 - dst0 >= 1 in ONE launch: a thread owns the rows of one residue class
+ * modulo src0 - dst0 and walks them in ascending order, so every write lands on a row the same thread has already read (csrc/kv_ops.hip).  Stream
+ * ordered, no allocation, no scratch.  Refused before any launch -- NTK_E_NULL: a NULL cache; NTK_E_SHAPE: a head size not listed, n_rows < 1,
+ * dst0 < 0, dst0 >= src0, src0 + n_rows > max_seq, n_layers outside 1 .. 65535; NTK_E_ALIGN: a cache that is not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+int ntk_kv_shift(uint16_t* k_cache, uint16_t* v_cache, int n_layers, int max_seq, int n_kv_heads, int head_dim, int src0, int dst0, int n_rows,
+                 const float* inv_freq, float theta_base, float freq_scale, int interleaved, void* stream);
+int ntk_kv_shift_q8(void* k_cache_q8, void* v_cache_q8, int n_layers, int max_seq, int n_kv_heads, int head_dim, int src0, int dst0, int n_rows,
+                    const float* inv_freq, float theta_base, float freq_scale, int interleaved, void* stream);
+
 /* Parity instrumentation: ntk_gemv_fused with the activation form of its Q4_K / Q6_K launches chosen by the CALL.  Those launches take,
  * from 48 MiB of weights on (a constant of the library: below it the conversion costs what the decode saves), the integer-activation
  * decoders of csrc/gemv_core.hip.h (three int8 digit planes per 32-column sub-block on v_dot4).  integer_activations = 1: whenever the

@@ -97,7 +97,15 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * (The option exists ONLY because the default refusal of "sequences" > 1 with "q8_0" is pinned by a test; a later change that may touch that test can
  * fold the option away and make this the behaviour of "sequences" + "q8_0".);
  * "score_rows" = "1" .. "1024" (default "256"): rows of logits nt_engine_score_tokens computes per pass over the LM head (score_rows x vocab floats of device
- * memory from the first scoring call on; any time). */
+ * memory from the first scoring call on; any time);
+ * "context_shift" = "0" (default) | "1" (any other value: NTK_E_SHAPE + last_error; any time before a generate call, kept across loads): what the generate loop
+ * behind nt_engine_generate, nt_engine_generate_tokens and the CLI does when the sequence reaches max_context.  "0": it prints
+ * "[context of N tokens exhausted]" and stops, as ever.  "1": a CONTEXT SHIFT -- with keep = min("context_keep", max_context - 2) and discard =
+ * nt_context_shift_discard(position, keep) it runs nt_engine_kv_shift(slot 0, keep, discard, position), goes on at position - discard and so returns
+ * every token asked for.  The repeat-penalty window is over tokens and does not change.  A prompt longer than the context stays refused.
+ * nt_engine_generate_batch / _ex keep dropping a sequence at the end of its context (a caller who drives nt_engine_decode_batch can shift a slot itself);
+ * "context_keep" = N >= 0 (default "1"; otherwise NTK_E_SHAPE + last_error; any time, kept across loads): the leading positions a context shift never
+ * discards -- the default keeps the BOS. */
 int  nt_engine_set_option(nt_engine_t e, const char* key, const char* value);
 const char* nt_engine_last_error(nt_engine_t e);
 void nt_gen_params_default(nt_gen_params* p);
@@ -148,6 +156,26 @@ int  nt_engine_decode_batch_sample(nt_engine_t e, const int* slots, const int* t
                                    const int* const* recent, const int* n_recent, const float* r, float* logits_out, int* next_out);
 int  nt_engine_generate_batch_ex(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* params, int* out,
                                  int out_stride, int* out_counts);
+/* ---- KV cache sequence operations (csrc/kv_ops.hip; llama.cpp's seq_rm + seq_add, and seq_cp) ------------------------------------------------------
+ * nt_engine_kv_shift: the CONTEXT SHIFT of sequence slot `slot` (0 on a one-slot engine) whose cache holds n_past positions: positions [keep, keep +
+ * discard) are dropped and rows [keep + discard, n_past) of every layer move down to [keep, ...), in the cache format the engine was loaded with.  V rows
+ * move byte for byte; K rows -- cached after RoPE -- are rotated by -discard positions with the engine's frequency table, so they are the keys the model
+ * would have cached at the new positions: to half an ulp of half per shift ("kv_cache" = "f16"), to half a quantisation step per shift ("q8_0": the head
+ * is dequantised, rotated and requantised).  Rows below keep, rows from the new n_past upward and every other slot keep their bytes.  Queued on the
+ * engine's stream (one launch whatever the overlap), no synchronisation.  Returns the new n_past = n_past - discard, where the caller's next token goes.
+ * The fused path's device position is not touched: nt_engine_decode_fused / _decode_greedy_steps / the generate calls re-base it themselves.
+ * nt_engine_kv_copy: rows [pos0, pos0 + n) of every layer and both sides from slot src_slot to slot dst_slot at the same positions, no rotation
+ * (stream-ordered device-to-device copies): a prefix prefilled once into one slot serves the others.  Returns n.
+ * Both: works with "kv_cache" = "f16" and "q8_0" (slots of a q8_0 engine: "batch_kv_q8"), "fused" = "0" and "1".  Refused with NTK_E_SHAPE + last_error, the
+ * engine staying usable: a slot outside 0 .. "sequences" - 1, src_slot == dst_slot, rows or n_past outside 0 .. max_context, keep < 0, discard < 1,
+ * keep + discard > n_past, a tensor-parallel engine.
+ * nt_kv_shift_validate / nt_kv_copy_validate: TEST SUPPORT, host only (no engine, no device): those argument checks for an engine of `sequences` slots and
+ * `max_seq` positions -- NTK_OK or NTK_E_SHAPE.  nt_context_shift_discard: the generate loop's discard rule, max(1, (n_past - keep) / 2). */
+int  nt_engine_kv_shift(nt_engine_t e, int slot, int keep, int discard, int n_past);
+int  nt_engine_kv_copy(nt_engine_t e, int src_slot, int dst_slot, int pos0, int n);
+int  nt_kv_shift_validate(int slot, int keep, int discard, int n_past, int sequences, int max_seq);
+int  nt_kv_copy_validate(int src_slot, int dst_slot, int pos0, int n, int sequences, int max_seq);
+int  nt_context_shift_discard(int n_past, int keep);
 /* Scoring: logprob_out[i] = log P(targets[i] | tokens[0..i]) (natural log) for targets[i] >= 0, 0 where targets[i] < 0; top1_out (optional, may be NULL):
  * the greedy token behind tokens[0..i] for every i.  Runs the prompt pass over tokens at start_pos (the KV cache afterwards = nt_engine_forward's), then
  * the LM head over "score_rows" positions at a time; returns the number of scored positions or a negative NTK_E_* (+ nt_engine_last_error: an id out of

@@ -132,6 +132,8 @@ def lib() -> C.CDLL:
         "ntk_attention_decode_q8": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_kv_dequant_q8_f16": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "ntk_attention_decode_q8_batch": (i, [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, i, f, f, f, i, vp, vp]),
+        "ntk_kv_shift": (i, [vp, vp, i, i, i, i, i, i, i, vp, f, f, i, vp]),
+        "ntk_kv_shift_q8": (i, [vp, vp, i, i, i, i, i, i, i, vp, f, f, i, vp]),
         "ntk_embed_rows": (i, [vp, vp, vp, i, i, i, vp]),
         "ntk_argmax": (i, [vp, i, vp, vp, vp, vp]),
         "ntk_logprob_rows": (i, [vp, i, i, i, vp, vp, vp, vp]),

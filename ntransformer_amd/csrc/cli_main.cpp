@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iterator>
@@ -34,6 +35,8 @@ static void usage(const char* prog) {
             "  --no-fuse / --no-graph   Use the 15-launch/layer sequence / launch eagerly\n"
             "  --no-batched-prefill     Prompt tokens one by one (the reference's GEMV loops) instead of 16 per weight pass\n"
             "  --kv-cache <f16|q8_0>    KV cache format (default: f16; q8_0 = 8-bit Q8_0 blocks, 1.0625 bytes per element)\n"
+            "  --context-shift          At the end of the context drop half of the oldest positions and go on (default: stop there)\n"
+            "  --keep <int>             Leading positions a context shift never drops (default: 1, the BOS)\n"
             "  --synthetic <shape:mix>  8b|70b|tiny : Q8_0|Q4_K_M|Q6_K|...  seeded synthetic weights, no file\n"
             "Accepted for CLI compatibility, no effect on the output (weights are always resident in 288 GB HBM;\n"
             "speculative decoding only changes speed, and plain decode is what runs):\n"
@@ -123,6 +126,12 @@ int main(int argc, char** argv) {
         else if (a == "--kv-cache") {
             const char* v = val();
             if (!v || engine.model().set_kv_cache(v) != NTK_OK) { fprintf(stderr, "Error: --kv-cache takes f16 or q8_0\n"); return 1; }
+        }
+        else if (a == "--context-shift") engine.options().context_shift = true;
+        else if (a == "--keep") {
+            const char* v = val();
+            if (!v || atoi(v) < 0) { fprintf(stderr, "Error: --keep takes a number of positions >= 0\n"); return 1; }
+            engine.options().context_keep = atoi(v);
         }
         else if (a == "--streaming") noop(a.c_str(), "weights are fully resident on MI355X");
         else if (a == "--self-spec") noop(a.c_str(), "plain decode runs (same tokens under greedy decoding, no draft pass)");

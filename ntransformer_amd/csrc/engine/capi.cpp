@@ -77,6 +77,17 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
         return rc;
     }
+    else if (k == "context_shift") {   // "0" (default) | "1": the generate loop shifts slot 0 at the end of the context instead of stopping; any time
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("context_shift must be 0 or 1"); return NTK_E_SHAPE; }
+        E(e)->options().context_shift = on;
+    }
+    else if (k == "context_keep") {   // N >= 0 (default 1): leading positions a context shift never drops; any time
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end != 0 || n < 0 || n > 0x7FFFFFFF) { E(e)->set_error("context_keep must be an integer >= 0"); return NTK_E_SHAPE; }
+        E(e)->options().context_keep = (int)n;
+    }
     else if (k == "prefill_row_max") E(e)->model().set_prefill_row_max(on);   // 1 (default): see Model::prefill_row_max_
     else if (k == "prefill_fused_split") E(e)->model().set_prefill_fused_split(on);   // 1 (default): see Model::prefill_fused_split_
     else if (k == "attention_merge") return E(e)->model().set_attention_merge(on);   // 1: split-KV attention without the combine launch (default 0: measured slower)
@@ -188,6 +199,32 @@ int nt_engine_generate_batch_ex(nt_engine_t e, const int* const* prompts, const 
     if (!e || !prompts || !prompt_lens || !params || !out || !out_counts) return NTK_E_NULL;
     try { return E(e)->generate_batch_ex(prompts, prompt_lens, n, params, out, out_stride, out_counts); } catch (...) { return NTK_E_NOMEM; }
 }
+
+int nt_engine_kv_shift(nt_engine_t e, int slot, int keep, int discard, int n_past) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    try {
+        const int rc = E(e)->model().kv_shift(slot, keep, discard, n_past);
+        if (rc < 0) E(e)->set_error(E(e)->model().error());
+        return rc;
+    } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_engine_kv_copy(nt_engine_t e, int src_slot, int dst_slot, int pos0, int n) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    try {
+        const int rc = E(e)->model().kv_copy(src_slot, dst_slot, pos0, n);
+        if (rc < 0) E(e)->set_error(E(e)->model().error());
+        return rc;
+    } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_kv_shift_validate(int slot, int keep, int discard, int n_past, int sequences, int max_seq) {
+    return nt::Model::validate_kv_shift(slot, keep, discard, n_past, sequences, max_seq, nullptr);   // host only
+}
+int nt_kv_copy_validate(int src_slot, int dst_slot, int pos0, int n, int sequences, int max_seq) {
+    return nt::Model::validate_kv_copy(src_slot, dst_slot, pos0, n, sequences, max_seq, nullptr);   // host only
+}
+int nt_context_shift_discard(int n_past, int keep) { return nt::Model::context_shift_discard(n_past, keep); }
 
 int nt_batch_validate(const int* slots, const int* tokens, const int* positions, int n, int sequences, int max_seq, int vocab) {
     return nt::Model::validate_batch(slots, tokens, positions, n, sequences, max_seq, vocab, nullptr);   // host only

@@ -258,7 +258,16 @@ int Engine::run(std::vector<int>& tokens, const GenerateConfig& cfg, std::string
     int queued = 0;   // greedy steps launched and not yet consumed
     for (int i = 1; i < cfg.max_tokens; ++i) {
         if (stop_at_eos && next == eos) break;              // engine.cpp:106
-        if (pos >= max_pos) { fprintf(stderr, "\n[context of %d tokens exhausted]\n", max_pos); break; }
+        if (pos >= max_pos) {
+            if (!opt_.context_shift) { fprintf(stderr, "\n[context of %d tokens exhausted]\n", max_pos); break; }
+            // Context shift: half of what lies behind the kept prefix goes, the rest of slot 0 moves down (K re-rotated: Model::kv_shift).  Nothing is
+            // in flight here: the run-ahead below queues no step past max_pos, and the token at max_pos - 1 has been waited for.
+            const int keep = std::max(0, std::min(opt_.context_keep, max_pos - 2));
+            const int shifted = model_.kv_shift(0, keep, Model::context_shift_discard(pos, keep), pos);
+            if (shifted < 0) { rc = shifted; break; }
+            pos = shifted;
+            if (opt_.fused && (rc = model_.set_device_pos(pos)) != NTK_OK) break;   // re-bases the device position and picks the attention regime
+        }
         if (opt_.fused) {
             if (dev_greedy) {
                 if (queued == 0) { if ((rc = model_.decode_step_fused(true, opt_.graph)) != NTK_OK) break; ++queued; }

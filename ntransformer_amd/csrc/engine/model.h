@@ -4,6 +4,7 @@
 // FFN::forward, RMSNorm::forward).  The reference's streaming / tiered / delta / speculative paths exist
 // to fit 24 GB of VRAM and are dropped: 288 GB of HBM holds every target model resident.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <cstdint>
@@ -109,6 +110,21 @@ public:
     // the host-side checks of decode_batch (no device): B in 1 .. sequences, every slot in range and named once, positions in [0, max_seq), token ids in
     // [0, vocab); NTK_OK or NTK_E_NULL / NTK_E_SHAPE with the reason in *why (optional)
     static int validate_batch(const int* slots, const int* tokens, const int* positions, int B, int sequences, int max_seq, int vocab, std::string* why);
+    // ---- KV cache sequence operations (csrc/kv_ops.hip) ------------------------------------------------------------------------------
+    // Context shift of one slot: positions [keep, keep + discard) are dropped, rows [keep + discard, n_past) move down to [keep, ...) in every layer, in
+    // the cache format the engine was loaded with (ntk_kv_shift / ntk_kv_shift_q8 with the engine's frequency table: K re-rotated by -discard positions,
+    // V byte for byte; ONE launch whatever the overlap).  Queued on the model's stream, no synchronisation; returns the new n_past - discard (>= 0) or a
+    // negative status.  The fused path's device position is NOT touched when slot 0 is shifted: the caller re-bases it (set_device_pos), as every run
+    // does.  keep + discard == n_past: nothing moves.  Refused (NTK_E_SHAPE + error(); nothing is launched): see validate_kv_shift, and tensor parallelism.
+    int kv_shift(int slot, int keep, int discard, int n_past);
+    // Rows [pos0, pos0 + n) of every layer and both sides from slot to slot, at the same positions, no rotation: stream-ordered device-to-device copies
+    // (F16: one range per layer and side; q8_0: quants and scales).  Returns n or a negative status; refusals: validate_kv_copy, tensor parallelism.
+    int kv_copy(int src_slot, int dst_slot, int pos0, int n);
+    // the host-side checks of the two (no device): NTK_OK or NTK_E_SHAPE with the reason in *why (optional)
+    static int validate_kv_shift(int slot, int keep, int discard, int n_past, int sequences, int max_seq, std::string* why);
+    static int validate_kv_copy(int src_slot, int dst_slot, int pos0, int n, int sequences, int max_seq, std::string* why);
+    // how many positions the generate loop drops when the context is full: half of what lies behind `keep`, one at the least
+    static int context_shift_discard(int n_past, int keep) { return std::max(1, (n_past - keep) / 2); }
     int set_score_rows(int rows);   // rows of logits per LM-head chunk, 1 .. 1024 (default 256: 131 MB at a vocabulary of 128 256); any time
 
     // Fused single-token step: 5 launches per layer, position and token id stay on the device so the whole

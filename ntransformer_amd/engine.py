@@ -110,6 +110,11 @@ def _bind():
     L.nt_engine_debug_kv_inputs_capture.argtypes = [vp, i]
     L.nt_engine_debug_kv_inputs_read.argtypes = [vp, i, vp, vp]
     L.nt_engine_kv_cache_bytes.argtypes = [vp]
+    L.nt_engine_kv_shift.argtypes = [vp, i, i, i, i]
+    L.nt_engine_kv_copy.argtypes = [vp, i, i, i, i]
+    L.nt_kv_shift_validate.argtypes = [i, i, i, i, i, i]
+    L.nt_kv_copy_validate.argtypes = [i, i, i, i, i, i]
+    L.nt_context_shift_discard.argtypes = [i, i]
     L.nt_engine_kv_cache_bytes.restype = C.c_uint64
     L._engine_bound = True
     return L
@@ -280,6 +285,22 @@ class Engine:
         self._check(self.L.nt_engine_debug_kv_write_slot(self.h, int(slot), layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p),
                                                          v.ctypes.data_as(C.c_void_p)), "kv_write_slot")
 
+    # ---- KV cache sequence operations (include/ntransformer.h: nt_engine_kv_shift / nt_engine_kv_copy) ----
+    def kv_shift(self, slot: int, keep: int, discard: int, n_past: int) -> int:
+        """Context shift of sequence slot `slot`: positions [keep, keep + discard) go, rows [keep + discard, n_past) move down to keep (K re-rotated, V as
+        it is).  Returns the new n_past - discard."""
+        n = self.L.nt_engine_kv_shift(self.h, int(slot), int(keep), int(discard), int(n_past))
+        if n < 0:
+            self._check(n, "kv_shift")
+        return int(n)
+
+    def kv_copy(self, src_slot: int, dst_slot: int, pos0: int, n: int) -> int:
+        """Rows [pos0, pos0 + n) of every layer and both sides from slot to slot at the same positions, no rotation.  Returns n."""
+        got = self.L.nt_engine_kv_copy(self.h, int(src_slot), int(dst_slot), int(pos0), int(n))
+        if got < 0:
+            self._check(got, "kv_copy")
+        return int(got)
+
     @property
     def max_context(self): return self.L.nt_engine_max_context(self.h)
 
@@ -447,6 +468,21 @@ class Engine:
         out = (C.c_int * 4096)()
         n = self.L.nt_engine_tokenize(self.h, text.encode(), int(add_bos), out, 4096)
         return list(out[:n])
+
+
+def kv_shift_validate(slot: int, keep: int, discard: int, n_past: int, sequences: int, max_seq: int) -> int:
+    """Host only (nt_kv_shift_validate): the argument checks of Engine.kv_shift for an engine of `sequences` slots and `max_seq` positions: 0 or NTK_E_SHAPE."""
+    return int(_bind().nt_kv_shift_validate(int(slot), int(keep), int(discard), int(n_past), int(sequences), int(max_seq)))
+
+
+def kv_copy_validate(src_slot: int, dst_slot: int, pos0: int, n: int, sequences: int, max_seq: int) -> int:
+    """Host only (nt_kv_copy_validate): the argument checks of Engine.kv_copy: 0 or NTK_E_SHAPE."""
+    return int(_bind().nt_kv_copy_validate(int(src_slot), int(dst_slot), int(pos0), int(n), int(sequences), int(max_seq)))
+
+
+def context_shift_discard(n_past: int, keep: int) -> int:
+    """Host only (nt_context_shift_discard): how many positions the generate loop drops when the context is full: max(1, (n_past - keep) // 2)."""
+    return int(_bind().nt_context_shift_discard(int(n_past), int(keep)))
 
 
 def sampler_draw_nth(logits: np.ndarray, params: GenParams, recent: Sequence[int], skip: int) -> int:
