@@ -6,7 +6,7 @@
 // infinite) the value is pinned: x * id = NaN -> 0, then clamped to [-127, 127] before the rounding -- no defined case is changed.
 // The input is the F32 post-RoPE k / the F32 v: nothing is rounded to half on the way.
 //
-// Device layout (the engine's own): one layer's K (or V) cache is ONE buffer of ntk_kv_q8_cache_bytes bytes --
+// Device layout (the engine's own; computed in kv_layout.h and nowhere else): one layer's K (or V) cache is ONE buffer of ntk_kv_q8_cache_bytes bytes --
 //   quants  int8 [max_seq][n_kv_heads * head_dim]        at byte 0          (a head's row = 128 bytes at head_dim 128: 16-byte pieces)
 //   scales  half [max_seq][n_kv_heads * head_dim / 32]   at byte max_seq * n_kv_heads * head_dim
 // = 1.0625 bytes per element.  The canonical 34-byte blocks exist at the API boundary only (ntransformer_amd/kv_q8.py, nt_engine_debug_kv_*_q8).
@@ -19,6 +19,7 @@
 #include "common.hip.h"
 #include "attention_merge.hip.h"
 #include "attention_q8_decode.hip.h"   // the quantiser, the int8 -> F16 helpers and the decode attention's body
+#include "kv_layout.h"
 
 namespace ntk {
 
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void attention_batch_q8_kernel(float* __restri
                                                                  const int n_heads, const int n_kv_heads, const int max_seq, const float scale,
                                                                  const float theta, const float fscale) {
     const int b = blockIdx.z;
-    const size_t per = (size_t)n_kv_heads * Q8_HD, planes = (size_t)max_seq * per;
+    const size_t per = (size_t)n_kv_heads * Q8_HD, planes = kv_q8_scale_offset(max_seq, per);
     uint8_t* const kc = caches.k[b];
     uint8_t* const vc = caches.v[b];
     attention_decode_q8_row(part + (size_t)b * part_row, q + (size_t)b * n_heads * Q8_HD, k + (size_t)b * per, v + (size_t)b * per,
@@ -159,7 +160,7 @@ struct Q8Planes {
 };
 static Q8Planes q8_planes(void* cache, int max_seq, int per) {
     uint8_t* b = static_cast<uint8_t*>(cache);
-    return {reinterpret_cast<int8_t*>(b), reinterpret_cast<uint16_t*>(b + (size_t)max_seq * per)};
+    return {reinterpret_cast<int8_t*>(b), reinterpret_cast<uint16_t*>(b + kv_q8_scale_offset(max_seq, (size_t)per))};
 }
 
 }  // namespace ntk
@@ -167,9 +168,7 @@ static Q8Planes q8_planes(void* cache, int max_seq, int per) {
 extern "C" {
 
 size_t ntk_kv_q8_cache_bytes(int max_seq, int n_kv_heads, int head_dim) {
-    if (max_seq <= 0 || n_kv_heads <= 0 || head_dim <= 0 || head_dim % 32 != 0) return 0;
-    const size_t per = (size_t)n_kv_heads * head_dim;
-    return ((size_t)max_seq * (per + per / 16) + 255) / 256 * 256;
+    return ntk::kv_q8_layer_bytes(max_seq, n_kv_heads, head_dim);
 }
 
 int ntk_kv_store_q8(void* k_cache, void* v_cache, const float* k, const float* v, int seq_len, int n_kv_heads, int head_dim, int start_pos,

@@ -45,11 +45,9 @@ void Model::free_all() {
     raw_scratch_ = nullptr; raw_scratch_bytes_ = raw_cursor_ = 0; raw_err_ = 0;
     repack_done_ = output_tied_ = false;
     host_pos_ = attn_regime_ = 0;
-    k_cache_ = v_cache_ = nullptr;
-    slot_k_.clear(); slot_v_.clear(); slot_k_q8_.clear(); slot_v_q8_.clear();
+    kv_.reset();
     batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = batch_recent_ = nullptr; batch_sample_scratch_ = nullptr;
     kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
-    k_cache_q8_ = v_cache_q8_ = nullptr; kv_f16_k_ = kv_f16_v_ = nullptr; kv_q8_layer_bytes_ = 0; kv_cache_bytes_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;
     positions_ = tokens_dev_ = d_pos_ = d_token_ = nullptr;
     score_logits_ = score_logprob_ = nullptr; score_targets_ = score_top1_ = nullptr; score_cap_ = 0;   // (they were in allocs_)
@@ -129,8 +127,7 @@ uint64_t Model::bytes_per_token(int pos) const {
         for (auto m : kLayerMatrices) b += (L.*m).nbytes;
     b += output_.nbytes;
     b += (uint64_t)(2 * cfg_.n_layers + 1) * cfg_.hidden_size * 4;
-    const uint64_t kv_elems = (uint64_t)cfg_.n_kv_heads * cfg_.head_dim;
-    const uint64_t kv_row = kv_q8_ ? kv_elems + kv_elems / 16 : kv_elems * 2;   // q8_0: an int8 per element + a half per 32
+    const uint64_t kv_row = kv_.row_bytes();
     b += 2ull * cfg_.n_layers * kv_row * (uint64_t)(pos + 1) + 2ull * cfg_.n_layers * kv_row;
     b += ntk_row_bytes(token_embd_.dtype, cfg_.hidden_size);
     return b;

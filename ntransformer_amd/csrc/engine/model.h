@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "gguf.h"
+#include "kv_cache.h"
 #include "synth.h"
 
 struct ntk_sample_rows;   // include/ntk_engine.h
@@ -70,8 +71,8 @@ public:
     int score(const int* tokens, const int* targets, int seq_len, int start_pos, float* logprob_out, int* top1_out, int slot = 0);
 
     // ---- sequence slots and the batched decode step ---------------------------------------------------------------------------------
-    // "sequences" = N (1 .. kMaxSequences, default 1; BEFORE the load, kept across loads; a sharing sequence takes its own): slots 1 .. N - 1 are extra F16
-    // caches of slot 0's [L][max_seq][n_kv][hd] layout, allocated at load and counted in kv_cache_bytes(), beside a [16][vocab] F32 logits buffer, the batch
+    // "sequences" = N (1 .. kMaxSequences, default 1; BEFORE the load, kept across loads; a sharing sequence takes its own): slots 1 .. N - 1 are extra
+    // caches of slot 0's format and layout (KvCache, kv_cache.h), allocated at load and counted in kv_cache_bytes(), beside a [16][vocab] F32 logits buffer, the batch
     // attention's scratch, the batched sampler's windows / scratch / pinned mirrors (batch_sample_buffers: about 0.9 MB, not counted) and -- where
     // score_buffers() would need one -- an LM-head GEMM workspace.  N = 1 allocates nothing (decode_batch with one row on slot 0 allocates the logits
     // buffers on its first call, as score() does).  Refused at load with kv_cache = q8_0 (unless "batch_kv_q8", below), tensor parallelism or a context of fewer than N positions (a
@@ -80,9 +81,8 @@ public:
     int set_sequences(int n);
     int sequences() const { return sequences_; }
     // "batch_kv_q8" = 1 (default 0; BEFORE the load, kept across loads; a sharing sequence takes its own): sequence slots and the batched step over the
-    // 8-bit cache.  With kv_cache = q8_0 the load then takes sequences = 1 .. 16 -- slot 0 is k_cache_q8_ / v_cache_q8_, slots 1 .. N - 1 are further
-    // L x kv_q8_layer_bytes_ buffers (zeroed), the one-layer F16 image of the prompt path stays ONE per engine (every prompt pass rebuilds rows
-    // [0, start_pos + T) of it per layer before reading it, on one stream, so it carries nothing from one pass or slot to the next) -- and decode_batch /
+    // 8-bit cache.  With kv_cache = q8_0 the load then takes sequences = 1 .. 16 -- every slot an 8-bit cache (zeroed), the one-layer F16 image of the
+    // prompt path stays ONE per engine (KvCache, kv_cache.h) -- and decode_batch /
     // decode_batch_sample run: their attention is ntk_attention_decode_q8_batch with kv_q8_splits(attention_regime(largest position)) splits.
     // kv_cache = f16: accepted, changes nothing.  The option exists ONLY because the default refusals (sequences > 1 at load, decode_batch on a q8_0
     // engine) are pinned by tests/test_batch_decode_gpu.py::test_refusals_leave_the_engine_usable: with it off every refusal and message is unchanged.
@@ -192,7 +192,7 @@ public:
     int set_kv_cache(const std::string& kind);
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
-    uint64_t kv_cache_bytes() const { return kv_cache_bytes_; }   // resident KV bytes of this sequence, the q8_0 mode's F16 scratch included
+    uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included
     int debug_kv_inputs_capture(int layer);
     int debug_kv_inputs_read(int n, float* k, float* v);
     // cache rows [pos0, pos0 + n) of a layer of sequence slot `slot` as canonical 34-byte GGUF block_q8_0, [n][n_kv_heads * head_dim / 32] blocks per
@@ -320,11 +320,9 @@ private:
     bool shares_weights_ = false;    // the tensor table points into ANOTHER Model's allocations (share_weights): nothing of it is freed here
 
     // buffers (reference transformer.cpp:330-391)
-    uint16_t* k_cache_ = nullptr;   // [L][max_seq][nkv][hd] half
-    uint16_t* v_cache_ = nullptr;
+    KvCache kv_;                    // every slot's K / V cache in the loaded format (kv_cache.h); slot 0 is the one the fused path decodes on
     bool kv_q8_ = false;            // the option (kept across loads)
     int sequences_ = 1;             // the option (kept across loads)
-    std::vector<uint16_t*> slot_k_, slot_v_;   // [sequences_] caches by slot; [0] = k_cache_ / v_cache_
     float* batch_logits_ = nullptr; // [kMaxSequences][V]: decode_batch's logits
     int* batch_in_ = nullptr;       // [3][kMaxSequences] device ints: tokens | positions | -1 (ntk_logprob_rows' "no target")
     int batch_host_[3 * 16] = {};   // ... and their host image
@@ -335,14 +333,7 @@ private:
     int* h_batch_recent_ = nullptr; // pinned staging of it (a step packs its windows at the step's own pitch)
     void* batch_sample_scratch_ = nullptr;   // ntk_sample_rows_scratch_bytes(kMaxSequences, V)
     int* h_batch_next_ = nullptr;   // pinned [kMaxSequences]: the sampled tokens (ntk_sample_rows_top_k's mirror)
-    uint8_t* k_cache_q8_ = nullptr; // [L] x kv_q8_layer_bytes_ (ntk_kv_q8_cache_bytes: int8 quants, then half scales)
-    uint8_t* v_cache_q8_ = nullptr;
-    size_t kv_q8_layer_bytes_ = 0;
     bool batch_kv_q8_ = false;      // the option (kept across loads): sequence slots / the batched step over the 8-bit cache
-    std::vector<uint8_t*> slot_k_q8_, slot_v_q8_;   // q8_0 mode: [sequences_] 8-bit caches by slot; [0] = k_cache_q8_ / v_cache_q8_
-    uint16_t* kv_f16_k_ = nullptr;  // q8_0 mode: [max_seq][nkv][hd] half, ONE layer's dequantised image for the prompt path, shared by all layers
-    uint16_t* kv_f16_v_ = nullptr;
-    uint64_t kv_cache_bytes_ = 0;
     float* kv_capture_ = nullptr;   // parity instrumentation (debug_kv_inputs_capture): [2][max_seq][nkv * hd] F32 k (unrotated) and v of one layer's last 1:1 pass
     int kv_capture_layer_ = -1, kv_capture_T_ = 0;
     float* hidden_ = nullptr;       // [max_seq][H]

@@ -47,14 +47,14 @@ int Model::debug_run_layers(const float* hidden_in, int T, int start_pos, int fi
 int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write, int slot) {
     if (!k || !v) return NTK_E_NULL;
     if (kv_q8_) { err_ = "debug_kv: the KV cache is q8_0 (use the _q8 form)"; return NTK_E_DTYPE; }
-    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= (int)slot_k_.size()) return NTK_E_SHAPE;
-    const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim;
-    uint16_t* const kcache = slot_k_[slot];
-    uint16_t* const vcache = slot_v_[slot];
-    const size_t off = ((size_t)layer * cfg_.max_seq_len + pos0) * per, bytes = (size_t)n * per * 2;
+    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= kv_.slots()) return NTK_E_SHAPE;
+    KvRange r[2];
+    kv_.row_ranges(pos0, n, r);   // (f16: one range)
+    uint8_t* const kd = static_cast<uint8_t*>(kv_.k(slot, layer)) + r[0].off;
+    uint8_t* const vd = static_cast<uint8_t*>(kv_.v(slot, layer)) + r[0].off;
     void* s = stream_;
-    NT_TRY(write ? ntk_memcpy_h2d_async(kcache + off, k, bytes, s) : ntk_memcpy_d2h_async(k, kcache + off, bytes, s));
-    NT_TRY(write ? ntk_memcpy_h2d_async(vcache + off, v, bytes, s) : ntk_memcpy_d2h_async(v, vcache + off, bytes, s));
+    NT_TRY(write ? ntk_memcpy_h2d_async(kd, k, r[0].bytes, s) : ntk_memcpy_d2h_async(k, kd, r[0].bytes, s));
+    NT_TRY(write ? ntk_memcpy_h2d_async(vd, v, r[0].bytes, s) : ntk_memcpy_d2h_async(v, vd, r[0].bytes, s));
     return ntk_stream_synchronize(s);
 }
 
@@ -63,16 +63,17 @@ int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool w
 int Model::debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write, int slot) {
     if (!k_blocks || !v_blocks) return NTK_E_NULL;
     if (!kv_q8_) { err_ = "debug_kv_q8: the KV cache is f16"; return NTK_E_DTYPE; }
-    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= (int)slot_k_q8_.size()) return NTK_E_SHAPE;
+    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= kv_.slots()) return NTK_E_SHAPE;
     if (n == 0) return NTK_OK;
-    const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim, nb = per / 32;
-    const size_t qbytes = (size_t)n * per, sbytes = (size_t)n * nb * 2;
+    const size_t nb = (size_t)cfg_.n_kv_heads * cfg_.head_dim / 32;   // blocks of a row
+    KvRange r[2];   // quants, scales
+    kv_.row_ranges(pos0, n, r);
+    const size_t qbytes = r[0].bytes, sbytes = r[1].bytes;
     void* s = stream_;
     std::vector<uint8_t> qh(qbytes), sh(sbytes);
     for (int side = 0; side < 2; ++side) {
-        uint8_t* base = (side ? slot_v_q8_[slot] : slot_k_q8_[slot]) + (size_t)layer * kv_q8_layer_bytes_;
-        uint8_t* qd = base + (size_t)pos0 * per;
-        uint8_t* sd = base + (size_t)cfg_.max_seq_len * per + (size_t)pos0 * nb * 2;
+        uint8_t* base = static_cast<uint8_t*>(side ? kv_.v(slot, layer) : kv_.k(slot, layer));
+        uint8_t *qd = base + r[0].off, *sd = base + r[1].off;
         uint8_t* blocks = side ? v_blocks : k_blocks;
         if (write) {
             for (size_t b = 0; b < (size_t)n * nb; ++b) {

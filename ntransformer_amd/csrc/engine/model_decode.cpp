@@ -124,7 +124,6 @@ int Model::enqueue_layers(int first, int last_layer) {
     const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
     void* s = stream_;
     const float scale = 1.0f / sqrtf((float)hd);
-    const size_t kv_layer = (size_t)cfg_.max_seq_len * nkv * hd;
     const Views act = views(1);
     auto project_add = [&](const DevTensor& w, const float* x, int kind) -> int {   // hidden += W . x
         const DevTensor* const wp = &w;
@@ -142,20 +141,17 @@ int Model::enqueue_layers(int first, int last_layer) {
         const int fused = fuse_attention_ ? attention_in_wo(L, i) : (int)NTK_E_SHAPE;
         if (fused != NTK_OK) {
             if (!not_taken(fused)) return fused;
-            uint16_t* kc = kv_q8_ ? nullptr : k_cache_ + (size_t)i * kv_layer;   // (q8_0: the launch takes the 8-bit caches)
-            uint16_t* vc = kv_q8_ ? nullptr : v_cache_ + (size_t)i * kv_layer;
             prof_mark(1, true);
             if (kv_q8_)
-                NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, k_cache_q8_ + (size_t)i * kv_q8_layer_bytes_,
-                                               v_cache_q8_ + (size_t)i * kv_q8_layer_bytes_, d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
-                                               cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
+                NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, kv_.k(0, i), kv_.v(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
+                                               cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
             else if (attn_regime_ == 0)
-                NT_TRY(ntk_attention_decode_fused(act.attn_out, act.q, act.k, act.v, kc, vc, d_pos_, rope_inv_freq_, nh, nkv, hd,
+                NT_TRY(ntk_attention_decode_fused(act.attn_out, act.q, act.k, act.v, kv_.k_f16(0, i), kv_.v_f16(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
                                                   cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, s));
             else
                 NT_TRY((attn_merge_ ? ntk_attention_decode_split_merged : ntk_attention_decode_split)(
-                    act.attn_out, act.q, act.k, act.v, kc, vc, d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale, cfg_.rope_theta,
-                    cfg_.rope_freq_scale, attention_splits(attn_regime_, hd), attn_scratch_, s));
+                    act.attn_out, act.q, act.k, act.v, kv_.k_f16(0, i), kv_.v_f16(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
+                    cfg_.rope_theta, cfg_.rope_freq_scale, attention_splits(attn_regime_, hd), attn_scratch_, s));
             prof_mark(1, false);
             NT_TRY(project_add(L.wo, act.attn_out, 2));
         }

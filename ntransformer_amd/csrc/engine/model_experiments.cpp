@@ -31,12 +31,11 @@ int Model::launch_persistent() {
 int Model::attention_in_wo(const LayerWeights& L, int layer) {
     if (attn_regime_ != 0 || !fuse_attention_ || kv_q8_ || !attn_sync_ || !is_quant(L.wo.dtype) || tp_world_ != 1) return NTK_E_SHAPE;
     const int hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
-    const size_t kv_layer = (size_t)cfg_.max_seq_len * nkv * hd;
     const Views act = views(1);
     raw_begin();
     ntk_gemv_seg wo = {raw_of(L.wo), hidden_, (int)L.wo.out_f, L.wo.dtype};
     prof_mark(0, true);
-    const int st = ntk_attention_gemv_fused(act.attn_out, act.q, act.k, act.v, k_cache_ + (size_t)layer * kv_layer, v_cache_ + (size_t)layer * kv_layer, d_pos_,
+    const int st = ntk_attention_gemv_fused(act.attn_out, act.q, act.k, act.v, kv_.k_f16(0, layer), kv_.v_f16(0, layer), d_pos_,
                                             rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, 1.0f / sqrtf((float)hd), cfg_.rope_theta, cfg_.rope_freq_scale, &wo,
                                             hidden_, attn_sync_, stream_);
     prof_mark(0, false);
@@ -78,11 +77,9 @@ int Model::check_experiments() {
 // The token's operator table for the persistent kernel: exactly the sequence enqueue_token() launches.
 int Model::build_persistent_plan(int kind) {
     const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
-    const int kvd = nkv * hd;
     if (hd != 64 && hd != 128) return NTK_E_SHAPE;
     if (const char* e = getenv("NTK_NO_PERSISTENT")) { if (atoi(e)) return NTK_E_SHAPE; }
     const float scale = 1.0f / sqrtf((float)hd);
-    const size_t kv_layer = (size_t)cfg_.max_seq_len * kvd;
     const Views act = views(1);
     std::vector<ntk_pop> ops;
     bool ok = true;
@@ -129,7 +126,7 @@ int Model::build_persistent_plan(int kind) {
         memset(&a, 0, sizeof a);
         a.kind = NTK_POP_ATTENTION; a.wait = 1; a.arrive = 1;
         a.out = act.attn_out; a.q = act.q; a.k = act.k; a.v = act.v;
-        a.k_cache = k_cache_ + (size_t)i * kv_layer; a.v_cache = v_cache_ + (size_t)i * kv_layer;
+        a.k_cache = kv_.k_f16(0, i); a.v_cache = kv_.v_f16(0, i);
         a.inv_freq = rope_inv_freq_;
         a.n_heads = nh; a.n_kv_heads = nkv; a.head_dim = hd; a.max_seq = cfg_.max_seq_len;
         a.scale = scale; a.theta_base = cfg_.rope_theta; a.freq_scale = cfg_.rope_freq_scale;

@@ -28,10 +28,10 @@ int Model::kv_shift(int slot, int keep, int discard, int n_past) {
     const int src0 = keep + discard, n_rows = n_past - src0;
     if (n_rows > 0) {
         const int L = cfg_.n_layers, S = cfg_.max_seq_len, nkv = cfg_.n_kv_heads, hd = cfg_.head_dim;
-        const int rc = kv_q8_ ? ntk_kv_shift_q8(slot_k_q8_[slot], slot_v_q8_[slot], L, S, nkv, hd, src0, keep, n_rows, rope_inv_freq_, cfg_.rope_theta,
+        const int rc = kv_q8_ ? ntk_kv_shift_q8(kv_.k(slot), kv_.v(slot), L, S, nkv, hd, src0, keep, n_rows, rope_inv_freq_, cfg_.rope_theta,
                                                 cfg_.rope_freq_scale, cfg_.rope_interleaved, stream_)
-                            : ntk_kv_shift(slot_k_[slot], slot_v_[slot], L, S, nkv, hd, src0, keep, n_rows, rope_inv_freq_, cfg_.rope_theta,
-                                           cfg_.rope_freq_scale, cfg_.rope_interleaved, stream_);
+                            : ntk_kv_shift(static_cast<uint16_t*>(kv_.k(slot)), static_cast<uint16_t*>(kv_.v(slot)), L, S, nkv, hd, src0, keep, n_rows,
+                                           rope_inv_freq_, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, stream_);
         if (rc != NTK_OK) { err_ = std::string("kv_shift: ") + ntk_status_string(rc); return rc; }
     }
     return n_past - discard;
@@ -43,20 +43,15 @@ int Model::kv_copy(int src_slot, int dst_slot, int pos0, int n) {
     NT_TRY(validate_kv_copy(src_slot, dst_slot, pos0, n, sequences_, cfg_.max_seq_len, &err_));
     if (n == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim, S = (size_t)cfg_.max_seq_len;
     auto d2d = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess; };
+    KvRange rows[2];   // the rows' byte ranges inside a layer buffer (f16: one; q8_0: quants, scales)
+    const int n_ranges = kv_.row_ranges(pos0, n, rows);
     bool ok = true;
     for (int l = 0; l < cfg_.n_layers && ok; ++l) {
         for (int side = 0; side < 2 && ok; ++side) {
-            if (kv_q8_) {   // a layer buffer: quants [S][per], then half scales [S][per / 32]
-                uint8_t* const d = (side ? slot_v_q8_[dst_slot] : slot_k_q8_[dst_slot]) + (size_t)l * kv_q8_layer_bytes_;
-                const uint8_t* const s = (side ? slot_v_q8_[src_slot] : slot_k_q8_[src_slot]) + (size_t)l * kv_q8_layer_bytes_;
-                const size_t q0 = (size_t)pos0 * per, s0 = S * per + (size_t)pos0 * (per / 32) * 2;
-                ok = d2d(d + q0, s + q0, (size_t)n * per) && d2d(d + s0, s + s0, (size_t)n * (per / 32) * 2);
-            } else {
-                const size_t off = ((size_t)l * S + pos0) * per;
-                ok = d2d((side ? slot_v_[dst_slot] : slot_k_[dst_slot]) + off, (side ? slot_v_[src_slot] : slot_k_[src_slot]) + off, (size_t)n * per * 2);
-            }
+            uint8_t* const d = static_cast<uint8_t*>(side ? kv_.v(dst_slot, l) : kv_.k(dst_slot, l));
+            const uint8_t* const s = static_cast<const uint8_t*>(side ? kv_.v(src_slot, l) : kv_.k(src_slot, l));
+            for (int r = 0; r < n_ranges && ok; ++r) ok = d2d(d + rows[r].off, s + rows[r].off, rows[r].bytes);
         }
     }
     if (!ok) { err_ = "kv_copy: a device-to-device copy failed"; return NTK_E_LAUNCH; }

@@ -294,7 +294,7 @@ const void* Model::raw_of(const DevTensor& t) {
 }
 
 int Model::alloc_buffers() {   // transformer.cpp:330-391
-    const size_t S = (size_t)cfg_.max_seq_len, H = (size_t)cfg_.hidden_size, L = (size_t)cfg_.n_layers;
+    const size_t S = (size_t)cfg_.max_seq_len, H = (size_t)cfg_.hidden_size;
     const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim;
     auto dev = [&](size_t bytes, bool zero) -> void* {
         void* p = nt_hip_malloc(bytes + 256);
@@ -304,7 +304,6 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     // the attention kernels address a layer's cache rows with 32-bit byte offsets (attention.hip): a context whose per-layer cache reaches
     // 3.75 GiB is refused here, at load, rather than as NTK_E_SHAPE from the first decode step (8 KV heads of 128: 1.9 M positions)
     if (S * per * sizeof(uint16_t) >= 0xF0000000ull) { err_ = "context too long: one layer's K cache must stay below 3.75 GiB (32-bit row offsets)"; return NTK_E_SHAPE; }
-    const size_t kvb = L * S * per * sizeof(uint16_t);
     if (kv_q8_) {   // the 8-bit cache (csrc/attention_q8.hip) + ONE layer's F16 image for the prompt path
         if (cfg_.head_dim != 128 || cfg_.n_kv_heads <= 0 || cfg_.n_heads % cfg_.n_kv_heads != 0 || cfg_.n_heads / cfg_.n_kv_heads > 16) {
             err_ = "kv_cache=q8_0 needs head_dim 128 and at most 16 query heads per KV head (this model: head_dim " + std::to_string(cfg_.head_dim) +
@@ -313,40 +312,14 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         }
         if (tp_world_ > 1) { err_ = "kv_cache=q8_0 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
         if (fuse_attention_) { err_ = "kv_cache=q8_0 is not supported with the attention-inside-Wo launch (fuse_attention)"; return NTK_E_SHAPE; }
-        kv_q8_layer_bytes_ = ntk_kv_q8_cache_bytes((int)S, cfg_.n_kv_heads, cfg_.head_dim);
-        k_cache_q8_ = (uint8_t*)dev(L * kv_q8_layer_bytes_, true);
-        v_cache_q8_ = (uint8_t*)dev(L * kv_q8_layer_bytes_, true);
-        kv_f16_k_ = (uint16_t*)dev(S * per * sizeof(uint16_t), true);
-        kv_f16_v_ = (uint16_t*)dev(S * per * sizeof(uint16_t), true);
-        if (!k_cache_q8_ || !v_cache_q8_ || !kv_f16_k_ || !kv_f16_v_) { err_ = "buffer allocation failed (8-bit KV cache)"; return NTK_E_NOMEM; }
-        kv_cache_bytes_ = 2ull * L * kv_q8_layer_bytes_ + 2ull * S * per * sizeof(uint16_t);
-    } else {
-        k_cache_ = (uint16_t*)dev(kvb, true);
-        v_cache_ = (uint16_t*)dev(kvb, true);
-        kv_cache_bytes_ = 2ull * kvb;
     }
-    slot_k_.assign(1, k_cache_);
-    slot_v_.assign(1, v_cache_);
-    slot_k_q8_.assign(1, k_cache_q8_);
-    slot_v_q8_.assign(1, v_cache_q8_);
     if (sequences_ > 1) {   // the extra sequence slots: caches of slot 0's layout
         if (kv_q8_ && !batch_kv_q8_) { err_ = "sequences > 1 is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
         if (tp_world_ > 1) { err_ = "sequences > 1 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
         // a batched step is a prompt pass of up to `sequences` rows through buffers of max_seq rows (hidden_, residual_, workspace_, row_max_, kv_capture_)
         if ((size_t)sequences_ > S) { err_ = "sequences = " + std::to_string(sequences_) + " needs a context of at least as many positions (this load: " + std::to_string(S) + ")"; return NTK_E_SHAPE; }
-        for (int i = 1; i < sequences_ && kv_q8_; ++i) {   // ("batch_kv_q8": 8-bit caches; the one-layer F16 image stays one per engine)
-            slot_k_q8_.push_back((uint8_t*)dev(L * kv_q8_layer_bytes_, true));
-            slot_v_q8_.push_back((uint8_t*)dev(L * kv_q8_layer_bytes_, true));
-            if (!slot_k_q8_.back() || !slot_v_q8_.back()) { err_ = "buffer allocation failed (8-bit KV cache of sequence slot " + std::to_string(i) + ")"; return NTK_E_NOMEM; }
-            kv_cache_bytes_ += 2ull * L * kv_q8_layer_bytes_;
-        }
-        for (int i = 1; i < sequences_ && !kv_q8_; ++i) {
-            slot_k_.push_back((uint16_t*)dev(kvb, true));
-            slot_v_.push_back((uint16_t*)dev(kvb, true));
-            if (!slot_k_.back() || !slot_v_.back()) { err_ = "buffer allocation failed (KV cache of sequence slot " + std::to_string(i) + ")"; return NTK_E_NOMEM; }
-            kv_cache_bytes_ += 2ull * kvb;
-        }
     }
+    NT_TRY(kv_.allocate(KvGeom{cfg_.n_layers, cfg_.max_seq_len, cfg_.n_kv_heads, cfg_.head_dim}, kv_q8_, sequences_, dev, &err_));
     hidden_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
     residual_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
     logits_ = (float*)dev((size_t)cfg_.vocab_size * 4, false);
@@ -384,7 +357,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     }
     d_recent_ = (int*)dev(kRecentCap * 4, false);
     h_recent_ = (int*)nt_hip_malloc_host(kRecentCap * 4);
-    if ((!kv_q8_ && (!k_cache_ || !v_cache_)) || !hidden_ || !residual_ || !logits_ || !workspace_ || !positions_ || !tokens_dev_ ||
+    if (!kv_.k(0) || !kv_.v(0) || !hidden_ || !residual_ || !logits_ || !workspace_ || !positions_ || !tokens_dev_ ||
         !d_pos_ || !d_token_ || !argmax_scratch_ || !h_token_ || !h_ring_) {
         err_ = "buffer allocation failed";
         return NTK_E_NOMEM;
@@ -395,7 +368,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         for (int i = 0; i < cfg_.head_dim / 2; ++i) f[i] = 1.0f / powf(cfg_.rope_theta, (2.0f * i) / cfg_.head_dim);
         nt_hip_memcpy_h2d(rope_inv_freq_, f.data(), f.size() * 4);
     }
-    if (sequences_ > 1) { NT_TRY(batch_buffers()); NT_TRY(batch_sample_buffers()); }   // (none of it counted in kv_cache_bytes_)
+    if (sequences_ > 1) { NT_TRY(batch_buffers()); NT_TRY(batch_sample_buffers()); }   // (none of it counted in kv_cache_bytes())
     return NTK_OK;
 }
 

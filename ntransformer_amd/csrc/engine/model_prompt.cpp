@@ -76,7 +76,6 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
     const int qd = nh * hd, kvd = nkv * hd;
     void* s = stream_;
-    const size_t kv_layer = (size_t)cfg_.max_seq_len * kvd;
     const float scale = 1.0f / sqrtf((float)hd);
     const Views act = views(T);
     int rc = NTK_OK;
@@ -246,8 +245,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     bool normed_ahead = false;   // residual_ (with its maxima or planes) already holds this layer's normalised input, written with the previous layer's down projection
     for (int i = first; i < last_layer; ++i) {
         const LayerWeights& L = layers_[i];
-        uint16_t* kc = kv_q8_ ? nullptr : slot_k_[kv.slot] + (size_t)i * kv_layer;   // (q8_0: the one-layer F16 image, set below)
-        uint16_t* vc = kv_q8_ ? nullptr : slot_v_[kv.slot] + (size_t)i * kv_layer;
+        uint16_t* const kc = kv_.attend_k(kv.slot, i);   // (q8_0: the one-layer F16 image, rebuilt below)
+        uint16_t* const vc = kv_.attend_v(kv.slot, i);
         if (!normed_ahead) norm(L.attn_norm, true, L.wq);
         normed_ahead = false;
         float* const qkv_out[3] = {act.q, act.k, act.v};
@@ -260,25 +259,19 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         }
         if (kv.slots && kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
             ntk_kv_batch caches{};
-            for (int t = 0; t < T; ++t) {
-                caches.k[t] = slot_k_q8_[kv.slots[t]] + (size_t)i * kv_q8_layer_bytes_;
-                caches.v[t] = slot_v_q8_[kv.slots[t]] + (size_t)i * kv_q8_layer_bytes_;
-            }
+            kv_.fill(caches, kv.slots, T, i);
             ok(ntk_attention_decode_q8_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len,
                                              scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attention_regime(kv.max_pos, hd)), batch_attn_scratch_, s));
         } else if (kv.slots) {   // a batch of sequences: rope / store / attention of every row on its own cache at its own position, one launch
             ntk_kv_batch caches{};
-            for (int t = 0; t < T; ++t) {
-                caches.k[t] = slot_k_[kv.slots[t]] + (size_t)i * kv_layer;
-                caches.v[t] = slot_v_[kv.slots[t]] + (size_t)i * kv_layer;
-            }
+            kv_.fill(caches, kv.slots, T, i);
             const bool splits_ok = batch_attn_scratch_ && (hd == 64 || hd == 128 || hd == 256);   // (pick_attention_regime's rule)
             const int regime = splits_ok ? attention_regime(kv.max_pos, hd) : 0;
             ok(ntk_attention_decode_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
                                           cfg_.rope_theta, cfg_.rope_freq_scale, regime == 0 ? 1 : attention_splits(regime, hd), batch_attn_scratch_, s));
         } else if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
-            uint8_t* kc8 = slot_k_q8_[kv.slot] + (size_t)i * kv_q8_layer_bytes_;   // (the image is shared by all slots: rebuilt here, for this slot, every pass)
-            uint8_t* vc8 = slot_v_q8_[kv.slot] + (size_t)i * kv_q8_layer_bytes_;
+            void* kc8 = kv_.k(kv.slot, i);   // (kc / vc: the image, shared by all slots: rebuilt here, for this slot, every pass)
+            void* vc8 = kv_.v(kv.slot, i);
             if (T >= 4) {
                 ok(ntk_rope_kv_store_q8(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
                                         kc8, vc8, start_pos, cfg_.max_seq_len, s));
@@ -286,8 +279,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
                 ok(ntk_rope(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, s));
                 ok(ntk_kv_store_q8(kc8, vc8, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
             }
-            ok(ntk_kv_dequant_q8_f16(kv_f16_k_, kv_f16_v_, kc8, vc8, start_pos + T, nkv, hd, cfg_.max_seq_len, s));
-            kc = kv_f16_k_; vc = kv_f16_v_;
+            ok(ntk_kv_dequant_q8_f16(kc, vc, kc8, vc8, start_pos + T, nkv, hd, cfg_.max_seq_len, s));
         } else if (with_max && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
             ok(ntk_rope_kv_store(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, kc, vc,
                                  start_pos, cfg_.max_seq_len, s));

@@ -18,6 +18,7 @@
 // (half(d) * q, exact in F32), rotated and requantised block by block with the store's arithmetic (attention_q8_decode.hip.h: q8 quantiser) -- a
 // 32-block lies in two neighbouring lanes (NeoX pairing) or in one (interleaved), so the block maximum is one lane exchange at the most.
 #include "common.hip.h"
+#include "kv_layout.h"
 
 namespace ntk {
 
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(256) void kv_shift_q8_kernel(uint8_t* k_cache, uint
     const size_t per = (size_t)(g.lanes / 4) * HD;   // elements of a row
     uint8_t* const layer = (is_k ? k_cache : v_cache) + (size_t)blockIdx.y * layer_bytes;
     uint8_t* const qbase = layer + (size_t)head * HD;
-    uint16_t* const sbase = reinterpret_cast<uint16_t*>(layer + (size_t)max_seq * per) + (size_t)head * 4;
+    uint16_t* const sbase = reinterpret_cast<uint16_t*>(layer + kv_q8_scale_offset(max_seq, per)) + (size_t)head * 4;
     const int o0 = interleaved ? 32 * j : 16 * j, o1 = interleaved ? 32 * j + 16 : 64 + 16 * j;
     const int b0 = o0 / 32, b1 = o1 / 32;
     float cs[16], sn[16];
@@ -245,7 +246,7 @@ int ntk_kv_shift_q8(void* k_cache_q8, void* v_cache_q8, int n_layers, int max_se
     const int rc = ntk::kv_shift_geom(g, grid, n_layers, max_seq, n_kv_heads, 4, src0, dst0, n_rows);
     if (rc != NTK_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(k_cache_q8) & 15) || (reinterpret_cast<uintptr_t>(v_cache_q8) & 15)) return NTK_E_ALIGN;
-    const size_t layer_bytes = ntk_kv_q8_cache_bytes(max_seq, n_kv_heads, head_dim);
+    const size_t layer_bytes = ntk::kv_q8_layer_bytes(max_seq, n_kv_heads, head_dim);
     hipLaunchKernelGGL(interleaved ? ntk::kv_shift_q8_kernel<true> : ntk::kv_shift_q8_kernel<false>, grid, dim3(256), 0, ntk::resolve_stream(stream),
                        static_cast<uint8_t*>(k_cache_q8), static_cast<uint8_t*>(v_cache_q8), layer_bytes, g, max_seq, inv_freq, theta_base, freq_scale);
     return ntk::last_launch_status();

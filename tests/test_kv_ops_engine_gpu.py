@@ -1,6 +1,6 @@
 """KV cache sequence operations through the engine on the GPU: nt_engine_kv_shift (context shift with K re-rotation) against the model's own RoPE and
 against the numpy checkers, the decode step behind a shift, generation past the end of the context ("context_shift"), nt_engine_kv_copy (slot copy),
-a shifted slot inside a batched step, the refusals, and the CLI flags.
+a shifted slot inside a batched step, a step on one slot of three (its own rows read, no other slot written), the refusals, and the CLI flags.
 
 The model is the tiny head-128 one of tests/test_kv_q8_gpu.py (hidden 256, 2 layers, 2 heads, 1 KV head, vocabulary 512, Q8_0 weights) at a context of 64.
 
@@ -260,6 +260,38 @@ def test_shifting_one_slot_leaves_its_companions_rows_of_a_batched_step_alone(kv
     assert np.isfinite(lx).all()
     assert np.array_equal(lx[0], ly[0]) and np.array_equal(lx[1], ly[1])
     assert not np.array_equal(lx[2], ly[2])
+    x.close()
+    y.close()
+
+
+# ------------------------------------------------------------------------------------------------ a step on one slot of three
+@pytest.mark.parametrize("kv", ["f16", "q8_0"])
+def test_a_step_on_one_slot_reads_its_own_rows_and_writes_no_other_slot(kv):
+    """Three slots hold three different prompts (4, 5, 6 rows, both layers).  A decode_batch on slot 1 alone at position 5 writes row 5 of slot 1 in
+    both layers and not one other byte of any slot; its logits are, bit for bit, those of the same step on an engine that holds the same prompt in
+    slot 2 behind other neighbours: the step read the rows of the slot it named, in every layer."""
+    r = rng(8)
+    prompts = [tokens(r, 4), tokens(r, 5), tokens(r, 6)]
+    x, y = slots_engine(kv, 3), slots_engine(kv, 3)
+    for s, t in ((0, 0), (1, 1), (2, 2)):
+        x.seq_forward(s, prompts[t], 0)
+    for s, t in ((0, 2), (1, 0), (2, 1)):
+        y.seq_forward(s, prompts[t], 0)
+    before = [read_slot(x, kv, s) for s in range(3)]
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        for l in range(LAYERS):                                   # (row 0 is the shared first token's; rows 1 .. 3 differ slot by slot)
+            assert not np.array_equal(before[a][0][l, 1:4], before[b][0][l, 1:4]) and not np.array_equal(before[a][1][l, 1:4], before[b][1][l, 1:4])
+    lx, _ = x.decode_batch([1], [77], [5])
+    ly, _ = y.decode_batch([2], [77], [5])
+    assert np.isfinite(lx).all() and np.array_equal(lx[0].view(np.uint32), ly[0].view(np.uint32))
+    after = [read_slot(x, kv, s) for s in range(3)]
+    for s in (0, 2):
+        assert np.array_equal(after[s][0], before[s][0]) and np.array_equal(after[s][1], before[s][1]), s
+    for side in (0, 1):
+        rest = [i for i in range(CTX) if i != 5]
+        assert np.array_equal(after[1][side][:, rest], before[1][side][:, rest])
+        for l in range(LAYERS):
+            assert not np.array_equal(after[1][side][l, 5], before[1][side][l, 5]), (side, l)
     x.close()
     y.close()
 
