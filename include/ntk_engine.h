@@ -127,6 +127,40 @@ int ntk_attention_decode_batch(float* output, const float* q, const float* k, co
                                int n_rows, const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq, float scale,
                                float theta_base, float freq_scale, int nsplit, float* scratch, void* stream);
 
+/* The PACKED PROMPT PASS (csrc/attention.hip, csrc/attention_mfma.hip; no reference counterpart): the rows of one pass are the concatenation of SEGMENTS,
+ * a segment being n_rows consecutive tokens of one sequence whose first row sits at cache position start_pos of that sequence's own F16 caches (a
+ * segment of one row at start_pos > 0 is a decode row, a longer one at start_pos > 0 a prompt chunk).  The descriptor is a HOST struct, copied BY VALUE
+ * into the launches as ntk_kv_batch is -- no device table; entries past n_seg are ignored.
+ *   ntk_kv_segments_validate       host only: NTK_E_SHAPE unless 1 <= n_seg <= NTK_ATTN_BATCH_MAX, row0[0] == 0, row0[s + 1] == row0[s] + n_rows[s], every
+ *                                  n_rows >= 1, the rows sum to total_rows, start_pos >= 0, start_pos + n_rows <= max_seq and no two segments name the same
+ *                                  k cache; NTK_E_NULL for a NULL descriptor or a NULL cache among the first n_seg.  Both launchers call it first.
+ *   ntk_rope_kv_store_segments     ntk_rope_kv_store for every segment in ONE launch, one workgroup per row: row r of segment s is rotated at position
+ *                                  start_pos[s] + (r - row0[s]) -- q in place; k and v are only read -- and its rotated k and its v go as F16 (RNE) into row
+ *                                  `position` of caches s: the device function of ntk_rope_kv_store's kernel, so a segment's q and cache rows are that
+ *                                  launch's bits on the segment alone.  No other cache byte is written.  q [total_rows][n_heads * head_dim], k, v
+ *                                  [total_rows][n_kv_heads * head_dim] F32.  head_dim <= 256 and even (NTK_E_SHAPE).
+ *   ntk_attention_prefill_segments ntk_attention_prefill for every segment: row t of segment s attends over rows 0 .. start_pos[s] + t of caches s and nothing
+ *                                  else.  A segment's output has the bits of ntk_attention_prefill on that segment alone, because every segment runs the
+ *                                  code that call would run: at head_dim 128 with 16-byte aligned operands all segments of two rows or more share ONE launch
+ *                                  of the matrix-core kernel's body (a workgroup finds its segment and query tile with a uniform scan of the <= 16 per-segment
+ *                                  tile counts in its arguments) and all single-row segments ONE launch of the single-query kernel's body, which is what
+ *                                  ntk_attention_prefill runs for a one-row prompt (head_dim 64 / 128 / 256, aligned caches); longer segments at other
+ *                                  head sizes, and unaligned operands, take ntk_attention_prefill's own launch, once per segment.  Q, output [total_rows][n_heads * head_dim] F32; cache rows past a segment's last key may
+ *                                  hold anything.  F16 caches only. */
+typedef struct ntk_kv_segments {
+    int   n_seg;                          /* 1 .. NTK_ATTN_BATCH_MAX */
+    int   row0[NTK_ATTN_BATCH_MAX];       /* first row of the segment in q / k / v / output; ascending, contiguous from 0 */
+    int   n_rows[NTK_ATTN_BATCH_MAX];     /* >= 1 */
+    int   start_pos[NTK_ATTN_BATCH_MAX];  /* cache position of the segment's first row */
+    void* k[NTK_ATTN_BATCH_MAX];          /* this layer's F16 cache of the segment's slot, [max_seq][n_kv_heads][head_dim] */
+    void* v[NTK_ATTN_BATCH_MAX];
+} ntk_kv_segments;
+int ntk_kv_segments_validate(const ntk_kv_segments* segs, int total_rows, int max_seq);
+int ntk_rope_kv_store_segments(float* q, const float* k, const float* v, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim,
+                               float theta_base, float freq_scale, int interleaved, int max_seq, void* stream);
+int ntk_attention_prefill_segments(float* output, const float* Q, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim, int max_seq,
+                                   float scale, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The 8-bit (Q8_0) KV cache (csrc/attention_q8.hip; no reference counterpart).  A cache row holds Q8_0 values along head_dim: every 32
  * consecutive elements of a head's row share one IEEE-half scale d and carry 32 int8 q -- ggml's quantize_row_q8_0_ref arithmetic in F32

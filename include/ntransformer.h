@@ -105,7 +105,11 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * every token asked for.  The repeat-penalty window is over tokens and does not change.  A prompt longer than the context stays refused.
  * nt_engine_generate_batch / _ex keep dropping a sequence at the end of its context (a caller who drives nt_engine_decode_batch can shift a slot itself);
  * "context_keep" = N >= 0 (default "1"; otherwise NTK_E_SHAPE + last_error; any time, kept across loads): the leading positions a context shift never
- * discards -- the default keeps the BOS. */
+ * discards -- the default keeps the BOS;
+ * "batch_prefill" = "0" (default) | "1" (any other value: NTK_E_SHAPE + last_error; any time, read per call): with "1" nt_engine_generate_batch / _ex prefill
+ * all their prompts with ONE nt_engine_forward_batch pass (below) instead of one nt_engine_seq_forward per slot; everything behind the prefill -- the first
+ * token from each sequence's own row of logits, the lockstep steps -- is unchanged.  Ignored (slot by slot, as with "0") on a "kv_cache" = "q8_0" engine and
+ * when the prompts together hold more tokens than max_context. */
 int  nt_engine_set_option(nt_engine_t e, const char* key, const char* value);
 const char* nt_engine_last_error(nt_engine_t e);
 void nt_gen_params_default(nt_gen_params* p);
@@ -148,6 +152,27 @@ int  nt_engine_forward(nt_engine_t e, const int* tokens, int n, int start_pos, f
  * does not take (top_k <= 0, > 64 or >= vocab; repeat_window > 4096) is sampled by its host sampler from its own row of logits (vocab floats per step).
  * A sequence leaves at its own max_tokens, at EOS if its own stop_at_eos is set, or at the end of the context; out_stride must hold the largest
  * max_tokens.  Returns n or a negative NTK_E_*; stats as nt_engine_generate_batch. */
+/* ---- the packed prompt pass: the tokens of several sequences in ONE pass over the weights --------------------------------------------------------
+ * nt_engine_forward_batch: the rows of the pass are n SEGMENTS back to back; segment i = lens[i] consecutive tokens of the sequence in slot slots[i], the
+ * first at position start_pos[i] of that slot's cache; `tokens` holds sum(lens) ids, segment after segment.  Every segment's K / V rows are stored at
+ * [start_pos[i], start_pos[i] + lens[i]) of its slot and its rows attend causally over rows 0 .. their own position of that slot alone.  So one call
+ * prefills several prompts (start 0), continues a chunked prefill (start > 0), steps decoding sequences (one token at their position) or mixes the three.
+ * logits_out [n][vocab]: the logits behind each segment's LAST token; next_out [n]: their first maxima; each may be NULL.  Eager, one synchronisation;
+ * leaves the fused path's slot-0 state alone.
+ * ARITHMETIC CONTRACT: (1) a segment's logits agree with nt_engine_seq_forward of the same tokens to the project's 1e-3 bar, not bit for bit (the LM head runs
+ * in nt_engine_decode_batch's form, and the GEMM form follows the pass's TOTAL row count); (2) a call with ONE segment of two tokens or more leaves exactly
+ * the cache rows nt_engine_seq_forward(slot, tokens, start_pos) leaves, in every layer; (3) within one total row count a segment's logits and cache rows
+ * depend on nothing but that segment -- not on its companions, their order, its row offset in the pass or the slot numbers; (4) no bit claim across total
+ * row counts; (5) no performance claim for one-token segments at long contexts: nt_engine_decode_batch stays the step for pure decoding; (6) caches of
+ * slots not named, and rows of a named slot outside its segment, are not written.
+ * Refused (NTK_E_SHAPE + last_error, nothing launched, the engine stays usable): n outside 1 .. "sequences", a slot out of range or named twice, a length
+ * below 1, a negative start, start + length beyond max_context, more than max_context tokens in all, a token id out of range, "kv_cache" = "q8_0" (with or
+ * without "batch_kv_q8": the prompt path's single one-layer F16 image cannot hold several slots at once), a tensor-parallel engine.
+ * nt_forward_batch_validate: TEST SUPPORT, host only (no engine, no device): those argument checks (token ids aside) for an engine of `sequences` slots and
+ * `max_seq` positions -- NTK_OK, NTK_E_NULL or NTK_E_SHAPE. */
+int  nt_engine_forward_batch(nt_engine_t e, const int* slots, const int* tokens, const int* lens, const int* start_pos, int n, float* logits_out,
+                             int* next_out);
+int  nt_forward_batch_validate(const int* slots, const int* lens, const int* start_pos, int n, int sequences, int max_seq);
 int  nt_engine_seq_forward(nt_engine_t e, int slot, const int* tokens, int n, int start_pos, float* logits_out);
 int  nt_engine_decode_batch(nt_engine_t e, const int* slots, const int* tokens, const int* positions, int n, float* logits_out, int* next_out);
 int  nt_engine_generate_batch(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* p, int* out, int out_stride,

@@ -30,6 +30,11 @@ class KvBatch(C.Structure):   # ntk_kv_batch: the rows' cache base pointers of o
     _fields_ = [("k", C.c_void_p * 16), ("v", C.c_void_p * 16)]
 
 
+class KvSegments(C.Structure):   # ntk_kv_segments: the segments of a packed prompt pass and their caches of one layer
+    _fields_ = [("n_seg", C.c_int), ("row0", C.c_int * 16), ("n_rows", C.c_int * 16), ("start_pos", C.c_int * 16), ("k", C.c_void_p * 16),
+                ("v", C.c_void_p * 16)]
+
+
 class SampleRows(C.Structure):   # ntk_sample_rows: the per-row settings of ntk_sample_rows_top_k
     _fields_ = [("temperature", C.c_float * 16), ("top_p", C.c_float * 16), ("repeat_penalty", C.c_float * 16), ("r", C.c_float * 16),
                 ("top_k", C.c_int * 16), ("n_recent", C.c_int * 16)]
@@ -126,6 +131,9 @@ def lib() -> C.CDLL:
         "ntk_attention_decode_split_merged": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_attention_decode_fused": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, vp]),
         "ntk_attention_decode_batch": (i, [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, i, f, f, f, i, vp, vp]),
+        "ntk_kv_segments_validate": (i, [vp, i, i]),
+        "ntk_rope_kv_store_segments": (i, [vp, vp, vp, vp, i, i, i, f, f, i, i, vp]),
+        "ntk_attention_prefill_segments": (i, [vp, vp, vp, i, i, i, i, f, vp]),
         "ntk_kv_q8_cache_bytes": (C.c_size_t, [i, i, i]),
         "ntk_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, i, vp]),
         "ntk_rope_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp]),

@@ -20,23 +20,46 @@
 
 namespace ntk {
 
+// one query of one head over keys 0 .. n_keys - 1 of a cache: out / q point at the (query, head) row; the body of the two kernels below
+template <int LPR>
+__device__ __forceinline__ void attention_one_query(float* __restrict__ out, const float* __restrict__ q, const uint16_t* __restrict__ kc,
+                                                    const uint16_t* __restrict__ vc, const int n_keys, const int head, const int n_heads,
+                                                    const int n_kv_heads, const int hd, const float scale) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* qs = lds;                        // [hd]
+    float* red = qs + hd;                   // [16]
+    float* part = red + 16;                 // [nwaves][hd]
+    float* sc = part + (blockDim.x >> 6) * hd;
+    for (int d = threadIdx.x; d < hd; d += blockDim.x) qs[d] = q[d];
+    __syncthreads();
+    attend<LPR>(out, qs, kc, vc, n_keys, nullptr, nullptr, head / (n_heads / n_kv_heads), n_kv_heads, hd, scale, sc, part, red);
+}
+
 template <int LPR>
 __global__ __launch_bounds__(256) void attention_kernel(float* __restrict__ output, const float* __restrict__ Q,
                                                         const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
                                                         int n_keys_base, int causal, int n_heads, int n_kv_heads, int hd,
                                                         float scale) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
     const int head = blockIdx.x, qi = blockIdx.y;
     const int n_keys = causal ? n_keys_base + qi + 1 : n_keys_base;   // prefill: keys 0..start_pos+qi
-    float* qs = lds;                        // [hd]
-    float* red = qs + hd;                   // [16]
-    float* part = red + 16;                 // [nwaves][hd]
-    float* sc = part + (blockDim.x >> 6) * hd;
     const size_t qoff = ((size_t)qi * n_heads + head) * hd;
-    for (int d = threadIdx.x; d < hd; d += blockDim.x) qs[d] = Q[qoff + d];
-    __syncthreads();
-    attend<LPR>(output + qoff, qs, kc, vc, n_keys, nullptr, nullptr, head / (n_heads / n_kv_heads), n_kv_heads, hd,
-                scale, sc, part, red);
+    attention_one_query<LPR>(output + qoff, Q + qoff, kc, vc, n_keys, head, n_heads, n_kv_heads, hd, scale);
+}
+
+// The SINGLE-ROW segments of a packed prompt pass (ntk_attention_prefill_segments), one launch: workgroup (head, j) is the one query of the j-th of them --
+// row row0[j] of Q / output, keys 0 .. start_pos[j] of its own cache -- i.e. attention_kernel's workgroup for a one-row prompt at start_pos[j], the same
+// bits.  The table travels in the kernel arguments.
+struct SingleRows {
+    const uint16_t* k[NTK_ATTN_BATCH_MAX];
+    const uint16_t* v[NTK_ATTN_BATCH_MAX];
+    int row0[NTK_ATTN_BATCH_MAX], start_pos[NTK_ATTN_BATCH_MAX];
+};
+template <int LPR>
+__global__ __launch_bounds__(256) void attention_single_rows_kernel(float* __restrict__ output, const float* __restrict__ Q, const SingleRows rows,
+                                                                    int n_heads, int n_kv_heads, int hd, float scale) {
+    const int head = blockIdx.x, j = blockIdx.y;
+    const size_t qoff = ((size_t)rows.row0[j] * n_heads + head) * hd;
+    attention_one_query<LPR>(output + qoff, Q + qoff, rows.k[j], rows.v[j], rows.start_pos[j] + 1, head, n_heads, n_kv_heads, hd, scale);
 }
 
 template <int LPR>
@@ -244,13 +267,13 @@ __global__ __launch_bounds__(256) void rope_rows_kernel(float* __restrict__ q, f
 
 // ... and the same launch also stores the token's K (rotated) and V rows into the half-precision caches (kv_store_kernel's conversions of the same
 // values: identical cache rows); q is rotated in place, k and v are only read.  One launch instead of two per prompt layer.
-__global__ __launch_bounds__(256) void rope_kv_store_rows_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                                 const int* __restrict__ positions, int n_heads, int n_kv_heads, int head_dim, float theta,
-                                                                 float fscale, int interleaved, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
-                                                                 int start_pos, int max_seq) {
+// (the work of one workgroup = one token: q / k / v are the token's rows, pos its rotation position, cp its cache row -- shared by the segmented launch below)
+__device__ __forceinline__ void rope_kv_store_row(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const int pos,
+                                                  const int n_heads, const int n_kv_heads, const int head_dim, const float theta, const float fscale,
+                                                  const int interleaved, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc, const int cp,
+                                                  const int max_seq) {
     __shared__ float cs[2][128];
-    const int sp = blockIdx.x, half_dim = head_dim / 2;
-    const int pos = positions[sp];
+    const int half_dim = head_dim / 2;
     for (int i = threadIdx.x; i < half_dim; i += blockDim.x) {
         const float freq = 1.0f / (float)pow((double)theta, (double)((2.0f * i) / head_dim));
         const float angle = pos * freq * fscale;
@@ -258,7 +281,7 @@ __global__ __launch_bounds__(256) void rope_kv_store_rows_kernel(float* __restri
         cs[1][i] = sinf(angle);
     }
     __syncthreads();
-    const int cp = start_pos + sp, per_pos = n_kv_heads * head_dim;
+    const int per_pos = n_kv_heads * head_dim;
     const bool store = cp < max_seq;   // reference attention.cu:336
     const int total = (n_heads + n_kv_heads) * half_dim;
     for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
@@ -266,12 +289,12 @@ __global__ __launch_bounds__(256) void rope_kv_store_rows_kernel(float* __restri
         const int i0 = interleaved ? 2 * pair : pair, i1 = interleaved ? 2 * pair + 1 : pair + half_dim;
         const float c = cs[0][pair], sn = cs[1][pair];
         if (head < n_heads) {
-            float* data = q + ((size_t)sp * n_heads + head) * head_dim;
+            float* data = q + (size_t)head * head_dim;
             const float a = data[i0], b = data[i1];
             rope_rotate(a, b, c, sn, data[i0], data[i1]);
         } else {
             const int kh = head - n_heads;
-            const float* data = k + ((size_t)sp * n_kv_heads + kh) * head_dim;
+            const float* data = k + (size_t)kh * head_dim;
             float ra, rb;
             rope_rotate(data[i0], data[i1], c, sn, ra, rb);
             if (store) {
@@ -282,7 +305,35 @@ __global__ __launch_bounds__(256) void rope_kv_store_rows_kernel(float* __restri
         }
     }
     if (store)
-        for (int e = threadIdx.x; e < per_pos; e += blockDim.x) vc[(size_t)cp * per_pos + e] = f2h(v[(size_t)sp * per_pos + e]);
+        for (int e = threadIdx.x; e < per_pos; e += blockDim.x) vc[(size_t)cp * per_pos + e] = f2h(v[e]);
+}
+
+__global__ __launch_bounds__(256) void rope_kv_store_rows_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                                 const int* __restrict__ positions, int n_heads, int n_kv_heads, int head_dim, float theta,
+                                                                 float fscale, int interleaved, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
+                                                                 int start_pos, int max_seq) {
+    const int sp = blockIdx.x;
+    rope_kv_store_row(q + (size_t)sp * n_heads * head_dim, k + (size_t)sp * n_kv_heads * head_dim, v + (size_t)sp * n_kv_heads * head_dim, positions[sp],
+                      n_heads, n_kv_heads, head_dim, theta, fscale, interleaved, kc, vc, start_pos + sp, max_seq);
+}
+
+// ... for the rows of a PACKED pass (ntk_rope_kv_store_segments): row blockIdx.x belongs to the segment a uniform scan of the <= 16 row0 values finds; its
+// position -- for the rotation and for the store -- is start_pos[s] + (row - row0[s]); its caches are segment s's.  The descriptor travels in the arguments.
+struct RopeSegments {
+    uint16_t* k[NTK_ATTN_BATCH_MAX];
+    uint16_t* v[NTK_ATTN_BATCH_MAX];
+    int row0[NTK_ATTN_BATCH_MAX], start_pos[NTK_ATTN_BATCH_MAX];
+    int n_seg;
+};
+__global__ __launch_bounds__(256) void rope_kv_store_segments_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                                     const RopeSegments segs, int n_heads, int n_kv_heads, int head_dim, float theta,
+                                                                     float fscale, int interleaved, int max_seq) {
+    const int row = blockIdx.x;
+    int s = 0;
+    while (s + 1 < segs.n_seg && row >= segs.row0[s + 1]) ++s;   // (uniform)
+    const int pos = segs.start_pos[s] + (row - segs.row0[s]);
+    rope_kv_store_row(q + (size_t)row * n_heads * head_dim, k + (size_t)row * n_kv_heads * head_dim, v + (size_t)row * n_kv_heads * head_dim, pos, n_heads,
+                      n_kv_heads, head_dim, theta, fscale, interleaved, segs.k[s], segs.v[s], pos, max_seq);
 }
 
 __global__ void kv_store_kernel(uint16_t* __restrict__ kc, uint16_t* __restrict__ vc, const float* __restrict__ k,
@@ -305,6 +356,12 @@ int launch_attention_decode_kvhead_mfma(float* part, const float* q, const float
                                         float fscale, int nsplit, float* merged_output, unsigned* counters, hipStream_t st);   // attention_mfma.hip
 int launch_attention_prefill_mfma(float* out, const float* Q, const uint16_t* kc, const uint16_t* vc, int T, int start_pos, int nh, int nkv,
                                   int hd, float scale, hipStream_t st);   // attention_mfma.hip
+int launch_attention_prefill_mfma_segments(float* out, const float* Q, const ntk_kv_segments& segs, const bool* mfma, int nh, int nkv, float scale,
+                                           hipStream_t st);   // attention_mfma.hip
+
+// (tuning builds only: the older prompt kernels)
+static bool prefill_tiled_off() { static const bool off = NTK_TUNE_ENV_INT("NTK_PREFILL_ATTENTION_1TO1", 0) != 0; return off; }
+static bool prefill_mfma_off() { static const bool off = NTK_TUNE_ENV_INT("NTK_PREFILL_ATTENTION_NO_MFMA", 0) != 0; return off; }
 
 static int launch_attention(float* out, const float* Q, const void* kc, const void* vc, int T, int n_keys_base, int causal,
                             int nh, int nkv, int hd, float scale, hipStream_t st) {
@@ -314,8 +371,7 @@ static int launch_attention(float* out, const float* Q, const void* kc, const vo
     const bool aligned = (reinterpret_cast<uintptr_t>(kc) & 15) == 0 && (reinterpret_cast<uintptr_t>(vc) & 15) == 0;
     const uint16_t* k16 = static_cast<const uint16_t*>(kc);
     const uint16_t* v16 = static_cast<const uint16_t*>(vc);
-    static const bool tiled_off = NTK_TUNE_ENV_INT("NTK_PREFILL_ATTENTION_1TO1", 0) != 0;      // (tuning builds only: the older prompt kernels)
-    static const bool mfma_off = NTK_TUNE_ENV_INT("NTK_PREFILL_ATTENTION_NO_MFMA", 0) != 0;
+    const bool tiled_off = prefill_tiled_off(), mfma_off = prefill_mfma_off();
     if (causal && T > 1 && aligned && hd == 128 && !tiled_off && !mfma_off) {   // prompt, head_dim 128: F16 matrix cores (attention_mfma.hip)
         const int rc = launch_attention_prefill_mfma(out, Q, k16, v16, T, n_keys_base, nh, nkv, hd, scale, st);
         if (rc != NTK_E_SHAPE && rc != NTK_E_ALIGN) return rc;
@@ -412,6 +468,112 @@ int ntk_attention_prefill(float* output, const float* Q, const void* k_cache, co
     if (seq_len < 0 || start_pos < 0) return NTK_E_SHAPE;
     return ntk::launch_attention(output, Q, k_cache, v_cache, seq_len, start_pos, 1, n_heads, n_kv_heads, head_dim, scale,
                                  ntk::resolve_stream(stream));
+}
+
+// the descriptor of a packed pass (ntk_engine.h); total_rows < 0: whatever its segments sum to
+static int kv_segments_check(const ntk_kv_segments* segs, int total_rows, int max_seq) {
+    if (!segs) return NTK_E_NULL;
+    if (segs->n_seg < 1 || segs->n_seg > NTK_ATTN_BATCH_MAX || max_seq <= 0) return NTK_E_SHAPE;
+    long long rows = 0;
+    for (int s = 0; s < segs->n_seg; ++s) {
+        if (segs->row0[s] != rows || segs->n_rows[s] < 1 || segs->start_pos[s] < 0) return NTK_E_SHAPE;
+        if ((long long)segs->start_pos[s] + segs->n_rows[s] > max_seq) return NTK_E_SHAPE;
+        rows += segs->n_rows[s];
+    }
+    if (rows > 0x7FFFFFFF || (total_rows >= 0 && rows != total_rows)) return NTK_E_SHAPE;
+    for (int s = 0; s < segs->n_seg; ++s) {
+        if (!segs->k[s] || !segs->v[s]) return NTK_E_NULL;
+        for (int t = 0; t < s; ++t)
+            if (segs->k[t] == segs->k[s]) return NTK_E_SHAPE;   // two segments of one pass would write (and attend over) the same cache
+    }
+    return NTK_OK;
+}
+
+int ntk_kv_segments_validate(const ntk_kv_segments* segs, int total_rows, int max_seq) {
+    if (total_rows < 0) return segs ? NTK_E_SHAPE : NTK_E_NULL;
+    return kv_segments_check(segs, total_rows, max_seq);
+}
+
+int ntk_rope_kv_store_segments(float* q, const float* k, const float* v, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim,
+                               float theta_base, float freq_scale, int interleaved, int max_seq, void* stream) {
+    if (!q || !k || !v || !segs) return NTK_E_NULL;
+    if (n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || (head_dim & 1) || head_dim > 256) return NTK_E_SHAPE;
+    const int rc = kv_segments_check(segs, -1, max_seq);
+    if (rc != NTK_OK) return rc;
+    ntk::RopeSegments d{};
+    for (int s = 0; s < NTK_ATTN_BATCH_MAX; ++s) {   // (entries past n_seg: never indexed, the scan stops at n_seg - 1)
+        const int u = s < segs->n_seg ? s : 0;
+        d.k[s] = static_cast<uint16_t*>(segs->k[u]); d.v[s] = static_cast<uint16_t*>(segs->v[u]);
+        d.row0[s] = segs->row0[u]; d.start_pos[s] = segs->start_pos[u];
+    }
+    d.n_seg = segs->n_seg;
+    const int rows = segs->row0[segs->n_seg - 1] + segs->n_rows[segs->n_seg - 1];
+    hipLaunchKernelGGL(ntk::rope_kv_store_segments_kernel, dim3(rows), dim3(256), 0, ntk::resolve_stream(stream), q, k, v, d, n_heads, n_kv_heads, head_dim,
+                       theta_base, freq_scale, interleaved, max_seq);
+    return ntk::last_launch_status();
+}
+
+int ntk_attention_prefill_segments(float* output, const float* Q, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim, int max_seq,
+                                   float scale, void* stream) {
+    if (!output || !Q || !segs) return NTK_E_NULL;
+    if (n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || n_heads % n_kv_heads != 0) return NTK_E_SHAPE;
+    int rc = kv_segments_check(segs, -1, max_seq);
+    if (rc != NTK_OK) return rc;
+    hipStream_t st = ntk::resolve_stream(stream);
+    // which segments ntk_attention_prefill would hand to the matrix-core kernel (launch_attention's rule + launch_attention_prefill_mfma's alignment
+    // check; a segment's rows of Q / output start a multiple of 512 bytes behind the arrays' first): those share ONE launch of that kernel's body
+    const bool io_aligned = (reinterpret_cast<uintptr_t>(Q) & 15) == 0 && (reinterpret_cast<uintptr_t>(output) & 15) == 0;
+    bool mfma[NTK_ATTN_BATCH_MAX] = {};
+    bool any = false;
+    for (int s = 0; s < segs->n_seg; ++s) {
+        const bool aligned = (reinterpret_cast<uintptr_t>(segs->k[s]) & 15) == 0 && (reinterpret_cast<uintptr_t>(segs->v[s]) & 15) == 0;
+        mfma[s] = segs->n_rows[s] > 1 && aligned && io_aligned && head_dim == 128 && !ntk::prefill_tiled_off() && !ntk::prefill_mfma_off();
+        any = any || mfma[s];
+    }
+    if (any) {
+        rc = ntk::launch_attention_prefill_mfma_segments(output, Q, *segs, mfma, n_heads, n_kv_heads, scale, st);
+        if (rc != NTK_OK) return rc;
+    }
+    // the single-row segments with 16-byte aligned caches at head_dim 64 / 128 / 256: ONE launch of the single-query kernel's body, which is what
+    // ntk_attention_prefill runs for a one-row prompt
+    ntk::SingleRows one{};
+    int n_one = 0, max_keys = 0;
+    bool single[NTK_ATTN_BATCH_MAX] = {};
+    for (int s = 0; s < segs->n_seg && (head_dim == 64 || head_dim == 128 || head_dim == 256); ++s) {
+        const bool aligned = (reinterpret_cast<uintptr_t>(segs->k[s]) & 15) == 0 && (reinterpret_cast<uintptr_t>(segs->v[s]) & 15) == 0;
+        if (segs->n_rows[s] != 1 || !aligned) continue;
+        single[s] = true;
+        one.k[n_one] = static_cast<const uint16_t*>(segs->k[s]); one.v[n_one] = static_cast<const uint16_t*>(segs->v[s]);
+        one.row0[n_one] = segs->row0[s]; one.start_pos[n_one] = segs->start_pos[s];
+        max_keys = segs->start_pos[s] + 1 > max_keys ? segs->start_pos[s] + 1 : max_keys;
+        ++n_one;
+    }
+    if (n_one > 0) {
+        const size_t lds = ntk::attn_lds(head_dim, max_keys, 1);   // (the score row of the longest prefix: a larger allocation changes no result)
+        if (lds > 160 * 1024) return NTK_E_SHAPE;
+#define NTK_ATT1(LPR_)                                                                                                          \
+    do {                                                                                                                        \
+        if (lds > 64 * 1024)                                                                                                    \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ntk::attention_single_rows_kernel<LPR_>),                   \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
+        hipLaunchKernelGGL(ntk::attention_single_rows_kernel<LPR_>, dim3(n_heads, n_one), dim3(256), lds, st, output, Q, one, n_heads, n_kv_heads, \
+                           head_dim, scale);                                                                                    \
+    } while (0)
+        if (head_dim == 128) NTK_ATT1(16);
+        else if (head_dim == 64) NTK_ATT1(8);
+        else NTK_ATT1(32);
+#undef NTK_ATT1
+        rc = ntk::last_launch_status();
+        if (rc != NTK_OK) return rc;
+    }
+    // every other segment: ntk_attention_prefill's own launch on the segment alone (head_dim 64 / 256: the tiled kernel; unaligned caches, other head sizes)
+    for (int s = 0; s < segs->n_seg; ++s) {
+        if (mfma[s] || single[s]) continue;
+        const size_t row = (size_t)segs->row0[s] * n_heads * head_dim;
+        rc = ntk::launch_attention(output + row, Q + row, segs->k[s], segs->v[s], segs->n_rows[s], segs->start_pos[s], 1, n_heads, n_kv_heads, head_dim, scale, st);
+        if (rc != NTK_OK) return rc;
+    }
+    return NTK_OK;
 }
 
 int ntk_attention_decode_fused(float* output, const float* q, const float* k, const float* v, void* k_cache, void* v_cache,

@@ -37,13 +37,13 @@ constexpr int AM_KT = 64;     // cache rows per tile
 constexpr int AM_KSTR = AM_HD + 8;   // halves per K row in LDS (272 B)
 constexpr int AM_VSTR = AM_KT + 4;   // halves per V^T row in LDS (136 B)
 
-__global__ __launch_bounds__(256, 2) void attention_prefill_mfma_kernel(float* __restrict__ output, const float* __restrict__ Q,
-                                                                        const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
-                                                                        int T, int start_pos, int n_heads, int n_kv_heads, float scale) {
+// One workgroup's work: queries q0 .. q0 + 63 of `head` of a sequence of T rows at start_pos (Q / output: the sequence's first row; kc / vc: its caches).
+// The body of both launches below: the single-sequence kernel and the segmented one differ in how a workgroup finds these arguments, nothing else.
+__device__ __forceinline__ void attention_prefill_mfma_tile(float* __restrict__ output, const float* __restrict__ Q, const uint16_t* __restrict__ kc,
+                                                            const uint16_t* __restrict__ vc, const int T, const int start_pos, const int q0,
+                                                            const int head, const int n_heads, const int n_kv_heads, const float scale) {
     __shared__ __attribute__((aligned(16))) uint16_t kt[AM_KT * AM_KSTR];    // 17 KB
     __shared__ __attribute__((aligned(16))) uint16_t vt[AM_HD * AM_VSTR];    // 17 KB, transposed
-    const int head = blockIdx.x;
-    const int q0 = ((int)gridDim.y - 1 - (int)blockIdx.y) * AM_QT;           // longest prefixes first
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
@@ -209,6 +209,34 @@ __global__ __launch_bounds__(256, 2) void attention_prefill_mfma_kernel(float* _
     }
 }
 
+__global__ __launch_bounds__(256, 2) void attention_prefill_mfma_kernel(float* __restrict__ output, const float* __restrict__ Q,
+                                                                        const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
+                                                                        int T, int start_pos, int n_heads, int n_kv_heads, float scale) {
+    const int q0 = ((int)gridDim.y - 1 - (int)blockIdx.y) * AM_QT;           // longest prefixes first
+    attention_prefill_mfma_tile(output, Q, kc, vc, T, start_pos, q0, (int)blockIdx.x, n_heads, n_kv_heads, scale);
+}
+
+// The same for the SEGMENTS of a packed prompt pass (ntk_attention_prefill_segments): blockIdx.y is a query tile of the whole pass; the workgroup finds
+// its segment with a uniform scan of the segments' tile counts (at most 16, from the kernel arguments: no device table, and no per-tile table -- a long
+// context has thousands of tiles) and runs the tile of that segment alone: its rows of Q / output, its caches, its start_pos.  Segments with ntile 0
+// (the launcher gives single-row segments to the single-query kernel, as ntk_attention_prefill does) are passed over.
+struct PrefillSegments {
+    const uint16_t* k[NTK_ATTN_BATCH_MAX];
+    const uint16_t* v[NTK_ATTN_BATCH_MAX];
+    int row0[NTK_ATTN_BATCH_MAX], n_rows[NTK_ATTN_BATCH_MAX], start_pos[NTK_ATTN_BATCH_MAX], ntile[NTK_ATTN_BATCH_MAX];
+    int n_seg;
+};
+
+__global__ __launch_bounds__(256, 2) void attention_prefill_mfma_segments_kernel(float* __restrict__ output, const float* __restrict__ Q,
+                                                                                 const PrefillSegments segs, int n_heads, int n_kv_heads, float scale) {
+    int tile = (int)blockIdx.y, s = 0;
+    while (s < segs.n_seg - 1 && tile >= segs.ntile[s]) tile -= segs.ntile[s++];   // (uniform: scalar loads of the arguments; the grid has sum(ntile) rows)
+    const int q0 = (segs.ntile[s] - 1 - tile) * AM_QT;                              // longest prefixes first within the segment
+    const size_t row = (size_t)segs.row0[s] * n_heads * AM_HD;
+    attention_prefill_mfma_tile(output + row, Q + row, segs.k[s], segs.v[s], segs.n_rows[s], segs.start_pos[s], q0, (int)blockIdx.x, n_heads, n_kv_heads,
+                                scale);
+}
+
 // head_dim 128, 16-byte aligned caches and Q / output; T >= 1.  Returns NTK_E_SHAPE for anything else (caller: the tiled kernel).
 int launch_attention_prefill_mfma(float* out, const float* Q, const uint16_t* kc, const uint16_t* vc, int T, int start_pos, int nh, int nkv,
                                   int hd, float scale, hipStream_t st) {
@@ -218,6 +246,26 @@ int launch_attention_prefill_mfma(float* out, const float* Q, const uint16_t* kc
         return NTK_E_ALIGN;
     const dim3 grid(nh, (T + AM_QT - 1) / AM_QT);
     hipLaunchKernelGGL(attention_prefill_mfma_kernel, grid, dim3(256), 0, st, out, Q, kc, vc, T, start_pos, nh, nkv, scale);
+    return last_launch_status();
+}
+
+// the segments with two rows or more of a packed pass, one launch (the caller has validated the descriptor; mfma[s]: segment s takes part)
+int launch_attention_prefill_mfma_segments(float* out, const float* Q, const ntk_kv_segments& segs, const bool* mfma, int nh, int nkv, float scale,
+                                           hipStream_t st) {
+    PrefillSegments p{};
+    int tiles = 0;
+    for (int s = 0; s < segs.n_seg; ++s) {
+        p.k[s] = static_cast<const uint16_t*>(segs.k[s]); p.v[s] = static_cast<const uint16_t*>(segs.v[s]);
+        p.row0[s] = segs.row0[s]; p.n_rows[s] = segs.n_rows[s]; p.start_pos[s] = segs.start_pos[s];
+        p.ntile[s] = mfma[s] ? (segs.n_rows[s] + AM_QT - 1) / AM_QT : 0;
+        tiles += p.ntile[s];
+    }
+    // the scan stops at the LAST segment with tiles, so that a trailing segment without any is never chosen
+    p.n_seg = segs.n_seg;
+    while (p.n_seg > 1 && p.ntile[p.n_seg - 1] == 0) --p.n_seg;
+    if (tiles == 0) return NTK_OK;
+    if (tiles > 65535) return NTK_E_SHAPE;
+    hipLaunchKernelGGL(attention_prefill_mfma_segments_kernel, dim3(nh, tiles), dim3(256), 0, st, out, Q, p, nh, nkv, scale);
     return last_launch_status();
 }
 

@@ -77,6 +77,11 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
         return rc;
     }
+    else if (k == "batch_prefill") {   // "0" (default) | "1": nt_engine_generate_batch / _ex prefill all prompts in one packed pass; any time, read per call
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("batch_prefill must be 0 or 1"); return NTK_E_SHAPE; }
+        E(e)->options().batch_prefill = on;
+    }
     else if (k == "context_shift") {   // "0" (default) | "1": the generate loop shifts slot 0 at the end of the context instead of stopping; any time
         const std::string v = value;
         if (v != "0" && v != "1") { E(e)->set_error("context_shift must be 0 or 1"); return NTK_E_SHAPE; }
@@ -180,6 +185,21 @@ int nt_engine_decode_batch(nt_engine_t e, const int* slots, const int* tokens, c
         if (rc != NTK_OK) E(e)->set_error(E(e)->model().error());
         return rc;
     } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_engine_forward_batch(nt_engine_t e, const int* slots, const int* tokens, const int* lens, const int* start_pos, int n, float* logits_out,
+                            int* next_out) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    try {
+        E(e)->model().set_batched_prefill(E(e)->options().batched_prefill);
+        const int rc = E(e)->model().forward_batch(slots, tokens, lens, start_pos, n, logits_out, next_out);
+        if (rc != NTK_OK) E(e)->set_error(E(e)->model().error());
+        return rc;
+    } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_forward_batch_validate(const int* slots, const int* lens, const int* start_pos, int n, int sequences, int max_seq) {
+    return nt::Model::validate_forward_batch(slots, lens, start_pos, n, sequences, max_seq, nullptr);   // host only
 }
 
 int nt_engine_generate_batch(nt_engine_t e, const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params* p, int* out, int out_stride,

@@ -41,6 +41,26 @@ int Engine::load_shared(Engine& src, int max_context) {
     return NTK_OK;
 }
 
+int Engine::prefill_slots(const int* const* prompts, const int* prompt_lens, int n, std::vector<float>& logits) {
+    const size_t V = (size_t)model_.config().vocab_size;
+    logits.resize((size_t)n * V);
+    long long total = 0;
+    for (int i = 0; i < n; ++i) total += prompt_lens[i];
+    if (opt_.batch_prefill && !model_.kv_q8() && total <= model_.config().max_seq_len) {
+        std::vector<int> flat, slots(n), starts(n, 0);
+        flat.reserve((size_t)total);
+        for (int i = 0; i < n; ++i) { slots[i] = i; flat.insert(flat.end(), prompts[i], prompts[i] + prompt_lens[i]); }
+        const int rc = model_.forward_batch(slots.data(), flat.data(), prompt_lens, starts.data(), n, logits.data(), nullptr);
+        if (rc != NTK_OK) err_ = model_.error();
+        return rc;
+    }
+    for (int i = 0; i < n; ++i) {   // slot by slot
+        if (!model_.forward(prompts[i], prompt_lens[i], 0, i)) { err_ = model_.error(); return NTK_E_LAUNCH; }
+        if (model_.copy_logits(logits.data() + (size_t)i * V) != NTK_OK) return NTK_E_LAUNCH;
+    }
+    return NTK_OK;
+}
+
 int Engine::generate_batch(const int* const* prompts, const int* prompt_lens, int n, const nt_gen_params& p, int* out, int out_stride, int* out_counts) {
     stats_ = Stats();
     if (!loaded_) { err_ = "model not loaded"; return NTK_E_NULL; }
@@ -55,15 +75,15 @@ int Engine::generate_batch(const int* const* prompts, const int* prompt_lens, in
         if (!prompts[i]) { err_ = "generate_batch: null prompt"; return NTK_E_NULL; }
         if (prompt_lens[i] < 1 || prompt_lens[i] > max_pos) { err_ = "generate_batch: a prompt is empty or exceeds the context"; return NTK_E_SHAPE; }
     }
-    // prefill, slot by slot; the first token of each sequence is the first maximum of its prompt's logits (Sampler::argmax)
-    std::vector<float> host(V);
+    // prefill, slot by slot ("batch_prefill": in one packed pass); the first token of each sequence is the first maximum of its prompt's logits (Sampler::argmax)
+    std::vector<float> prefill_logits;
     std::vector<int> last(n), pos(n);
     std::vector<char> live(n, 1);
     model_.set_batched_prefill(opt_.batched_prefill);
     auto t0 = Clock::now();
+    { const int rc = prefill_slots(prompts, prompt_lens, n, prefill_logits); if (rc != NTK_OK) return rc; }
     for (int i = 0; i < n; ++i) {
-        if (!model_.forward(prompts[i], prompt_lens[i], 0, i)) { err_ = model_.error(); return NTK_E_LAUNCH; }
-        if (model_.copy_logits(host.data()) != NTK_OK) return NTK_E_LAUNCH;
+        const float* host = prefill_logits.data() + (size_t)i * V;
         int best = 0;
         for (int j = 1; j < V; ++j) if (host[j] > host[best]) best = j;
         out[(size_t)i * out_stride] = last[i] = best;
@@ -127,23 +147,23 @@ int Engine::generate_batch_ex(const int* const* prompts, const int* prompt_lens,
         if (!prompts[i]) { err_ = "generate_batch_ex: null prompt"; return NTK_E_NULL; }
         if (prompt_lens[i] < 1 || prompt_lens[i] > max_pos) { err_ = "generate_batch_ex: a prompt is empty or exceeds the context"; return NTK_E_SHAPE; }
     }
-    // prefill, slot by slot; the first token of each sequence is sampled on the host from its prompt's logits, as Engine::run does
-    std::vector<float> host(V), host_rows;
+    // prefill, slot by slot ("batch_prefill": in one packed pass); the first token of each sequence is sampled on the host from its prompt's logits, as Engine::run does
+    std::vector<float> prefill_logits, host_rows;
     std::vector<Sampler> sampler(n);
     std::vector<std::vector<int>> seq(n);   // prompt + generated ids: the repeat-penalty windows are cut from these
     std::vector<int> pos(n);
     std::vector<char> live(n, 1), on_host(n, 0);
     model_.set_batched_prefill(opt_.batched_prefill);
     auto t0 = Clock::now();
+    { const int rc = prefill_slots(prompts, prompt_lens, n, prefill_logits); if (rc != NTK_OK) return rc; }
     for (int i = 0; i < n; ++i) {
+        float* const host = prefill_logits.data() + (size_t)i * V;
         sampler[i].init(sampler_config(params[i]));
         // what the device sampler does not take stays with this sequence's host Sampler (its row's logits alone are downloaded)
         on_host[i] = !Model::device_sampler_supports(params[i].temperature, params[i].top_k, V) || params[i].repeat_window > Model::kMaxRecent;
         seq[i].assign(prompts[i], prompts[i] + prompt_lens[i]);
-        if (!model_.forward(prompts[i], prompt_lens[i], 0, i)) { err_ = model_.error(); return NTK_E_LAUNCH; }
-        if (model_.copy_logits(host.data()) != NTK_OK) return NTK_E_LAUNCH;
-        sampler[i].apply_repeat_penalty(host.data(), V, seq[i]);
-        const int first = sampler[i].sample(host.data(), V);
+        sampler[i].apply_repeat_penalty(host, V, seq[i]);
+        const int first = sampler[i].sample(host, V);
         seq[i].push_back(first);
         out[(size_t)i * out_stride] = first;
         out_counts[i] = 1;

@@ -52,6 +52,7 @@ struct EngineOptions {
     int synth_threads = 0;        // 0 = hardware concurrency
     bool context_shift = false;   // the generate loop at the end of the context: drop half of what lies behind context_keep and go on (false: stop)
     int context_keep = 1;         // leading positions a context shift never drops (the default keeps the BOS)
+    bool batch_prefill = false;   // generate_batch(_ex): all prompts in ONE packed pass (Model::forward_batch) instead of one forward() per slot; read per call
 };
 
 class Engine {
@@ -90,6 +91,10 @@ public:
 
 private:
     int run(std::vector<int>& tokens, const GenerateConfig& cfg, std::string* text, TokenCallback cb, bool print, bool stop_at_eos);
+    // The prefill of generate_batch(_ex): prompt i into slot i from position 0, row i of `logits` ([n][vocab], resized here) = its last position's logits.
+    // "batch_prefill" = 1: ONE Model::forward_batch over all prompts -- unless the cache is 8-bit (that pass refuses it) or the prompts together exceed the
+    // context-sized activation buffers: then, and with 0, one forward() per slot, as ever.
+    int prefill_slots(const int* const* prompts, const int* prompt_lens, int n, std::vector<float>& logits);
     Model model_;
     Tokenizer tok_;
     Stats stats_;

@@ -51,6 +51,10 @@ public:
     void fill(ntk_kv_batch& out, const int* slots, int T, int layer) const {
         for (int t = 0; t < T; ++t) { out.k[t] = k(slots[t], layer); out.v[t] = v(slots[t], layer); }
     }
+    // ... and of the segments of a packed prompt pass: segment j lives in slot slots[j] (F16 caches: the caller refuses the 8-bit format)
+    void fill(ntk_kv_segments& out, const int* slots, int layer) const {
+        for (int j = 0; j < out.n_seg; ++j) { out.k[j] = k(slots[j], layer); out.v[j] = v(slots[j], layer); }
+    }
     // rows [pos0, pos0 + n) as byte ranges of a layer buffer; returns how many: f16 one, q8_0 two (quants, then scales)
     int row_ranges(int pos0, int n, KvRange out[2]) const {
         out[0] = q8_ ? ntk::kv_q8_quant_rows(g_.per(), pos0, n) : ntk::kv_f16_rows(g_.per(), pos0, n);

@@ -15,6 +15,7 @@
 #include "synth.h"
 
 struct ntk_sample_rows;   // include/ntk_engine.h
+struct ntk_kv_segments;
 
 struct ihipGraphExec_t;   // hipGraphExec_t
 
@@ -110,6 +111,21 @@ public:
     // the host-side checks of decode_batch (no device): B in 1 .. sequences, every slot in range and named once, positions in [0, max_seq), token ids in
     // [0, vocab); NTK_OK or NTK_E_NULL / NTK_E_SHAPE with the reason in *why (optional)
     static int validate_batch(const int* slots, const int* tokens, const int* positions, int B, int sequences, int max_seq, int vocab, std::string* why);
+    // ---- the packed prompt pass -----------------------------------------------------------------------------------------------------
+    // SEVERAL sequences' tokens in ONE pass over the weights: segment i = lens[i] consecutive tokens of the sequence in slot slots[i], the first at cache
+    // position start_pos[i]; tokens_flat holds the segments' tokens back to back (a one-token segment at start_pos > 0 is a decode row, a longer one a prompt
+    // chunk).  Eager: one H2D copy of the tokens and one of the gather indices, embedding, layers_1to1 over all rows with the SEGMENT form of the KV target
+    // (rope / store: ntk_rope_kv_store_segments, attention: ntk_attention_prefill_segments, each over the slots' own caches), the last row of every segment
+    // gathered into n contiguous rows, the final RMSNorm and the LM head over those n rows (lm_head: score()'s, full_form), ntk_logprob_rows for the first
+    // maxima, one D2H copy of whichever of logits_out [n][vocab] / next_out [n] is non-null, one synchronisation.  Allocates nothing sized by the context
+    // (the batch buffers of decode_batch on a first call).  ARITHMETIC: forward()'s layer arithmetic for the pass's total row count, so one
+    // segment of two tokens or more leaves forward()'s cache rows bit for bit; logits within 1e-3 of forward's (another LM-head form); within one total row
+    // count a segment depends on nothing but itself.  Refused (NTK_E_SHAPE + error(); nothing launched): validate_forward_batch, a token id out of range,
+    // kv_cache = q8_0 (the prompt path's ONE one-layer F16 image cannot hold several slots at once), tensor parallelism.
+    int forward_batch(const int* slots, const int* tokens_flat, const int* lens, const int* start_pos, int n, float* logits_out, int* next_out);
+    // its host-side checks (no device): n in 1 .. sequences, slots in range and named once, every lens[i] >= 1, start_pos[i] >= 0 and start_pos[i] +
+    // lens[i] <= max_seq, the lengths summing to at most max_seq (the pass runs through the max_seq-row activation buffers)
+    static int validate_forward_batch(const int* slots, const int* lens, const int* start_pos, int n, int sequences, int max_seq, std::string* why);
     // ---- KV cache sequence operations (csrc/kv_ops.hip) ------------------------------------------------------------------------------
     // Context shift of one slot: positions [keep, keep + discard) are dropped, rows [keep + discard, n_past) move down to [keep, ...) in every layer, in
     // the cache format the engine was loaded with (ntk_kv_shift / ntk_kv_shift_q8 with the engine's frequency table: K re-rotated by -discard positions,
@@ -288,9 +304,11 @@ private:
     int decode_project(const DevTensor* const* ws, float* const* ys, int n, const float* x, const DevTensor* norm, const float* resid, int kind,
                        int silu_pair = 0, bool timed = true);
     // where the T rows of a layer pass keep their K / V: one slot's cache at rows start_pos .. (forward, score), or -- slots != nullptr -- row t in the cache
-    // of slot slots[t] at its own position positions_[t] (decode_batch; max_pos: the largest of them, which picks the attention regime)
-    struct KvTarget { int slot; const int* slots; int max_pos; };
-    int layers_1to1(int T, int start_pos, int first, int last, const KvTarget& kv = KvTarget{0, nullptr, 0});   // the layer loop of forward(), score() and decode_batch()
+    // of slot slots[t] at its own position positions_[t] (decode_batch; max_pos: the largest of them, which picks the attention regime), or -- segs !=
+    // nullptr -- the rows are the segments *segs describes (rows, lengths, first positions; the cache pointers are filled per layer) and segment j lives in
+    // slot slots[j] (forward_batch)
+    struct KvTarget { int slot; const int* slots; int max_pos; const ntk_kv_segments* segs; };
+    int layers_1to1(int T, int start_pos, int first, int last, const KvTarget& kv = KvTarget{0, nullptr, 0, nullptr});   // the layer loop of forward(), score(), decode_batch() and forward_batch()
     // logits [n][vocab] of the final-normed rows X [n][H] (row_max: their largest |x| or null): one pass over the LM head, in the form score() takes
     int lm_head(float* logits, const float* X, int n, const float* row_max);
     bool lm_head_f16() const;         // ... is the FP16 GEMM
@@ -326,6 +344,7 @@ private:
     float* batch_logits_ = nullptr; // [kMaxSequences][V]: decode_batch's logits
     int* batch_in_ = nullptr;       // [3][kMaxSequences] device ints: tokens | positions | -1 (ntk_logprob_rows' "no target")
     int batch_host_[3 * 16] = {};   // ... and their host image
+    std::vector<int> packed_tokens_;   // forward_batch's tokens between its H2D copy and its synchronisation (the caller's array may be a temporary)
     float* batch_logprob_ = nullptr;   // [kMaxSequences] (unused result of ntk_logprob_rows)
     int* batch_next_ = nullptr;     // [kMaxSequences] first maxima
     float* batch_attn_scratch_ = nullptr;   // kMaxSequences x the single-row split scratch

@@ -257,7 +257,13 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));
             kv_capture_T_ = T;
         }
-        if (kv.slots && kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
+        if (kv.segs) {   // a packed prompt pass: every segment rotated, stored and attended on its own slot's cache from its own start position, one launch each
+            ntk_kv_segments segs = *kv.segs;
+            kv_.fill(segs, kv.slots, i);
+            ok(ntk_rope_kv_store_segments(act.q, act.k, act.v, &segs, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
+                                          cfg_.max_seq_len, s));
+            ok(ntk_attention_prefill_segments(act.attn_out, act.q, &segs, nh, nkv, hd, cfg_.max_seq_len, scale, s));
+        } else if (kv.slots && kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
             ntk_kv_batch caches{};
             kv_.fill(caches, kv.slots, T, i);
             ok(ntk_attention_decode_q8_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len,
@@ -519,6 +525,73 @@ int Model::decode_batch(const int* slots, const int* tokens, const int* position
     ok(ntk_stream_synchronize(s));
     if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
     if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("decode_batch failed: ") + ntk_status_string(rc);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The packed prompt pass: the tokens of several sequences in one pass over the weights (see model.h)
+// ---------------------------------------------------------------------------------------------------
+int Model::validate_forward_batch(const int* slots, const int* lens, const int* start_pos, int n, int sequences, int max_seq, std::string* why) {
+    auto fail = [&](int rc, const char* msg) { if (why) *why = msg; return rc; };
+    if (!slots || !lens || !start_pos) return fail(NTK_E_NULL, "forward_batch: null argument");
+    if (n < 1 || n > sequences || n > kMaxSequences) return fail(NTK_E_SHAPE, "forward_batch: the pass must hold 1 .. `sequences` segments");
+    unsigned seen = 0;
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= sequences || slots[i] >= kMaxSequences) return fail(NTK_E_SHAPE, "forward_batch: no such sequence slot");
+        if (seen & (1u << slots[i])) return fail(NTK_E_SHAPE, "forward_batch: the same sequence slot twice in one pass");
+        seen |= 1u << slots[i];
+        if (lens[i] < 1) return fail(NTK_E_SHAPE, "forward_batch: an empty segment");
+        if (start_pos[i] < 0 || (long long)start_pos[i] + lens[i] > max_seq) return fail(NTK_E_SHAPE, "forward_batch: a segment exceeds the context");
+        total += lens[i];
+    }
+    if (total > max_seq) return fail(NTK_E_SHAPE, "forward_batch: more rows than the context holds (the pass runs through the context-sized activation buffers)");
+    return NTK_OK;
+}
+
+int Model::forward_batch(const int* slots, const int* tokens, const int* lens, const int* start_pos, int n, float* logits_out, int* next_out) {
+    NT_TRY(validate_forward_batch(slots, lens, start_pos, n, sequences_, cfg_.max_seq_len, &err_));
+    if (!tokens) { err_ = "forward_batch: null argument"; return NTK_E_NULL; }
+    if (kv_q8_ || tp_world_ > 1) { err_ = "forward_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    const int H = cfg_.hidden_size, V = cfg_.vocab_size, N = kMaxSequences;
+    ntk_kv_segments segs{};   // rows, lengths and first positions; layers_1to1 fills in each layer's caches
+    segs.n_seg = n;
+    int T = 0;
+    for (int i = 0; i < n; ++i) { segs.row0[i] = T; segs.n_rows[i] = lens[i]; segs.start_pos[i] = start_pos[i]; T += lens[i]; }
+    for (int t = 0; t < T; ++t)   // the embedding gather indexes the table with these on the device
+        if (tokens[t] < 0 || tokens[t] >= V) { err_ = "forward_batch: token id out of range"; return NTK_E_SHAPE; }
+    NT_TRY(batch_buffers());
+    void* s = stream_;
+    tp_call_ = 0;
+    packed_tokens_.assign(tokens, tokens + T);
+    int* const host = batch_host_;   // the segments' last rows | unused | "no target": ONE copy, as batch_logits()
+    for (int b = 0; b < N; ++b) {
+        host[b] = b < n ? segs.row0[b] + segs.n_rows[b] - 1 : 0;
+        host[N + b] = 0;
+        host[2 * N + b] = -1;
+    }
+    NT_TRY(ntk_memcpy_h2d_async(tokens_dev_, packed_tokens_.data(), (size_t)T * 4, s));
+    NT_TRY(ntk_memcpy_h2d_async(batch_in_, host, sizeof batch_host_, s));
+    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, tokens_dev_, T, H, token_embd_.dtype, s);
+    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
+    else if (est != NTK_OK) return est;
+
+    KvTarget kv{0, slots, 0};
+    kv.segs = &segs;
+    int rc = layers_1to1(T, 0, 0, cfg_.n_layers, kv);
+    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
+    // the last row of every segment, gathered (hidden_ read as an F32 table) into n contiguous rows; the final RMSNorm and the LM head over those alone
+    ok(ntk_embed_rows(residual_, hidden_, batch_in_, n, H, NTK_DT_F32, s));
+    const float* rm = lm_head_f16() && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
+    if (rm) ok(ntk_rmsnorm_rowmax(hidden_, residual_, (const float*)output_norm_.ptr, n, H, cfg_.norm_eps, row_max_, nullptr, s));
+    else ok(ntk_rmsnorm(hidden_, residual_, (const float*)output_norm_.ptr, n, H, cfg_.norm_eps, s));
+    ok(lm_head(batch_logits_, hidden_, n, rm));
+    if (next_out) ok(ntk_logprob_rows(batch_logits_, n, V, V, batch_in_ + 2 * N, batch_logprob_, batch_next_, s));
+    if (rc == NTK_OK && logits_out) ok(ntk_memcpy_d2h_async(logits_out, batch_logits_, (size_t)n * V * 4, s));
+    if (rc == NTK_OK && next_out) ok(ntk_memcpy_d2h_async(next_out, batch_next_, (size_t)n * 4, s));
+    ok(ntk_stream_synchronize(s));
+    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
+    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("forward_batch failed: ") + ntk_status_string(rc);
     return rc;
 }
 

@@ -69,6 +69,8 @@ def _bind():
     L.nt_engine_decode_fused.argtypes = [vp, i, i, i, vp]
     L.nt_engine_seq_forward.argtypes = [vp, i, C.POINTER(i), i, i, vp]
     L.nt_engine_decode_batch.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), i, vp, vp]
+    L.nt_engine_forward_batch.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, vp, vp]
+    L.nt_forward_batch_validate.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, i]
     L.nt_engine_generate_batch.argtypes = [vp, C.POINTER(C.POINTER(i)), C.POINTER(i), i, C.POINTER(GenParams), C.POINTER(i), i, C.POINTER(i)]
     L.nt_engine_decode_batch_sample.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), i, C.POINTER(GenParams), C.POINTER(C.POINTER(i)), C.POINTER(i),
                                                 C.POINTER(f), vp, vp]
@@ -220,6 +222,18 @@ class Engine:
         nxt = (C.c_int * max(n, 1))()
         self._check(self.L.nt_engine_decode_batch(self.h, ia(slots), ia(tokens), ia(positions), n,
                                                   out.ctypes.data_as(C.c_void_p) if logits else None, C.cast(nxt, C.c_void_p)), "decode_batch")
+        return out, list(nxt[:n])
+
+    def forward_batch(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], start_positions: Sequence[int], logits: bool = True):
+        """The packed prompt pass: token_lists[i] goes into slot slots[i] from position start_positions[i], all in one pass over the weights:
+        (logits behind each list's last token [n, vocab] or None, their greedy tokens [n])."""
+        n = len(slots)
+        ia = lambda xs: (C.c_int * max(len(xs), 1))(*[int(x) for x in xs])
+        out = np.empty((n, self.vocab_size), np.float32) if logits else None
+        nxt = (C.c_int * max(n, 1))()
+        flat = [t for q in token_lists for t in q]
+        self._check(self.L.nt_engine_forward_batch(self.h, ia(slots), ia(flat), ia([len(q) for q in token_lists]), ia(start_positions), n,
+                                                   out.ctypes.data_as(C.c_void_p) if logits else None, C.cast(nxt, C.c_void_p)), "forward_batch")
         return out, list(nxt[:n])
 
     def generate_batch(self, prompts: Sequence[Sequence[int]], max_tokens: int, stop_at_eos: bool = True, temperature: float = 0.0,
@@ -468,6 +482,13 @@ class Engine:
         out = (C.c_int * 4096)()
         n = self.L.nt_engine_tokenize(self.h, text.encode(), int(add_bos), out, 4096)
         return list(out[:n])
+
+
+def forward_batch_validate(slots: Sequence[int], lens: Sequence[int], start_positions: Sequence[int], sequences: int, max_seq: int, n: Optional[int] = None) -> int:
+    """Host only (nt_forward_batch_validate): the argument checks of Engine.forward_batch (token ids aside) for an engine of `sequences` slots and
+    `max_seq` positions: 0, NTK_E_NULL or NTK_E_SHAPE.  n: the segment count passed (default: len(slots))."""
+    ia = lambda xs: (C.c_int * max(len(xs), 1))(*[int(x) for x in xs])
+    return int(_bind().nt_forward_batch_validate(ia(slots), ia(lens), ia(start_positions), len(slots) if n is None else int(n), int(sequences), int(max_seq)))
 
 
 def kv_shift_validate(slot: int, keep: int, discard: int, n_past: int, sequences: int, max_seq: int) -> int:

@@ -445,6 +445,39 @@ def attention_decode_batch(output, q, k, v, k_caches, v_caches, positions, n_row
     return None
 
 
+def kv_segments(segments, k_caches=None, v_caches=None, n_seg=None, row0=None):
+    """An ntk_kv_segments descriptor from segments = [(n_rows, start_pos), ...] laid back to back from row 0 (row0: other first rows, for the refusal
+    tests) and the segments' caches (DeviceBuffers, raw addresses or None = NULL); n_seg overrides the count."""
+    d = _lib.KvSegments()
+    d.n_seg = len(segments) if n_seg is None else n_seg
+    row = 0
+    for s, (n, start) in enumerate(segments[:16]):
+        d.row0[s], d.n_rows[s], d.start_pos[s] = (row if row0 is None else row0[s]), n, start
+        row += n
+        for side, caches in ((d.k, k_caches), (d.v, v_caches)):
+            c = caches[s] if caches is not None else None
+            side[s] = c if c is None or isinstance(c, int) else _p(c)
+    return d
+
+
+def kv_segments_validate(desc, total_rows, max_seq) -> int:
+    """ntk_kv_segments_validate (host only): NTK_OK, NTK_E_SHAPE or NTK_E_NULL; desc: a _lib.KvSegments or None"""
+    return int(_lib.lib().ntk_kv_segments_validate(C.addressof(desc) if desc is not None else None, int(total_rows), int(max_seq)))
+
+
+def rope_kv_store_segments(q, k, v, desc, n_heads, n_kv_heads, head_dim, theta_base, max_seq, freq_scale=1.0, interleaved=False, stream=None) -> int:
+    """ntk_rope_kv_store_segments: RoPE of q (in place) and the F16 store of the rotated k and of v for every segment of a packed pass, one launch; returns
+    the status (the caller checks it: the refusal tests read it)"""
+    return int(_lib.lib().ntk_rope_kv_store_segments(_p(q), _p(k), _p(v), C.addressof(desc) if desc is not None else None, n_heads, n_kv_heads, head_dim,
+                                                     theta_base, freq_scale, int(interleaved), max_seq, stream))
+
+
+def attention_prefill_segments(output, Q, desc, n_heads, n_kv_heads, head_dim, max_seq, scale, stream=None) -> int:
+    """ntk_attention_prefill_segments: causal prompt attention of every segment of a packed pass over its own caches; returns the status"""
+    return int(_lib.lib().ntk_attention_prefill_segments(_p(output), _p(Q), C.addressof(desc) if desc is not None else None, n_heads, n_kv_heads, head_dim,
+                                                         max_seq, scale, stream))
+
+
 def embed_rows(out, table, tokens, n_tokens, hidden, dtype, stream=None, allow_unsupported=False):
     st = _lib.lib().ntk_embed_rows(_p(out), _p(table), _p(tokens), n_tokens, hidden, int(dtype), stream)
     if not (allow_unsupported and st == -1):
