@@ -71,6 +71,27 @@ int ntk_rp_unpack(void* raw, const void* rp, int rows, int in_features, int dtyp
 int ntk_gemv_rp(float* y, const void* rp, const float* x, int out_features, int in_features, int weight_dtype, void* stream);
 int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in_features, const float* norm_w, float eps,
                       const float* resid, int silu_pair, void* stream);
+/* The static decode activations (csrc/gemv.hip): fixed slots of one module-scope device buffer for the single-token vectors the decode GEMVs
+ * read as x.  Their addresses are link-time constants of the kernels, so a lane-major Q8_0 launch (ntk_gemv_rp_fused, all segments Q8_0) whose
+ * x IS a slot -- and whose in_features is the slot's form: hidden x 4096 with a fused RMSNorm, attention output x 4096, SiLU x up x 14336 -- requests x before
+ * its kernel arguments have arrived (same loads, same values, same bits; any other x / width: the ordinary kernel).  One owner per process and
+ * device: an engine's fused single-token path; everything else keeps buffers of its own.
+ *   ntk_decode_arena_acquire   >= 0: the caller owns the current device's arena until _release -- the value is that device's index, the token
+ *                              _release takes; -1: somebody else owns it (or no device)
+ *   ntk_decode_arena_release   by the owner, with the index _acquire returned (whichever device is current by then)
+ *   ntk_decode_arena_slot      the slot's device address on the current device (NULL: no such slot / no device); owning is not needed to ask
+ *   ntk_debug_gemv_static_x    parity instrumentation: the slot whose early-x form this thread's last lane-major Q8_0 launch took (0: the ordinary kernel) */
+#define NTK_ARENA_HIDDEN 1
+#define NTK_ARENA_ATTN_OUT 2
+#define NTK_ARENA_GATE 3
+#define NTK_ARENA_HIDDEN_FLOATS 8192
+#define NTK_ARENA_ATTN_FLOATS 8192
+#define NTK_ARENA_GATE_FLOATS 32768
+int ntk_decode_arena_acquire(void);
+void ntk_decode_arena_release(int device);
+float* ntk_decode_arena_slot(int slot);
+int ntk_debug_gemv_static_x(void);
+
 /* parity instrumentation of the above: the LDS image its prologue builds from x (4 in + 68 in/256 bytes: three digit planes, a zero plane,
  * 64 bytes of sub-block-sum digits and one 2^(e-22) per super-block; nsub = 8: 32-column sub-blocks (Q4_K / Q5_K), 16: Q6_K), and
  * D[16][16] = A[16][64] . B[64][16] on the matrix instruction under the lane maps the kernel assumes */

@@ -96,6 +96,11 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * With "kv_cache" = "f16" the option is accepted and changes nothing.  With "0" every refusal and message is what it was before the option existed.
  * (The option exists ONLY because the default refusal of "sequences" > 1 with "q8_0" is pinned by a test; a later change that may touch that test can
  * fold the option away and make this the behaviour of "sequences" + "q8_0".);
+ * "static_activations" = "1" (default) | "0" (any other value: NTK_E_SHAPE + last_error): the fused single-token path keeps its hidden state, attention
+ * output and SiLU x up vector in the library's static decode slots (ntk_decode_arena_*, ntk_engine.h), where the Q8_0 decode GEMVs request them before their
+ * kernel arguments have arrived.  Set it BEFORE the load (afterwards: NTK_E_SHAPE + last_error); kept across loads.  One engine per process and device holds
+ * the slots, from its load to its close: the first to ask.  Any other engine, an nt_engine_load_shared sequence, tensor-parallel ranks and models beyond a
+ * slot's size run the same launches on buffers of their own, as with "0".  The results are the same bits either way; nt_engine_decode_path says which ran;
  * "score_rows" = "1" .. "1024" (default "256"): rows of logits nt_engine_score_tokens computes per pass over the LM head (score_rows x vocab floats of device
  * memory from the first scoring call on; any time);
  * "context_shift" = "0" (default) | "1" (any other value: NTK_E_SHAPE + last_error; any time before a generate call, kept across loads): what the generate loop

@@ -122,6 +122,8 @@ def lib() -> C.CDLL:
         "ntk_rp_unpack": (i, [vp, vp, i, i, i, vp]),
         "ntk_gemv_rp": (i, [vp, vp, vp, i, i, i, vp]),
         "ntk_gemv_rp_fused": (i, [C.POINTER(GemvSeg), i, vp, i, vp, f, vp, i, vp]),
+        "ntk_decode_arena_acquire": (i, []), "ntk_decode_arena_release": (None, [i]),
+        "ntk_decode_arena_slot": (vp, [i]), "ntk_debug_gemv_static_x": (i, []),
         "ntk_debug_rp_prologue": (i, [vp, vp, vp, f, i, i, i, vp]),
         "ntk_debug_mfma_i8_probe": (i, [vp, vp, vp, vp]),
         "ntk_gemm_quant": (i, [vp, vp, vp, i, i, i, i, vp, vp]),

@@ -77,6 +77,13 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
         return rc;
     }
+    else if (k == "static_activations") {   // "1" (default) | "0": the fused single-token path's activations in the library's static slots; before the load only (model.h)
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("static_activations must be 0 or 1"); return NTK_E_SHAPE; }
+        const int rc = E(e)->loaded() ? (E(e)->set_error("static_activations must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_static_activations(on);
+        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
+        return rc;
+    }
     else if (k == "batch_prefill") {   // "0" (default) | "1": nt_engine_generate_batch / _ex prefill all prompts in one packed pass; any time, read per call
         const std::string v = value;
         if (v != "0" && v != "1") { E(e)->set_error("batch_prefill must be 0 or 1"); return NTK_E_SHAPE; }

@@ -32,6 +32,10 @@ void Model::free_all() {
     stream_ = nullptr;
     for (void* p : allocs_) nt_hip_free(p);
     allocs_.clear();
+    if (arena_owner_) ntk_decode_arena_release(arena_device_);
+    arena_owner_ = false;
+    arena_device_ = -1;
+    hidden1_ = arena_attn_ = arena_gate_ = nullptr;
     auto free_host = [](auto*& p) { if (p) nt_hip_free_host(p); p = nullptr; };
     free_host(h_token_); free_host(h_ring_); free_host(h_recent_); free_host(h_batch_recent_); free_host(h_batch_next_);
     sample_scratch_ = gemm_ws_ = gemm_ws2_ = nullptr;
@@ -216,6 +220,12 @@ int Model::set_batch_kv_q8(bool on) {
     return NTK_OK;
 }
 
+int Model::set_static_activations(bool on) {
+    if (!layers_.empty()) { err_ = "static_activations must be set before the model is loaded"; return NTK_E_SHAPE; }
+    static_act_ = on;
+    return NTK_OK;
+}
+
 int Model::set_kv_cache(const std::string& kind) {
     if (kind != "f16" && kind != "q8_0") { err_ = "kv_cache: unknown format '" + kind + "' (f16 or q8_0)"; return NTK_E_DTYPE; }
     if (!layers_.empty()) { err_ = "kv_cache must be set before the model is loaded"; return NTK_E_SHAPE; }
@@ -259,7 +269,7 @@ const char* Model::decode_path() const {
     if (persistent_plan_ && persistent_on_)
         return attn_regime_ == 0 ? "persistent (1 launch per token in the single-pass attention regime, fused launches beyond)"
                                  : "fused (5 launches/layer; persistent below the split-attention regime)";
-    return "fused (5 launches/layer)";
+    return arena_owner_ ? "fused (5 launches/layer; static activations)" : "fused (5 launches/layer)";
 }
 
 // after a sync: NTK_OK, or NTK_E_LAUNCH when an in-kernel bounded wait gave up (tensor-parallel exchange; with
@@ -269,10 +279,12 @@ int Model::check_persistent() {
     return check_experiments();
 }
 
-Model::Views Model::views(int T) const {
+Model::Views Model::views(int T, bool fused) const {
     const size_t qd = (size_t)T * cfg_.n_heads * cfg_.head_dim, kvd = (size_t)T * cfg_.n_kv_heads * cfg_.head_dim;
     float* const q = workspace_;
-    return {q, q + qd, q + qd + kvd, q + qd + 2 * kvd, workspace_, workspace_ + (size_t)T * cfg_.intermediate_size};
+    Views v{q, q + qd, q + qd + kvd, q + qd + 2 * kvd, workspace_, workspace_ + (size_t)T * cfg_.intermediate_size};
+    if (fused && T == 1 && arena_owner_) { v.attn_out = arena_attn_; v.gate = arena_gate_; }
+    return v;
 }
 
 int Model::init_device() {

@@ -89,6 +89,12 @@ public:
     // engine) are pinned by tests/test_batch_decode_gpu.py::test_refusals_leave_the_engine_usable: with it off every refusal and message is unchanged.
     // A later change that may touch that test can fold the option away.
     int set_batch_kv_q8(bool on);
+    // "static_activations" = 1 (default; BEFORE the load, kept across loads): the fused single-token path keeps its hidden state, attention output and
+    // SiLU x up vector in the library's static decode slots (ntk_decode_arena_*, ntk_engine.h), where the Q8_0 decode GEMVs request x before their kernel
+    // arguments have arrived.  One engine per process and device owns the slots -- the first to load, until it closes; every other one (a second engine,
+    // a sharing sequence, tensor-parallel ranks, sizes beyond a slot) and = 0 run the same launches on buffers of their own.  Same bits either way.
+    int set_static_activations(bool on);
+    bool static_activations_active() const { return arena_owner_; }
     bool batch_kv_q8() const { return batch_kv_q8_; }
     // One decode step of B sequences in ONE pass over the weights: row b = token tokens[b] of the sequence in slot slots[b] at positions[b].  Eager and
     // host-driven: one H2D copy of tokens | positions, embedding, the layer loop as for a prompt of B tokens (layers_1to1 in batch mode: rope / store /
@@ -297,7 +303,7 @@ private:
     void drop_graphs(int slot = -1);  // destroy the captured tokens of one slot, or of all
     // the activations of T tokens in workspace_: q | k | v | attn_out, and gate | up over the same floats once attention is done
     struct Views { float *q, *k, *v, *attn_out, *gate, *up; };
-    Views views(int T) const;
+    Views views(int T, bool fused = false) const;   // fused: the single-token path's (attention output and SiLU x up in the static slots when this model owns them)
     int enqueue_token(bool greedy);   // the fused launch sequence for one token
     int enqueue_layers(int first, int last);            // its layer loop
     // y_k = W_k . f(x) for n <= 3 matrices sharing x, in as few fused launches as their formats allow (model_decode.cpp)
@@ -356,6 +362,12 @@ private:
     float* kv_capture_ = nullptr;   // parity instrumentation (debug_kv_inputs_capture): [2][max_seq][nkv * hd] F32 k (unrotated) and v of one layer's last 1:1 pass
     int kv_capture_layer_ = -1, kv_capture_T_ = 0;
     float* hidden_ = nullptr;       // [max_seq][H]
+    float* hidden1_ = nullptr;      // [H]: the fused single-token path's hidden state -- hidden_, or the static slot
+    bool static_act_ = true;        // the option (kept across loads)
+    bool arena_owner_ = false;      // this model holds the device's static decode slots (released in free_all)
+    int arena_device_ = -1;         // ... of this device: ntk_decode_arena_acquire's token
+    float* arena_attn_ = nullptr;   // ... its attention-output and SiLU x up slots
+    float* arena_gate_ = nullptr;
     float* residual_ = nullptr;     // [max_seq][H]
     float* workspace_ = nullptr;    // max(attention, ffn) floats, shared by all layers
     size_t workspace_floats_ = 0;

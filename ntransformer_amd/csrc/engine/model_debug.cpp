@@ -16,7 +16,8 @@ int Model::debug_run_layers(const float* hidden_in, int T, int start_pos, int fi
     if (tp_world_ > 1) return NTK_E_SHAPE;
     const size_t bytes = (size_t)T * cfg_.hidden_size * 4;
     void* s = stream_;
-    NT_TRY(ntk_memcpy_h2d_async(hidden_, hidden_in, bytes, s));
+    float* const hid = mode == 0 ? hidden_ : hidden1_;   // (the fused path's hidden state may live in the static slot)
+    NT_TRY(ntk_memcpy_h2d_async(hid, hidden_in, bytes, s));
     int rc;
     if (mode == 0) {
         std::vector<int> pos(T);
@@ -39,7 +40,7 @@ int Model::debug_run_layers(const float* hidden_in, int T, int start_pos, int fi
         }
     }
     if (rc != NTK_OK) return rc;
-    NT_TRY(ntk_memcpy_d2h_async(hidden_out, hidden_, bytes, s));
+    NT_TRY(ntk_memcpy_d2h_async(hidden_out, hid, bytes, s));
     return ntk_stream_synchronize(s);
 }
 

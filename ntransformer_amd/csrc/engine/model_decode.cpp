@@ -29,7 +29,7 @@ int Model::enqueue_token(bool greedy) {
     void* s = stream_;
     tp_call_ = 0;
     prof_mark(2, true);
-    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, d_token_, 1, H, token_embd_.dtype, s);
+    const int est = ntk_embed_rows(hidden1_, token_embd_.ptr, d_token_, 1, H, token_embd_.dtype, s);
     prof_mark(2, false);
     if (est != NTK_OK && est != NTK_E_DTYPE) return est;
     if (use_persistent_now()) {   // (experiments builds) every layer and the LM head in one launch
@@ -40,7 +40,7 @@ int Model::enqueue_token(bool greedy) {
         const DevTensor* const w = &output_;
         const bool timed = is_quant(w->dtype);
         if (timed) prof_mark(0, true);
-        NT_TRY(decode_project(&w, &logits_, 1, hidden_, &output_norm_, nullptr, 16, 0, false));
+        NT_TRY(decode_project(&w, &logits_, 1, hidden1_, &output_norm_, nullptr, 16, 0, false));
         if (timed) prof_mark(0, false);
     }
     prof_mark(2, true);
@@ -119,24 +119,24 @@ int Model::decode_project(const DevTensor* const* ws, float* const* ys, int n, c
     return NTK_OK;
 }
 
-// layers [first, last) of the fused single-token path on hidden_[H] (position in *d_pos_)
+// layers [first, last) of the fused single-token path on hidden1_[H] (position in *d_pos_)
 int Model::enqueue_layers(int first, int last_layer) {
     const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
     void* s = stream_;
     const float scale = 1.0f / sqrtf((float)hd);
-    const Views act = views(1);
+    const Views act = views(1, true);
     auto project_add = [&](const DevTensor& w, const float* x, int kind) -> int {   // hidden += W . x
         const DevTensor* const wp = &w;
-        float* y = tp_world_ > 1 ? tp_slot() : hidden_;   // tensor parallelism: this rank's partial sum -> exchange slot -> hidden += sum over ranks
-        NT_TRY(decode_project(&wp, &y, 1, x, nullptr, tp_world_ > 1 ? nullptr : hidden_, kind));
-        return tp_world_ > 1 ? tp_allreduce(hidden_, H) : (int)NTK_OK;
+        float* y = tp_world_ > 1 ? tp_slot() : hidden1_;   // tensor parallelism: this rank's partial sum -> exchange slot -> hidden += sum over ranks
+        NT_TRY(decode_project(&wp, &y, 1, x, nullptr, tp_world_ > 1 ? nullptr : hidden1_, kind));
+        return tp_world_ > 1 ? tp_allreduce(hidden1_, H) : (int)NTK_OK;
     };
 
     for (int i = first; i < last_layer; ++i) {
         const LayerWeights& L = layers_[i];
         const DevTensor* const qkv[3] = {&L.wq, &L.wk, &L.wv};
         float* const qkv_out[3] = {act.q, act.k, act.v};
-        NT_TRY(decode_project(qkv, qkv_out, 3, hidden_, &L.attn_norm, nullptr, 1));
+        NT_TRY(decode_project(qkv, qkv_out, 3, hidden1_, &L.attn_norm, nullptr, 1));
         // (experiments builds: attention inside the Wo launch; not taken = shapes only the two launches take)
         const int fused = fuse_attention_ ? attention_in_wo(L, i) : (int)NTK_E_SHAPE;
         if (fused != NTK_OK) {
@@ -160,7 +160,7 @@ int Model::enqueue_layers(int first, int last_layer) {
         // one quantised format: SiLU x up in the launch's epilogue, one profiler interval whichever form takes it; otherwise a launch of its own
         const bool pair = is_quant(L.w_gate.dtype) && L.w_gate.dtype == L.w_up.dtype;
         if (pair) prof_mark(0, true);
-        NT_TRY(decode_project(ffn, ffn_out, 2, hidden_, &L.ffn_norm, nullptr, 4, pair, !pair));
+        NT_TRY(decode_project(ffn, ffn_out, 2, hidden1_, &L.ffn_norm, nullptr, 4, pair, !pair));
         if (pair) prof_mark(0, false);
         else NT_TRY(ntk_silu_mul(act.gate, act.gate, act.up, I, s));
         NT_TRY(project_add(L.w_down, act.gate, 8));

@@ -369,6 +369,16 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         nt_hip_memcpy_h2d(rope_inv_freq_, f.data(), f.size() * 4);
     }
     if (sequences_ > 1) { NT_TRY(batch_buffers()); NT_TRY(batch_sample_buffers()); }   // (none of it counted in kv_cache_bytes())
+    // the fused single-token path's activations: the device's static slots if this model is the first to ask and fits them, else its own buffers
+    hidden1_ = hidden_;
+    const bool fits = H <= NTK_ARENA_HIDDEN_FLOATS && (size_t)cfg_.n_heads * cfg_.head_dim <= NTK_ARENA_ATTN_FLOATS &&
+                      (size_t)cfg_.intermediate_size <= NTK_ARENA_GATE_FLOATS;
+    if (static_act_ && fits && !shares_weights_ && tp_world_ == 1 && !experiments_built() && (arena_device_ = ntk_decode_arena_acquire()) >= 0) {
+        arena_owner_ = true;
+        hidden1_ = ntk_decode_arena_slot(NTK_ARENA_HIDDEN);
+        arena_attn_ = ntk_decode_arena_slot(NTK_ARENA_ATTN_OUT);
+        arena_gate_ = ntk_decode_arena_slot(NTK_ARENA_GATE);
+    }
     return NTK_OK;
 }
 

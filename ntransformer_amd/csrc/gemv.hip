@@ -29,7 +29,10 @@
 #include "ntk_experiments.h"
 #endif
 #include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <cstddef>
+#include <mutex>
 #include <cstdio>
 #include <cstdlib>
 
@@ -56,11 +59,33 @@ struct AttnFuse {};             // (the ATT instantiations exist in EXPERIMENTS=
 //   NS_ONE    rows of one slice: a wave owns whole rows
 //   NS_SPLIT  rows of several slices, one wave per slice, partial sums combined through LDS
 enum { NS_ANY = 0, NS_ONE = 1, NS_SPLIT = 2 };
-template <int DT, bool NORM, bool XFAST, bool A16, bool ATT = false, bool XI = false, bool LM = false, int NSF = NS_ANY>
+
+// The static decode activations (ntk_decode_arena_*, ntk_engine.h): the single-token vectors the decode GEMVs read as x, at an address the
+// kernel knows at link time.  A workgroup's kernel arguments are cold every token (0.5-0.8 us), and x's address is one of them: with x in a
+// slot, the x requests go out in the kernel's first instructions and land while the arguments are still on their way -- two round trips side
+// by side instead of one after the other.  XS names the slot of an "early-x" form and fixes its column count (the 8B shapes):
+//   XS_HIDDEN    the hidden state behind a fused RMSNorm, 4096 columns (Q|K|V, gate|up, LM head: every reader of it)
+//   XS_ATTN      the attention output, 4096 columns (Wo)
+//   XS_GATE      SiLU(gate) x up, 14336 columns (down)
+// The host (q8l_gemv_fused) picks a form only when the call's x IS that slot and `in` is that count; 512 threads per workgroup.
+enum { XS_NONE = 0, XS_HIDDEN = NTK_ARENA_HIDDEN, XS_ATTN = NTK_ARENA_ATTN_OUT, XS_GATE = NTK_ARENA_GATE };
+struct DecodeArena {
+    float hidden[NTK_ARENA_HIDDEN_FLOATS];
+    float attn_out[NTK_ARENA_ATTN_FLOATS];
+    float gate[NTK_ARENA_GATE_FLOATS];   // the widest row the GEMV accepts
+};
+__device__ __attribute__((aligned(256))) DecodeArena g_decode_arena;
+template <int XS> struct XSlot { static constexpr int IN = XS == XS_GATE ? 14336 : 4096; };
+template <int XS> __device__ __forceinline__ const float* xslot_ptr() {
+    return XS == XS_HIDDEN ? g_decode_arena.hidden : XS == XS_ATTN ? g_decode_arena.attn_out : g_decode_arena.gate;
+}
+
+template <int DT, bool NORM, bool XFAST, bool A16, bool ATT = false, bool XI = false, bool LM = false, int NSF = NS_ANY, int XS = XS_NONE>
 __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int bid, const int nblk, const AttnFuse* attp = nullptr) {   // workgroup bid of nblk
     using F = Fmt<DT>;
     static_assert(!LM || (DT == NTK_DT_Q8_0 && !A16 && !ATT && !XI), "lane-major rows: Q8_0");
     static_assert(NSF == NS_ANY || LM, "compile-time slice forms: the lane-major kernels");
+    static_assert(XS == XS_NONE || (LM && XFAST && NSF != NS_ANY), "early-x forms: the lane-major kernels, fast prologue");
     constexpr int NL = LM ? 4 : F::NL;
     constexpr int STAGE = LM ? 0 : NL * 1024 + 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -69,17 +94,21 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 #endif
     GV_STAMP(0);   // entry
 #ifndef NTK_GEMV_NO_KARG_PREFETCH
-    {
-        // The kernel arguments are 5 cache lines; hipcc fetches them piecemeal, each piece right before its first use, so the
-        // prologue used to pay a scalar-cache miss per line one after the other before the first weight row could be requested.
-        // Touch every line at once: the later loads hit the scalar cache.
-        const auto* ka = __builtin_amdgcn_kernarg_segment_ptr();
-        unsigned d0, d1, d2, d3, d4;
+    // The kernel arguments are 5 cache lines; hipcc fetches them piecemeal, each piece right before its first use, so the
+    // prologue used to pay a scalar-cache miss per line one after the other before the first weight row could be requested.
+    // Touch every line at once: the later loads hit the scalar cache.
+    const auto* ka = __builtin_amdgcn_kernarg_segment_ptr();
+    unsigned d0, d1, d2, d3, d4;
+    if constexpr (XS == XS_NONE) {
         asm volatile("s_load_dword %0, %5, 0x0\n\ts_load_dword %1, %5, 0x40\n\ts_load_dword %2, %5, 0x80\n\ts_load_dword %3, %5, 0xc0\n\t"
                      "s_load_dword %4, %5, 0x100\n\ts_waitcnt lgkmcnt(0)"
                      : "=&s"(d0), "=&s"(d1), "=&s"(d2), "=&s"(d3), "=&s"(d4) : "s"(ka) : "memory");
-        __builtin_amdgcn_sched_barrier(0);   // ... before the compiler's own argument loads
+    } else {   // early x: the wait stands behind the x requests below
+        asm volatile("s_load_dword %0, %5, 0x0\n\ts_load_dword %1, %5, 0x40\n\ts_load_dword %2, %5, 0x80\n\ts_load_dword %3, %5, 0xc0\n\t"
+                     "s_load_dword %4, %5, 0x100"
+                     : "=&s"(d0), "=&s"(d1), "=&s"(d2), "=&s"(d3), "=&s"(d4) : "s"(ka) : "memory");
     }
+    __builtin_amdgcn_sched_barrier(0);   // ... before the compiler's own argument loads
 #endif
 
     const int tid = threadIdx.x;
@@ -88,6 +117,31 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
     // (4096 columns use 2 of the 8; the dead loads alone cost 4 % of the token: they queue in front of the first weight row).
     constexpr int XIT = 8, WIT = 4;
     u32x4 xv[XIT], wv[WIT];
+    if constexpr (XS != XS_NONE) {
+        // x from its static slot: the same per-thread quads and the same clamping as below, with `in` and the thread count (512) known at
+        // compile time -- nothing here reads an argument, so the requests fly beside the argument lines
+        constexpr int IN = XSlot<XS>::IN, step0 = 512 * 4;
+        const float* const xs = xslot_ptr<XS>();
+#pragma unroll
+        for (int i = 0; i < XIT; ++i) {
+            xv[i] = u32x4{0u, 0u, 0u, 0u};
+            if (i * step0 < IN) xv[i] = *reinterpret_cast<const u32x4*>(xs + min(tid * 4 + i * step0, IN - 4));
+        }
+        GV_STAMP(7);   // x requested
+        __builtin_amdgcn_sched_barrier(0);
+#ifndef NTK_GEMV_NO_KARG_PREFETCH
+        // the argument lines have landed; the registers of the five loads stay reserved up to here
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(d0), "+s"(d1), "+s"(d2), "+s"(d3), "+s"(d4) : : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+        if constexpr (NORM) {   // (the norm weights' address is an argument)
+#pragma unroll
+            for (int i = 0; i < WIT; ++i) {
+                wv[i] = u32x4{0u, 0u, 0u, 0u};
+                if (i * step0 < IN) wv[i] = *reinterpret_cast<const u32x4*>(p.norm_w + min(tid * 4 + i * step0, IN - 4));
+            }
+        }
+    } else
     if constexpr (XFAST && !ATT) {
         const int step0 = (int)blockDim.x * 4;
 #pragma unroll
@@ -275,6 +329,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
             //  alternated three times: 8B Q8_0 553.6 -> 546.8 tok/s, Wo 5.6 -> 6.5 us -- the wait stays.  profiles/r05_ab_variants.txt)
 #ifndef NTK_GEMV_NO_XWAIT
             asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7]));
+            // (early x: letting the first row go without the norm weights measured the same as waiting for them -- NEGATIVE_RESULTS 12)
             if constexpr (NORM) asm volatile("" : "+v"(wv[0]), "+v"(wv[1]), "+v"(wv[2]), "+v"(wv[3]));
 #endif
             issue_first();   // unconditional (a wave without rows re-reads row 0)
@@ -603,9 +658,9 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 }
 
 // Q8_0 rows in the lane-major layout of the engine's repack (LM above)
-template <bool NORM, bool XFAST, int NSF>
+template <bool NORM, bool XFAST, int NSF, int XS = XS_NONE>
 __global__ __launch_bounds__(512, Fmt<NTK_DT_Q8_0>::MINW) void gemv_q8l_kernel(const GemvParams p) {
-    gemv_quant_body<NTK_DT_Q8_0, NORM, XFAST, false, false, false, true, NSF>(p, (int)blockIdx.x, (int)gridDim.x);
+    gemv_quant_body<NTK_DT_Q8_0, NORM, XFAST, false, false, false, true, NSF, XS>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 // GGUF Q8_0 rows -> lane-major rows (UNPACK: back).  One thread per (row, 64-column lane): its two blocks are 17 dwords
 // [d0 | 32 quants | d1 | 32 quants] in the file (4-byte aligned: the tensor is, and a row is a multiple of 272 bytes), 16 quant dwords + 1 scale dword packed.
@@ -918,9 +973,51 @@ static int q8l_pack(void* dst, const void* raw, int rows, int in, bool unpack, h
     return last_launch_status();
 }
 
+// ---- the static decode activations: slot addresses per device (asked once, outside any stream capture), ownership ----
+constexpr int kArenaDevices = 16;
+struct ArenaDev {
+    std::atomic<int> known{0};   // 1: addr[] is valid, -1: the lookup failed
+    std::atomic<int> owned{0};
+    const float* addr[4] = {nullptr, nullptr, nullptr, nullptr};   // [XS_*]
+};
+static ArenaDev g_arena_dev[kArenaDevices];
+static std::mutex g_arena_mu;
+static thread_local int t_last_static_x = XS_NONE;
+
+static ArenaDev* arena_dev(bool lookup) {   // the current device's entry (lookup: resolve the symbol if nobody has)
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kArenaDevices) return nullptr;
+    ArenaDev& a = g_arena_dev[dev];
+    if (a.known.load(std::memory_order_acquire) == 0 && lookup) {
+        std::lock_guard<std::mutex> lk(g_arena_mu);
+        if (a.known.load(std::memory_order_relaxed) == 0) {
+            void* base = nullptr;
+            const bool ok = hipGetSymbolAddress(&base, HIP_SYMBOL(g_decode_arena)) == hipSuccess && base != nullptr;
+            if (ok) {
+                auto* f = static_cast<const float*>(base);
+                a.addr[XS_HIDDEN] = f + offsetof(DecodeArena, hidden) / 4;
+                a.addr[XS_ATTN] = f + offsetof(DecodeArena, attn_out) / 4;
+                a.addr[XS_GATE] = f + offsetof(DecodeArena, gate) / 4;
+            }
+            a.known.store(ok ? 1 : -1, std::memory_order_release);
+        }
+    }
+    return a.known.load(std::memory_order_acquire) == 1 ? &a : nullptr;
+}
+// the slot whose early-x form takes (x, in), or XS_NONE
+static int static_x_slot(const float* x, int in) {
+    const ArenaDev* a = arena_dev(false);
+    if (!a) return XS_NONE;
+    if (x == a->addr[XS_HIDDEN] && in == XSlot<XS_HIDDEN>::IN) return XS_HIDDEN;
+    if (x == a->addr[XS_ATTN] && in == XSlot<XS_ATTN>::IN) return XS_ATTN;
+    if (x == a->addr[XS_GATE] && in == XSlot<XS_GATE>::IN) return XS_GATE;
+    return XS_NONE;
+}
+
 int q8l_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in, const float* norm_w, float eps, const float* resid,
                    int silu_pair, hipStream_t st) {
     int ns, sc;
+    t_last_static_x = XS_NONE;
     if (!q8l_layout(in, ns, sc)) return NTK_E_SHAPE;
     for (int i = 0; i < nseg; ++i)
         if (reinterpret_cast<uintptr_t>(segs[i].W) & 15) return NTK_E_ALIGN;   // rows are read with 16-byte requests from the tensor's own start
@@ -946,7 +1043,20 @@ int q8l_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in, c
     static int trace_counter = 0;
     L.p.trace_slot = trace_counter++;
 #endif
-    hipLaunchKernelGGL(table[norm_w ? 1 : 0][L.xfast ? 1 : 0][L.p.ns == 1 ? 0 : 1], dim3(L.grid), dim3(64 * L.nwaves), L.lds, st, L.p);
+    // x in a static slot (pointer identity), the slot's width, the fast prologue on 512 threads: the early-x form of the same kernel
+    KernelFn fn = table[norm_w ? 1 : 0][L.xfast ? 1 : 0][L.p.ns == 1 ? 0 : 1];
+    if (L.xfast && L.nwaves == 8) {
+        const int xs = static_x_slot(x, in);
+        KernelFn early = nullptr;
+        if (xs == XS_HIDDEN && L.p.ns == 1 && norm_w) early = gemv_q8l_kernel<true, true, NS_ONE, XS_HIDDEN>;   // (every reader of the hidden state norms it)
+        else if (xs == XS_ATTN && L.p.ns == 1 && !norm_w) early = gemv_q8l_kernel<false, true, NS_ONE, XS_ATTN>;
+        else if (xs == XS_GATE && L.p.ns > 1 && !norm_w) {   // (14336 columns: the activation image of four slices, 68 KiB)
+            static const bool raised = raise_lds_limit((const void*)gemv_q8l_kernel<false, true, NS_SPLIT, XS_GATE>);
+            if (raised || L.lds <= 64 * 1024) early = gemv_q8l_kernel<false, true, NS_SPLIT, XS_GATE>;
+        }
+        if (early && L.lds <= 160 * 1024) { fn = early; t_last_static_x = xs; }
+    }
+    hipLaunchKernelGGL(fn, dim3(L.grid), dim3(64 * L.nwaves), L.lds, st, L.p);
     return last_launch_status();
 }
 
@@ -1032,6 +1142,20 @@ NTK_EXTRA_API int ntk_debug_gemv_trace(unsigned long long* out, size_t n) {   //
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(ntk::g_gemv_trace), n * sizeof(unsigned long long)) == hipSuccess ? 0 : -3;
 }
 #endif
+
+int ntk_decode_arena_acquire(void) {
+    ntk::ArenaDev* a = ntk::arena_dev(true);
+    int free_ = 0;
+    return a && a->owned.compare_exchange_strong(free_, 1) ? (int)(a - ntk::g_arena_dev) : -1;
+}
+void ntk_decode_arena_release(int device) {   // by index: whichever device is current when the owner closes
+    if (device >= 0 && device < ntk::kArenaDevices) ntk::g_arena_dev[device].owned.store(0);
+}
+float* ntk_decode_arena_slot(int slot) {
+    const ntk::ArenaDev* a = ntk::arena_dev(true);
+    return a && slot >= NTK_ARENA_HIDDEN && slot <= NTK_ARENA_GATE ? const_cast<float*>(a->addr[slot]) : nullptr;
+}
+int ntk_debug_gemv_static_x(void) { return ntk::t_last_static_x; }
 
 size_t ntk_q8l_bytes(int rows, int in_features) { return ntk::q8l_bytes(rows, in_features); }
 int ntk_q8l_pack(void* dst, const void* raw, int rows, int in_features, void* stream) {

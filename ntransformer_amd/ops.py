@@ -227,6 +227,27 @@ def gemv_rp_fused(segs: Sequence[tuple], x, in_features, norm_w=None, eps=0.0, r
                                        stream), "gemv_rp_fused")
 
 
+ARENA_HIDDEN, ARENA_ATTN_OUT, ARENA_GATE = 1, 2, 3   # NTK_ARENA_* (include/ntk_engine.h)
+
+
+def decode_arena_slot(slot: int) -> int:
+    """device address of a static decode-activation slot (ntk_decode_arena_slot); write it with upload_to / read it with download_from"""
+    p = _lib.lib().ntk_decode_arena_slot(int(slot))
+    if not p:
+        raise _lib.NtkError(-1, "ntk_decode_arena_slot(%d)" % slot)
+    return int(p)
+
+
+def upload_to(ptr: int, a: np.ndarray) -> None:
+    a = np.ascontiguousarray(a)
+    _lib.lib().nt_hip_memcpy_h2d(ptr, a.ctypes.data_as(C.c_void_p), a.nbytes)
+
+
+def gemv_static_x() -> int:
+    """the slot whose early-x form this thread's last lane-major Q8_0 launch took (0: the ordinary kernel)"""
+    return int(_lib.lib().ntk_debug_gemv_static_x())
+
+
 def _gemm_quant_f16(segs, X, n_tokens, in_features, resid=None, row_max=None, partials=None, stream=None, keep=None, repacked=False, workspace=None,
                     reuse_x=0, full_form=False):
     """ntk_gemm_quant_f16 behind its descriptor (include/ntk_engine.h: ntk_gemm_desc); segs = [(W, Y, rows, dtype), ...] of one format sharing X.  The

@@ -7,6 +7,7 @@ spread (min / median / max over workgroups) of every stamp relative to the launc
 usage: python tools/gemv_trace.py [--dtypes Q8_0] [--shapes ...]
        python tools/gemv_trace.py --lm                         (Q8_0 over lane-major rows, ntk_gemv_rp_fused: the kernel the engine launches;
                                                                 the pool's bytes are read as packed rows -- timing only)
+       python tools/gemv_trace.py --lm --static-x              (... with x in the static decode slots: the early-x forms of that kernel)
        python tools/gemv_trace.py --rp --dtypes Q4_K,Q6_K     (the matrix-core GEMV over the engine's repack, csrc/gemv_rp.hip: its own stamps)"""
 import argparse
 import ctypes as C
@@ -40,6 +41,7 @@ def main():
     ap.add_argument("--pool-mb", type=int, default=1536, help="weight pool the launches rotate over (small = Infinity-Cache resident)")
     ap.add_argument("--rp", action="store_true", help="ntk_gemv_rp_fused over repacked copies of the pool's matrices (Q4_K / Q5_K / Q6_K)")
     ap.add_argument("--lm", action="store_true", help="Q8_0: the lane-major kernel (ntk_gemv_rp_fused) over the same pool")
+    ap.add_argument("--static-x", action="store_true", help="with --lm: x in the static decode slot of the shape (ntk_decode_arena_slot): the early-x forms")
     a = ap.parse_args()
     if a.lm:
         a.dtypes = "Q8_0"
@@ -69,6 +71,11 @@ def main():
             per_al = (per_launch + 4095) // 4096 * 4096
             nslots = max(2, pool_bytes // per_al)
             x = DB.from_numpy(rng.standard_normal(in_f).astype(np.float32))
+            if a.static_x:   # the slot the engine's launch of this shape reads: hidden (Q|K|V, gate|up), attention output (Wo), SiLU x up (down)
+                slot = ops.ARENA_HIDDEN if kind in ("qkv", "silu") else ops.ARENA_ATTN_OUT if in_f == 4096 else ops.ARENA_GATE
+                xs = ops.decode_arena_slot(slot)
+                ops.upload_to(xs, x.numpy())
+                x = xs
             nw = DB.from_numpy(np.ones(in_f, np.float32))
             ys = [DB.zeros(max(r, 1) * 4) for r in (rlist if kind != "silu" else [rlist[0], rlist[0]])]
 
@@ -102,6 +109,8 @@ def main():
             assert L.ntk_debug_gemv_trace(buf, SLOTS * WG * EV) == 0
             t = np.frombuffer(buf, dtype=np.uint64).astype(np.int64).reshape(SLOTS, WG, EV)
             HIP.hipGraphExecDestroy(gexec); HIP.hipGraphDestroy(graph)
+            if a.lm:
+                print("   (early-x form of the last launch: slot %d)" % ops.gemv_static_x())
             print("== %s%s %s: %.2f MB per launch, chain of %d (10 ns clock; us relative to the launch's first workgroup entry)" % (dname, " lane-major" if a.lm else "", sname, per_launch / 1e6, n))
             gaps, totals, rows_ = [], [], []
             agg = {k: [] for k in range(1, 12)}
