@@ -70,7 +70,7 @@ int  nt_engine_load_synthetic(nt_engine_t e, const nt_synth_spec* spec, int max_
  * "repack" level meanwhile; a tensor-parallel source is refused (NTK_E_SHAPE). */
 int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
 /* "fused" / "graph" / "device_sampling" / "batched_prefill" / "f16_prefill" (alias "bf16_prefill") = "0" | "1"; "persistent" / "fuse_attention" are accepted
- * everywhere and take effect only in builds of experiments/ (experiments/ntk_experiments.h); "repack" = "0" raw-GGUF decode GEMVs | "1" load-time repack with the GGUF
+ * and do nothing (the structures they selected lost to the fused launches and were removed: profiles/NEGATIVE_RESULTS.md); "repack" = "0" raw-GGUF decode GEMVs | "1" load-time repack with the GGUF
  * bytes kept resident (K-quant weights twice in HBM) | "2" one resident copy: the GGUF bytes of a repacked matrix are freed and unpacked into a scratch
  * for the launches that read raw blocks (prompt GEMM, 1:1 sequence; a fixed cost per prompt pass) | "3" (default) "2" when both copies would leave less than
  * a fifth of the device's memory free, else "1"; "attention_merge" = "1" split-KV decode attention as one launch | "0" (default) with the separate merge
@@ -80,7 +80,7 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * layers).  Set it BEFORE the load (afterwards: NTK_E_SHAPE + last_error); an nt_engine_load_shared sequence takes its own option.  Decode steps read
  * the 8-bit rows on the matrix cores using half(d) * q exactly; prompt passes (and "fused" = "0") dequantise rows [0, start_pos + n) into the F16 image
  * -- rounded to half, the chunk's own rows included -- and run the F16 attention kernels over it.  Refused at load (NTK_E_SHAPE + last_error): head_dim
- * other than 128, more than 16 query heads per KV head, tensor parallelism, "fuse_attention";
+ * other than 128, more than 16 query heads per KV head, tensor parallelism;
  * "sequences" = "1" .. "16" (default "1"): sequence slots of this engine for the batched decode step below.  Slot 0 is the KV cache every other entry point
  * uses, exactly as without the option; slots 1 .. N - 1 are extra F16 caches of the same layout, allocated at load (counted in nt_engine_kv_cache_bytes)
  * beside a [16][vocab] F32 logits buffer and the batched sampler's buffers (under 1 MB; neither is counted there).  Set it BEFORE the load (afterwards:
@@ -229,11 +229,9 @@ uint64_t nt_engine_weight_bytes(nt_engine_t e);            /* the model's tensor
 uint64_t nt_engine_resident_weight_bytes(nt_engine_t e);   /* what they occupy in HBM now: GGUF bytes still resident + the decode repack + the unpack scratch */
 uint64_t nt_engine_repacked_bytes(nt_engine_t e);          /* of which the decode repack (tensors that did not fit stay on the raw path and are not counted) */
 int  nt_engine_max_context(nt_engine_t e);
-/* which form the fused decode step takes at the current position: "fused (5 launches/layer)", or (EXPERIMENTS=1 builds with the
- * "persistent" option on) "persistent (...)" */
+/* which form the fused decode step takes: "fused (5 launches/layer)", or "fused (5 launches/layer; static activations)" when this engine
+ * holds the device's static decode slots */
 const char* nt_engine_decode_path(nt_engine_t e);
-void* nt_engine_persistent_plan(nt_engine_t e);   /* plan handle for ntk_persistent_debug / ntk_layer_engine_debug; NULL outside EXPERIMENTS=1 builds */
-int   nt_engine_persistent_kind(nt_engine_t e);   /* 0 none, 1 decode_persistent.hip, 2 layer_engine.hip ("persistent" = "2") */
 /* Tensor-parallel decoding over `world` GPUs, one engine (normally one process) per rank -- SURVEY 8(f) rank 4, no reference
  * counterpart.  nt_engine_tp_configure BEFORE load: the engine then keeps rows [rank/world) of Wq/Wk/Wv/gate/up (whole heads) and
  * the matching columns of Wo/down; n_heads, n_kv_heads and the FFN width must divide by `world`, column slices must be whole

@@ -130,13 +130,6 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 // gfx950 does execute ds_read_b32/b128 at any byte address (hipcc emits them for a 2-byte-aligned pointer), but
 // measured on MI355X the misaligned wide reads are slower than aligned dwords + v_alignbyte_b32 (Q8_0 GEMVs lost
 // 10-14 %), so a block's dwords are assembled from aligned reads.
-// 4 bytes at any even offset: two aligned dwords + v_alignbyte_b32
-__device__ __forceinline__ uint32_t lds_u32_at(const uint8_t* base, int off) {
-    const int a = off & ~3;
-    const uint32_t lo = *reinterpret_cast<const uint32_t*>(base + a);
-    const uint32_t hi = *reinterpret_cast<const uint32_t*>(base + a + 4);
-    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(off & 3));
-}
 // N consecutive dwords starting at any even offset (N+1 aligned reads)
 template <int N>
 __device__ __forceinline__ void lds_read_dwords(uint32_t (&dst)[N], const uint8_t* base, int off) {

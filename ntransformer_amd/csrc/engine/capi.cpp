@@ -54,35 +54,32 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
     if (!e || !key || !value) return NTK_E_NULL;
     const bool on = atoi(value) != 0;
     const std::string k = key;
+    // an option that shapes the load: refused afterwards, and the model's own refusal becomes the engine's error
+    auto before_load = [&](auto set) -> int {
+        if (E(e)->loaded()) { E(e)->set_error(k + " must be set before the model is loaded"); return NTK_E_SHAPE; }
+        const int rc = set();
+        if (rc != NTK_OK) E(e)->set_error(E(e)->model().error());
+        return rc;
+    };
     if (k == "fused") E(e)->options().fused = on;
     else if (k == "graph") E(e)->options().graph = on;
     else if (k == "batched_prefill") { E(e)->options().batched_prefill = on; E(e)->model().set_batched_prefill(on); }
     else if (k == "device_sampling") E(e)->options().device_sampling = on;
     else if (k == "f16_prefill" || k == "bf16_prefill") E(e)->model().set_bf16_prefill(on);   // (the round-2 name stays accepted)
-    else if (k == "fuse_attention") { const int rc = E(e)->model().set_fuse_attention(on); if (rc != NTK_OK) E(e)->set_error(E(e)->model().error()); return rc; }
-    else if (k == "kv_cache") {   // "f16" (default) | "q8_0": before the load only
-        const int rc = E(e)->loaded() ? (E(e)->set_error("kv_cache must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_kv_cache(value);
-        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
-        return rc;
+    else if (k == "persistent" || k == "fuse_attention") {   // accepted and without effect: the structures they selected were retired
+        if (on) fprintf(stderr, "note: \"%s\" selected an experiment that lost to the fused launches and was removed (profiles/NEGATIVE_RESULTS.md); the option does nothing\n", key);
     }
-    else if (k == "sequences") {   // "1" .. "16" sequence slots: before the load only
-        const int rc = E(e)->loaded() ? (E(e)->set_error("sequences must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_sequences(atoi(value));
-        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
-        return rc;
-    }
+    else if (k == "kv_cache") return before_load([&] { return E(e)->model().set_kv_cache(value); });   // "f16" (default) | "q8_0": before the load only
+    else if (k == "sequences") return before_load([&] { return E(e)->model().set_sequences(atoi(value)); });   // "1" .. "16" sequence slots: before the load only
     else if (k == "batch_kv_q8") {   // "0" (default) | "1": sequence slots and the batched step over the 8-bit cache; before the load only (model.h)
         const std::string v = value;
         if (v != "0" && v != "1") { E(e)->set_error("batch_kv_q8 must be 0 or 1"); return NTK_E_SHAPE; }
-        const int rc = E(e)->loaded() ? (E(e)->set_error("batch_kv_q8 must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_batch_kv_q8(on);
-        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
-        return rc;
+        return before_load([&] { return E(e)->model().set_batch_kv_q8(on); });
     }
     else if (k == "static_activations") {   // "1" (default) | "0": the fused single-token path's activations in the library's static slots; before the load only (model.h)
         const std::string v = value;
         if (v != "0" && v != "1") { E(e)->set_error("static_activations must be 0 or 1"); return NTK_E_SHAPE; }
-        const int rc = E(e)->loaded() ? (E(e)->set_error("static_activations must be set before the model is loaded"), NTK_E_SHAPE) : E(e)->model().set_static_activations(on);
-        if (rc != NTK_OK && !E(e)->loaded()) E(e)->set_error(E(e)->model().error());
-        return rc;
+        return before_load([&] { return E(e)->model().set_static_activations(on); });
     }
     else if (k == "batch_prefill") {   // "0" (default) | "1": nt_engine_generate_batch / _ex prefill all prompts in one packed pass; any time, read per call
         const std::string v = value;
@@ -104,7 +101,6 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
     else if (k == "prefill_fused_split") E(e)->model().set_prefill_fused_split(on);   // 1 (default): see Model::prefill_fused_split_
     else if (k == "attention_merge") return E(e)->model().set_attention_merge(on);   // 1: split-KV attention without the combine launch (default 0: measured slower)
     else if (k == "repack") return E(e)->model().set_repack(atoi(value));   // 0 raw path, 1 repack + GGUF bytes resident, 2 one resident copy (Q8_0 matrices keep both: model.h), 3 (default): 2
-    else if (k == "persistent") { E(e)->options().persistent = on; E(e)->model().set_persistent(atoi(value)); }   // 1: decode_persistent.hip, 2: layer_engine.hip
     else if (k == "score_rows") {   // rows of logits per LM-head chunk of nt_engine_score_tokens, 1 .. 1024 (default 256)
         const int rc = E(e)->model().set_score_rows(atoi(value));
         if (rc != NTK_OK) E(e)->set_error(E(e)->model().error());
@@ -279,7 +275,7 @@ int nt_engine_decode_fused(nt_engine_t e, int token, int pos, int use_graph, flo
     if (rc != NTK_OK) return rc;
     rc = m.copy_logits(logits_out);
     if (rc != NTK_OK) return rc;
-    return m.check_persistent();
+    return m.check_tp();   // the tensor-parallel exchange's bounded wait that gave up invalidates the result
 }
 
 int nt_engine_debug_run_layers(nt_engine_t e, const float* hidden_in, int n_tokens, int start_pos, int first_layer, int n_layers, int mode,
@@ -328,8 +324,6 @@ int nt_engine_debug_kv_write_q8_slot(nt_engine_t e, int slot, int layer, int pos
     return E(e)->model().debug_kv_q8(layer, pos0, n, static_cast<uint8_t*>(const_cast<void*>(k_blocks)), static_cast<uint8_t*>(const_cast<void*>(v_blocks)), true, slot);
 }
 
-void* nt_engine_persistent_plan(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().persistent_plan() : nullptr; }
-int nt_engine_persistent_kind(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().persistent_kind() : 0; }
 const char* nt_engine_decode_path(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().decode_path() : ""; }
 
 // ---- tensor parallelism (one engine per rank; csrc/tp.hip) ---------------------------------------------------------------

@@ -333,7 +333,7 @@ int Engine::run(std::vector<int>& tokens, const GenerateConfig& cfg, std::string
     // both -- set_device_pos -- before it decodes.)
     stats_.decode_ms = ms_since(d0);
     if (opt_.fused) { const int sr = model_.sync(); if (rc == NTK_OK) rc = sr; }
-    if (rc == NTK_OK && opt_.fused) rc = model_.check_persistent();
+    if (rc == NTK_OK && opt_.fused) rc = model_.check_tp();   // the error word of the tensor-parallel exchange
     if (rc != NTK_OK) err_ = std::string("decode failed: ") + ntk_status_string(rc);
     return rc;
 }
@@ -359,7 +359,7 @@ int Engine::decode_greedy_steps(int token, int pos, int n, int* out) {
             if (out) out[i] = next;
         }
         { const int rc = model_.sync(); if (rc != NTK_OK) return rc; }
-        return model_.check_persistent();   // a bounded in-kernel wait that gave up invalidates the run (and disables the path)
+        return model_.check_tp();   // a bounded wait of the tensor-parallel exchange that gave up invalidates the run
     }
     std::vector<float> host(model_.config().vocab_size);
     for (int i = 0; i < n; ++i) {

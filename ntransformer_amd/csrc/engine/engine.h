@@ -48,7 +48,6 @@ struct EngineOptions {
     bool graph = true;            // replay the fused token from a hipGraph
     bool batched_prefill = true;  // prompts: one pass over each weight matrix per 16 tokens (false: per-token GEMV loops)
     bool device_sampling = true;  // greedy argmax on the device when temperature <= 0 and repeat_penalty <= 1
-    bool persistent = false;      // short contexts: the whole token in one persistent launch (decode_persistent.hip)
     int synth_threads = 0;        // 0 = hardware concurrency
     bool context_shift = false;   // the generate loop at the end of the context: drop half of what lies behind context_keep and go on (false: stop)
     int context_keep = 1;         // leading positions a context shift never drops (the default keeps the BOS)

@@ -6,19 +6,16 @@ namespace nt {
 
 Model::~Model() { free_all(); }
 
-void Model::drop_graphs(int slot) {
+void Model::drop_graphs() {
     for (auto& row : graphs_)
-        for (int k = 0; k <= kAttnRegimes; ++k) {
-            if (slot >= 0 && k != slot) continue;
-            if (row[k]) (void)hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(row[k]));
-            row[k] = nullptr;
+        for (auto& g : row) {
+            if (g) (void)hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(g));
+            g = nullptr;
         }
 }
 
 void Model::free_all() {
     drop_graphs();
-    destroy_persistent_plan();
-    persistent_on_ = false;
     for (int r = 0; r < 8; ++r) {   // peers' communication buffers mapped through hipIpc
         if (tp_peer_opened_[r] && tp_peers_[r]) (void)ntk_ipc_close(tp_peers_[r]);
         tp_peers_[r] = nullptr;
@@ -40,7 +37,6 @@ void Model::free_all() {
     free_host(h_token_); free_host(h_ring_); free_host(h_recent_); free_host(h_batch_recent_); free_host(h_batch_next_);
     sample_scratch_ = gemm_ws_ = gemm_ws2_ = nullptr;
     d_recent_ = nullptr;
-    attn_sync_ = nullptr;
     shares_weights_ = false;   // (allocs_ held only this object's own buffers: the tensors belong to the model they were shared from)
     layers_.clear();
     // a second load() on the same object starts from a clean slate
@@ -117,11 +113,7 @@ int Model::set_repack(int level) {
     }
     if (rc != NTK_OK) { err_ = std::string("set_repack: ") + ntk_status_string(rc); return rc; }
     repack_ = level;
-    if (level == 2) {
-        destroy_persistent_plan();   // the persistent kernels stream the uploaded GGUF bytes through the pointers their plan recorded: a plan must not outlive them
-        persistent_on_ = false;
-        rc = drop_raw_all();
-    }
+    if (level == 2) rc = drop_raw_all();
     return rc;
 }
 
@@ -230,53 +222,13 @@ int Model::set_kv_cache(const std::string& kind) {
     if (kind != "f16" && kind != "q8_0") { err_ = "kv_cache: unknown format '" + kind + "' (f16 or q8_0)"; return NTK_E_DTYPE; }
     if (!layers_.empty()) { err_ = "kv_cache must be set before the model is loaded"; return NTK_E_SHAPE; }
     const bool q8 = kind == "q8_0";
-    if (q8 && fuse_attention_) { err_ = "kv_cache=q8_0 is not supported with the attention-inside-Wo launch (fuse_attention)"; return NTK_E_SHAPE; }
     kv_q8_ = q8;
     return NTK_OK;
 }
 
-int Model::set_fuse_attention(bool on) {
-    if (on && kv_q8_) { err_ = "fuse_attention (attention inside the Wo launch) is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
-    fuse_attention_ = on;
-    return NTK_OK;
-}
-
-bool Model::use_persistent_now() const {
-    return persistent_plan_ && persistent_on_ && attn_regime_ == 0 && !prof_;
-}
-
-void Model::set_persistent(int level) {   // 0 off, 1 the round-2 token kernel (decode_persistent.hip), 2 the loader / consumer engine (layer_engine.hip)
-    const bool on = level != 0;
-    persistent_on_ = false;
-    persistent_wanted_ = level;   // (asked before the load: finish_load() applies it)
-    if (on && !experiments_built()) fprintf(stderr, "note: the persistent token kernels are built by experiments/Makefile only (experiments/libntransformer_hip_exp.so); this library decodes with fused launches\n");
-    if (persistent_plan_ && persistent_kind_ != (level == 2 ? 2 : 1)) {   // the other kernel's plan: drop it and its captured graphs
-        (void)sync();
-        destroy_persistent_plan();
-    }
-    if (!on || tp_world_ != 1 || layers_.empty()) return;
-    if (kv_q8_) { fprintf(stderr, "note: the persistent token kernels read the F16 KV cache; kv_cache=q8_0 decodes with fused launches\n"); return; }
-    if (raw_freed_bytes_ > 0) (void)set_repack(1);   // the persistent kernels stream the GGUF bytes themselves: those must be resident
-    if (!persistent_plan_) (void)build_persistent_plan(level == 2 ? 2 : 1);   // built on first use (EXPERIMENTS=1 builds only): it allocates device memory
-    persistent_on_ = persistent_plan_ != nullptr;
-}
-
-// what decode_step_fused() emits at the CURRENT position (the persistent form covers the single-pass attention regime only)
+// what decode_step_fused() emits
 const char* Model::decode_path() const {
-    if (persistent_plan_ && persistent_on_ && persistent_kind_ == 2)
-        return attn_regime_ == 0 ? "persistent layer engine (1 launch per token: loader / consumer waves, granule hand-offs; fused launches beyond the single-pass attention regime)"
-                                 : "fused (5 launches/layer; persistent layer engine below the split-attention regime)";
-    if (persistent_plan_ && persistent_on_)
-        return attn_regime_ == 0 ? "persistent (1 launch per token in the single-pass attention regime, fused launches beyond)"
-                                 : "fused (5 launches/layer; persistent below the split-attention regime)";
     return arena_owner_ ? "fused (5 launches/layer; static activations)" : "fused (5 launches/layer)";
-}
-
-// after a sync: NTK_OK, or NTK_E_LAUNCH when an in-kernel bounded wait gave up (tensor-parallel exchange; with
-// EXPERIMENTS=1 also the persistent token kernel and the attention-in-Wo launch, which are then disabled)
-int Model::check_persistent() {
-    NT_TRY(check_tp());
-    return check_experiments();
 }
 
 Model::Views Model::views(int T, bool fused) const {

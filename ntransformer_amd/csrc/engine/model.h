@@ -200,12 +200,6 @@ public:
     // Prompts (seq_len > 1) project all tokens of a chunk with one pass over each weight matrix (ntk_gemm_quant) instead
     // of the reference's per-token GEMV loops; off = the reference's exact launch sequence.
     void set_batched_prefill(bool on) { batched_prefill_ = on; }
-    // One decode token as ONE persistent launch (csrc/decode_persistent.hip) instead of 5 launches per layer.  On by default
-    // when the model qualifies (quantised matrices, head_dim 64 / 128); short contexts only (single-pass attention regime),
-    // longer ones keep the launch path.  Turned off for good if the kernel ever reports a bounded wait that gave up.
-    void set_persistent(int level);   // 0 off, 1 decode_persistent.hip, 2 layer_engine.hip (round 5); EXPERIMENTS=1 builds only, otherwise stays off
-    int persistent_kind() const { return persistent_plan_ ? persistent_kind_ : 0; }
-    int set_fuse_attention(bool on);   // (refused with the 8-bit KV cache)
     // KV cache format: "f16" (default) or "q8_0" (csrc/attention_q8.hip: Q8_0 blocks along head_dim, 1.0625 bytes per element + ONE layer's F16
     // scratch image for the prompt path).  Set BEFORE the load (load / load_synthetic / share_weights: a sharing sequence takes its own option);
     // refused afterwards.  q8_0 needs head_dim 128, <= 16 query heads per KV head and no tensor parallelism: the load refuses otherwise.
@@ -245,12 +239,9 @@ public:
     uint64_t repack_bytes() const { return repack_bytes_; }
     uint64_t resident_weight_bytes() const { return weight_bytes_ - raw_freed_bytes_ + repack_bytes_ + raw_scratch_bytes_; }
     void set_bf16_prefill(bool on) { bf16_prefill_ = on; }   // batched prompt: FP16-MFMA (gemm_f16.hip; the option keeps its round-2 name) or the F32-MFMA form (16)
-    bool persistent_available() const { return persistent_plan_ != nullptr; }
-    void* persistent_plan() const { return persistent_plan_; }
-    // which form decode_step_fused(…) emits at the current position: "persistent" / "fused launches"
+    // which form decode_step_fused(…) emits at the current position: the fused launches of its attention regime
     const char* decode_path() const;
-    int check_persistent();   // after a sync: NTK_OK, or NTK_E_LAUNCH if an in-kernel bounded wait gave up (TP exchange, experiments)
-    int check_tp();           // the tensor-parallel part of it: error word of the exchange kernel, surfaced and cleared
+    int check_tp();   // after a sync: NTK_OK, or NTK_E_LAUNCH if the exchange kernel's bounded wait gave up (its error word, surfaced and cleared)
     // parity instrumentation (tests): layers [first, first+count) on caller-supplied hidden states; KV cache rows in / out
     int debug_run_layers(const float* hidden_in, int T, int start_pos, int first, int count, int mode, float* hidden_out);
     int debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write, int slot = 0);
@@ -300,7 +291,7 @@ private:
     int tp_allreduce(float* hidden, int n);   // hidden += sum over ranks of the partial vectors in the current slot
     float* tp_slot() const;           // where the next partial vector goes
     void free_all();
-    void drop_graphs(int slot = -1);  // destroy the captured tokens of one slot, or of all
+    void drop_graphs();               // destroy the captured tokens
     // the activations of T tokens in workspace_: q | k | v | attn_out, and gate | up over the same floats once attention is done
     struct Views { float *q, *k, *v, *attn_out, *gate, *up; };
     Views views(int T, bool fused = false) const;   // fused: the single-token path's (attention output and SiLU x up in the static slots when this model owns them)
@@ -324,14 +315,6 @@ private:
     int batch_sample_buffers();       // ... and what decode_batch_sample() needs beside them (windows, sampler scratch, pinned mirrors): the same rule
     int score_buffers();              // the buffers of score(), on its first call (and again when score_rows grew)
     void prof_mark(int cls, bool begin);
-    bool use_persistent_now() const;
-    // hooks of experiments/ (model_experiments.cpp); in the product they launch nothing: NTK_E_SHAPE = "not taken", no plan, no error to report
-    static bool experiments_built();
-    int build_persistent_plan(int kind);   // the same operator sequence as a table for ntk_persistent_launch / ntk_layer_engine_launch (nullptr plan if unsupported)
-    void destroy_persistent_plan();                          // ... and the tokens captured with it
-    int launch_persistent();                                 // every layer and the LM head of a token in one launch
-    int attention_in_wo(const LayerWeights& L, int layer);   // attention producers inside the Wo launch
-    int check_experiments();                                 // the error words of those kernels' bounded waits
 
     ModelConfig cfg_;
     GgufVocab vocab_;
@@ -399,8 +382,7 @@ private:
     bool prof_coarse_ = false;
     std::vector<Timed>* prof_ = nullptr;   // non-null while profile_token() runs
     // one captured token per (greedy?, attention regime)
-    static constexpr int kPersistentSlot = kAttnRegimes;   // the persistent forms of regime 0 have their own slot
-    ihipGraphExec_t* graphs_[2][kAttnRegimes + 1] = {};   // [greedy][attention regime 0..2, 3 = persistent]
+    ihipGraphExec_t* graphs_[2][kAttnRegimes] = {};   // [greedy][attention regime 0..2]
     int host_pos_ = 0;               // host mirror of *d_pos_ (set_device_pos + one per fused step): picks the regime
     int attn_regime_ = 0;            // regime enqueue_token() emits
     float* attn_scratch_ = nullptr;  // partial softmax states of the split-KV attention
@@ -412,7 +394,6 @@ private:
     bool prefill_fused_split_ = true;   // (A/B switch of that: 0 = the FP16 GEMM's own pre-pass launches)
     size_t gemm_ws_bytes_ = 0;
     bool bf16_prefill_ = true;
-    unsigned* attn_sync_ = nullptr;  // 3 words for ntk_attention_gemv_fused (attention producers inside the Wo launch)
     int repack_ = 3;                 // EFFECTIVE level: 0 raw path, 1 repack + raw resident, 2 repack only (one resident copy); 3 only before a load
     int repack_wanted_ = 3;          // the level as ASKED (3 = the default: resolves to 2 at load): re-evaluated by every load
     bool repack_done_ = false;       // repack_all() ran on the loaded tensors
@@ -422,7 +403,6 @@ private:
     size_t raw_scratch_bytes_ = 0, raw_cursor_ = 0;
     int raw_err_ = 0;                // first failure inside raw_of() (it returns a pointer): ok() folds it into the forward's status
     bool attn_merge_ = false;        // split-KV attention without the combine launch (round 5; identical bits, measured 0-2 us per layer SLOWER: opt-in)
-    bool fuse_attention_ = false;    // attention + Wo projection as one launch: measured SLOWER than two launches (profiles/r02_*): opt-in
     int tp_rank_ = 0, tp_world_ = 1;
     void* tp_comm_ = nullptr;        // this rank's communication buffer (flags + two slots of max_seq x H floats)
     size_t tp_max_floats_ = 0;
@@ -432,10 +412,6 @@ private:
     unsigned tp_call_ = 0;           // all-reduce calls of the forward being enqueued (call k uses slot k & 1)
     bool own_stream_ = false;        // tensor-parallel ranks that share a process need private streams
     ModelConfig cfg_full_;           // the unsliced configuration (cfg_ holds the local head / FFN counts)
-    void* persistent_plan_ = nullptr;
-    bool persistent_on_ = false;   // opt-in until it beats the launch path on the bench (set_persistent / "persistent" option)
-    int persistent_wanted_ = 0;    // the option as last set (re-applied after a load)
-    int persistent_kind_ = 1;      // which kernel persistent_plan_ belongs to
 };
 
 }  // namespace nt

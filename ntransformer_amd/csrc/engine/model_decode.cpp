@@ -32,17 +32,13 @@ int Model::enqueue_token(bool greedy) {
     const int est = ntk_embed_rows(hidden1_, token_embd_.ptr, d_token_, 1, H, token_embd_.dtype, s);
     prof_mark(2, false);
     if (est != NTK_OK && est != NTK_E_DTYPE) return est;
-    if (use_persistent_now()) {   // (experiments builds) every layer and the LM head in one launch
-        NT_TRY(launch_persistent());
-    } else {
-        NT_TRY(enqueue_layers(0, cfg_.n_layers));
-        // final RMSNorm + LM head: one launch for a quantised output matrix (timed as one interval whichever form takes it), two 1:1 launches for a dense one
-        const DevTensor* const w = &output_;
-        const bool timed = is_quant(w->dtype);
-        if (timed) prof_mark(0, true);
-        NT_TRY(decode_project(&w, &logits_, 1, hidden1_, &output_norm_, nullptr, 16, 0, false));
-        if (timed) prof_mark(0, false);
-    }
+    NT_TRY(enqueue_layers(0, cfg_.n_layers));
+    // final RMSNorm + LM head: one launch for a quantised output matrix (timed as one interval whichever form takes it), two 1:1 launches for a dense one
+    const DevTensor* const w = &output_;
+    const bool timed = is_quant(w->dtype);
+    if (timed) prof_mark(0, true);
+    NT_TRY(decode_project(&w, &logits_, 1, hidden1_, &output_norm_, nullptr, 16, 0, false));
+    if (timed) prof_mark(0, false);
     prof_mark(2, true);
     // greedy: arg-max, token -> device word + pinned ring, position + 1 in ONE tail (ntk_argmax_advance); otherwise only the position
     if (greedy) NT_TRY(ntk_argmax_advance(logits_, cfg_.vocab_size, d_token_, h_token_, h_ring_, d_pos_, argmax_scratch_, s));
@@ -137,24 +133,19 @@ int Model::enqueue_layers(int first, int last_layer) {
         const DevTensor* const qkv[3] = {&L.wq, &L.wk, &L.wv};
         float* const qkv_out[3] = {act.q, act.k, act.v};
         NT_TRY(decode_project(qkv, qkv_out, 3, hidden1_, &L.attn_norm, nullptr, 1));
-        // (experiments builds: attention inside the Wo launch; not taken = shapes only the two launches take)
-        const int fused = fuse_attention_ ? attention_in_wo(L, i) : (int)NTK_E_SHAPE;
-        if (fused != NTK_OK) {
-            if (!not_taken(fused)) return fused;
-            prof_mark(1, true);
-            if (kv_q8_)
-                NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, kv_.k(0, i), kv_.v(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
-                                               cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
-            else if (attn_regime_ == 0)
-                NT_TRY(ntk_attention_decode_fused(act.attn_out, act.q, act.k, act.v, kv_.k_f16(0, i), kv_.v_f16(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
-                                                  cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, s));
-            else
-                NT_TRY((attn_merge_ ? ntk_attention_decode_split_merged : ntk_attention_decode_split)(
-                    act.attn_out, act.q, act.k, act.v, kv_.k_f16(0, i), kv_.v_f16(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
-                    cfg_.rope_theta, cfg_.rope_freq_scale, attention_splits(attn_regime_, hd), attn_scratch_, s));
-            prof_mark(1, false);
-            NT_TRY(project_add(L.wo, act.attn_out, 2));
-        }
+        prof_mark(1, true);
+        if (kv_q8_)
+            NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, kv_.k(0, i), kv_.v(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
+                                           cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
+        else if (attn_regime_ == 0)
+            NT_TRY(ntk_attention_decode_fused(act.attn_out, act.q, act.k, act.v, kv_.k_f16(0, i), kv_.v_f16(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
+                                              cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, s));
+        else
+            NT_TRY((attn_merge_ ? ntk_attention_decode_split_merged : ntk_attention_decode_split)(
+                act.attn_out, act.q, act.k, act.v, kv_.k_f16(0, i), kv_.v_f16(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
+                cfg_.rope_theta, cfg_.rope_freq_scale, attention_splits(attn_regime_, hd), attn_scratch_, s));
+        prof_mark(1, false);
+        NT_TRY(project_add(L.wo, act.attn_out, 2));
         const DevTensor* const ffn[2] = {&L.w_gate, &L.w_up};
         float* const ffn_out[2] = {act.gate, act.up};
         // one quantised format: SiLU x up in the launch's epilogue, one profiler interval whichever form takes it; otherwise a launch of its own
@@ -177,7 +168,7 @@ void Model::pick_attention_regime() {
 int Model::decode_step_fused(bool greedy, bool use_graph) {
     pick_attention_regime();
     if (!use_graph) return enqueue_token(greedy);
-    ihipGraphExec_t*& slot = graphs_[greedy ? 1 : 0][use_persistent_now() ? kPersistentSlot : attn_regime_];
+    ihipGraphExec_t*& slot = graphs_[greedy ? 1 : 0][attn_regime_];
     hipStream_t st = static_cast<hipStream_t>(stream_);
     if (!slot) {   // capture once: every per-token quantity (token id, position) lives in device memory
         hipGraphExec_t ex = nullptr;

@@ -184,7 +184,6 @@ int Model::finish_load() {
         if (repack_ == 3) repack_ = 2;   // round 6: the prompt GEMM reads the repack itself, so the second copy buys the batched paths nothing
         if (repack_ == 2) NT_TRY(drop_raw_all());
     }
-    if (persistent_wanted_) set_persistent(persistent_wanted_);
     size_t fr = 0, tot = 0;
     ntk_device_mem_info(&fr, &tot);
     uint64_t q8_twice = 0;   // Q8_0 matrices resident in both forms (GGUF blocks for the prompt pass, lane-major rows for decode)
@@ -311,7 +310,6 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
             return NTK_E_SHAPE;
         }
         if (tp_world_ > 1) { err_ = "kv_cache=q8_0 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
-        if (fuse_attention_) { err_ = "kv_cache=q8_0 is not supported with the attention-inside-Wo launch (fuse_attention)"; return NTK_E_SHAPE; }
     }
     if (sequences_ > 1) {   // the extra sequence slots: caches of slot 0's layout
         if (kv_q8_ && !batch_kv_q8_) { err_ = "sequences > 1 is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
@@ -339,7 +337,6 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     h_ring_ = (unsigned long long*)nt_hip_malloc_host(64);
     if (h_ring_) memset(h_ring_, 0, 64);
     sample_scratch_ = dev(ntk_sample_scratch_bytes(cfg_.vocab_size), false);
-    attn_sync_ = (unsigned*)dev(4096, true);
     {   // one workspace for every projection: the largest need over the launches the prompt pass makes (Q|K|V and gate|up go out as one)
         const int H = cfg_.hidden_size, I = cfg_.intermediate_size, qkv = (cfg_.n_heads + 2 * cfg_.n_kv_heads) * cfg_.head_dim;
         const int shapes[][2] = {{H, qkv}, {H, cfg_.n_heads * cfg_.head_dim}, {H, cfg_.n_kv_heads * cfg_.head_dim}, {cfg_.n_heads * cfg_.head_dim, H},
@@ -373,7 +370,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     hidden1_ = hidden_;
     const bool fits = H <= NTK_ARENA_HIDDEN_FLOATS && (size_t)cfg_.n_heads * cfg_.head_dim <= NTK_ARENA_ATTN_FLOATS &&
                       (size_t)cfg_.intermediate_size <= NTK_ARENA_GATE_FLOATS;
-    if (static_act_ && fits && !shares_weights_ && tp_world_ == 1 && !experiments_built() && (arena_device_ = ntk_decode_arena_acquire()) >= 0) {
+    if (static_act_ && fits && !shares_weights_ && tp_world_ == 1 && (arena_device_ = ntk_decode_arena_acquire()) >= 0) {
         arena_owner_ = true;
         hidden1_ = ntk_decode_arena_slot(NTK_ARENA_HIDDEN);
         arena_attn_ = ntk_decode_arena_slot(NTK_ARENA_ATTN_OUT);

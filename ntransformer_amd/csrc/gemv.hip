@@ -25,9 +25,6 @@
 //
 // HBM-bound: algorithmic bytes per launch = rows * row_bytes (+ in*4 for x per workgroup from L2).
 #include "gemv_core.hip.h"
-#ifdef NTK_EXPERIMENTS
-#include "ntk_experiments.h"
-#endif
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -44,12 +41,6 @@ namespace ntk {
 //            one column slice, the staging areas over the image -- behind a barrier -- for wider rows)
 //   [A, ..)  partial sums [2][rw][ns][RB] + 16 floats reduction scratch
 // ------------------------------------------------------------------------------------------------
-#ifdef NTK_EXPERIMENTS
-#include "gemv_attfuse.hip.h"   // AttnFuse, att_produce / att_wait / att_finish, asm_load16_sc1
-#else
-struct AttnFuse {};             // (the ATT instantiations exist in EXPERIMENTS=1 builds only)
-#endif
-
 // LM: the lane-major Q8_0 repack (gemv_core.hip.h: q8l_layout) -- the same kernel with the row transport replaced: a lane loads its own 64 quants (four
 // coalesced 16-byte requests) and its two scales (one dword) straight into registers; no staging areas, no ds_write / read-back / realign.
 //
@@ -80,10 +71,10 @@ template <int XS> __device__ __forceinline__ const float* xslot_ptr() {
     return XS == XS_HIDDEN ? g_decode_arena.hidden : XS == XS_ATTN ? g_decode_arena.attn_out : g_decode_arena.gate;
 }
 
-template <int DT, bool NORM, bool XFAST, bool A16, bool ATT = false, bool XI = false, bool LM = false, int NSF = NS_ANY, int XS = XS_NONE>
-__device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int bid, const int nblk, const AttnFuse* attp = nullptr) {   // workgroup bid of nblk
+template <int DT, bool NORM, bool XFAST, bool A16, bool XI = false, bool LM = false, int NSF = NS_ANY, int XS = XS_NONE>
+__device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int bid, const int nblk) {   // workgroup bid of nblk
     using F = Fmt<DT>;
-    static_assert(!LM || (DT == NTK_DT_Q8_0 && !A16 && !ATT && !XI), "lane-major rows: Q8_0");
+    static_assert(!LM || (DT == NTK_DT_Q8_0 && !A16 && !XI), "lane-major rows: Q8_0");
     static_assert(NSF == NS_ANY || LM, "compile-time slice forms: the lane-major kernels");
     static_assert(XS == XS_NONE || (LM && XFAST && NSF != NS_ANY), "early-x forms: the lane-major kernels, fast prologue");
     constexpr int NL = LM ? 4 : F::NL;
@@ -142,7 +133,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
             }
         }
     } else
-    if constexpr (XFAST && !ATT) {
+    if constexpr (XFAST) {
         const int step0 = (int)blockDim.x * 4;
 #pragma unroll
         for (int i = 0; i < XIT; ++i) {
@@ -270,7 +261,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
     //      global reads, conflict-free ds_read_b128), optional RMSNorm (reference rmsnorm.cu:16-70) ----
     f32x2 x2[32];   // the lane's 64 activations as 32 (even, odd) pairs
     XInt xi;         // ... or (XI) as integer byte planes (gemv_core.hip.h)
-    static_assert(!XI || (XFAST && !ATT && ((DT == NTK_DT_Q4_K && A16) || DT == NTK_DT_Q6_K)), "integer activations: fast prologue, Q4_K (aligned rows) / Q6_K");
+    static_assert(!XI || (XFAST && ((DT == NTK_DT_Q4_K && A16) || DT == NTK_DT_Q6_K)), "integer activations: fast prologue, Q4_K (aligned rows) / Q6_K");
     {
         // The activations reach registers through a padded LDS image holding ALL slices: image row (sp*64 + l)
         // = the 64 columns lane l of slice sp owns (pitch 68 floats: conflict-free ds_read_b128).
@@ -307,17 +298,6 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
             }
         };
         if constexpr (XFAST) {   // host guarantees: x (and norm_w) 16-byte aligned, in % 4 == 0, (!NORM || in <= WIT * step)
-            if constexpr (ATT) {
-#ifdef NTK_EXPERIMENTS
-                // x is produced INSIDE this launch: weights first (they depend on nothing), then the attention heads and the
-                // grid-wide hand-off, then x through cache-bypassing loads (the first weight row has landed long before)
-                issue_first();
-                att_wait(*attp);
-#pragma unroll
-                for (int i = 0; i < XIT; ++i) xv[i] = asm_load16_sc1(p.x, 4u * (unsigned)min(tid * 4 + i * step, p.in - 4));
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7]));
-#endif
-            } else {
             // x (and the norm weights) were requested at the top and have LANDED before the first weight row is requested: a CU
             // returns its loads in request order, so an x request queued behind weight rows (this wave's, or those of the waves of
             // the workgroup that started earlier) comes back with HBM latency, and the prologue's barrier waits for the slowest
@@ -334,7 +314,6 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 #endif
             issue_first();   // unconditional (a wave without rows re-reads row 0)
             GV_STAMP(8);   // first weight row requested
-            }
             __builtin_amdgcn_sched_barrier(0);
             GV_STAMP(1);   // x (and the norm weights) have landed
             float rms_inv = 1.0f;
@@ -645,9 +624,6 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
         }
         for (; done < p.nbatch; ++done) __syncthreads();
     }
-#ifdef NTK_EXPERIMENTS
-    if constexpr (ATT) att_finish(*attp, nblk);
-#endif
 #ifdef NTK_GEMV_TRACE
     GV_STAMP(6);   // end
     if (tid == 0 && bid < GT_WG) {
@@ -660,7 +636,7 @@ __device__ __forceinline__ void gemv_quant_body(const GemvParams& p, const int b
 // Q8_0 rows in the lane-major layout of the engine's repack (LM above)
 template <bool NORM, bool XFAST, int NSF, int XS = XS_NONE>
 __global__ __launch_bounds__(512, Fmt<NTK_DT_Q8_0>::MINW) void gemv_q8l_kernel(const GemvParams p) {
-    gemv_quant_body<NTK_DT_Q8_0, NORM, XFAST, false, false, false, true, NSF, XS>(p, (int)blockIdx.x, (int)gridDim.x);
+    gemv_quant_body<NTK_DT_Q8_0, NORM, XFAST, false, false, true, NSF, XS>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 // GGUF Q8_0 rows -> lane-major rows (UNPACK: back).  One thread per (row, 64-column lane): its two blocks are 17 dwords
 // [d0 | 32 quants | d1 | 32 quants] in the file (4-byte aligned: the tensor is, and a row is a multiple of 272 bytes), 16 quant dwords + 1 scale dword packed.
@@ -704,20 +680,6 @@ __global__ __launch_bounds__(256) void q8l_pack_kernel(uint8_t* __restrict__ dst
     }
 }
 
-#ifdef NTK_EXPERIMENTS
-// the Wo projection with the attention pre-phase (AttnFuse): aligned fast prologue, no norm
-template <int DT>
-__global__ __launch_bounds__(512, Fmt<DT>::MINW) void gemv_quant_att_kernel(const GemvParams p, const AttnFuse att) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t att_smem[];
-    const int nh = att.n_heads;
-    if ((int)blockIdx.x < nh) {   // the attention workgroups come first in the grid: they are resident before any waiter
-        att_produce(att, reinterpret_cast<float*>(att_smem), (int)blockIdx.x);
-        return;
-    }
-    gemv_quant_body<DT, false, true, A16_OK<DT>, true>(p, (int)blockIdx.x - nh, (int)gridDim.x - nh, &att);
-}
-#endif
-
 template <int DT, bool NORM, bool XFAST, bool A16>
 __global__ __launch_bounds__(512, Fmt<DT>::MINW) void gemv_quant_kernel(const GemvParams p) {
     gemv_quant_body<DT, NORM, XFAST, A16>(p, (int)blockIdx.x, (int)gridDim.x);
@@ -725,7 +687,7 @@ __global__ __launch_bounds__(512, Fmt<DT>::MINW) void gemv_quant_kernel(const Ge
 // integer-activation form (Q4_K, aligned fast prologue, rows of <= 16384 columns): gemv_core.hip.h XInt / DotI
 template <int DT, bool NORM>
 __global__ __launch_bounds__(512, Fmt<DT>::MINW) void gemv_quant_xi_kernel(const GemvParams p) {
-    gemv_quant_body<DT, NORM, true, A16_OK<DT>, false, true>(p, (int)blockIdx.x, (int)gridDim.x);
+    gemv_quant_body<DT, NORM, true, A16_OK<DT>, true>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 // Two weight formats in ONE launch (llama.cpp's Q4_K_M stores attn_v as Q6_K / Q5_K next to Q4_K attn_q / attn_k): the first
 // `split` workgroups run format A on its segments, the rest format B on its own -- the two halves share nothing but x.  One
@@ -735,10 +697,6 @@ __global__ __launch_bounds__(512, 4) void gemv_quant_pair_kernel(const GemvParam
     if ((int)blockIdx.x < split) gemv_quant_body<DTA, NORM, true, A16_OK<DTA>>(pa, (int)blockIdx.x, split);
     else gemv_quant_body<DTB, NORM, true, A16_OK<DTB>>(pb, (int)blockIdx.x - split, (int)gridDim.x - split);
 }
-
-#ifdef NTK_EXPERIMENTS
-#include "gemv_colsplit.hip.h"   // EXPERIMENTS=1: the column-split form of the Q8_0 GEMV at 4096 columns (slower: profiles/r03_gemv_colsplit.txt)
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // Dense F16 / F32 rows (reference gemm.cu:476-671): one wave per row, 16-byte lane loads when the row
@@ -903,27 +861,6 @@ static int launch_quant(const ntk_gemv_seg* segs, int nseg, const float* x, int 
         }();
         if (!once || L.lds > 160 * 1024) return NTK_E_SHAPE;
     }
-#ifdef NTK_EXPERIMENTS
-    if constexpr (DT == NTK_DT_Q8_0) {
-        // column-split form (gemv_colsplit.hip.h): rows of exactly 4096 columns, everything 16-byte aligned.  Opt-in: NTK_GEMV_COLSPLIT=1.
-        static const int cs_mode = NTK_TUNE_ENV_INT("NTK_GEMV_COLSPLIT", 0);
-        bool cs = cs_mode != 0 && in == CS_COLS && L.xfast && !(kAblate & 7);
-        for (int i = 0; i < nseg && cs; ++i) cs = L.p.seg[i].delta == 0;
-        if (cs) {
-            const int total = L.p.total_rows, mats = silu_pair ? 2 : 1;
-            const int cgrid = std::min(total, max_workgroups());
-            const size_t items = (size_t)((total + cgrid - 1) / cgrid) * mats;
-            const size_t clds = (size_t)8 * CS_RBT * CS_STRIPE + items * 8 * sizeof(float) + 64;
-            using CFn = void (*)(const GemvParams);
-            static const CFn ct[2] = {gemv_q8_colsplit_kernel<false>, gemv_q8_colsplit_kernel<true>};
-            static const bool ok = raise_lds_limit((const void*)ct[0]) && raise_lds_limit((const void*)ct[1]);
-            if (ok && clds <= 150 * 1024) {
-                hipLaunchKernelGGL(ct[norm_w ? 1 : 0], dim3(cgrid), dim3(512), clds, st, L.p);
-                return last_launch_status();
-            }
-        }
-    }
-#endif
     const dim3 g(L.grid), b(64 * L.nwaves);
 #ifdef NTK_GEMV_TRACE
     static int trace_counter = 0;
@@ -1060,24 +997,6 @@ int q8l_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in, c
     return last_launch_status();
 }
 
-#ifdef NTK_EXPERIMENTS
-template <int DT>
-static int launch_att(const AttnFuse& att, const ntk_gemv_seg* seg, int in, const float* resid, hipStream_t st) {
-    GemvLaunch L;
-    const int rc = prepare_quant<DT>(seg, 1, att.out, in, nullptr, 0.0f, resid, 0, max_workgroups(), L);
-    if (rc != NTK_OK) return rc;
-    // the attention variant exists for the aligned fast prologue on 8-wave workgroups, rows starting 16-byte aligned
-    if (!L.xfast || L.nwaves != 8 || L.p.seg[0].delta != 0 || L.p.total_rows == 0 || L.grid < 1) return NTK_E_ALIGN;
-    const size_t att_lds = sizeof(float) * ((size_t)3 * att.hd + 16 + (size_t)8 * att.hd);
-    if (att_lds > L.lds) return NTK_E_SHAPE;
-    if (L.lds > 64 * 1024) {
-        static bool once = hipFuncSetAttribute((const void*)gemv_quant_att_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-        if (!once || L.lds > 160 * 1024) return NTK_E_SHAPE;
-    }
-    hipLaunchKernelGGL(gemv_quant_att_kernel<DT>, dim3(L.grid + att.n_heads), dim3(64 * L.nwaves), L.lds, st, L.p, att);
-    return last_launch_status();
-}
-#endif
 
 // segments of two formats sharing x (no residual / SiLU epilogue): one launch, workgroups split by bytes
 template <int DTA, int DTB>
@@ -1185,33 +1104,6 @@ int ntk_gemv_add(float* y, const void* W, const float* x, int out_features, int 
     return ntk::launch_dense<true>(y, W, x, out_features, in_features, weight_dtype, ntk::resolve_stream(stream));
 }
 
-#ifdef NTK_EXPERIMENTS
-int ntk_attention_gemv_fused(float* attn_out, const float* q, const float* k, const float* v, void* k_cache, void* v_cache,
-                             const int* d_pos, const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq,
-                             float scale, float theta_base, float freq_scale, const ntk_gemv_seg* wo, const float* resid,
-                             unsigned* sync3, void* stream) {
-    if (!attn_out || !q || !k || !v || !k_cache || !v_cache || !d_pos || !wo || !wo->W || !wo->y || !sync3) return NTK_E_NULL;
-    if (n_heads <= 0 || n_kv_heads <= 0 || n_heads % n_kv_heads != 0 || max_seq <= 0) return NTK_E_SHAPE;
-    if (head_dim != 64 && head_dim != 128 && head_dim != 256) return NTK_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(k_cache) & 15) || (reinterpret_cast<uintptr_t>(v_cache) & 15)) return NTK_E_ALIGN;
-    ntk::AttnFuse a{};
-    a.q = q; a.k = k; a.v = v; a.out = attn_out;
-    a.kc = static_cast<uint16_t*>(k_cache); a.vc = static_cast<uint16_t*>(v_cache);
-    a.d_pos = d_pos; a.inv_freq = inv_freq; a.sync = sync3;
-    a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.hd = head_dim; a.max_seq = max_seq;
-    a.scale = scale; a.theta = theta_base; a.fscale = freq_scale;
-    const int in = n_heads * head_dim;
-    hipStream_t st = ntk::resolve_stream(stream);
-    switch (wo->dtype) {
-        case NTK_DT_Q8_0: return ntk::launch_att<NTK_DT_Q8_0>(a, wo, in, resid, st);
-        case NTK_DT_Q4_0: return ntk::launch_att<NTK_DT_Q4_0>(a, wo, in, resid, st);
-        case NTK_DT_Q4_K: return ntk::launch_att<NTK_DT_Q4_K>(a, wo, in, resid, st);
-        case NTK_DT_Q5_K: return ntk::launch_att<NTK_DT_Q5_K>(a, wo, in, resid, st);
-        case NTK_DT_Q6_K: return ntk::launch_att<NTK_DT_Q6_K>(a, wo, in, resid, st);
-        default: return NTK_E_DTYPE;
-    }
-}
-#endif
 
 static int gemv_fused_form(const ntk_gemv_seg* segs, int nseg, const float* x, int in_features, const float* norm_w, float eps,
                            const float* resid, int silu_pair, void* stream, int xi_mode) {

@@ -1,4 +1,4 @@
-// gemv_core.hip.h -- per-format decode of the dequant-fused GEMV (shared by gemv.hip and decode_persistent.hip).
+// gemv_core.hip.h -- per-format decode of the dequant-fused GEMV (gemv.hip).
 //
 // Replaces the arithmetic of the reference's gemv_{q4_0,q8_0,q4_k,q5_k,q6_k}_kernel (reference src/cuda/gemm.cu:32-470):
 // same per-block math (integer quant x F32 activation, F32 accumulate, FP16 scale per block / 6-bit sub-scale per
@@ -10,13 +10,6 @@
 namespace ntk {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// 16-byte global load the compiler does not see in its s_waitcnt bookkeeping (base: uniform pointer, off: bytes)
-__device__ __forceinline__ u32x4 asm_load16(const void* base, unsigned off) {
-    u32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(off), "s"(base) : "memory");
-    return v;
-}
 
 constexpr int RB = 4;            // rows (items) per batch between cross-wave combines (8 measured the same)
 constexpr int XPITCH = 68;       // floats per 64-column lane row in the prologue LDS image (conflict-free b128)
@@ -42,53 +35,15 @@ template <int DT> struct Fmt;
 // BW/BB: weights / bytes per GGUF block; NL: 1 KiB chunks per <=4096-column slice (+15 alignment bytes);
 // MINW: waves per SIMD the register allocator must leave room for (4 -> <=128 VGPRs, 3 -> <=168: the 5/6-bit
 // decoders keep more packed dwords live and would otherwise spill the prefetch registers)
-// NBUF: row slices per wave of an LDS-DMA ring (EXPERIMENTS=1 builds: the persistent token kernel)
-template <> struct Fmt<NTK_DT_Q8_0> { static constexpr int BW = 32, BB = 34, NL = 5, MINW = 4, NBUF = 1; };
-template <> struct Fmt<NTK_DT_Q4_0> { static constexpr int BW = 32, BB = 18, NL = 3, MINW = 4, NBUF = 3; };
-template <> struct Fmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, NL = 3, MINW = 4, NBUF = 3; };
-template <> struct Fmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, NL = 3, MINW = 4, NBUF = 2; };
-template <> struct Fmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, NL = 4, MINW = 4, NBUF = 2; };
-// bytes of one ring slot: a <= 4096-column slice + its alignment shift, rounded to 16, + 16 (the row's residual value)
-template <int DT> constexpr int DMA_SLOT = ((4096 / Fmt<DT>::BW * Fmt<DT>::BB + 30) / 16) * 16 + 16;
-// (Round 3 also built the row stream of gemv.hip on such a ring -- two or three row slices in flight per wave instead of one -- and measured
+template <> struct Fmt<NTK_DT_Q8_0> { static constexpr int BW = 32, BB = 34, NL = 5, MINW = 4; };
+template <> struct Fmt<NTK_DT_Q4_0> { static constexpr int BW = 32, BB = 18, NL = 3, MINW = 4; };
+template <> struct Fmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, NL = 3, MINW = 4; };
+template <> struct Fmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, NL = 3, MINW = 4; };
+template <> struct Fmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, NL = 4, MINW = 4; };
+// (Round 3 also built the row stream of gemv.hip on an LDS-DMA ring -- two or three row slices in flight per wave instead of one -- and measured
 // NOTHING: Q4_K gate|up 16.7 -> 16.3 us, LM head 52.8 -> 52.7, 70B gate|up 48.7 -> 49.1 (profiles/r03_gemv_lds_dma_ring_experiment.txt):
 // the long K-quant launches were bound by VALU issue, not by bytes in flight.  That form was removed in round 4, when the matrix-core
 // GEMV of gemv_rp.hip took the K-quant launches of the engine.)
-
-// ---- LDS-DMA: up to 1 KiB per wave instruction straight from HBM into the wave's ring slot (no VGPR bounce, no ds_write) ----
-// lds_dst: wave-uniform LDS byte address the wave's lane 0 writes (lane l writes lds_dst + 16 l / 4 l); gsrc: this lane's source.
-// M0 is compiler-reserved: saved, set and restored inside the one statement that uses it (cdna_hip_programming.md 5.7).  Inactive
-// lanes (EXEC) move nothing.  The compiler does not count these loads: the waits are explicit (wait_vm).
-__device__ __forceinline__ void dma16(uint32_t lds_dst, const uint8_t* gsrc) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma4(uint32_t lds_dst, const float* gsrc) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// wait until at most n of the wave's vector-memory operations are outstanding (they complete in order): n = the operations issued
-// AFTER the last DMA instruction of the row that must have landed.  An operation issued and not counted only makes the wait
-// stricter than needed, never weaker; counting one that was not issued would be the bug.
-__device__ __forceinline__ void wait_vm(unsigned n) {   // wave-uniform
-    if (n >= 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-    else if (n == 13) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-    else if (n == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (n == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-    else if (n == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if (n == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if (n == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (n == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if (n == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (n == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if (n == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (n == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if (n == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if (n == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
 
 // ---- how a row is cut into column slices (host): ns slices of slice_cols columns, the last one possibly shorter.  ONE rule for the launcher
 // (prepare_quant, gemv.hip) and for the lane-major Q8_0 packer below: the packed layout follows the launch's slices.

@@ -62,18 +62,16 @@ def test_reference_surface_header_is_the_reference_surface():
     assert not [n for n in names if "debug" in n or "fused" in n or "_rp" in n or "gemm_quant" in n]
 
 
-def test_experiments_are_a_separate_library():
-    """experiments/ntk_experiments.h (the persistent token kernel, the layer engine, attention inside the Wo launch: all measured slower than the
-    launch path) is exported by experiments/libntransformer_hip_exp.so (make -C experiments; not built by default) and by nothing in the shipping library."""
-    names = declared_functions("ntk_experiments.h", "experiments")
-    assert "ntk_persistent_launch" in names and "ntk_attention_gemv_fused" in names
+RETIRED_ENTRY_POINTS = ["ntk_persistent_plan_create", "ntk_persistent_launch", "ntk_persistent_error", "ntk_layer_engine_plan_create",
+                        "ntk_layer_engine_launch", "ntk_layer_engine_error", "ntk_attention_gemv_fused", "nt_engine_persistent_plan",
+                        "nt_engine_persistent_kind"]
+
+
+def test_retired_experiments_are_not_in_the_library():
+    """The persistent token kernel, the layer engine and attention inside the Wo launch all measured slower than the launch path
+    (profiles/NEGATIVE_RESULTS.md) and were removed with their engine hooks: the shipping library exports none of their entry points."""
     L = _lib.lib()
-    assert not [n for n in names if hasattr(L, n)]
-    exp = os.path.join(ROOT, "experiments", "libntransformer_hip_exp.so")
-    if not os.path.exists(exp):
-        pytest.skip("libntransformer_hip_exp.so not built")
-    X = C.CDLL(exp)
-    assert not [n for n in names if not hasattr(X, n)]
+    assert not [n for n in RETIRED_ENTRY_POINTS if hasattr(L, n)]
 
 
 def test_prompt_gemm_workspace_covers_its_layout():

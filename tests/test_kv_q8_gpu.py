@@ -314,11 +314,6 @@ def test_engine_refuses_what_the_8_bit_cache_does_not_cover():
         e.load_synthetic(small_spec(), 256)
     assert "tensor parallelism" in str(ei.value)
     e.close()
-    e = E.Engine()
-    e.set_option("kv_cache", "q8_0")
-    with pytest.raises(_lib.NtkError):
-        e.set_option("fuse_attention", 1)
-    e.close()
 
 
 def test_engine_cache_contents_after_a_prompt_pass():

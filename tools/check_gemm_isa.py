@@ -5,7 +5,7 @@ are asynchronous, so the build is only correct if NO compiler-generated instruct
 compiles the kernel to ISA and checks, per instantiation, that every VGPR written by a ring load appears in no other instruction
 than ring loads and the ds_write_b128 that consume them.
 usage: python tools/check_gemm_isa.py [--hipcc HIPCC] [--flags "HIPFLAGS"]   (exit code 1 on a violation)
-The Makefile runs it on the exact compiler and flags of every build of the library (shipping, trace, tuning, experiments)."""
+The Makefile runs it on the exact compiler and flags of every build of the library (shipping, trace, tuning)."""
 import argparse, os, re, shlex, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()

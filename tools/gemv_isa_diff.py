@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Did a change of the decode GEMV's sources change its kernels?  Compiles ntransformer_amd/csrc/gemv.hip of git revision <rev> and of the working
-tree to gfx950 assembly with the Makefile's flags (no GPU needed, ~20 s each) and compares them kernel symbol by kernel symbol: the instruction
-streams with labels renumbered and comments dropped, and the compiler's figures per kernel (VGPRs, spilled VGPRs, private segment, occupancy,
-static LDS, SGPRs, code length).  Prints the list of symbols and per kernel "identical" or the figures and the first differing lines.
+"""Did a change of the sources change the kernels?  Compiles one device source of ntransformer_amd/csrc (--source, default gemv.hip: the decode
+GEMV) of git revision <rev> and of the working tree to gfx950 assembly with the Makefile's flags -- the per-file extra flags included (the FLAGS_<stem>
+lines of each tree's csrc/Makefile) -- and compares them kernel symbol by kernel symbol (no GPU needed, ~20 s per build of gemv.hip): the
+instruction streams with labels renumbered and comments dropped, and the compiler's figures per kernel (VGPRs, spilled VGPRs, private segment,
+occupancy, static LDS, SGPRs, code length).  Prints the list of symbols and per kernel "identical" or the figures and the first differing lines.
 
     python tools/gemv_isa_diff.py f5f1f26 > profiles/gemv_stages_isa.txt
+    python tools/gemv_isa_diff.py f5f1f26 --source attention_q8.hip
 """
 import argparse
 import difflib
@@ -23,14 +25,18 @@ FIGURES = [("vgprs", r"; NumVgprs: (\d+)"), ("spilled_vgprs", None), ("private_s
 BOUNDED = {"vgprs": "max", "spilled_vgprs": "max", "private_segment": "max", "occupancy": "min", "static_lds": "eq"}   # the rest is reported only
 
 
-def assembly(tree, hipcc, extra):
+def assembly(tree, hipcc, extra, source):
+    """(assembly text, flags used): HIPFLAGS + the tree's own `FLAGS_<stem> := ...` line of csrc/Makefile for this source + extra"""
+    with open(os.path.join(tree, CSRC, "Makefile")) as f:
+        own = re.search(r"^FLAGS_%s\s*:=\s*(.*)$" % re.escape(os.path.splitext(source)[0]), f.read(), re.M)
+    extra = " ".join(x for x in (own.group(1).strip() if own else "", extra) if x)
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
-    cmd = [hipcc] + FLAGS.split() + extra.split() + ["-S", "--cuda-device-only", "gemv.hip", "-o", out]
+    cmd = [hipcc] + FLAGS.split() + extra.split() + ["-S", "--cuda-device-only", source, "-o", out]
     subprocess.run(cmd, cwd=os.path.join(tree, CSRC), check=True, stderr=subprocess.DEVNULL)
     with open(out) as f:
         text = f.read()
     os.unlink(out)
-    return text
+    return text, extra
 
 
 def kernels(text):
@@ -70,15 +76,17 @@ def main():
     ap.add_argument("rev")
     ap.add_argument("--hipcc", default="/opt/rocm/bin/hipcc")
     ap.add_argument("--flags", default="", help="extra flags for both builds (e.g. -DNTK_GEMV_TRACE)")
+    ap.add_argument("--source", default="gemv.hip", help="the device source of ntransformer_amd/csrc to compare (sources.mk)")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         tar = subprocess.run(["git", "archive", a.rev, CSRC, "include"], cwd=ROOT, check=True, capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
-        old = kernels(assembly(tmp, a.hipcc, a.flags))
-    new = kernels(assembly(ROOT, a.hipcc, a.flags))
+        old = kernels(assembly(tmp, a.hipcc, a.flags, a.source)[0])
+    text, extra = assembly(ROOT, a.hipcc, a.flags, a.source)
+    new = kernels(text)
     rev = subprocess.run(["git", "rev-parse", "--short", a.rev], cwd=ROOT, check=True, capture_output=True, text=True).stdout.strip()
     nice = demangle(sorted(set(old) | set(new)))
-    print("# gemv.hip -> gfx950 assembly, %s against the working tree; flags: %s %s" % (rev, FLAGS, a.flags))
+    print("# %s -> gfx950 assembly, %s against the working tree; flags: %s %s" % (a.source, rev, FLAGS, extra))
     print("# kernels: %d at %s, %d now; symbols only at %s: %s; only now: %s" % (len(old), rev, len(new), rev, sorted(set(old) - set(new)) or "none",
                                                                                sorted(set(new) - set(old)) or "none"))
     bad = 0
