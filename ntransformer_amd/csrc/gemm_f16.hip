@@ -37,6 +37,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include "gemm_f16_plan.h"
 
 namespace ntk {
 
@@ -45,22 +46,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-constexpr int GB_TOK = 64;           // tokens per pass
-// K splits x 64-token chunks of one launch never exceed this (size of the partial-sum area): 32 for matrices of up to 8192 rows (the narrow
-// ones are the ones that need splits at many chunks), 16 above
-constexpr int gb_split_rows(int out_total) { return out_total <= 8192 ? 32 : 16; }
-constexpr int GB_MAX_CHUNKS = 16;   // 64-token chunks per launch (32 measured no better: 15.1k vs 16.0k tok/s at 2048 tokens)
-constexpr int GB_PIECE = 1024;       // bytes of one (step, plane, token block) operand record
-constexpr int GB_PLANES = 2;         // FP16 pieces of an activation
-constexpr int GB_STEP_BYTES = GB_PLANES * 4 * GB_PIECE;   // 8 KB of activation operands per step
-#ifdef NTK_GEMM_OCC3   // tuning build: three workgroups (12 waves) per CU -- 168 VGPRs, 53 KB of LDS each (Q8_0 without the plane prefetch fits)
-constexpr int GB_WG_PER_CU = 3, GB_LDS_WG = 53 * 1024, GB_NRING_Q8 = 1;
-#else
-constexpr int GB_WG_PER_CU = 2, GB_LDS_WG = 80 * 1024, GB_NRING_Q8 = 2;
-#endif
-constexpr int GB_AUX_BYTES = GB_TOK * 4;                  // per step: one eighth of its unit's record of sums (K-quant minimum term)
-constexpr int GB_MIN_UNIT_BYTES = 8 * GB_AUX_BYTES;       // per unit of 8 steps and 64-token chunk: 2 pieces x 4 token blocks x 2 x 16 tokens x 4 steps x FP16
 
 // bytes k, k + 1 of a dword -> an FP16 pair, one SDWA conversion each (through F32 it is two conversions and a pack per pair: the
 // VALU slots of a step are what the kernel runs out of first); `s_nop 1`: see cvt8_s8_f16 below (these feed the minimum term's matrix instruction)
@@ -262,9 +247,6 @@ __global__ __launch_bounds__(256) void silu_mul_rowmax_kernel(float* __restrict_
 // token's row knows its largest |x| and can split the row itself: planes, step sums and 1 / s go straight into the GEMM workspace and the projection runs
 // with reuse_x = 1.  split_row is split_x_kernel's arithmetic element for element (same scale, same two roundings, the step sums in the same order): the
 // workspace holds the same bits.  Layout of the workspace: [chunk][(in / 32 + 1) step records of 8 KB | sums of the units], then [1 / s][s] of the pass.
-static __host__ __device__ size_t ws_chunk_bytes(int in) {
-    return ((size_t)(in / 32 + 1) * GB_STEP_BYTES + (size_t)((in / 32 + 15) / 8) * GB_MIN_UNIT_BYTES + 255) / 256 * 256;
-}
 // row: the token's `in` floats (global memory; written by THIS workgroup before a __syncthreads()), or null for a padding token (zeros: the records the
 // matrix instructions read beside the prompt's last tokens).  Every thread of the workgroup calls it.
 __device__ __forceinline__ void split_row(const float* row, uint32_t max_bits, int t, int in, uint8_t* __restrict__ ws) {
@@ -316,8 +298,6 @@ __device__ __forceinline__ void split_row(const float* row, uint32_t max_bits, i
         }
     }
 }
-// tokens of the launch rounded up to the token blocks the matrix instructions read (16 per block; the 64-token form reads whole chunks)
-static inline int split_pad_tokens(int T) { return T <= 32 ? (T + 15) / 16 * 16 : (T + GB_TOK - 1) / GB_TOK * GB_TOK; }
 
 // X[T][in] (any producer) -> workspace: row maximum + split, one workgroup per token (instead of row_scale_kernel + split_x_kernel)
 __global__ __launch_bounds__(256) void rowmax_split_kernel(const float* __restrict__ X, int T, int in, uint8_t* __restrict__ ws) {
@@ -385,13 +365,10 @@ template <int DT> struct DeqI;
 // j = step within the unit, k = parity of the unit (both compile-time after unrolling).  row = the row's image + the unit's
 // shift (4-byte aligned: the launch checks the row pitch), rowg = row + 4 g.
 
-template <> struct DeqI<NTK_DT_Q8_0> {   // types.h:104-108: half d, int8 qs[32]
-    static constexpr int BW = 32, BB = 34;
-    static constexpr int SPU = 4, UB = 136, NCH = 10, STRIDE = 176;   // window: shift (0, 4, 8 or 12) + 136 <= 160
-    static constexpr int ROW_ALIGN = 4;                               // row pitch: in_features a multiple of 64
+template <> struct DeqI<NTK_DT_Q8_0> : GemmFmt<NTK_DT_Q8_0> {   // types.h:104-108: half d, int8 qs[32]
+    static constexpr int UB = 136, NCH = 10;                          // unit = 4 blocks; window: shift (0, 4, 8 or 12) + 136 <= 160 (< STRIDE = 176)
     static constexpr int NRING = GB_NRING_Q8;                         // units in flight per wave (register ring): 8 steps ahead of the MFMAs
-    static constexpr bool SPLIT16 = false, HAS_MIN = false, PF = true;
-    static constexpr bool RP = false; static constexpr int PPI = 0, ITEM = 0, S1 = 0, S2 = 0;
+    static constexpr int PPI = 0;
     struct Hdr {};
     struct MinOp {};
     __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
@@ -414,40 +391,9 @@ template <> struct DeqI<NTK_DT_Q8_0> {   // types.h:104-108: half d, int8 qs[32]
     }
 };
 
-// Q8_0 in WIDE units for the K-slice form (round 6, late; NOT the default): 16 or 8 blocks = 544 / 272 bytes per row and request instead of 136.  The idea:
-// the short-prompt launches keep ~18 MB in flight and still stream at 2.5 TB/s -- a 7 us queue -- so maybe the memory side does not deliver more to requests
-// of 160 bytes per row.  Measured, same box, alternated twice (profiles/r06_prompt_kslice.txt section 7): SLOWER -- 8B Q8_0 16 tokens 4.73 -> 4.94 (16 blocks) /
-// 4.98 ms (8), 32 tokens 5.79 -> 6.86: the request shape is not the bound; bigger images leave room for fewer steps of planes, i.e. more slices.  Same bytes,
-// same decode (load / convert are DeqI<NTK_DT_Q8_0>'s with j up to 15), image rows of 592 = 16 x 37 bytes (conflict-free like 176 = 16 x 11); bit-identical
-// per slice plan and checked against the oracle (tools/debug/dbg_kslice2.py).  -DNTK_GK_Q8_BLOCKS=16 (or 8) rebuilds it.
-constexpr int GB_WIDE = 64;   // DT + GB_WIDE (internal to this file)
-template <> struct DeqI<NTK_DT_Q8_0 + GB_WIDE> {
-    static constexpr int BW = 32, BB = 34;
-#ifndef NTK_GK_Q8_BLOCKS
-#define NTK_GK_Q8_BLOCKS 4    // blocks per unit: 4 = the units of the other kernels (the default: no wide form), 16 (544 bytes per row and request) or 8 (272)
-#endif
-#if NTK_GK_Q8_BLOCKS == 8
-    static constexpr int SPU = 8, UB = 272, NCH = 18, STRIDE = 304;    // window: shift (0, 4, 8 or 12) + 272 <= 288; 304 = 16 x 19
-#else
-    static constexpr int SPU = 16, UB = 544, NCH = 35, STRIDE = 592;   // window: shift (0, 4, 8 or 12) + 544 <= 560; 592 = 16 x 37
-#endif
-    static constexpr int ROW_ALIGN = 4, NRING = 1;
-    static constexpr bool SPLIT16 = false, HAS_MIN = false, PF = true;
-    static constexpr bool RP = false; static constexpr int PPI = 0, ITEM = 0, S1 = 0, S2 = 0;
-    using Base = DeqI<NTK_DT_Q8_0>;
-    using Hdr = Base::Hdr; using MinOp = Base::MinOp; using Raw = Base::Raw;
-    __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
-    __device__ static Hdr header(const uint8_t*, const uint8_t*) { return Hdr{}; }
-    template <bool AL> __device__ static Raw load(const uint8_t* row, const uint8_t* rowg, const Hdr& h, int j, int k) { return Base::template load<AL>(row, rowg, h, j, k); }
-    template <bool AL> __device__ static AOp convert(const Raw& r, int j, int k) { return Base::template convert<AL>(r, j, k); }
-};
-
-template <> struct DeqI<NTK_DT_Q4_0> {   // types.h:97-100: half d, 16 bytes of nibbles: w_j = d (lo_j - 8), w_{j+16} = d (hi_j - 8)  (gemm.cu:32-86)
-    static constexpr int BW = 32, BB = 18;
-    static constexpr int SPU = 8, UB = 144, NCH = 10, STRIDE = 176;   // unit = 8 blocks; window: shift (<= 14) + 144 <= 160
-    static constexpr int ROW_ALIGN = 4, NRING = 1;                    // row pitch: in_features a multiple of 64
-    static constexpr bool SPLIT16 = false, HAS_MIN = false, PF = true;
-    static constexpr bool RP = false; static constexpr int PPI = 0, ITEM = 0, S1 = 0, S2 = 0;
+template <> struct DeqI<NTK_DT_Q4_0> : GemmFmt<NTK_DT_Q4_0> {   // types.h:97-100: half d, 16 bytes of nibbles: w_j = d (lo_j - 8), w_{j+16} = d (hi_j - 8)  (gemm.cu:32-86)
+    static constexpr int UB = 144, NCH = 10;                          // unit = 8 blocks; window: shift (<= 14) + 144 <= 160 (< STRIDE = 176)
+    static constexpr int NRING = 1, PPI = 0;
     struct Hdr {};
     struct MinOp {};
     __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
@@ -474,12 +420,9 @@ template <> struct DeqI<NTK_DT_Q4_0> {   // types.h:97-100: half d, 16 bytes of 
     }
 };
 
-template <> struct DeqI<NTK_DT_Q4_K> {   // types.h:112-117: half d, dmin; 12 packed 6-bit (scale, min); 128 bytes of nibbles
-    static constexpr int BW = 256, BB = 144;
-    static constexpr int SPU = 8, UB = 144, NCH = 9, STRIDE = 144;     // rows are 16-byte aligned: no shift
-    static constexpr int ROW_ALIGN = 16, NRING = 1;
-    static constexpr bool SPLIT16 = false, HAS_MIN = true, PF = true;
-    static constexpr bool RP = false; static constexpr int PPI = 0, ITEM = 0, S1 = 0, S2 = 0;
+template <> struct DeqI<NTK_DT_Q4_K> : GemmFmt<NTK_DT_Q4_K> {   // types.h:112-117: half d, dmin; 12 packed 6-bit (scale, min); 128 bytes of nibbles
+    static constexpr int UB = 144, NCH = 9;                            // rows are 16-byte aligned: no shift (STRIDE = UB)
+    static constexpr int NRING = 1, PPI = 0;
     struct Hdr { u32x4 h; };   // d | dmin, 12 scale bytes
     // the unit's 8 minima as the weight-side operand of the minimum-term MFMA: lane group g < 2 holds m_{4g} .. m_{4g+3} (FP16, exact),
     // the others zeros; -64 dmin for the FMA behind it (the sums are stored divided by 64)   (6-bit packing: gemm.cu:206-222)
@@ -508,12 +451,9 @@ template <> struct DeqI<NTK_DT_Q4_K> {   // types.h:112-117: half d, dmin; 12 pa
     }
 };
 
-template <> struct DeqI<NTK_DT_Q5_K> {   // types.h:122-128: half d, dmin; 12 packed 6-bit (scale, min); qh[32]; ql[128]
-    static constexpr int BW = 256, BB = 176;
-    static constexpr int SPU = 8, UB = 176, NCH = 11, STRIDE = 176;    // rows are 16-byte aligned: no shift
-    static constexpr int ROW_ALIGN = 16, NRING = 1;
-    static constexpr bool SPLIT16 = false, HAS_MIN = true, PF = true;
-    static constexpr bool RP = false; static constexpr int PPI = 0, ITEM = 0, S1 = 0, S2 = 0;
+template <> struct DeqI<NTK_DT_Q5_K> : GemmFmt<NTK_DT_Q5_K> {   // types.h:122-128: half d, dmin; 12 packed 6-bit (scale, min); qh[32]; ql[128]
+    static constexpr int UB = 176, NCH = 11;                           // rows are 16-byte aligned: no shift (STRIDE = UB)
+    static constexpr int NRING = 1, PPI = 0;
     struct Hdr { u32x4 h; uint32_t qh_lo, qh_hi; };   // d | dmin, 12 scale bytes; the lane's 8 bytes of fifth bits (all 8 steps)
     // the unit's 8 minima as the weight-side operand of the minimum-term MFMA: lane group g < 2 holds m_{4g} .. m_{4g+3} (FP16, exact),
     // the others zeros; -64 dmin for the FMA behind it (the sums are stored divided by 64)   (6-bit packing: gemm.cu:206-222)
@@ -544,12 +484,9 @@ template <> struct DeqI<NTK_DT_Q5_K> {   // types.h:122-128: half d, dmin; 12 pa
     }
 };
 
-template <> struct DeqI<NTK_DT_Q6_K> {   // types.h:132-137: ql[128], qh[64], int8 scales[16], half d
-    static constexpr int BW = 256, BB = 210;
-    static constexpr int SPU = 8, UB = 210, NCH = 14, STRIDE = 240;    // window: shift (even, <= 14) + 210 <= 224
-    static constexpr int ROW_ALIGN = 4, NRING = 1;                     // row pitch: in_features a multiple of 512
-    static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
-    static constexpr bool RP = false; static constexpr int PPI = 0, ITEM = 0, S1 = 0, S2 = 0;
+template <> struct DeqI<NTK_DT_Q6_K> : GemmFmt<NTK_DT_Q6_K> {   // types.h:132-137: ql[128], qh[64], int8 scales[16], half d
+    static constexpr int UB = 210, NCH = 14;                           // window: shift (even, <= 14) + 210 <= 224 (< STRIDE = 240)
+    static constexpr int NRING = 1, PPI = 0;
     struct Hdr { float d; };
     struct MinOp {};
     __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
@@ -601,14 +538,11 @@ template <> struct DeqI<NTK_DT_Q6_K> {   // types.h:132-137: ql[128], qh[64], in
 //   column c of the super-block: step s = c >> 7, half h = (c >> 6) & 1 (low / high nibble), lane group kg = (c >> 4) & 3, byte b = c & 15 of lane 16 kg + i's chunk
 //   => sub-block j: s = j >> 2, h = (j >> 1) & 1, the two 16-column groups kg = 2 (j & 1) and 2 (j & 1) + 1
 // `row` = the tile's image + 16 i, `rowg` = row + 4 g (so P1 of (s, kg) is rowg + s S1 + 256 kg and the row record row + 2 S1).
-constexpr int GB_RP = 32;   // DT + GB_RP = the same format read from the repack (internal to this file)
+// (DT + GB_RP = the same format read from the repack: gemm_f16_plan.h)
 struct RpHdr { u32x4 rec; uint32_t dd; };
 
-template <> struct DeqI<NTK_DT_Q4_K + GB_RP> {
-    static constexpr bool RP = true;
-    static constexpr int S1 = 1024, S2 = 320, ITEM = 2 * S1 + S2, PPI = ITEM / 16;
-    static constexpr int BW = 256, BB = 144, SPU = 8, UB = 0, NCH = 0, STRIDE = ITEM / 16, ROW_ALIGN = 16, NRING = 1;
-    static constexpr bool SPLIT16 = false, HAS_MIN = true, PF = true;
+template <> struct DeqI<NTK_DT_Q4_K + GB_RP> : GemmFmt<NTK_DT_Q4_K + GB_RP> {
+    static constexpr int PPI = ITEM / 16, UB = 0, NCH = 0, NRING = 1;
     using Hdr = RpHdr;
     struct MinOp { uint32_t m0, m1; float ndmin64; };
     template <typename H> __device__ static MinOp min_operand(const H& hd, int g) {   // record bytes 8..15: m_0 .. m_7
@@ -635,11 +569,8 @@ template <> struct DeqI<NTK_DT_Q4_K + GB_RP> {
     }
 };
 
-template <> struct DeqI<NTK_DT_Q5_K + GB_RP> {
-    static constexpr bool RP = true;
-    static constexpr int S1 = 1280, S2 = 320, ITEM = 2 * S1 + S2, PPI = ITEM / 16;
-    static constexpr int BW = 256, BB = 176, SPU = 8, UB = 0, NCH = 0, STRIDE = ITEM / 16, ROW_ALIGN = 16, NRING = 1;
-    static constexpr bool SPLIT16 = false, HAS_MIN = true, PF = true;
+template <> struct DeqI<NTK_DT_Q5_K + GB_RP> : GemmFmt<NTK_DT_Q5_K + GB_RP> {
+    static constexpr int PPI = ITEM / 16, UB = 0, NCH = 0, NRING = 1;
     using Hdr = RpHdr;
     struct MinOp { uint32_t m0, m1; float ndmin64; };
     template <typename H> __device__ static MinOp min_operand(const H& hd, int g) {
@@ -671,11 +602,8 @@ template <> struct DeqI<NTK_DT_Q5_K + GB_RP> {
     }
 };
 
-template <> struct DeqI<NTK_DT_Q6_K + GB_RP> {
-    static constexpr bool RP = true;
-    static constexpr int S1 = 1536, S2 = 288, ITEM = 2 * S1 + S2, PPI = ITEM / 16;
-    static constexpr int BW = 256, BB = 210, SPU = 8, UB = 0, NCH = 0, STRIDE = ITEM / 16, ROW_ALIGN = 16, NRING = 1;
-    static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
+template <> struct DeqI<NTK_DT_Q6_K + GB_RP> : GemmFmt<NTK_DT_Q6_K + GB_RP> {
+    static constexpr int PPI = ITEM / 16, UB = 0, NCH = 0, NRING = 1;
     struct Hdr { u32x4 rec; float d; };   // sc[16] (int8), d
     struct MinOp {};
     __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
@@ -710,15 +638,12 @@ template <> struct DeqI<NTK_DT_Q6_K + GB_RP> {
 // Step timeline (tuning builds only: make trace): lane 0 of every wave of workgroup 0 records the shader clock before the step's
 // wait, after its barrier and (level 2) once the step's LDS reads have returned; read back with ntk_debug_gemm_f16_trace(),
 // printed by tools/gemm_f16_trace.py.  The stamps sit in LDS (a global store would join the vmcnt arithmetic).
-#ifdef NTK_GEMM_TRACE
-constexpr int GBT_STEPS = 96, GBT_EV = 3;
+#ifdef NTK_GEMM_TRACE   // (GBT_STEPS, GBT_EV, GB_TRACE_LDS: gemm_f16_plan.h)
 __device__ unsigned long long g_gemm_f16_trace[4][GBT_STEPS][GBT_EV];
 __device__ unsigned long long g_gemm_f16_clock[4];   // workgroup 0: shader clock and the constant 100 MHz clock at its first and last step
-constexpr int GB_TRACE_LDS = 4 * GBT_STEPS * GBT_EV * 8;
 #define GB_STAMP(step, ev) do { if (gbt_on && (step) < GBT_STEPS) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
         if (lane == 0) gbt[((size_t)wave * GBT_STEPS + (step)) * GBT_EV + (ev)] = t_; } } while (0)
 #else
-constexpr int GB_TRACE_LDS = 0;
 #define GB_STAMP(step, ev) do {} while (0)
 #endif
 
@@ -731,27 +656,9 @@ constexpr int GB_TRACE_LDS = 0;
 constexpr int kGbAblate = NTK_GEMM_ABLATE;
 
 // the scale-FMAs of a token-block pair one pair behind its MFMAs (two-chunk form of the formats without a minimum term): round 6, same box, alternated twice:
-// 8B Q8_0 1024-token prompt 25 550 -> 26 400 tok/s (+3.3 %), gate | up 381 -> 363 us (profiles/r06_prompt_gemm_ab.txt).  -DNTK_GEMM_NO_SWP: the former order.
-#ifndef NTK_GEMM_NO_SWP
+// 8B Q8_0 1024-token prompt 25 550 -> 26 400 tok/s (+3.3 %), gate | up 381 -> 363 us (profiles/r06_prompt_gemm_ab.txt).
 constexpr bool GB_SWP = true;
-#else
-constexpr bool GB_SWP = false;
-#endif
-constexpr int GB_UPT = 2;     // units per loop trip (Q6_K: the parity of a unit, which decides its alignment, is then a compile-time constant)
-// LDS of a workgroup: a ring of NS activation step records (8 KB each, filled by LDS-DMA NS - 1 steps ahead), the ring of the steps'
-// per-token sums, the 4 waves' weight images.  NS = as many slots as leave room for two workgroups per CU (160 KB): a record that
-// misses the XCD's L2 takes ~2 us to arrive, and the records in flight are what hides it (a step consumes one in 0.3-0.4 us)
-// CW = 64-token chunks per workgroup (1 or 2: a slot then holds the records of both)
-template <int DT, int CW> constexpr int gb_aux_lds() { return DeqI<DT>::HAS_MIN ? CW * 2 * GB_MIN_UNIT_BYTES : 0; }   // two units of sums per chunk
-template <int DT, int RT, int CW> constexpr int gb_slots() {
-    const int n = (GB_LDS_WG - 4 * 16 * RT * DeqI<DT>::STRIDE - GB_TRACE_LDS - gb_aux_lds<DT, CW>()) / (CW * GB_STEP_BYTES);
-    return n > 8 ? 8 : (n < 3 ? 3 : n);
-}
-template <int DT, int RT, int CW> constexpr int gb_lds_bytes() {
-    return gb_slots<DT, RT, CW>() * CW * GB_STEP_BYTES + gb_aux_lds<DT, CW>() + 4 * 16 * RT * DeqI<DT>::STRIDE + GB_TRACE_LDS;
-}
 
-constexpr int GB_MAX_SEG = 3;   // matrices sharing X in one launch (Q | K | V, gate | up)
 struct GemmBSeg {
     const uint8_t* W;
     float* Y;               // [T][out]
@@ -1344,7 +1251,6 @@ struct GemmSParams {
     int T, in, steps;
     unsigned row_bytes;
 };
-template <int DT, int RT, int NTB> constexpr int gs_lds_bytes(int nw) { return nw * (16 * RT * DeqI<DT>::STRIDE + NTB * RT * 1024); }
 
 template <int DT, int RT, int NTB, bool AL>
 __global__ __launch_bounds__(512) void gemm_quant_f16_small_kernel(const GemmSParams p) {
@@ -1553,13 +1459,6 @@ __global__ __launch_bounds__(512) void gemm_quant_f16_small_kernel(const GemmSPa
 // and reads the B operands of a step from LDS.  Planes traffic = slice bytes per workgroup (Wo: 8 MB instead of 67); the slices' partial sums go to the
 // partial-sum area the K splits of the large kernel use ([slice][token][row]; summed in slice order by the launch that consumes the projection or by
 // reduce_splits_kernel), a launch with ONE slice writes Y itself.
-#ifndef NTK_GK_DEPTH4
-#define NTK_GK_DEPTH4 4   // units of 4 steps (Q8_0: 2176 B per 16 rows) in flight per wave
-#endif
-#ifndef NTK_GK_DEPTH8
-#define NTK_GK_DEPTH8 2   // units of 8 steps
-#endif
-template <int SPU> constexpr int gk_depth() { return SPU <= 4 ? NTK_GK_DEPTH4 : (SPU <= 8 ? NTK_GK_DEPTH8 : 1); }   // (16-step units: the next one, 8.7 KB per wave)
 struct GemmKParams {
     GemmBSeg seg[GB_MAX_SEG];
     int nseg;
@@ -1573,21 +1472,6 @@ struct GemmKParams {
     int tiles;                     // row tiles (16 RT rows) of all matrices; (blockIdx.x + job * gridDim.x) * NW + wave = this wave's in job `job`
     int jobs;                      // row groups per workgroup
 };
-// waves per workgroup: 8.  (16 -- four per SIMD at <= 128 registers, for the 16 rows x 16 tokens form -- measured SLOWER, same box, alternated twice: 8B Q8_0
-// 16 tokens 4.74 -> 5.60 ms, Q4_K_M 4.26 -> 4.66: twice the slices at half the length.  -DNTK_GK_WAVES_RT1=16 rebuilds it.  profiles/r06_prompt_kslice.txt)
-#ifndef NTK_GK_WAVES_RT1
-#define NTK_GK_WAVES_RT1 8
-#endif
-template <int DT, int RT, int NTB> constexpr int gk_waves() { return RT == 1 && NTB == 1 && !(DeqI<DT>::SPLIT16 && !DeqI<DT>::RP) ? NTK_GK_WAVES_RT1 : 8; }
-template <int DT, int RT, int NTB> constexpr int gk_lds_bytes(int nw, int slice_steps) {
-    return slice_steps * GB_PLANES * NTB * GB_PIECE + nw * (16 * RT * DeqI<DT>::STRIDE);
-}
-// steps of planes that fit beside the waves' images in the CU's 160 KB (whole units).  The images are counted at 256 bytes per row whatever the format
-// (176 .. 240 in fact): the raw GGUF form of a matrix and its decode repack then get the SAME slices -- and with them the same sums in the same order.
-template <int DT, int RT, int NTB> constexpr int gk_max_steps() {
-    constexpr int row = DeqI<DT>::STRIDE <= 256 ? 256 : DeqI<DT>::STRIDE;   // (the wide Q8_0 units: their own 592 -- Q8_0 has no repacked twin)
-    return (160 * 1024 - gk_waves<DT, RT, NTB>() * (16 * RT * row)) / (GB_PLANES * NTB * GB_PIECE) / DeqI<DT>::SPU * DeqI<DT>::SPU;
-}
 
 template <int DT, int RT, int NTB, bool AL>
 __global__ __launch_bounds__((64 * gk_waves<DT, RT, NTB>())) void gemm_quant_f16_kslice_kernel(const GemmKParams p) {
@@ -1612,11 +1496,7 @@ __global__ __launch_bounds__((64 * gk_waves<DT, RT, NTB>())) void gemm_quant_f16
         const uint8_t* src0 = p.xb + (size_t)u_lo * SPU * GB_STEP_BYTES + (size_t)lane * 16;
         for (int r = wave; r < nrec; r += NW) {
             const int s = r / (GB_PLANES * NTB), q = r - s * (GB_PLANES * NTB), pl = q / NTB, tb = q - pl * NTB;
-#ifdef NTK_GK_NO_DMA
-            *reinterpret_cast<u32x4*>(gk_lds + (size_t)r * GB_PIECE + lane * 16) = *reinterpret_cast<const u32x4*>(src0 + (size_t)s * GB_STEP_BYTES + (size_t)(pl * 4 + tb) * GB_PIECE);
-#else
             gb_dma16(__builtin_amdgcn_readfirstlane(lds0 + (uint32_t)r * GB_PIECE), src0 + (size_t)s * GB_STEP_BYTES + (size_t)(pl * 4 + tb) * GB_PIECE);
-#endif
         }
     }
     for (int it = 0; it < p.jobs; ++it) {
@@ -1974,328 +1854,164 @@ __global__ __launch_bounds__(256) void reduce_silu_mul_rowmax_kernel(float* __re
     if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(row_max) + t, __float_as_uint(m));
 }
 
-// one chunk's planes + sums (+ the record of zeros), rounded to 256 B
-// (the sums: whole units of 8 steps covering steps 0 .. in/32 + 7 -- the pre-pass writes a full unit of zeros behind the last step)
-
-constexpr size_t GB_SCALE_BYTES = 2 * GB_MAX_CHUNKS * GB_TOK * sizeof(float);   // the launch's 1 / s and s
-
 struct HostSeg { float* Y; const void* W; int out; };
+using I1 = std::integral_constant<int, 1>;
+using I2 = std::integral_constant<int, 2>;
 
-// T <= GB_MAX_CHUNKS * 64 = 1024 tokens in one launch; nseg matrices [out_s][in] of one format sharing X
-template <int DT>
-static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T, int in, const float* resid, void* ws, int reuse_x,
-                            const float* row_max, ntk_gemm_partials* defer, bool full_form, hipStream_t st) {
-    // (full_form: the form, K split and chunk pairing of a full pass -- GB_MAX_CHUNKS chunks -- whatever T is, never the short-prompt forms: a token's
-    // sums then run in the same order however the caller cuts its tokens into calls -- ntk_gemm_desc.full_form)
-    using D = DeqI<DT>;
-    constexpr int TRIP = GB_UPT * D::SPU;   // steps per loop trip: K ranges are whole trips
-    // whole units only (Q8_0: in a multiple of 128, Q4_0 and the K-quants: of 256): a partial last unit would decode the next row's bytes as
-    // scales -- any bit pattern, NaNs included -- against the zero activations of the padding steps
-    if (nseg < 1 || nseg > GB_MAX_SEG || (resid && nseg != 1) || in % (32 * D::SPU) != 0) return NTK_E_SHAPE;
-    const size_t row_bytes = (size_t)in / D::BW * D::BB;
-    long out_total = 0;
+// the plan's tuning switches (tuning builds only: the shipping library runs the defaults and reads no environment), read once
+static const GemmTune& gemm_tune() {
+    static constexpr GemmTune d{};
+    static const GemmTune t = [] {
+        GemmTune t;
+        t.kslice = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE", d.kslice); t.kslice_jobs = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_JOBS", d.kslice_jobs);
+        t.kslice_c0 = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_C0", d.kslice_c0); t.kslice_c1 = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_C1", d.kslice_c1);
+        t.kslice_rt = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_RT", d.kslice_rt); t.kslice_n = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_N", d.kslice_n);
+        t.small = NTK_TUNE_ENV_INT("NTK_GEMM_SMALL", d.small); t.small_rt = NTK_TUNE_ENV_INT("NTK_GEMM_SMALL_RT", d.small_rt);
+        t.small_nw = NTK_TUNE_ENV_INT("NTK_GEMM_SMALL_NW", d.small_nw); t.map = NTK_TUNE_ENV_INT("NTK_GEMM_MAP", d.map);
+        t.rt = NTK_TUNE_ENV_INT("NTK_GEMM_RT", d.rt); t.wgs = NTK_TUNE_ENV_INT("NTK_GEMM_WGS", d.wgs);
+        t.no_pf = NTK_TUNE_ENV_INT("NTK_GEMM_NO_PF", d.no_pf); t.cw = NTK_TUNE_ENV_INT("NTK_GEMM_CW", d.cw);
+        return t;
+    }();
+    return t;
+}
+
+// what a consumer needs of a launch: nsplit > 1 -- the partial sums are `part`'s and it sums them (and adds the residual) itself; 1 -- Y is written
+static void set_partials(ntk_gemm_partials* d, const HostSeg* segs, int nseg, int T, int nsplit, float* const* part) {
+    if (!d) return;
+    d->nseg = nseg; d->n_tokens = T; d->nsplit = nsplit;
+    for (int i = 0; i < nseg; ++i) { d->part[i] = part && nsplit > 1 ? part[i] : nullptr; d->y[i] = segs[i].Y; d->rows[i] = segs[i].out; }
+}
+static void reduce_splits(const HostSeg* segs, float* const* part, int nseg, int T, int nsplit, const float* resid, hipStream_t st) {
+    ReduceArgs ra{};
+    ra.nseg = nseg; ra.T = T; ra.nsplit = nsplit; ra.resid = resid;
+    size_t biggest = 0;
     for (int i = 0; i < nseg; ++i) {
-        if (segs[i].out <= 0 || segs[i].out % 16 != 0 || (size_t)segs[i].out * row_bytes > 0xFFFFFF00ull) return NTK_E_SHAPE;   // 32-bit piece offsets
-        if constexpr (D::RP) {
-            if ((size_t)(segs[i].out / 16) * (size_t)(in / 256) * (size_t)D::ITEM > 0xFFFFFFF0ull) return NTK_E_SHAPE;
-        }
-        if ((reinterpret_cast<uintptr_t>(segs[i].W) & 15) || (reinterpret_cast<uintptr_t>(segs[i].Y) & 15)) return NTK_E_ALIGN;
-        out_total += segs[i].out;
+        ra.Y[i] = segs[i].Y; ra.part[i] = part[i]; ra.out[i] = segs[i].out;
+        biggest = std::max(biggest, ((size_t)T * segs[i].out + 3) / 4);
     }
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (resid && (reinterpret_cast<uintptr_t>(resid) & 15))) return NTK_E_ALIGN;
-    GemmBParams p{};
-    p.nseg = nseg;
-    p.T = T; p.in = in; p.steps = in / 32;
-    p.chunks = (T + GB_TOK - 1) / GB_TOK;
-    p.chunk_bytes = ws_chunk_bytes(in);
-    p.row_bytes = (unsigned)row_bytes;
-    uint8_t* wsb = static_cast<uint8_t*>(ws);
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)((biggest + 255) / 256), nseg), dim3(256), 0, st, ra);
+}
+// what the three parameter structs share: the matrices in the plan's tile numbering, the operand planes, step sums and 1 / s in the workspace
+template <class P>
+static void fill_params(P& p, const GemmPlan& plan, const HostSeg* segs, int nseg, int T, int in, const float* resid, uint8_t* wsb, float* const* part) {
+    p.nseg = nseg; p.T = T; p.in = in; p.steps = in / 32; p.row_bytes = plan.row_bytes;
     p.xb = wsb;
-    p.aux = reinterpret_cast<const float*>(wsb + (size_t)(p.steps + 1) * GB_STEP_BYTES);
-    float* scales = reinterpret_cast<float*>(wsb + (size_t)GB_MAX_CHUNKS * p.chunk_bytes);   // [inv: 1024][scale: 1024]
-    p.inv = scales;
+    p.aux = reinterpret_cast<decltype(p.aux)>(wsb + (size_t)(p.steps + 1) * GB_STEP_BYTES);
+    p.inv = reinterpret_cast<const float*>(wsb + (size_t)GB_MAX_CHUNKS * ws_chunk_bytes(in));   // [inv: 1024][scale: 1024]
     p.resid = resid;
-    if (!reuse_x && row_max) {   // the tokens' largest |x| came with X: one pre-pass launch
-        hipLaunchKernelGGL(split_x_kernel<true>, dim3(p.steps + 8, p.chunks), dim3(256), 0, st, X, T, in, reinterpret_cast<u32x4*>(wsb),
-                           const_cast<float*>(p.aux), p.chunk_bytes, row_max, scales);
-    } else if (!reuse_x) {
-        hipLaunchKernelGGL(row_scale_kernel, dim3((T + 3) / 4), dim3(256), 0, st, X, T, in, scales + GB_MAX_CHUNKS * GB_TOK, scales);
-        hipLaunchKernelGGL(split_x_kernel<false>, dim3(p.steps + 8, p.chunks), dim3(256), 0, st, X, T, in, reinterpret_cast<u32x4*>(wsb),
-                           const_cast<float*>(p.aux), p.chunk_bytes, scales + GB_MAX_CHUNKS * GB_TOK, static_cast<float*>(nullptr));
-    }
-    // ---- short prompts (<= 32 tokens), second form: K-slice-stationary (gemm_quant_f16_kslice_kernel) ----
-    // Plan: RT (16 or 32 rows per wave) and the number of K slices, by a two-term model of the launch -- rounds of workgroups over the 256 CUs x (steps of
-    // a slice x RT + a fixed part worth `c0` steps: the copy of the planes, the first weights' round trip, the partial sums) -- over the slice counts that
-    // keep the planes within LDS (gk_max_steps: 64 / NTB steps beside 16-row images, 48 / NTB beside 32-row ones) and the partial sums within their area.
-    static const int kslice_env = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE", -1);   // (tuning builds only: 0 = never, n = up to n tokens)
-    const int kslice_max = kslice_env >= 0 ? kslice_env : 32;
-    // (Four token blocks -- 33 .. 64 tokens -- were built and measured as well: 8B Q8_0 64 tokens 6.38 -> 8.74 ms, Q4_K_M 6.75 -> 9.57: 16-step slices, 8 - 28 of
-    // them per matrix, and up to 58 MB of partial sums per launch; the 64-token chunk form keeps those.  profiles/r06_prompt_kslice.txt)
-    // (Q8_0: -DNTK_GK_Q8_BLOCKS=16 or 8 runs this form in wide units, DeqI<NTK_DT_Q8_0 + GB_WIDE> -- measured slower: see there; the default keeps KDT = DT)
-    constexpr int KDT = (DT == NTK_DT_Q8_0 && NTK_GK_Q8_BLOCKS > 4) ? NTK_DT_Q8_0 + GB_WIDE : DT;
-    using KD = DeqI<KDT>;
-    if (!full_form && T <= kslice_max && T <= 32 && in % (32 * KD::SPU) == 0) {
-        const int ntb = T <= 16 ? 1 : 2;
-        const int units = in / (32 * KD::SPU);
-        static const int c0 = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_C0", 32), force_krt = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_RT", 0),
-                         force_kn = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_N", 0);   // (tuning builds only)
-        static const int c1 = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_C1", 8), max_jobs = NTK_TUNE_ENV_INT("NTK_GEMM_KSLICE_JOBS", 64);   // (tuning builds only; JOBS=1: one row group per workgroup)
-        int best_n = 0, best_rt = 0, best_ups = 0, best_jobs = 1;
-        double best_cost = 1e30;
-        for (int krt = 1; krt <= 2; ++krt) {
-            if (force_krt && krt != force_krt) continue;
-            // over the register budget (the build's ISA shows spills): 32 rows x 32 tokens of the K-quant decoders; the raw Q6_K decoder beyond 16 x 16
-            // (Q6_K: the same rule for the raw tensor and its repack -- they must take the same slices to give the same bits)
-            if ((krt == 2 && ntb >= 2 && (KD::SPLIT16 || KD::HAS_MIN)) || (KD::SPLIT16 && (krt == 2 || ntb >= 2))) continue;
-            int kt = 0;
-            for (int i = 0; i < nseg; ++i) kt += (segs[i].out + 16 * krt - 1) / (16 * krt);
-            const int max_steps = krt == 1 ? (ntb == 1 ? gk_max_steps<KDT, 1, 1>() : gk_max_steps<KDT, 1, 2>()) : (ntb == 1 ? gk_max_steps<KDT, 2, 1>() : gk_max_steps<KDT, 2, 2>());
-            const int knw = krt == 1 ? (ntb == 1 ? gk_waves<KDT, 1, 1>() : gk_waves<KDT, 1, 2>()) : 8;
-            const int wgx = (kt + knw - 1) / knw, max_units = max_steps / KD::SPU;
-            if (max_units < 1) continue;
-            const int n_min = (units + max_units - 1) / max_units, n_cap = std::min(units, gb_split_rows((int)out_total));
-            for (int n = n_min; n <= n_cap; ++n) {
-                const int ups = units / n;
-                if (units % n != 0 || ups % gk_depth<KD::SPU>() != 0 || (force_kn && n != force_kn)) continue;   // (equal slices of whole groups of units)
-                // rounds over the 256 CUs, folded into the workgroups (the planes are copied once): the fewest row groups per workgroup with which
-                // the whole grid -- ceil(wgx / jobs) x n -- is ONE round
-                int jobs = 1;
-                while (jobs < max_jobs && (long)((wgx + jobs - 1) / jobs) * n > 256) ++jobs;
-                const double cost = (double)jobs * (double)(ups * KD::SPU * krt) + c0 + (jobs - 1) * c1;
-                if (cost < best_cost) { best_cost = cost; best_n = n; best_rt = krt; best_ups = ups; best_jobs = jobs; }
-            }
-        }
-        if (best_n > 0) {
-            GemmKParams kp{};
-            kp.nseg = nseg; kp.T = T; kp.in = in; kp.steps = in / 32; kp.row_bytes = (unsigned)row_bytes;
-            kp.xb = wsb; kp.aux = reinterpret_cast<const uint8_t*>(p.aux); kp.inv = scales; kp.resid = best_n == 1 ? resid : nullptr;
-            kp.nsplit = best_n; kp.units_per_split = best_ups;
-            float* kpart = reinterpret_cast<float*>(wsb + (size_t)GB_MAX_CHUNKS * p.chunk_bytes + GB_SCALE_BYTES);
-            int kt = 0;
-            for (int i = 0; i < nseg; ++i) {
-                kp.seg[i].W = static_cast<const uint8_t*>(segs[i].W); kp.seg[i].Y = segs[i].Y; kp.seg[i].out = segs[i].out;
-                kp.seg[i].w_last = (unsigned)((size_t)segs[i].out * row_bytes - 16);
-                kp.seg[i].tiles16 = segs[i].out / 16;
-                kp.seg[i].p2_off = (unsigned)((size_t)kp.seg[i].tiles16 * (size_t)(in / 256) * (size_t)(2 * KD::S1));
-                kp.seg[i].tile0 = kt;
-                kt += (segs[i].out + 16 * best_rt - 1) / (16 * best_rt);
-                kp.seg[i].part = kpart;   // partial-sum areas, one after the other: nsplit x T x out_i floats each
-                kpart += (size_t)best_n * T * segs[i].out;
-            }
-            kp.tiles = kt;
-            kp.jobs = best_jobs;
-            const bool kal = KD::RP || row_bytes % DeqI<KDT>::ROW_ALIGN == 0;
-            const int knw = best_rt == 1 ? (ntb == 1 ? gk_waves<KDT, 1, 1>() : gk_waves<KDT, 1, 2>()) : 8;
-            const int kwgx = (kt + knw - 1) / knw;
-            const dim3 kgrid((unsigned)((kwgx + best_jobs - 1) / best_jobs), (unsigned)best_n), kblock((unsigned)(64 * knw));
-            const int slice_steps = best_ups * KD::SPU;
-            static const bool kslice_lds_ok = [] {   // up to 160 KB of dynamic LDS: opt in once per kernel
-                bool ok = true;
-                auto set = [&](const void* f, size_t n) { ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n) == hipSuccess; };
-                set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 1, 1, true>), gk_lds_bytes<KDT, 1, 1>(gk_waves<KDT, 1, 1>(), gk_max_steps<KDT, 1, 1>()));
-                set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 1, 1, false>), gk_lds_bytes<KDT, 1, 1>(gk_waves<KDT, 1, 1>(), gk_max_steps<KDT, 1, 1>()));
-                set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 2, 1, true>), gk_lds_bytes<KDT, 2, 1>(gk_waves<KDT, 2, 1>(), gk_max_steps<KDT, 2, 1>()));
-                set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 2, 1, false>), gk_lds_bytes<KDT, 2, 1>(gk_waves<KDT, 2, 1>(), gk_max_steps<KDT, 2, 1>()));
-                set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 1, 2, true>), gk_lds_bytes<KDT, 1, 2>(gk_waves<KDT, 1, 2>(), gk_max_steps<KDT, 1, 2>()));
-                set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 1, 2, false>), gk_lds_bytes<KDT, 1, 2>(gk_waves<KDT, 1, 2>(), gk_max_steps<KDT, 1, 2>()));
-                if constexpr (!KD::SPLIT16) {
-                    set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 2, 2, true>), gk_lds_bytes<KDT, 2, 2>(gk_waves<KDT, 2, 2>(), gk_max_steps<KDT, 2, 2>()));
-                    set(reinterpret_cast<const void*>(&gemm_quant_f16_kslice_kernel<KDT, 2, 2, false>), gk_lds_bytes<KDT, 2, 2>(gk_waves<KDT, 2, 2>(), gk_max_steps<KDT, 2, 2>()));
-                }
-                return ok;
-            }();
-            if (!kslice_lds_ok) return NTK_E_LAUNCH;
-            // (one launch site per instantiation: RT x NTB x AL)
-            auto go = [&](auto rt_c, auto ntb_c) {
-                constexpr int R = decltype(rt_c)::value, N = decltype(ntb_c)::value;
-                if constexpr (R == 2 && N >= 2 && KD::SPLIT16) return;
-                else {
-                    const size_t klds = gk_lds_bytes<KDT, R, N>(gk_waves<KDT, R, N>(), slice_steps);
-                    if (kal) hipLaunchKernelGGL((gemm_quant_f16_kslice_kernel<KDT, R, N, true>), kgrid, kblock, klds, st, kp);
-                    else hipLaunchKernelGGL((gemm_quant_f16_kslice_kernel<KDT, R, N, false>), kgrid, kblock, klds, st, kp);
-                }
-            };
-            using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-            if (best_rt == 1) { if (ntb == 1) go(I1{}, I1{}); else go(I1{}, I2{}); }
-            else { if (ntb == 1) go(I2{}, I1{}); else go(I2{}, I2{}); }
-            if (defer) {   // the caller's next launch sums the slices (and adds the residual) itself
-                defer->nseg = nseg; defer->n_tokens = T; defer->nsplit = best_n;
-                for (int i = 0; i < nseg; ++i) { defer->part[i] = best_n > 1 ? kp.seg[i].part : nullptr; defer->y[i] = segs[i].Y; defer->rows[i] = segs[i].out; }
-                if (best_n > 1) return last_launch_status();
-            }
-            if (best_n > 1) {
-                ReduceArgs ra{};
-                ra.nseg = nseg; ra.T = T; ra.nsplit = best_n; ra.resid = resid;
-                size_t biggest = 0;
-                for (int i = 0; i < nseg; ++i) {
-                    ra.Y[i] = segs[i].Y; ra.part[i] = kp.seg[i].part; ra.out[i] = segs[i].out;
-                    biggest = std::max(biggest, ((size_t)T * segs[i].out + 3) / 4);
-                }
-                hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)((biggest + 255) / 256), nseg), dim3(256), 0, st, ra);
-            }
-            return last_launch_status();
-        }
-    }
-    // ---- short prompts (<= 32 tokens): the weight-streaming form (gemm_quant_f16_small_kernel) ----
-    // Measured (profiles/r06_prompt_small_tokens.txt, same box): <= 16 tokens it wins for every format (8B Q8_0 16 tokens 5.99 -> 5.53 ms per pass, the F32-MFMA
-    // form of rounds 1-5: 7.18; 8B Q4_K_M 6.39 -> 5.22; 70B Q4_K_M 37.3 -> 28.4); with two token blocks (17 .. 32 tokens) only for the K-quant decoders
-    // (8B Q4_K_M 32 tokens 6.45 -> 5.73 ms; Q8_0 6.09 -> 6.23: the 64-token form keeps those).  It streams at 1.4-2.4 TB/s, not at the decode GEMV's 4-6: a
-    // wave's steps each wait for their activation planes' L2 round trip (one step ahead is 100 cycles of work against ~600), and a ring of four units of
-    // weights in flight per wave changed nothing -- the next step up needs the planes resident in LDS, i.e. the large kernel's structure.
-    static const int small_env = NTK_TUNE_ENV_INT("NTK_GEMM_SMALL", -1);   // (tuning builds only: 0 = never, n = up to n tokens)
-    const int small_max = small_env >= 0 ? small_env : ((D::HAS_MIN || D::SPLIT16) ? 32 : 16);
-    if (!full_form && T <= small_max && T <= 32) {
-        GemmSParams sp{};
-        sp.nseg = nseg; sp.T = T; sp.in = in; sp.steps = in / 32; sp.row_bytes = (unsigned)row_bytes;
-        sp.xb = wsb; sp.aux = reinterpret_cast<const uint8_t*>(p.aux); sp.inv = scales; sp.resid = resid;
-        static const int force_srt = NTK_TUNE_ENV_INT("NTK_GEMM_SMALL_RT", 0), force_snw = NTK_TUNE_ENV_INT("NTK_GEMM_SMALL_NW", 0);   // (tuning builds only)
-        int srt = force_srt ? force_srt : (out_total >= 16384 ? 2 : 1);
-        if (D::SPLIT16 && T > 16) srt = 1;   // (32 rows x 32 tokens of the format that scales per 16 columns: over the register budget)
-        int stiles = 0;
-        for (int i = 0; i < nseg; ++i) {
-            sp.seg[i].W = static_cast<const uint8_t*>(segs[i].W); sp.seg[i].Y = segs[i].Y; sp.seg[i].out = segs[i].out;
-            sp.seg[i].w_last = (unsigned)((size_t)segs[i].out * row_bytes - 16);
-            sp.seg[i].tiles16 = segs[i].out / 16;
-            sp.seg[i].p2_off = (unsigned)((size_t)sp.seg[i].tiles16 * (size_t)(in / 256) * (size_t)(2 * D::S1));
-            sp.seg[i].tile0 = stiles;
-            stiles += (segs[i].out + 16 * srt - 1) / (16 * srt);
-        }
-        const int units = sp.steps / D::SPU;
-        const int snw = std::min(8, force_snw ? std::min(force_snw, std::max(1, units)) : std::min(8, std::max(1, units)));   // (__launch_bounds__(512))
-        const bool sal = D::RP || row_bytes % DeqI<DT>::ROW_ALIGN == 0;
-        const dim3 sgrid((unsigned)stiles), sblock((unsigned)(64 * snw));
-        const size_t l11 = gs_lds_bytes<DT, 1, 1>(snw), l21 = gs_lds_bytes<DT, 2, 1>(snw), l12 = gs_lds_bytes<DT, 1, 2>(snw), l22 = gs_lds_bytes<DT, 2, 2>(snw);
-        static const bool small_lds_ok = [] {   // 8 waves x (32-row image + partial sums) can exceed 64 KB of dynamic LDS: opt in once per kernel
-            bool ok = true;
-            auto set = [&](const void* f, size_t n) { ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n) == hipSuccess; };
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 1, 1, true>), gs_lds_bytes<DT, 1, 1>(8));
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 1, 1, false>), gs_lds_bytes<DT, 1, 1>(8));
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 2, 1, true>), gs_lds_bytes<DT, 2, 1>(8));
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 2, 1, false>), gs_lds_bytes<DT, 2, 1>(8));
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 1, 2, true>), gs_lds_bytes<DT, 1, 2>(8));
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 1, 2, false>), gs_lds_bytes<DT, 1, 2>(8));
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 2, 2, true>), gs_lds_bytes<DT, 2, 2>(8));
-            set(reinterpret_cast<const void*>(&gemm_quant_f16_small_kernel<DT, 2, 2, false>), gs_lds_bytes<DT, 2, 2>(8));
-            return ok;
-        }();
-        if (!small_lds_ok) return NTK_E_LAUNCH;
-        if (T <= 16) {
-            if (srt == 2) { if (sal) hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 2, 1, true>), sgrid, sblock, l21, st, sp);
-                            else hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 2, 1, false>), sgrid, sblock, l21, st, sp); }
-            else { if (sal) hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 1, 1, true>), sgrid, sblock, l11, st, sp);
-                   else hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 1, 1, false>), sgrid, sblock, l11, st, sp); }
-        } else {
-            if (srt == 2) { if (sal) hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 2, 2, true>), sgrid, sblock, l22, st, sp);
-                            else hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 2, 2, false>), sgrid, sblock, l22, st, sp); }
-            else { if (sal) hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 1, 2, true>), sgrid, sblock, l12, st, sp);
-                   else hipLaunchKernelGGL((gemm_quant_f16_small_kernel<DT, 1, 2, false>), sgrid, sblock, l12, st, sp); }
-        }
-        if (defer) {   // K is split inside the launch: nothing is left to a consumer (Y is written, residual included)
-            defer->nseg = nseg; defer->n_tokens = T; defer->nsplit = 1;
-            for (int i = 0; i < nseg; ++i) { defer->part[i] = nullptr; defer->y[i] = segs[i].Y; defer->rows[i] = segs[i].out; }
-        }
-        return last_launch_status();
-    }
-    // Rows per wave (RT x 16): a workgroup streams ALL B operands of its K range from L2 whatever its height, so taller tiles
-    // cut that traffic and the LDS reads per MFMA; K is then split (in whole trips) while fewer than one workgroup per CU exists.
-    static const int map8 = NTK_TUNE_ENV_INT("NTK_GEMM_MAP", 1);   // (tuning builds only)
-    p.map8 = map8;
-    static const int force_rt = NTK_TUNE_ENV_INT("NTK_GEMM_RT", 0);   // (tuning builds only)
-    // K is split (in whole trips) until every CU has two workgroups -- from 4 chunks (193 tokens) on; below that one per CU: the partial
-    // sums of many splits cost more than the idle half buys (same box, 8B Q8_0: 256 tokens 16 370 -> 17 000 tok/s, 512 19 830 -> 20 950;
-    // 64 tokens 8 090 -> 7 570 with the same rule, which is why it stops there)
-    static const int want_env = NTK_TUNE_ENV_INT("NTK_GEMM_WGS", 0);   // (tuning builds only)
-    const int plan_chunks = full_form ? GB_MAX_CHUNKS : p.chunks;   // the chunk count the plan below is made for
-    const int want_wgs = want_env ? want_env : (plan_chunks >= 4 ? 512 : 256);
-    int rt = out_total >= 2048 ? 2 : 1;
-    if (force_rt == 1 || force_rt == 2) rt = force_rt;
-    int tiles = 0;
-    float* part = reinterpret_cast<float*>(wsb + (size_t)GB_MAX_CHUNKS * p.chunk_bytes + GB_SCALE_BYTES);
     for (int i = 0; i < nseg; ++i) {
-        p.seg[i].W = static_cast<const uint8_t*>(segs[i].W);
-        p.seg[i].Y = segs[i].Y;
-        p.seg[i].out = segs[i].out;
-        p.seg[i].w_last = (unsigned)((size_t)segs[i].out * row_bytes - 16);
-        p.seg[i].tiles16 = segs[i].out / 16;
-        p.seg[i].p2_off = (unsigned)((size_t)p.seg[i].tiles16 * (size_t)(in / 256) * (size_t)(2 * D::S1));   // (csrc/gemv_rp.hip: P1 of every item, then P2)
-        p.seg[i].tile0 = tiles;
-        tiles += (segs[i].out + 64 * rt - 1) / (64 * rt);
+        GemmBSeg& s = p.seg[i];
+        s.W = static_cast<const uint8_t*>(segs[i].W); s.Y = segs[i].Y; s.part = part[i]; s.out = segs[i].out;
+        s.tile0 = plan.seg[i].tile0; s.tiles16 = plan.seg[i].tiles16; s.w_last = plan.seg[i].w_last; s.p2_off = plan.seg[i].p2_off;
     }
-    p.row_wgs = tiles;
-    const int trips = (p.steps + TRIP - 1) / TRIP;
-    // AL: every row starts on a dword boundary, so that the decoders' LDS dword reads are aligned (Q8_0 / Q4_0: in a multiple of 64, Q6_K: of
-    // 512 -- every projection of the target models; other row pitches take the same kernel with 2-byte aligned reads, slower)
-    const bool al = D::RP || row_bytes % DeqI<DT>::ROW_ALIGN == 0;
-    static const int no_pf = NTK_TUNE_ENV_INT("NTK_GEMM_NO_PF", 0);   // (tuning builds only)
-    static const int force_cw = NTK_TUNE_ENV_INT("NTK_GEMM_CW", 0);   // (tuning builds only)
-    constexpr bool PFD = DeqI<DT>::PF, CW2_OK = !DeqI<DT>::SPLIT16 && DT != NTK_DT_Q5_K && DT != NTK_DT_Q5_K + GB_RP;   // (Q5_K: 15 registers over the budget in that form)
-    // K splits of a plan with `groups` workgroup columns: doubled while the grid is short of `want_wgs`, whole trips, and
-    // splits x 64-token chunks within the partial-sum area (gb_split_rows)
-    const int chunks64 = plan_chunks, max_rows = gb_split_rows((int)out_total);
-    auto splits_for = [&](int groups) {
-        int n = 1;
-        while (n * 2 * chunks64 <= max_rows && (long)p.row_wgs * groups * n < want_wgs && trips / (n * 2) >= 1) n *= 2;
-        return n;
+}
+
+// The instantiations of each form, visited with their template arguments as constants: the LDS opt-in visits them all, a launch runs the one its plan names.
+template <bool SKIP22, class F> static void each_rt_ntb_al(F f) {   // the short forms: RT x NTB x AL
+    auto both = [&](auto rt, auto ntb) {
+        if constexpr (!(SKIP22 && decltype(rt)::value == 2 && decltype(ntb)::value == 2)) { f(rt, ntb, std::true_type{}); f(rt, ntb, std::false_type{}); }
     };
-    // two chunks (128 tokens) per workgroup when that still gives every CU two workgroups -- directly, or (narrow matrices: the 8B down /
-    // o / Q|K|V projections at 1024 tokens) with K split in two
-    int nsplit = splits_for(chunks64);
-    bool cw2 = false;
-    if (CW2_OK && al && rt == 2 && chunks64 >= 2 && force_cw != 1) {
-        const int pairs = (chunks64 + 1) / 2, n2 = splits_for(pairs);
-        if ((n2 <= 2 && (long)p.row_wgs * pairs * n2 >= 512) || force_cw == 2) { cw2 = true; nsplit = n2; p.chunks = (p.chunks + 1) / 2; }
-    }
-    const int tps = (trips + nsplit - 1) / nsplit;   // trips per split
-    nsplit = (trips + tps - 1) / tps;                // no empty split
-    p.nsplit = nsplit;
-    p.steps_per_split = tps * TRIP;
-    for (int i = 0; i < nseg; ++i) {                 // partial-sum areas, one after the other: nsplit x T x out_i floats each
-        p.seg[i].part = part;
-        part += (size_t)nsplit * T * segs[i].out;
-    }
-    const dim3 grid((unsigned)((p.row_wgs + 7) / 8 * 8 * p.chunks), nsplit);
-    const size_t lds2 = gb_lds_bytes<DT, 2, 1>(), lds1 = gb_lds_bytes<DT, 1, 1>(), lds22 = gb_lds_bytes<DT, 2, 2>();
-    static const bool lds_ok = [&] {   // more than 64 KB of dynamic LDS: opt in once per kernel
+    both(I1{}, I1{}); both(I2{}, I1{}); both(I1{}, I2{}); both(I2{}, I2{});
+}
+template <int DT, class F> static void each_chunk_kernel(F f) {   // the chunk form: RT x AL x PF x CW
+    using PFD = std::bool_constant<DeqI<DT>::PF>; using Y = std::true_type; using N = std::false_type;
+    f(I2{}, Y{}, PFD{}, I1{}); f(I2{}, N{}, PFD{}, I1{}); f(I1{}, Y{}, PFD{}, I1{}); f(I1{}, N{}, PFD{}, I1{});
+    if constexpr (PFD::value) { f(I2{}, Y{}, N{}, I1{}); f(I1{}, Y{}, N{}, I1{}); }   // (without the plane prefetch: aligned rows only)
+    if constexpr (gb_cw2_ok<DT>()) f(I2{}, Y{}, N{}, I2{});
+}
+
+// visit(f) calls f(kernel, the most dynamic LDS it can be launched with, whether it is the plan's) for every instantiation of a form: each opts in to its
+// LDS (more than 64 KB, up to 160) once, and the plan's is launched
+template <class P, class V> static int launch_form(const GemmPlan& plan, const P& params, hipStream_t st, V visit) {
+    static const bool lds_ok = [&] {
         bool ok = true;
-        auto set = [&](const void* f, size_t n) { ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n) == hipSuccess; };
-        set(reinterpret_cast<const void*>(&gemm_quant_f16_kernel<DT, 2, true, PFD, 1>), lds2);
-        set(reinterpret_cast<const void*>(&gemm_quant_f16_kernel<DT, 2, false, PFD, 1>), lds2);
-        set(reinterpret_cast<const void*>(&gemm_quant_f16_kernel<DT, 1, true, PFD, 1>), lds1);
-        set(reinterpret_cast<const void*>(&gemm_quant_f16_kernel<DT, 1, false, PFD, 1>), lds1);
-        set(reinterpret_cast<const void*>(&gemm_quant_f16_kernel<DT, 2, true, false, 1>), lds2);
-        set(reinterpret_cast<const void*>(&gemm_quant_f16_kernel<DT, 1, true, false, 1>), lds1);
-        if constexpr (CW2_OK) set(reinterpret_cast<const void*>(&gemm_quant_f16_kernel<DT, 2, true, false, 2>), lds22);
+        visit([&](auto* k, size_t lds, bool) { ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; });
         return ok;
     }();
     if (!lds_ok) return NTK_E_LAUNCH;
-    if (cw2) {
-        if constexpr (CW2_OK) hipLaunchKernelGGL((gemm_quant_f16_kernel<DT, 2, true, false, 2>), grid, dim3(256), lds22, st, p);
-    } else if (al && (no_pf || !PFD)) {   // (NTK_GEMM_NO_PF=1: the A/B switch of the plane prefetch)
-        if (rt == 2) hipLaunchKernelGGL((gemm_quant_f16_kernel<DT, 2, true, false, 1>), grid, dim3(256), lds2, st, p);
-        else hipLaunchKernelGGL((gemm_quant_f16_kernel<DT, 1, true, false, 1>), grid, dim3(256), lds1, st, p);
-    } else if (al) {
-        if (rt == 2) hipLaunchKernelGGL((gemm_quant_f16_kernel<DT, 2, true, PFD, 1>), grid, dim3(256), lds2, st, p);
-        else hipLaunchKernelGGL((gemm_quant_f16_kernel<DT, 1, true, PFD, 1>), grid, dim3(256), lds1, st, p);
+    visit([&](auto* k, size_t, bool mine) { if (mine) hipLaunchKernelGGL(k, dim3(plan.grid_x, plan.grid_y), dim3(plan.block), plan.lds, st, params); });
+    return NTK_OK;
+}
+
+// T <= GB_MAX_CHUNKS * 64 = 1024 tokens in one launch; nseg matrices [out_s][in] of one format sharing X: the plan (gemm_f16_plan.h: form, tiles, K
+// slices, grid), the operand pre-pass, the form's kernel, and the sum of the K slices -- here, or left to the launch that consumes the projection
+template <int DT>
+static int launch_gemm_f16(const HostSeg* segs, int nseg, const float* X, int T, int in, const float* resid, void* ws, int reuse_x,
+                            const float* row_max, ntk_gemm_partials* defer, bool full_form, hipStream_t st) {
+    if (nseg < 1 || nseg > GB_MAX_SEG || (resid && nseg != 1)) return NTK_E_SHAPE;
+    int rows[GB_MAX_SEG];
+    for (int i = 0; i < nseg; ++i) rows[i] = segs[i].out;
+    const GemmPlan plan = gemm_f16_plan<DT>(rows, nseg, T, in, full_form, gemm_tune());
+    if (plan.status != NTK_OK) return plan.status;
+    for (int i = 0; i < nseg; ++i)
+        if ((reinterpret_cast<uintptr_t>(segs[i].W) & 15) || (reinterpret_cast<uintptr_t>(segs[i].Y) & 15)) return NTK_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(X) & 15) || (resid && (reinterpret_cast<uintptr_t>(resid) & 15))) return NTK_E_ALIGN;
+    // ---- the operand pre-pass into the workspace: [chunk][planes | sums], [1 / s][s], then the partial sums of the K slices ----
+    uint8_t* wsb = static_cast<uint8_t*>(ws);
+    const int steps = in / 32, chunks = (T + GB_TOK - 1) / GB_TOK;
+    const size_t chunk_bytes = ws_chunk_bytes(in);
+    float* aux = reinterpret_cast<float*>(wsb + (size_t)(steps + 1) * GB_STEP_BYTES);
+    float* scales = reinterpret_cast<float*>(wsb + (size_t)GB_MAX_CHUNKS * chunk_bytes);   // [inv: 1024][scale: 1024]
+    if (!reuse_x && row_max) {   // the tokens' largest |x| came with X: one pre-pass launch
+        hipLaunchKernelGGL(split_x_kernel<true>, dim3(steps + 8, chunks), dim3(256), 0, st, X, T, in, reinterpret_cast<u32x4*>(wsb), aux, chunk_bytes, row_max, scales);
+    } else if (!reuse_x) {
+        hipLaunchKernelGGL(row_scale_kernel, dim3((T + 3) / 4), dim3(256), 0, st, X, T, in, scales + GB_MAX_CHUNKS * GB_TOK, scales);
+        hipLaunchKernelGGL(split_x_kernel<false>, dim3(steps + 8, chunks), dim3(256), 0, st, X, T, in, reinterpret_cast<u32x4*>(wsb), aux, chunk_bytes,
+                           scales + GB_MAX_CHUNKS * GB_TOK, static_cast<float*>(nullptr));
+    }
+    float* part[GB_MAX_SEG] = {};   // (the small form splits K over its waves: no partial sums)
+    if (plan.form != GEMM_FORM_SMALL)
+        for (int i = 0; i < nseg; ++i) part[i] = reinterpret_cast<float*>(wsb + (size_t)GB_MAX_CHUNKS * chunk_bytes + GB_SCALE_BYTES) + plan.seg[i].part_off;
+    int rc;
+    if (plan.form == GEMM_FORM_KSLICE) {
+        GemmKParams kp{};
+        fill_params(kp, plan, segs, nseg, T, in, plan.nsplit == 1 ? resid : nullptr, wsb, part);
+        kp.nsplit = plan.nsplit; kp.units_per_split = plan.per_split; kp.tiles = plan.tiles; kp.jobs = plan.jobs;
+        rc = launch_form(plan, kp, st, [&](auto f) {   // (32 rows x 32 tokens of the format that scales per 16 columns: over the register budget, never planned)
+            each_rt_ntb_al<DeqI<DT>::SPLIT16>([&](auto rt, auto ntb, auto al) {
+                constexpr int R = decltype(rt)::value, N = decltype(ntb)::value; constexpr bool A = decltype(al)::value;
+                f(&gemm_quant_f16_kslice_kernel<DT, R, N, A>, gk_lds_bytes<DT, R, N>(gk_waves<DT, R, N>(), gk_max_steps<DT, R, N>()), R == plan.rt && N == plan.ntb && A == plan.al);
+            });
+        });
+    } else if (plan.form == GEMM_FORM_SMALL) {
+        GemmSParams sp{};
+        fill_params(sp, plan, segs, nseg, T, in, resid, wsb, part);
+        rc = launch_form(plan, sp, st, [&](auto f) {   // (8 waves x (32-row image + partial sums) can exceed 64 KB)
+            each_rt_ntb_al<false>([&](auto rt, auto ntb, auto al) {
+                constexpr int R = decltype(rt)::value, N = decltype(ntb)::value; constexpr bool A = decltype(al)::value;
+                f(&gemm_quant_f16_small_kernel<DT, R, N, A>, gs_lds_bytes<DT, R, N>(8), (R == 2) == (plan.rt == 2) && N == plan.ntb && A == plan.al);
+            });
+        });
     } else {
-        if (rt == 2) hipLaunchKernelGGL((gemm_quant_f16_kernel<DT, 2, false, PFD, 1>), grid, dim3(256), lds2, st, p);
-        else hipLaunchKernelGGL((gemm_quant_f16_kernel<DT, 1, false, PFD, 1>), grid, dim3(256), lds1, st, p);
+        GemmBParams p{};
+        fill_params(p, plan, segs, nseg, T, in, resid, wsb, part);
+        p.chunks = plan.chunks; p.chunk_bytes = chunk_bytes; p.row_wgs = plan.tiles; p.map8 = gemm_tune().map;
+        p.nsplit = plan.nsplit; p.steps_per_split = plan.per_split;
+        rc = launch_form(plan, p, st, [&](auto f) {
+            each_chunk_kernel<DT>([&](auto rt, auto al, auto pf, auto cw) {
+                constexpr int R = decltype(rt)::value, C = decltype(cw)::value; constexpr bool A = decltype(al)::value, PF = decltype(pf)::value;
+                f(&gemm_quant_f16_kernel<DT, R, A, PF, C>, gb_lds_bytes<DT, R, C>(), R == plan.rt && A == plan.al && PF == plan.pf && C == plan.cw);
+            });
+        });
     }
-    if (defer) {   // the caller's next launch sums the splits (and adds the residual) itself
-        defer->nseg = nseg; defer->n_tokens = T; defer->nsplit = nsplit;
-        for (int i = 0; i < nseg; ++i) { defer->part[i] = nsplit > 1 ? p.seg[i].part : nullptr; defer->y[i] = segs[i].Y; defer->rows[i] = segs[i].out; }
-        if (nsplit > 1) return last_launch_status();
-    }
-    if (nsplit > 1) {
-        ReduceArgs ra{};
-        ra.nseg = nseg; ra.T = T; ra.nsplit = nsplit; ra.resid = resid;
-        size_t biggest = 0;
-        for (int i = 0; i < nseg; ++i) {
-            ra.Y[i] = segs[i].Y; ra.part[i] = p.seg[i].part; ra.out[i] = segs[i].out;
-            biggest = std::max(biggest, ((size_t)T * segs[i].out + 3) / 4);
-        }
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)((biggest + 255) / 256), nseg), dim3(256), 0, st, ra);
-    }
+    if (rc != NTK_OK) return rc;
+    set_partials(defer, segs, nseg, T, plan.nsplit, part);
+    if (plan.nsplit > 1 && !defer) reduce_splits(segs, part, nseg, T, plan.nsplit, resid, st);
     return last_launch_status();
+}
+
+// f(std::integral_constant<int, DT>{}) for the format of a call (weight_dtype + GB_RP: the matrices are tensors of the engine's decode repack)
+template <class F> static int with_gemm_format(int weight_dtype, F f) {
+    switch (weight_dtype) {
+        case NTK_DT_Q8_0: return f(std::integral_constant<int, NTK_DT_Q8_0>{});
+        case NTK_DT_Q4_0: return f(std::integral_constant<int, NTK_DT_Q4_0>{});
+        case NTK_DT_Q4_K: return f(std::integral_constant<int, NTK_DT_Q4_K>{});
+        case NTK_DT_Q5_K: return f(std::integral_constant<int, NTK_DT_Q5_K>{});
+        case NTK_DT_Q4_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q4_K + GB_RP>{});
+        case NTK_DT_Q5_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q5_K + GB_RP>{});
+        case NTK_DT_Q6_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q6_K + GB_RP>{});
+        default: return f(std::integral_constant<int, NTK_DT_Q6_K>{});
+    }
 }
 
 }  // namespace ntk
@@ -2319,14 +2035,10 @@ size_t ntk_gemm_quant_workspace_bytes(int in_features, int out_features) {
 
 static int gemm_ws_dispatch(const ntk::HostSeg* segs, int nseg, const float* X, int n_tokens, int in_features, int weight_dtype, const float* resid,
                             void* workspace, int reuse_x, const float* row_max, ntk_gemm_partials* defer, int full_form, hipStream_t st) {
-    // (weight_dtype + ntk::GB_RP: the matrices are tensors of the engine's decode repack)
     constexpr int PASS = ntk::GB_MAX_CHUNKS * ntk::GB_TOK;
     if (n_tokens > PASS) reuse_x = 0;   // the planes hold one pass (1024 tokens) at a time
-    if (defer) {
-        defer->nseg = nseg; defer->n_tokens = n_tokens; defer->nsplit = 1;   // (more than one pass: each pass reduces itself, nothing is deferred)
-        for (int i = 0; i < nseg; ++i) { defer->part[i] = nullptr; defer->y[i] = segs[i].Y; defer->rows[i] = segs[i].out; }
-        if (n_tokens > PASS) defer = nullptr;
-    }
+    ntk::set_partials(defer, segs, nseg, n_tokens, 1, nullptr);   // (more than one pass: each pass reduces itself, nothing is deferred)
+    if (n_tokens > PASS) defer = nullptr;
     for (int t0 = 0; t0 < n_tokens; t0 += PASS) {   // up to 16 x 64 tokens per launch: the chunks share the weights in L2
         const int T = std::min(PASS, n_tokens - t0);
         ntk::HostSeg sg[ntk::GB_MAX_SEG];
@@ -2334,17 +2046,9 @@ static int gemm_ws_dispatch(const ntk::HostSeg* segs, int nseg, const float* X, 
         const float* x = X + (size_t)t0 * in_features;
         const float* rs = resid ? resid + (size_t)t0 * segs[0].out : nullptr;
         const float* rm = row_max ? row_max + t0 : nullptr;
-        int rc;
-        switch (weight_dtype) {
-            case NTK_DT_Q8_0: rc = ntk::launch_gemm_f16<NTK_DT_Q8_0>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-            case NTK_DT_Q4_0: rc = ntk::launch_gemm_f16<NTK_DT_Q4_0>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-            case NTK_DT_Q4_K: rc = ntk::launch_gemm_f16<NTK_DT_Q4_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-            case NTK_DT_Q5_K: rc = ntk::launch_gemm_f16<NTK_DT_Q5_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-            case NTK_DT_Q4_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q4_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-            case NTK_DT_Q5_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q5_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-            case NTK_DT_Q6_K + ntk::GB_RP: rc = ntk::launch_gemm_f16<NTK_DT_Q6_K + ntk::GB_RP>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-            default: rc = ntk::launch_gemm_f16<NTK_DT_Q6_K>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st); break;
-        }
+        const int rc = ntk::with_gemm_format(weight_dtype, [&](auto dt) {
+            return ntk::launch_gemm_f16<decltype(dt)::value>(sg, nseg, x, T, in_features, rs, workspace, reuse_x, rm, defer, full_form != 0, st);
+        });
         if (rc != NTK_OK) return rc;
     }
     return NTK_OK;
@@ -2372,10 +2076,7 @@ int ntk_gemm_quant_f16(const ntk_gemm_desc* d, void* stream) {
     }
     if (d->workspace_bytes < ntk_gemm_quant_workspace_bytes(in_features, (int)total) || (reinterpret_cast<uintptr_t>(d->workspace) & 15)) return NTK_E_SHAPE;
     ntk_gemm_partials* defer = d->partials;
-    if (defer) {
-        defer->nseg = nseg; defer->n_tokens = n_tokens; defer->nsplit = 1;
-        for (int i = 0; i < nseg; ++i) { defer->part[i] = nullptr; defer->y[i] = sg[i].Y; defer->rows[i] = sg[i].out; }
-    }
+    ntk::set_partials(defer, sg, nseg, n_tokens, 1, nullptr);
     if (n_tokens == 0 || total == 0) return NTK_OK;
     // (resid with partials: added by the launch's own epilogue when it does not split K -- nothing is deferred then; left to the consumer when it does)
     return gemm_ws_dispatch(sg, nseg, d->X, n_tokens, in_features, dt, d->resid, d->workspace, d->reuse_x, d->row_max, defer, d->full_form, ntk::resolve_stream(stream));
