@@ -23,6 +23,17 @@ extern "C" {
  * place, the rotated k and v converted to F16 (RNE) into the caches at start_pos; k and v are only read.  Identical q and cache rows.  head_dim <= 256. */
 int ntk_rope_kv_store(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
                       float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq, void* stream);
+/* RoPE FREQUENCY TABLE forms of the prompt-side rotations (ntk_rope of ntk.h, ntk_rope_kv_store above, ntk_rope_kv_store_segments and
+ * ntk_rope_kv_store_q8 below): the same arguments plus inv_freq, a DEVICE table of head_dim / 2 floats or NULL -- the convention of the decode
+ * launches (ntk_attention_decode_fused ...): entry i replaces the in-kernel 1 / pow(theta_base, 2i / head_dim), so a model's frequency factors
+ * (Llama 3.1's rope_freqs.weight) are folded in on the host once; the angle of pair i stays (float)pos * inv_freq[i] * freq_scale, left to right in
+ * F32.  NULL: the in-kernel frequency -- the entry points without _tab ARE these with NULL, same kernels, same bits.  A workgroup reads its
+ * head_dim / 2 entries once, where it otherwise evaluates pow. */
+int ntk_rope_tab(float* q, float* k, const int* positions, int batch_size, int seq_len, int n_heads, int n_kv_heads, int head_dim, float theta_base,
+                 float freq_scale, int interleaved, const float* inv_freq, void* stream);
+int ntk_rope_kv_store_tab(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
+                          float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
+                          const float* inv_freq, void* stream);
 /* ---------------------------------------------------------------------------------------------
  * Engine-level fused operators (no reference counterpart; they compute exactly what the listed
  * sequence of reference launchers computes, in fewer launches, with device-resident positions so a
@@ -179,6 +190,8 @@ typedef struct ntk_kv_segments {
 int ntk_kv_segments_validate(const ntk_kv_segments* segs, int total_rows, int max_seq);
 int ntk_rope_kv_store_segments(float* q, const float* k, const float* v, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim,
                                float theta_base, float freq_scale, int interleaved, int max_seq, void* stream);
+int ntk_rope_kv_store_segments_tab(float* q, const float* k, const float* v, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim,
+                                   float theta_base, float freq_scale, int interleaved, int max_seq, const float* inv_freq, void* stream);   /* (the table forms: above) */
 int ntk_attention_prefill_segments(float* output, const float* Q, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim, int max_seq,
                                    float scale, void* stream);
 
@@ -216,6 +229,9 @@ int ntk_kv_store_q8(void* k_cache, void* v_cache, const float* k, const float* v
 int ntk_rope_kv_store_q8(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
                          float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
                          void* stream);
+int ntk_rope_kv_store_q8_tab(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
+                             float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
+                             const float* inv_freq, void* stream);   /* (the table forms: above) */
 int ntk_attention_decode_q8(float* output, const float* q, const float* k, const float* v, void* k_cache, void* v_cache, const int* d_pos,
                             const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq, float scale, float theta_base,
                             float freq_scale, int nsplit, float* scratch, void* stream);

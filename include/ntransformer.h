@@ -114,7 +114,19 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * "batch_prefill" = "0" (default) | "1" (any other value: NTK_E_SHAPE + last_error; any time, read per call): with "1" nt_engine_generate_batch / _ex prefill
  * all their prompts with ONE nt_engine_forward_batch pass (below) instead of one nt_engine_seq_forward per slot; everything behind the prefill -- the first
  * token from each sequence's own row of logits, the lockstep steps -- is unchanged.  Ignored (slot by slot, as with "0") on a "kv_cache" = "q8_0" engine and
- * when the prompts together hold more tokens than max_context. */
+ * when the prompts together hold more tokens than max_context;
+ * RoPE FREQUENCY SCALING -- three options, all BEFORE the load (afterwards: NTK_E_SHAPE + last_error), kept across loads, malformed values NTK_E_SHAPE +
+ * last_error; an nt_engine_load_shared sequence runs with its source's table and scale whatever its own options say:
+ * "rope_scaling" = "file" (default): what the GGUF says -- the tensor rope_freqs.weight (F32 [head_dim / 2] per-pair frequency DIVISORS, Llama 3.1 / 3.2)
+ * and <arch>.rope.scaling.type = "linear" with .factor (or the legacy <arch>.rope.scale_linear): freq_scale = 1 / factor; "yarn" and unknown types load
+ * unscaled with one line on stderr | "none": the file's factors and scaling keys are ignored (the engine's behaviour before it read them) | "linear:<factor>":
+ * freq_scale = 1 / factor whatever the file's scaling keys say, while the file's rope_freqs.weight divisors STAY (as under llama.cpp's --rope-scaling linear)
+ * | "llama3:<factor>,<low_freq_factor>,<high_freq_factor>,<original_context>": the engine computes the Llama-3.1 divisors itself (nt_rope_llama3_factors), in
+ * place of the file's --
+ * the way a synthetic model gets a Llama-3.1-shaped rotation.  The angle of pair i at position pos is (float)pos * tab[i] * freq_scale, left to right in F32,
+ * tab[i] = (1 / powf(theta, 2i / head_dim)) / divisor[i] (nt_rope_build_table);
+ * "rope_freq_base" = F > 0: theta, overriding the file's <arch>.rope.freq_base (a synthetic spec's theta);
+ * "rope_freq_scale" = F > 0: freq_scale, overriding whatever "rope_scaling" resolved to. */
 int  nt_engine_set_option(nt_engine_t e, const char* key, const char* value);
 const char* nt_engine_last_error(nt_engine_t e);
 void nt_gen_params_default(nt_gen_params* p);
@@ -284,8 +296,20 @@ int64_t nt_synth_tensor(const nt_synth_spec* spec, const char* name, void* dst, 
 /* ------------------------------------------------------------------ host-only entry points ---------
  * GGUF parsing, tokenisation and sampling never touch the GPU; these let tools (and the CPU test-suite)
  * use them without a device. */
-/* JSON description of a GGUF file: config, tensor table, vocab size. Returns bytes needed (excl. NUL) or negative. */
+/* JSON description of a GGUF file: config, tensor table, vocab size. Returns bytes needed (excl. NUL) or negative.  RoPE scaling as the FILE states it:
+ * "rope_scaling_type" (<arch>.rope.scaling.type; "linear" for a bare legacy rope.scale_linear; "none" without either), "rope_freq_scale" (1 / factor for
+ * linear, else 1), "rope_factors" (elements of rope_freqs.weight, 0 without the tensor), "rope_orig_ctx" (.original_context_length, 0 when absent). */
 int   nt_gguf_describe(const char* path, char* json_out, int cap);
+/* The rotation a LOADED engine runs with, as JSON: "rope_theta", "rope_scaling_type" ("none" | "linear" | "llama3"; a file's "yarn" / unknown type is
+ * reported as it is named, and is not applied), "rope_freq_scale", "rope_factors" (per-pair divisors folded into the frequency table: 0 or head_dim / 2),
+ * "rope_orig_ctx".  Returns bytes needed (excl. NUL) or negative. */
+int   nt_engine_rope_info(nt_engine_t e, char* json_out, int cap);
+/* Llama-3.1 frequency divisors (what a converter writes into rope_freqs.weight): out[head_dim / 2], computed in double, stored as F32.  Pair i of
+ * wavelength 2 pi theta^(2i / head_dim): 1 below orig_ctx / high, `factor` above orig_ctx / low, 1 / ((1 - s) / factor + s) with s = (orig_ctx / wavelen -
+ * low) / (high - low) in between.  NTK_E_SHAPE: head_dim odd or < 2, theta / factor / low / high / orig_ctx not > 0, high == low. */
+int   nt_rope_llama3_factors(int head_dim, float theta, float factor, float low_freq_factor, float high_freq_factor, int orig_ctx, float* out);
+/* The engine's frequency table: out[i] = (1.0f / powf(theta, (2.0f * i) / head_dim)) / factors[i] in F32 (factors NULL: no division -- the plain table). */
+int   nt_rope_build_table(int head_dim, float theta, const float* factors_or_null, float* out);
 typedef void* nt_tokenizer_t;
 nt_tokenizer_t nt_tokenizer_open(const char* gguf_path);       /* NULL on failure */
 void  nt_tokenizer_close(nt_tokenizer_t t);

@@ -136,6 +136,10 @@ def lib() -> C.CDLL:
         "ntk_kv_segments_validate": (i, [vp, i, i]),
         "ntk_rope_kv_store_segments": (i, [vp, vp, vp, vp, i, i, i, f, f, i, i, vp]),
         "ntk_attention_prefill_segments": (i, [vp, vp, vp, i, i, i, i, f, vp]),
+        "ntk_rope_tab": (i, [vp, vp, vp, i, i, i, i, i, f, f, i, vp, vp]),
+        "ntk_rope_kv_store_tab": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp, vp]),
+        "ntk_rope_kv_store_segments_tab": (i, [vp, vp, vp, vp, i, i, i, f, f, i, i, vp, vp]),
+        "ntk_rope_kv_store_q8_tab": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp, vp]),
         "ntk_kv_q8_cache_bytes": (C.c_size_t, [i, i, i]),
         "ntk_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, i, vp]),
         "ntk_rope_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp]),

@@ -222,7 +222,8 @@ __global__ __launch_bounds__(256) void attention_prefill_tiled_kernel(float* __r
 }
 
 __global__ void rope_kernel(float* __restrict__ q, float* __restrict__ k, const int* __restrict__ positions, int seq_len,
-                            int n_heads, int n_kv_heads, int head_dim, float theta, float fscale, int interleaved) {
+                            int n_heads, int n_kv_heads, int head_dim, float theta, float fscale, int interleaved,
+                            const float* __restrict__ inv_freq) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int half_dim = head_dim / 2;
     const int total_q = seq_len * n_heads * half_dim, total_k = seq_len * n_kv_heads * half_dim;
@@ -234,7 +235,7 @@ __global__ void rope_kernel(float* __restrict__ q, float* __restrict__ k, const 
     float* data = (is_key ? k : q) + ((size_t)sp * n_h + head) * head_dim;
     const int i0 = interleaved ? 2 * pair : pair, i1 = interleaved ? 2 * pair + 1 : pair + half_dim;
     float a = data[i0], b = data[i1];
-    rope_pair(a, b, positions[sp], pair, head_dim, theta, fscale);
+    rope_pair(a, b, positions[sp], pair, head_dim, theta, fscale, inv_freq);
     data[i0] = a;
     data[i1] = b;
 }
@@ -244,12 +245,13 @@ __global__ void rope_kernel(float* __restrict__ q, float* __restrict__ k, const 
 // re-evaluates pow / cosf / sinf for every head: 40 times per pair on the 8B shapes, 29 us per 1024-token layer against the ~8 us the
 // 42 MB of traffic take).  head_dim <= 256.
 __global__ __launch_bounds__(256) void rope_rows_kernel(float* __restrict__ q, float* __restrict__ k, const int* __restrict__ positions,
-                                                        int n_heads, int n_kv_heads, int head_dim, float theta, float fscale, int interleaved) {
+                                                        int n_heads, int n_kv_heads, int head_dim, float theta, float fscale, int interleaved,
+                                                        const float* __restrict__ inv_freq) {
     __shared__ float cs[2][128];
     const int sp = blockIdx.x, half_dim = head_dim / 2;
     const int pos = positions[sp];
     for (int i = threadIdx.x; i < half_dim; i += blockDim.x) {
-        const float freq = 1.0f / (float)pow((double)theta, (double)((2.0f * i) / head_dim));
+        const float freq = rope_freq(inv_freq, i, head_dim, theta);
         const float angle = pos * freq * fscale;
         cs[0][i] = cosf(angle);
         cs[1][i] = sinf(angle);
@@ -271,11 +273,11 @@ __global__ __launch_bounds__(256) void rope_rows_kernel(float* __restrict__ q, f
 __device__ __forceinline__ void rope_kv_store_row(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const int pos,
                                                   const int n_heads, const int n_kv_heads, const int head_dim, const float theta, const float fscale,
                                                   const int interleaved, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc, const int cp,
-                                                  const int max_seq) {
+                                                  const int max_seq, const float* __restrict__ inv_freq) {
     __shared__ float cs[2][128];
     const int half_dim = head_dim / 2;
     for (int i = threadIdx.x; i < half_dim; i += blockDim.x) {
-        const float freq = 1.0f / (float)pow((double)theta, (double)((2.0f * i) / head_dim));
+        const float freq = rope_freq(inv_freq, i, head_dim, theta);
         const float angle = pos * freq * fscale;
         cs[0][i] = cosf(angle);
         cs[1][i] = sinf(angle);
@@ -311,10 +313,10 @@ __device__ __forceinline__ void rope_kv_store_row(float* __restrict__ q, const f
 __global__ __launch_bounds__(256) void rope_kv_store_rows_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                                  const int* __restrict__ positions, int n_heads, int n_kv_heads, int head_dim, float theta,
                                                                  float fscale, int interleaved, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
-                                                                 int start_pos, int max_seq) {
+                                                                 int start_pos, int max_seq, const float* __restrict__ inv_freq) {
     const int sp = blockIdx.x;
     rope_kv_store_row(q + (size_t)sp * n_heads * head_dim, k + (size_t)sp * n_kv_heads * head_dim, v + (size_t)sp * n_kv_heads * head_dim, positions[sp],
-                      n_heads, n_kv_heads, head_dim, theta, fscale, interleaved, kc, vc, start_pos + sp, max_seq);
+                      n_heads, n_kv_heads, head_dim, theta, fscale, interleaved, kc, vc, start_pos + sp, max_seq, inv_freq);
 }
 
 // ... for the rows of a PACKED pass (ntk_rope_kv_store_segments): row blockIdx.x belongs to the segment a uniform scan of the <= 16 row0 values finds; its
@@ -327,13 +329,13 @@ struct RopeSegments {
 };
 __global__ __launch_bounds__(256) void rope_kv_store_segments_kernel(float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                                      const RopeSegments segs, int n_heads, int n_kv_heads, int head_dim, float theta,
-                                                                     float fscale, int interleaved, int max_seq) {
+                                                                     float fscale, int interleaved, int max_seq, const float* __restrict__ inv_freq) {
     const int row = blockIdx.x;
     int s = 0;
     while (s + 1 < segs.n_seg && row >= segs.row0[s + 1]) ++s;   // (uniform)
     const int pos = segs.start_pos[s] + (row - segs.row0[s]);
     rope_kv_store_row(q + (size_t)row * n_heads * head_dim, k + (size_t)row * n_kv_heads * head_dim, v + (size_t)row * n_kv_heads * head_dim, pos, n_heads,
-                      n_kv_heads, head_dim, theta, fscale, interleaved, segs.k[s], segs.v[s], pos, max_seq);
+                      n_kv_heads, head_dim, theta, fscale, interleaved, segs.k[s], segs.v[s], pos, max_seq, inv_freq);
 }
 
 __global__ void kv_store_kernel(uint16_t* __restrict__ kc, uint16_t* __restrict__ vc, const float* __restrict__ k,
@@ -418,29 +420,44 @@ int launch_attention_split_combine(float* output, const float* part, int n_heads
 
 extern "C" {
 
-int ntk_rope(float* q, float* k, const int* positions, int /*batch_size*/, int seq_len, int n_heads, int n_kv_heads,
-             int head_dim, float theta_base, float freq_scale, int interleaved, void* stream) {
+// The prompt-side rotations with the per-pair frequencies from a DEVICE table (inv_freq [head_dim / 2]: entry i replaces the in-kernel 1 / pow(theta,
+// 2i / head_dim); NULL: the in-kernel frequency, which is what the entry points without _tab pass)
+int ntk_rope_tab(float* q, float* k, const int* positions, int /*batch_size*/, int seq_len, int n_heads, int n_kv_heads,
+                 int head_dim, float theta_base, float freq_scale, int interleaved, const float* inv_freq, void* stream) {
     if (!q || !k || !positions) return NTK_E_NULL;
     if (seq_len < 0 || n_heads < 0 || n_kv_heads < 0 || head_dim <= 0 || (head_dim & 1)) return NTK_E_SHAPE;
     const int total = seq_len * (n_heads + n_kv_heads) * (head_dim / 2);
     if (total == 0) return NTK_OK;
     if (seq_len >= 4 && head_dim <= 256)   // prompts: the token's (cos, sin) pairs once for all heads
         hipLaunchKernelGGL(ntk::rope_rows_kernel, dim3(seq_len), dim3(256), 0, ntk::resolve_stream(stream), q, k, positions, n_heads, n_kv_heads,
-                           head_dim, theta_base, freq_scale, interleaved);
+                           head_dim, theta_base, freq_scale, interleaved, inv_freq);
     else
         hipLaunchKernelGGL(ntk::rope_kernel, dim3((total + 255) / 256), dim3(256), 0, ntk::resolve_stream(stream), q, k,
-                           positions, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved);
+                           positions, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, inv_freq);
+    return ntk::last_launch_status();
+}
+
+int ntk_rope(float* q, float* k, const int* positions, int batch_size, int seq_len, int n_heads, int n_kv_heads,
+             int head_dim, float theta_base, float freq_scale, int interleaved, void* stream) {
+    return ntk_rope_tab(q, k, positions, batch_size, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, nullptr, stream);
+}
+
+int ntk_rope_kv_store_tab(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
+                          float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
+                          const float* inv_freq, void* stream) {
+    if (!q || !k || !v || !positions || !k_cache || !v_cache) return NTK_E_NULL;
+    if (seq_len < 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || (head_dim & 1) || head_dim > 256 || start_pos < 0 || max_seq <= 0) return NTK_E_SHAPE;
+    if (seq_len == 0) return NTK_OK;
+    hipLaunchKernelGGL(ntk::rope_kv_store_rows_kernel, dim3(seq_len), dim3(256), 0, ntk::resolve_stream(stream), q, k, v, positions, n_heads, n_kv_heads,
+                       head_dim, theta_base, freq_scale, interleaved, static_cast<uint16_t*>(k_cache), static_cast<uint16_t*>(v_cache), start_pos, max_seq,
+                       inv_freq);
     return ntk::last_launch_status();
 }
 
 int ntk_rope_kv_store(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
                       float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq, void* stream) {
-    if (!q || !k || !v || !positions || !k_cache || !v_cache) return NTK_E_NULL;
-    if (seq_len < 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || (head_dim & 1) || head_dim > 256 || start_pos < 0 || max_seq <= 0) return NTK_E_SHAPE;
-    if (seq_len == 0) return NTK_OK;
-    hipLaunchKernelGGL(ntk::rope_kv_store_rows_kernel, dim3(seq_len), dim3(256), 0, ntk::resolve_stream(stream), q, k, v, positions, n_heads, n_kv_heads,
-                       head_dim, theta_base, freq_scale, interleaved, static_cast<uint16_t*>(k_cache), static_cast<uint16_t*>(v_cache), start_pos, max_seq);
-    return ntk::last_launch_status();
+    return ntk_rope_kv_store_tab(q, k, v, positions, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, k_cache, v_cache, start_pos,
+                                 max_seq, nullptr, stream);
 }
 
 int ntk_copy_to_kv_cache(void* k_cache, void* v_cache, const float* k, const float* v, int seq_len, int n_kv_heads,
@@ -494,8 +511,8 @@ int ntk_kv_segments_validate(const ntk_kv_segments* segs, int total_rows, int ma
     return kv_segments_check(segs, total_rows, max_seq);
 }
 
-int ntk_rope_kv_store_segments(float* q, const float* k, const float* v, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim,
-                               float theta_base, float freq_scale, int interleaved, int max_seq, void* stream) {
+int ntk_rope_kv_store_segments_tab(float* q, const float* k, const float* v, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim,
+                                   float theta_base, float freq_scale, int interleaved, int max_seq, const float* inv_freq, void* stream) {
     if (!q || !k || !v || !segs) return NTK_E_NULL;
     if (n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || (head_dim & 1) || head_dim > 256) return NTK_E_SHAPE;
     const int rc = kv_segments_check(segs, -1, max_seq);
@@ -509,8 +526,13 @@ int ntk_rope_kv_store_segments(float* q, const float* k, const float* v, const n
     d.n_seg = segs->n_seg;
     const int rows = segs->row0[segs->n_seg - 1] + segs->n_rows[segs->n_seg - 1];
     hipLaunchKernelGGL(ntk::rope_kv_store_segments_kernel, dim3(rows), dim3(256), 0, ntk::resolve_stream(stream), q, k, v, d, n_heads, n_kv_heads, head_dim,
-                       theta_base, freq_scale, interleaved, max_seq);
+                       theta_base, freq_scale, interleaved, max_seq, inv_freq);
     return ntk::last_launch_status();
+}
+
+int ntk_rope_kv_store_segments(float* q, const float* k, const float* v, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim,
+                               float theta_base, float freq_scale, int interleaved, int max_seq, void* stream) {
+    return ntk_rope_kv_store_segments_tab(q, k, v, segs, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, max_seq, nullptr, stream);
 }
 
 int ntk_attention_prefill_segments(float* output, const float* Q, const ntk_kv_segments* segs, int n_heads, int n_kv_heads, int head_dim, int max_seq,

@@ -53,13 +53,13 @@ __global__ __launch_bounds__(256) void rope_kv_store_q8_rows_kernel(float* __res
                                                                     const int* __restrict__ positions, int n_heads, int n_kv_heads, int head_dim,
                                                                     float theta, float fscale, int interleaved, int8_t* __restrict__ kq,
                                                                     uint16_t* __restrict__ ks, int8_t* __restrict__ vq, uint16_t* __restrict__ vs,
-                                                                    int start_pos, int max_seq) {
+                                                                    int start_pos, int max_seq, const float* __restrict__ inv_freq) {
     __shared__ float cs[2][128];
     extern __shared__ __attribute__((aligned(16))) float krot[];   // [n_kv_heads * head_dim]
     const int sp = blockIdx.x, half_dim = head_dim / 2;
     const int pos = positions[sp];
     for (int i = threadIdx.x; i < half_dim; i += blockDim.x) {
-        const float freq = 1.0f / (float)pow((double)theta, (double)((2.0f * i) / head_dim));
+        const float freq = rope_freq(inv_freq, i, head_dim, theta);
         const float angle = pos * freq * fscale;
         cs[0][i] = cosf(angle);
         cs[1][i] = sinf(angle);
@@ -188,6 +188,14 @@ int ntk_kv_store_q8(void* k_cache, void* v_cache, const float* k, const float* v
 int ntk_rope_kv_store_q8(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
                          float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
                          void* stream) {
+    return ntk_rope_kv_store_q8_tab(q, k, v, positions, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, k_cache, v_cache,
+                                    start_pos, max_seq, nullptr, stream);
+}
+
+// ... with the per-pair frequencies from the device table inv_freq [head_dim / 2] (NULL: the in-kernel frequency)
+int ntk_rope_kv_store_q8_tab(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
+                             float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
+                             const float* inv_freq, void* stream) {
     if (!q || !k || !v || !positions || !k_cache || !v_cache) return NTK_E_NULL;
     if (seq_len < 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || head_dim % 32 != 0 || head_dim > 256 || start_pos < 0 || max_seq <= 0)
         return NTK_E_SHAPE;
@@ -196,7 +204,7 @@ int ntk_rope_kv_store_q8(float* q, const float* k, const float* v, const int* po
     if (seq_len == 0) return NTK_OK;
     const ntk::Q8Planes kp = ntk::q8_planes(k_cache, max_seq, per), vp = ntk::q8_planes(v_cache, max_seq, per);
     hipLaunchKernelGGL(ntk::rope_kv_store_q8_rows_kernel, dim3(seq_len), dim3(256), (size_t)per * 4, ntk::resolve_stream(stream), q, k, v, positions,
-                       n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, kp.q, kp.s, vp.q, vp.s, start_pos, max_seq);
+                       n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, kp.q, kp.s, vp.q, vp.s, start_pos, max_seq, inv_freq);
     return ntk::last_launch_status();
 }
 

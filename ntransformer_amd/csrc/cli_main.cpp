@@ -35,6 +35,10 @@ static void usage(const char* prog) {
             "  --no-fuse / --no-graph   Use the 15-launch/layer sequence / launch eagerly\n"
             "  --no-batched-prefill     Prompt tokens one by one (the reference's GEMV loops) instead of 16 per weight pass\n"
             "  --kv-cache <f16|q8_0>    KV cache format (default: f16; q8_0 = 8-bit Q8_0 blocks, 1.0625 bytes per element)\n"
+            "  --rope-scaling <s>       file (default: the GGUF's rope_freqs.weight and linear scaling) | none | linear:<factor> |\n"
+            "                           llama3:<factor>,<low>,<high>,<orig_ctx> (Llama-3.1 frequency factors computed by the engine)\n"
+            "  --rope-freq-base <float> RoPE theta, overriding the model's\n"
+            "  --rope-freq-scale <float> RoPE linear position scale, overriding the model's\n"
             "  --context-shift          At the end of the context drop half of the oldest positions and go on (default: stop there)\n"
             "  --keep <int>             Leading positions a context shift never drops (default: 1, the BOS)\n"
             "  --synthetic <shape:mix>  8b|70b|tiny : Q8_0|Q4_K_M|Q6_K|...  seeded synthetic weights, no file\n"
@@ -126,6 +130,12 @@ int main(int argc, char** argv) {
         else if (a == "--kv-cache") {
             const char* v = val();
             if (!v || engine.model().set_kv_cache(v) != NTK_OK) { fprintf(stderr, "Error: --kv-cache takes f16 or q8_0\n"); return 1; }
+        }
+        else if (a == "--rope-scaling" || a == "--rope-freq-base" || a == "--rope-freq-scale") {
+            const char* v = val();
+            const int rc = !v ? NTK_E_NULL : a == "--rope-scaling" ? engine.model().set_rope_scaling(v)
+                                           : a == "--rope-freq-base" ? engine.model().set_rope_freq_base(v) : engine.model().set_rope_freq_scale(v);
+            if (rc != NTK_OK) { fprintf(stderr, "Error: %s: %s\n", a.c_str(), v ? engine.model().error().c_str() : "a value is needed"); return 1; }
         }
         else if (a == "--context-shift") engine.options().context_shift = true;
         else if (a == "--keep") {

@@ -53,6 +53,13 @@ __device__ __forceinline__ void rope_rotate(const float a, const float b, const 
     rb = b * c + a * s;
 }
 
+// ---- the frequency of rotation pair i: entry i of the DEVICE table when there is one (the engine's, a model's scaling factors folded in), else
+//      powf evaluated in double and rounded once: reproduces a correctly-rounded powf (what IEEE libm gives the oracle); a 1-ulp slip in the
+//      frequency is a 4e-4 rad phase error at position 4095 ----
+__device__ __forceinline__ float rope_freq(const float* __restrict__ inv_freq, const int i, const int head_dim, const float theta) {
+    return inv_freq ? inv_freq[i] : 1.0f / (float)pow((double)theta, (double)((2.0f * i) / head_dim));
+}
+
 // ---- wave64 reductions on the DPP path (no LDS traffic, ~6 dependent VALU ops instead of six ds_bpermute round
 //      trips): quad swaps, half-row and row mirrors leave every lane of a 16-lane row with the row total;
 //      row_bcast:15 / row_bcast:31 then chain the four rows, so the wave total lands in lanes 48..63. ----

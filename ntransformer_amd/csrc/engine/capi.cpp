@@ -70,6 +70,9 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (on) fprintf(stderr, "note: \"%s\" selected an experiment that lost to the fused launches and was removed (profiles/NEGATIVE_RESULTS.md); the option does nothing\n", key);
     }
     else if (k == "kv_cache") return before_load([&] { return E(e)->model().set_kv_cache(value); });   // "f16" (default) | "q8_0": before the load only
+    else if (k == "rope_scaling") return before_load([&] { return E(e)->model().set_rope_scaling(value); });   // file (default) | none | linear:<f> | llama3:<f>,<low>,<high>,<ctx>: before the load only (model.h)
+    else if (k == "rope_freq_base") return before_load([&] { return E(e)->model().set_rope_freq_base(value); });   // theta > 0, overriding the file's
+    else if (k == "rope_freq_scale") return before_load([&] { return E(e)->model().set_rope_freq_scale(value); });   // the linear scale > 0, overriding the file's
     else if (k == "sequences") return before_load([&] { return E(e)->model().set_sequences(atoi(value)); });   // "1" .. "16" sequence slots: before the load only
     else if (k == "batch_kv_q8") {   // "0" (default) | "1": sequence slots and the batched step over the 8-bit cache; before the load only (model.h)
         const std::string v = value;
@@ -426,6 +429,11 @@ int nt_gguf_describe(const char* path, char* out, int cap) {
                  c.n_kv_heads, c.head_dim, c.max_seq_len, (double)c.norm_eps, (double)c.rope_theta, c.bos_token_id,
                  c.eos_token_id, f.vocab().tokens.size(), f.vocab().scores.size(), f.vocab().token_types.size());
         j += b;
+        snprintf(b, sizeof b, "\"rope_freq_scale\":%.9g,\"rope_factors\":%d,\"rope_orig_ctx\":%d,\"rope_scaling_type\":\"", (double)c.rope_freq_scale, c.rope_factors,
+                 c.rope_orig_ctx);
+        j += b;
+        json_escape(j, c.rope_scaling_type);
+        j += "\",";
         j += "\"architecture\":\""; json_escape(j, c.architecture); j += "\",\"name\":\""; json_escape(j, c.model_name);
         j += "\",\"tensors\":[";
         bool first = true;
@@ -446,6 +454,32 @@ int nt_gguf_describe(const char* path, char* out, int cap) {
         }
         return (int)j.size();
     } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_engine_rope_info(nt_engine_t e, char* out, int cap) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    try {
+        const nt::ModelConfig& c = E(e)->model().config();
+        char b[256];
+        snprintf(b, sizeof b, "{\"rope_theta\":%.9g,\"rope_freq_scale\":%.9g,\"rope_factors\":%d,\"rope_orig_ctx\":%d,\"rope_scaling_type\":\"", (double)c.rope_theta,
+                 (double)c.rope_freq_scale, c.rope_factors, c.rope_orig_ctx);
+        std::string j = b;
+        json_escape(j, c.rope_scaling_type);
+        j += "\"}";
+        if (out && cap > 0) {
+            const size_t k = std::min<size_t>(j.size(), (size_t)cap - 1);
+            memcpy(out, j.data(), k);
+            out[k] = 0;
+        }
+        return (int)j.size();
+    } catch (...) { return NTK_E_NOMEM; }
+}
+
+int nt_rope_llama3_factors(int head_dim, float theta, float factor, float low_freq_factor, float high_freq_factor, int orig_ctx, float* out) {
+    return nt::rope_llama3_factors(head_dim, theta, factor, low_freq_factor, high_freq_factor, orig_ctx, out);   // host only
+}
+int nt_rope_build_table(int head_dim, float theta, const float* factors_or_null, float* out) {
+    return nt::rope_build_table(head_dim, theta, factors_or_null, out);   // host only
 }
 
 nt_tokenizer_t nt_tokenizer_open(const char* path) {

@@ -2,6 +2,7 @@
 #include "gguf.h"
 #include "../../../include/ntk.h"
 
+#include <algorithm>
 #include <cinttypes>
 #include <cstdio>
 #include <cstring>
@@ -205,6 +206,13 @@ int GgufFile::parse() {   // reference loader.cpp:56-187
     m.max_seq_len = geti(pre + "context_length", m.max_seq_len);
     m.norm_eps = getf(pre + "attention.layer_norm_rms_epsilon", m.norm_eps);
     m.rope_theta = getf(pre + "rope.freq_base", m.rope_theta);
+    {   // RoPE scaling (llama.cpp's keys; the reference reads none of them): only "linear" changes freq_scale, the Model decides what else it applies
+        const float legacy = getf(pre + "rope.scale_linear", 0.0f);
+        m.rope_scaling_type = gets(pre + "rope.scaling.type", legacy > 0.0f ? "linear" : "none");
+        const float factor = getf(pre + "rope.scaling.factor", legacy);
+        if (m.rope_scaling_type == "linear" && factor > 0.0f && factor <= 3.0e38f) m.rope_freq_scale = 1.0f / factor;
+        m.rope_orig_ctx = geti(pre + "rope.scaling.original_context_length", 0);
+    }
     m.bos_token_id = geti("tokenizer.ggml.bos_token_id", m.bos_token_id);
     m.eos_token_id = geti("tokenizer.ggml.eos_token_id", m.eos_token_id);
     if (!vocab_.tokens.empty() && (int)vocab_.tokens.size() != m.vocab_size) m.vocab_size = (int)vocab_.tokens.size();  // loader.cpp:139-141
@@ -227,6 +235,7 @@ int GgufFile::parse() {   // reference loader.cpp:56-187
         index_[ti.name] = (size_t)t;
     }
     if (!c.ok) { err_ = "Truncated GGUF tensor table"; return NTK_E_FORMAT; }
+    if (const GgufTensor* rf = find("rope_freqs.weight")) m.rope_factors = (int)std::min<int64_t>(rf->numel(), 0x7FFFFFFF);
 
     size_t align = 32;   // loader.cpp:172-183
     if (auto it = meta_.find("general.alignment"); it != meta_.end() && it->second.kind == GgufValue::INT && it->second.i > 0)

@@ -22,7 +22,11 @@ struct ModelConfig {   // reference src/model/config.h:16-60 (same defaults)
     int head_dim = 128;
     float norm_eps = 1e-5f;
     float rope_theta = 10000.0f;
-    float rope_freq_scale = 1.0f;   // never read from GGUF by the reference (config.h:35): stays 1
+    float rope_freq_scale = 1.0f;   // never read from GGUF by the reference (config.h:35); here: 1 / <arch>.rope.scaling.factor for type "linear" (or the
+                                    // legacy <arch>.rope.scale_linear), else 1
+    std::string rope_scaling_type = "none";   // <arch>.rope.scaling.type as the file names it ("linear" for a bare scale_linear); a loaded Model: what it applies
+    int rope_orig_ctx = 0;          // <arch>.rope.scaling.original_context_length (0: absent)
+    int rope_factors = 0;           // elements of the tensor rope_freqs.weight (0: absent); a loaded Model: the divisors folded into its frequency table
     bool rope_interleaved = false;  // never set by the reference (config.h:36): NeoX pairing always
     int max_seq_len = 4096;
     int bos_token_id = 1;

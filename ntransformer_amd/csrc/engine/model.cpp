@@ -46,6 +46,7 @@ void Model::free_all() {
     repack_done_ = output_tied_ = false;
     host_pos_ = attn_regime_ = 0;
     kv_.reset();
+    rope_factors_.clear();
     batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = batch_recent_ = nullptr; batch_sample_scratch_ = nullptr;
     kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;
@@ -62,7 +63,8 @@ int Model::share_weights(const Model& src, int max_context) {
         err_ = "share_weights: the source must hold whole tensors of its own (no tensor parallelism, not itself a sharing sequence)";
         return NTK_E_SHAPE;
     }
-    cfg_ = src.cfg_;
+    cfg_ = src.cfg_;                     // (theta, the linear scale and ...
+    rope_factors_ = src.rope_factors_;   // ... the frequency divisors: this sequence rotates as its source does, whatever its own rope options say)
     cfg_full_ = src.cfg_;
     if (max_context > 0) cfg_.max_seq_len = max_context;
     vocab_ = src.vocab_;
@@ -223,6 +225,81 @@ int Model::set_kv_cache(const std::string& kind) {
     if (!layers_.empty()) { err_ = "kv_cache must be set before the model is loaded"; return NTK_E_SHAPE; }
     const bool q8 = kind == "q8_0";
     kv_q8_ = q8;
+    return NTK_OK;
+}
+
+int Model::set_rope_scaling(const std::string& text) {
+    if (!layers_.empty()) { err_ = "rope_scaling must be set before the model is loaded"; return NTK_E_SHAPE; }
+    RopeScalingOption o;
+    if (!parse_rope_scaling(text, &o, &err_)) return NTK_E_SHAPE;
+    rope_opt_ = o;
+    return NTK_OK;
+}
+
+int Model::set_rope_freq_base(const std::string& text) {
+    if (!layers_.empty()) { err_ = "rope_freq_base must be set before the model is loaded"; return NTK_E_SHAPE; }
+    if (!parse_positive_float(text, &rope_base_opt_)) { err_ = "rope_freq_base must be a number > 0"; return NTK_E_SHAPE; }
+    return NTK_OK;
+}
+
+int Model::set_rope_freq_scale(const std::string& text) {
+    if (!layers_.empty()) { err_ = "rope_freq_scale must be set before the model is loaded"; return NTK_E_SHAPE; }
+    if (!parse_positive_float(text, &rope_scale_opt_)) { err_ = "rope_freq_scale must be a number > 0"; return NTK_E_SHAPE; }
+    return NTK_OK;
+}
+
+// The rotation of the model being loaded: cfg_ holds the file's (or the synthetic spec's) theta, linear scale and scaling type; f (null: synthetic) may
+// carry the divisors.  Refusals name the tensor.
+int Model::resolve_rope(const GgufFile* f) {
+    rope_factors_.clear();
+    const int half = cfg_.head_dim / 2;
+    if (rope_base_opt_ > 0.0f) cfg_.rope_theta = rope_base_opt_;
+    // the file's divisors: kept under "file" and under "linear:<f>" (which overrides the linear scale alone, as llama.cpp's --rope-scaling linear
+    // does); "none" ignores them and "llama3:..." replaces them
+    const bool file_factors = rope_opt_.mode == RopeScalingOption::FILE || rope_opt_.mode == RopeScalingOption::LINEAR;
+    const GgufTensor* t = f && file_factors ? f->find("rope_freqs.weight") : nullptr;
+    if (t) {
+        if (t->dtype != NTK_DT_F32 || !t->known_type) { err_ = "rope_freqs.weight must be F32"; return NTK_E_DTYPE; }
+        if (t->numel() != half) {
+            err_ = "rope_freqs.weight holds " + std::to_string(t->numel()) + " factors, head_dim / 2 = " + std::to_string(half) + " are needed";
+            return NTK_E_SHAPE;
+        }
+        rope_factors_.resize((size_t)half);
+        memcpy(rope_factors_.data(), f->data(*t), (size_t)half * 4);
+        for (int i = 0; i < half; ++i)
+            if (!std::isfinite(rope_factors_[i]) || !(rope_factors_[i] > 0.0f)) {
+                err_ = "rope_freqs.weight: factor " + std::to_string(i) + " is not a finite number > 0";
+                rope_factors_.clear();
+                return NTK_E_SHAPE;
+            }
+    }
+    switch (rope_opt_.mode) {
+        case RopeScalingOption::FILE:   // (cfg_.rope_freq_scale: the file's linear scale, 1 otherwise)
+            if (cfg_.rope_scaling_type != "none" && cfg_.rope_scaling_type != "linear")
+                fprintf(stderr, "note: RoPE scaling type '%s' is not applied: the model runs with unscaled positions\n", cfg_.rope_scaling_type.c_str());
+            break;
+        case RopeScalingOption::NONE:
+            cfg_.rope_freq_scale = 1.0f; cfg_.rope_scaling_type = "none"; cfg_.rope_orig_ctx = 0;
+            break;
+        case RopeScalingOption::LINEAR:
+            cfg_.rope_freq_scale = 1.0f / rope_opt_.factor; cfg_.rope_scaling_type = "linear"; cfg_.rope_orig_ctx = 0;
+            break;
+        case RopeScalingOption::LLAMA3: {
+            rope_factors_.resize((size_t)half);
+            const int st = rope_llama3_factors(cfg_.head_dim, cfg_.rope_theta, rope_opt_.factor, rope_opt_.low, rope_opt_.high, rope_opt_.orig_ctx, rope_factors_.data());
+            if (st != NTK_OK) { rope_factors_.clear(); err_ = "rope_scaling: llama3 factors cannot be computed for this model"; return st; }
+            cfg_.rope_freq_scale = 1.0f; cfg_.rope_scaling_type = "llama3"; cfg_.rope_orig_ctx = rope_opt_.orig_ctx;
+            break;
+        }
+    }
+    // (the decode attention's generic form -- any other head size -- derives the frequency from theta and takes no table: ntk_attention_decode_fused)
+    if (!rope_factors_.empty() && cfg_.head_dim != 64 && cfg_.head_dim != 128 && cfg_.head_dim != 256) {
+        rope_factors_.clear();
+        err_ = "RoPE frequency factors (rope_freqs.weight / rope_scaling=llama3) need head_dim 64, 128 or 256 (this model: " + std::to_string(cfg_.head_dim) + ")";
+        return NTK_E_SHAPE;
+    }
+    if (rope_scale_opt_ > 0.0f) cfg_.rope_freq_scale = rope_scale_opt_;
+    cfg_.rope_factors = (int)rope_factors_.size();
     return NTK_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <vector>
 #include "gguf.h"
 #include "kv_cache.h"
+#include "rope_scaling.h"
 #include "synth.h"
 
 struct ntk_sample_rows;   // include/ntk_engine.h
@@ -206,6 +207,18 @@ public:
     // Decode: ntk_attention_decode_q8 + the combine launch in every regime (splits: kv_q8_splits).  Prompt pass / 1:1 sequence: 8-bit store, then
     // rows [0, start_pos + T) dequantised (rounded to half) into the scratch that the unchanged F16 attention kernels read.
     int set_kv_cache(const std::string& kind);
+    // RoPE frequency scaling (rope_scaling.h).  Three options, BEFORE the load, kept across loads, refused afterwards (NTK_E_SHAPE + error();
+    // malformed text too): "rope_scaling" = file (default: the GGUF's rope_freqs.weight divisors and its linear scaling keys) | none (ignore them) |
+    // linear:<factor> (the linear scale alone: the file's divisors stay) | llama3:<factor>,<low>,<high>,<orig_ctx> (the engine computes the divisors,
+    // replacing the file's: how a synthetic model gets them); "rope_freq_base" =
+    // theta, "rope_freq_scale" = the linear scale, each overriding what file and rope_scaling gave.  A load resolves them into cfg_.rope_theta,
+    // cfg_.rope_freq_scale and rope_factors_; alloc_buffers folds the divisors into rope_inv_freq_, the table every decode launch and the context shift
+    // already read.  The prompt-side launches get that table ONLY when there are divisors (rope_tab()): a model without them passes NULL as it always
+    // has, so its prompt passes keep the in-kernel frequency and every bit they had.  A sharing sequence takes its source's table and scale.
+    int set_rope_scaling(const std::string& text);
+    int set_rope_freq_base(const std::string& text);
+    int set_rope_freq_scale(const std::string& text);
+    int rope_factor_count() const { return (int)rope_factors_.size(); }
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
     uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included
@@ -268,7 +281,8 @@ public:
 private:
     int load_impl(const std::string& gguf_path, int max_context);
     int finish_load();
-    int init_device();                // the GPU NTK_DEVICE names (default 0)
+    int resolve_rope(const GgufFile* f);   // the rope options + the file (null: synthetic) -> cfg_.rope_theta / rope_freq_scale / rope_scaling_type / rope_orig_ctx / rope_factors, rope_factors_
+    int init_device();               // the GPU NTK_DEVICE names (default 0)
     int own_stream();                 // a private non-blocking stream: sequences and ranks that share a process must not queue behind each other
     int alloc_buffers();
     int upload(DevTensor& dst, const void* host, int dtype, int64_t in_f, int64_t out_f, size_t nbytes);
@@ -375,7 +389,11 @@ private:
     int* d_recent_ = nullptr;       // device copy of the repeat-penalty window
     int* h_recent_ = nullptr;       // pinned staging of it
     static constexpr int kRecentCap = kMaxRecent;
-    float* rope_inv_freq_ = nullptr; // [hd/2] 1/powf(theta, 2i/hd), computed once on the host (rotary.cu:47)
+    float* rope_inv_freq_ = nullptr; // [hd/2] (1/powf(theta, 2i/hd)) / divisor[i], computed once on the host (rotary.cu:47; rope_build_table)
+    std::vector<float> rope_factors_;   // the loaded model's per-pair frequency divisors (host; empty: none -- the prompt-side launches then pass NULL)
+    const float* rope_tab() const { return rope_factors_.empty() ? nullptr : rope_inv_freq_; }   // the prompt-side launches' table argument
+    RopeScalingOption rope_opt_;     // the options (kept across loads)
+    float rope_base_opt_ = 0.0f, rope_scale_opt_ = 0.0f;   // 0: not set
     void* stream_ = nullptr;
     bool batched_prefill_ = true;
     struct Timed { int cls; void* a; void* b; int n; bool shared_a; };   // n launches between events a and b

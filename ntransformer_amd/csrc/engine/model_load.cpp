@@ -75,6 +75,8 @@ int Model::load_impl(const std::string& path, int max_context) {
         fprintf(stderr, "Note: Capping context from %d to %d tokens (use --ctx-size to change)\n", cfg_.max_seq_len, max_context);
         cfg_.max_seq_len = max_context;
     }
+    st = resolve_rope(&f);   // (before anything is allocated: a bad rope_freqs.weight refuses the load)
+    if (st != NTK_OK) { fprintf(stderr, "%s\n", err_.c_str()); return st; }
     cfg_.print();
     f.print_info();
     st = init_device();
@@ -135,6 +137,7 @@ int Model::load_synthetic(const SynthSpec& spec, int max_context, int nthreads) 
     cfg_.max_seq_len = std::min(spec.ctx, max_context);
     cfg_.bos_token_id = spec.bos; cfg_.eos_token_id = spec.eos;
     synth_vocab(spec, vocab_.tokens, vocab_.token_types);
+    NT_TRY(resolve_rope(nullptr));   // (the spec carries no scaling: the rope options give a synthetic model one)
     NT_TRY(init_device());
     NT_TRY(tp_check_shapes());
 
@@ -362,7 +365,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     *h_token_ = 0;
     if (rope_inv_freq_) {
         std::vector<float> f((size_t)cfg_.head_dim / 2);
-        for (int i = 0; i < cfg_.head_dim / 2; ++i) f[i] = 1.0f / powf(cfg_.rope_theta, (2.0f * i) / cfg_.head_dim);
+        NT_TRY(rope_build_table(cfg_.head_dim, cfg_.rope_theta, rope_factors_.empty() ? nullptr : rope_factors_.data(), f.data()));
         nt_hip_memcpy_h2d(rope_inv_freq_, f.data(), f.size() * 4);
     }
     if (sequences_ > 1) { NT_TRY(batch_buffers()); NT_TRY(batch_sample_buffers()); }   // (none of it counted in kv_cache_bytes())

@@ -257,11 +257,12 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));
             kv_capture_T_ = T;
         }
+        // (every rotation below takes rope_tab(): the frequency table when the model carries frequency divisors, NULL -- the in-kernel frequency -- otherwise)
         if (kv.segs) {   // a packed prompt pass: every segment rotated, stored and attended on its own slot's cache from its own start position, one launch each
             ntk_kv_segments segs = *kv.segs;
             kv_.fill(segs, kv.slots, i);
-            ok(ntk_rope_kv_store_segments(act.q, act.k, act.v, &segs, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
-                                          cfg_.max_seq_len, s));
+            ok(ntk_rope_kv_store_segments_tab(act.q, act.k, act.v, &segs, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
+                                              cfg_.max_seq_len, rope_tab(), s));
             ok(ntk_attention_prefill_segments(act.attn_out, act.q, &segs, nh, nkv, hd, cfg_.max_seq_len, scale, s));
         } else if (kv.slots && kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
             ntk_kv_batch caches{};
@@ -279,18 +280,18 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             void* kc8 = kv_.k(kv.slot, i);   // (kc / vc: the image, shared by all slots: rebuilt here, for this slot, every pass)
             void* vc8 = kv_.v(kv.slot, i);
             if (T >= 4) {
-                ok(ntk_rope_kv_store_q8(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
-                                        kc8, vc8, start_pos, cfg_.max_seq_len, s));
+                ok(ntk_rope_kv_store_q8_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
+                                            kc8, vc8, start_pos, cfg_.max_seq_len, rope_tab(), s));
             } else {
-                ok(ntk_rope(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, s));
+                ok(ntk_rope_tab(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, rope_tab(), s));
                 ok(ntk_kv_store_q8(kc8, vc8, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
             }
             ok(ntk_kv_dequant_q8_f16(kc, vc, kc8, vc8, start_pos + T, nkv, hd, cfg_.max_seq_len, s));
         } else if (with_max && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
-            ok(ntk_rope_kv_store(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, kc, vc,
-                                 start_pos, cfg_.max_seq_len, s));
+            ok(ntk_rope_kv_store_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, kc, vc,
+                                     start_pos, cfg_.max_seq_len, rope_tab(), s));
         } else {
-            ok(ntk_rope(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, s));
+            ok(ntk_rope_tab(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, rope_tab(), s));
             ok(ntk_copy_to_kv_cache(kc, vc, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
         }
         if (kv.slots) {}   // (attended above)

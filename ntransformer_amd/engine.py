@@ -118,6 +118,10 @@ def _bind():
     L.nt_kv_copy_validate.argtypes = [i, i, i, i, i, i]
     L.nt_context_shift_discard.argtypes = [i, i]
     L.nt_engine_kv_cache_bytes.restype = C.c_uint64
+    L.nt_rope_llama3_factors.argtypes = [i, f, f, f, f, i, vp]
+    L.nt_rope_build_table.argtypes = [i, f, vp, vp]
+    L.nt_engine_rope_info.argtypes = [vp, C.c_char_p, i]
+    L.nt_gguf_describe.argtypes = [C.c_char_p, C.c_char_p, i]
     L._engine_bound = True
     return L
 
@@ -185,8 +189,34 @@ class Engine:
         return int(self.L.nt_engine_tp_error(self.h))
 
     def set_option(self, key: str, value) -> None:
-        text = value if isinstance(value, str) else str(int(value))   # ("kv_cache" takes "f16" / "q8_0")
+        # ("kv_cache" takes "f16" / "q8_0", "rope_scaling" its own strings; "rope_freq_base" / "rope_freq_scale" a float)
+        if isinstance(value, str):
+            text = value
+        elif key in ("rope_freq_base", "rope_freq_scale"):
+            text = repr(float(value))          # (any real number type: float, numpy.float32, int)
+        else:
+            text = str(int(value))
         self._check(self.L.nt_engine_set_option(self.h, key.encode(), text.encode()), "set_option " + key)
+
+    def rope_info(self) -> dict:
+        """The rotation the loaded model runs with (nt_engine_rope_info): rope_theta, rope_scaling_type ("none", "linear", "llama3", or the file's
+        type where it is not applied), rope_freq_scale, rope_factors (how many per-pair divisors the frequency table carries: 0 or head_dim / 2),
+        rope_orig_ctx."""
+        import json
+        buf = C.create_string_buffer(512)
+        n = self.L.nt_engine_rope_info(self.h, buf, len(buf))
+        if n < 0:
+            self._check(n, "rope_info")
+        return json.loads(buf.value.decode())
+
+    @property
+    def rope_scaling_type(self) -> str: return self.rope_info()["rope_scaling_type"]
+    @property
+    def rope_freq_scale(self) -> float: return float(self.rope_info()["rope_freq_scale"])
+    @property
+    def rope_factors(self) -> int: return int(self.rope_info()["rope_factors"])
+    @property
+    def rope_orig_ctx(self) -> int: return int(self.rope_info()["rope_orig_ctx"])
 
     @property
     def vocab_size(self): return self.L.nt_engine_vocab_size(self.h)
@@ -504,6 +534,36 @@ def kv_copy_validate(src_slot: int, dst_slot: int, pos0: int, n: int, sequences:
 def context_shift_discard(n_past: int, keep: int) -> int:
     """Host only (nt_context_shift_discard): how many positions the generate loop drops when the context is full: max(1, (n_past - keep) // 2)."""
     return int(_bind().nt_context_shift_discard(int(n_past), int(keep)))
+
+
+def rope_llama3_factors(head_dim: int, theta: float, factor: float = 8.0, low_freq_factor: float = 1.0, high_freq_factor: float = 4.0,
+                        orig_ctx: int = 8192) -> np.ndarray:
+    """Host only (nt_rope_llama3_factors): the Llama-3.1 frequency divisors as the engine computes them for rope_scaling=llama3:..., float32 [head_dim / 2]."""
+    out = np.zeros(head_dim // 2, np.float32)
+    check(_bind().nt_rope_llama3_factors(int(head_dim), theta, factor, low_freq_factor, high_freq_factor, int(orig_ctx), out.ctypes.data_as(C.c_void_p)),
+          "rope_llama3_factors")
+    return out
+
+
+def rope_build_table(head_dim: int, theta: float, factors: Optional[np.ndarray] = None) -> np.ndarray:
+    """Host only (nt_rope_build_table): the engine's frequency table, (1 / powf(theta, 2i / head_dim)) / factors[i] in F32, float32 [head_dim / 2]."""
+    out = np.zeros(head_dim // 2, np.float32)
+    fa = None if factors is None else np.ascontiguousarray(factors, dtype=np.float32)
+    check(_bind().nt_rope_build_table(int(head_dim), theta, None if fa is None else fa.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)),
+          "rope_build_table")
+    return out
+
+
+def gguf_describe(path: str) -> dict:
+    """Host only (nt_gguf_describe): the C++ reader's view of a GGUF file -- hyper-parameters, the RoPE scaling fields and the tensor table."""
+    import json
+    L = _bind()
+    n = L.nt_gguf_describe(path.encode(), None, 0)
+    if n < 0:
+        raise _lib.NtkError(int(n), "gguf_describe " + path)
+    buf = C.create_string_buffer(n + 1)
+    L.nt_gguf_describe(path.encode(), buf, n + 1)
+    return json.loads(buf.value.decode())
 
 
 def sampler_draw_nth(logits: np.ndarray, params: GenParams, recent: Sequence[int], skip: int) -> int:

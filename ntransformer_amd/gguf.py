@@ -435,10 +435,33 @@ def synth_vocab(shape: LlamaShape, rng: np.random.Generator) -> Tuple[List[bytes
     return toks, types
 
 
+def llama3_rope_factors(head_dim: int, theta: float, factor: float = 8.0, low_freq_factor: float = 1.0, high_freq_factor: float = 4.0,
+                        orig_ctx: int = 8192) -> np.ndarray:
+    """The Llama-3.1 frequency divisors a converter writes into rope_freqs.weight: float32 [head_dim / 2], computed in float64.  Pair i of wavelength
+    2 pi theta^(2i/hd): 1 below orig_ctx / high, `factor` above orig_ctx / low, 1 / ((1 - s) / factor + s) with s = (orig_ctx / wavelen - low) / (high -
+    low) in between."""
+    i = np.arange(head_dim // 2, dtype=np.float64)
+    wavelen = 2.0 * np.pi * np.power(np.float64(theta), 2.0 * i / head_dim)
+    out = np.empty(head_dim // 2, np.float64)
+    for j, w in enumerate(wavelen):
+        if w < orig_ctx / high_freq_factor:
+            out[j] = 1.0
+        elif w > orig_ctx / low_freq_factor:
+            out[j] = factor
+        else:
+            s = (orig_ctx / w - low_freq_factor) / (high_freq_factor - low_freq_factor)
+            out[j] = 1.0 / ((1.0 - s) / factor + s)
+    return out.astype(np.float32)
+
+
 def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: int = 20260925,
-                         with_scores: bool = False, overrides: Optional[Dict[str, str]] = None) -> Dict[str, int]:
+                         with_scores: bool = False, overrides: Optional[Dict[str, str]] = None,
+                         rope_freqs: Optional[np.ndarray] = None, rope_scaling: Optional[Dict[str, object]] = None) -> Dict[str, int]:
     """Write a seeded synthetic Llama-architecture GGUF; returns {tensor name: ggml type}.
-    overrides: per-matrix types on top of the mix, in every layer ({"ffn_up": "Q4_K"})."""
+    overrides: per-matrix types on top of the mix, in every layer ({"ffn_up": "Q4_K"}).
+    rope_freqs: the per-pair frequency divisors, appended as the tensor rope_freqs.weight (float32; a float16 array is written as F16, any length is
+    written as given: the loader's refusals).  rope_scaling: {"type": "linear" | "yarn" | ..., "factor": F, "original_context_length": N,
+    "scale_linear": F (the legacy key)} -> the llama.rope.scaling.* / llama.rope.scale_linear keys that are named.  Both None: nothing is appended."""
     types = tensor_types(shape, mix)
     for m, t in (overrides or {}).items():
         for i in range(shape.layers):
@@ -500,6 +523,19 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
     if with_scores:
         sc = -np.arange(shape.vocab, dtype=np.float32)  # earlier id = better merge
         kvs.append(kv_arr_f32("tokenizer.ggml.scores", sc))
+    if rope_scaling:
+        if "type" in rope_scaling:
+            kvs.append(kv_str("llama.rope.scaling.type", str(rope_scaling["type"])))
+        if "factor" in rope_scaling:
+            kvs.append(kv_f32("llama.rope.scaling.factor", float(rope_scaling["factor"])))
+        if "original_context_length" in rope_scaling:
+            kvs.append(kv_u32("llama.rope.scaling.original_context_length", int(rope_scaling["original_context_length"])))
+        if "scale_linear" in rope_scaling:
+            kvs.append(kv_f32("llama.rope.scale_linear", float(rope_scaling["scale_linear"])))
+    if rope_freqs is not None:
+        rf = np.asarray(rope_freqs)
+        f16 = rf.dtype == np.float16
+        specs.append(TensorSpec("rope_freqs.weight", (int(rf.size),), GGML_F16 if f16 else GGML_F32, rf.astype("<f2" if f16 else "<f4").tobytes()))
     write_gguf(path, kvs, specs)
     return types
 

@@ -125,6 +125,13 @@ def rope_kv_store_q8(q, k, v, positions, seq_len, n_heads, n_kv_heads, head_dim,
                                           interleaved, _p(kc), _p(vc), start_pos, kc.max_seq, stream), "rope_kv_store_q8")
 
 
+def rope_kv_store_q8_tab(q, k, v, positions, seq_len, n_heads, n_kv_heads, head_dim, theta_base, kc: Q8Cache, vc: Q8Cache, start_pos, freq_scale=1.0,
+                         interleaved=0, inv_freq=None, stream=None):
+    """ntk_rope_kv_store_q8_tab: rope_kv_store_q8 with the frequency table (None: the in-kernel frequency)"""
+    check(_lib.lib().ntk_rope_kv_store_q8_tab(_p(q), _p(k), _p(v), _p(positions), seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale,
+                                              interleaved, _p(kc), _p(vc), start_pos, kc.max_seq, _p(inv_freq), stream), "rope_kv_store_q8_tab")
+
+
 def kv_dequant_q8_f16(k16, v16, kc: Q8Cache, vc: Q8Cache, n_rows, n_kv_heads, head_dim, stream=None):
     check(_lib.lib().ntk_kv_dequant_q8_f16(_p(k16), _p(v16), _p(kc), _p(vc), n_rows, n_kv_heads, head_dim, kc.max_seq, stream), "kv_dequant_q8_f16")
 

@@ -96,6 +96,12 @@ def launch_rope(q, k, positions, batch_size, seq_len, n_heads, n_kv_heads, head_
                               theta_base, freq_scale, int(bool(interleaved)), stream), "rope")
 
 
+def rope_tab(q, k, positions, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, inv_freq=None, stream=None):
+    """ntk_rope_tab: ntk_rope with the per-pair frequencies from the device table inv_freq [head_dim / 2] (None: the in-kernel frequency)"""
+    check(_lib.lib().ntk_rope_tab(_p(q), _p(k), _p(positions), 1, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale,
+                                  int(bool(interleaved)), _p(inv_freq), stream), "rope_tab")
+
+
 def launch_softmax(output, input, rows, cols, stream=None):
     check(_lib.lib().ntk_softmax(_p(output), _p(input), rows, cols, stream), "softmax")
 
@@ -342,6 +348,13 @@ def rope_kv_store(q, k, v, positions, seq_len, n_heads, n_kv_heads, head_dim, th
                                        int(bool(interleaved)), _p(k_cache), _p(v_cache), start_pos, max_seq, None), "rope_kv_store")
 
 
+def rope_kv_store_tab(q, k, v, positions, seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale, interleaved, k_cache, v_cache, start_pos, max_seq,
+                      inv_freq=None):
+    """ntk_rope_kv_store_tab: rope_kv_store with the frequency table (None: the in-kernel frequency)"""
+    check(_lib.lib().ntk_rope_kv_store_tab(_p(q), _p(k), _p(v), _p(positions), seq_len, n_heads, n_kv_heads, head_dim, theta_base, freq_scale,
+                                           int(bool(interleaved)), _p(k_cache), _p(v_cache), start_pos, max_seq, _p(inv_freq), None), "rope_kv_store_tab")
+
+
 def gemm_workspace(in_features, rows):
     L = _lib.lib()
     L.ntk_gemm_quant_workspace_bytes.restype = C.c_size_t
@@ -491,6 +504,13 @@ def rope_kv_store_segments(q, k, v, desc, n_heads, n_kv_heads, head_dim, theta_b
     the status (the caller checks it: the refusal tests read it)"""
     return int(_lib.lib().ntk_rope_kv_store_segments(_p(q), _p(k), _p(v), C.addressof(desc) if desc is not None else None, n_heads, n_kv_heads, head_dim,
                                                      theta_base, freq_scale, int(interleaved), max_seq, stream))
+
+
+def rope_kv_store_segments_tab(q, k, v, desc, n_heads, n_kv_heads, head_dim, theta_base, max_seq, freq_scale=1.0, interleaved=False, inv_freq=None,
+                               stream=None) -> int:
+    """ntk_rope_kv_store_segments_tab: rope_kv_store_segments with the frequency table (None: the in-kernel frequency); returns the status"""
+    return int(_lib.lib().ntk_rope_kv_store_segments_tab(_p(q), _p(k), _p(v), C.addressof(desc) if desc is not None else None, n_heads, n_kv_heads,
+                                                         head_dim, theta_base, freq_scale, int(interleaved), max_seq, _p(inv_freq), stream))
 
 
 def attention_prefill_segments(output, Q, desc, n_heads, n_kv_heads, head_dim, max_seq, scale, stream=None) -> int:

@@ -46,6 +46,7 @@ def main():
     ap.add_argument("--model", default="8b", help="engine part: synthetic model preset (8b, 70b)")
     ap.add_argument("--layers", type=int, default=0, help="engine part: layers of the preset to build (0 = all)")
     ap.add_argument("--option", action="append", default=[], help="engine part: key=value engine options (e.g. prefill_fused_split=0)")
+    ap.add_argument("--ab-rope-scaling", default="", help="engine part: a rope_scaling option value (e.g. llama3:8,1,4,8192): the prompt pass without and with it, two engines in this process, alternated, median of 3")
     ap.add_argument("--bf16-only", action="store_true", help="per-matrix table: only the FP16 GEMM launches (profiling; the flag keeps its round-2 name)")
     a = ap.parse_args()
     ops.init(0)
@@ -83,7 +84,30 @@ def main():
             res["gemm"].append(row)
             print("%-5s %-12s %8.2f MB  gemm(16 tok) %8.1f us = %6.1f GB/s of weights, %5.1f TFLOP/s | 16 x gemv %8.1f us  (x%.1f)"
                   % (dname, sname, mb, row["gemm_us"], row["weight_GBps"], row["TFLOPs"], row["gemv_loop_us"], t_loop / t_gemm), flush=True)
-    if not a.no_engine:
+    if not a.no_engine and a.ab_rope_scaling:
+        # two engines in this process, the same synthetic model without and with the option (it shapes the load), their prompt passes alternated
+        engines = []
+        for spec in (None, a.ab_rope_scaling):
+            eng = E.Engine()
+            if spec: eng.set_option("rope_scaling", spec)
+            eng.load_synthetic(E.synth_spec(a.model, a.mix, layers=a.layers) if a.layers else E.synth_spec(a.model, a.mix), 4096)
+            engines.append((spec or "unscaled", eng))
+        r = np.random.Generator(np.random.Philox(key=[20260925, 99]))
+        for T in [int(t) for t in a.tokens.split(',')]:
+            prompt = [128000] + [int(t) for t in r.integers(0, 128000, T - 1)]
+            ts = {name: [] for name, _ in engines}
+            for name, eng in engines: eng.forward(prompt, 0)
+            for rep in range(3):
+                for name, eng in engines:
+                    t0 = time.perf_counter(); eng.forward(prompt, 0); ts[name].append(time.perf_counter() - t0)
+            for name, eng in engines:
+                med = sorted(ts[name])[1]
+                res["engine"].append({"mix": a.mix, "prompt_tokens": T, "rope_scaling": name, "rope_factors": eng.rope_factors, "ms": round(med * 1e3, 2),
+                                      "all_ms": [round(t * 1e3, 2) for t in ts[name]]})
+                print("%s %s prompt of %4d tokens, rope_scaling %-22s (%2d factors): median of 3 %9.2f ms = %9.1f tokens/s   [%s]" %
+                      (a.model.upper(), a.mix, T, name, eng.rope_factors, med * 1e3, T / med, " ".join("%.2f" % (t * 1e3) for t in ts[name])), flush=True)
+        for _, eng in engines: eng.close()
+    elif not a.no_engine:
         eng = E.Engine()
         if a.repack >= 0: eng.set_option("repack", a.repack)
         for kv in a.option: eng.set_option(kv.split("=")[0], int(kv.split("=")[1]))
