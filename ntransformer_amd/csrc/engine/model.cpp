@@ -14,6 +14,20 @@ void Model::drop_graphs() {
         }
 }
 
+void* Model::dev_alloc(size_t bytes, bool zero) {
+    void* p = nt_hip_malloc(bytes + 256);
+    if (!p) return nullptr;
+    allocs_.push_back(p);
+    if (zero) nt_hip_memset(p, 0, bytes);
+    return p;
+}
+
+void Model::dev_free(void* p) {
+    if (!p) return;
+    allocs_.erase(std::remove(allocs_.begin(), allocs_.end(), p), allocs_.end());
+    nt_hip_free(p);
+}
+
 void Model::free_all() {
     drop_graphs();
     for (int r = 0; r < 8; ++r) {   // peers' communication buffers mapped through hipIpc
@@ -76,9 +90,8 @@ int Model::share_weights(const Model& src, int max_context) {
     repack_bytes_ = 0;                   // none of it is this object's
     shares_weights_ = true;
     if (src.raw_freed_bytes_ > 0 && src.raw_scratch_bytes_ > 0) {   // one resident copy: what still reads raw blocks (the 1:1 sequence, the prompt's LM head) unpacks
-        void* d = nt_hip_malloc(src.raw_scratch_bytes_);         // into a scratch of THIS sequence (stream ordered on this sequence's stream)
+        void* d = dev_alloc(src.raw_scratch_bytes_, false);      // into a scratch of THIS sequence (stream ordered on this sequence's stream)
         if (!d) { err_ = "share_weights: no device memory for the unpack scratch"; free_all(); return NTK_E_NOMEM; }
-        allocs_.push_back(d);
         raw_scratch_ = d; raw_scratch_bytes_ = src.raw_scratch_bytes_;
         raw_freed_bytes_ = src.raw_freed_bytes_;
     }

@@ -31,6 +31,8 @@ struct DevTensor {
     size_t rp_bytes = 0;
 };
 
+struct PassStatus;   // model_impl.h
+
 struct LayerWeights {
     DevTensor attn_norm, wq, wk, wv, wo, ffn_norm, w_gate, w_up, w_down;
 };
@@ -319,7 +321,24 @@ private:
     // nullptr -- the rows are the segments *segs describes (rows, lengths, first positions; the cache pointers are filled per layer) and segment j lives in
     // slot slots[j] (forward_batch)
     struct KvTarget { int slot; const int* slots; int max_pos; const ntk_kv_segments* segs; };
-    int layers_1to1(int T, int start_pos, int first, int last, const KvTarget& kv = KvTarget{0, nullptr, 0, nullptr});   // the layer loop of forward(), score(), decode_batch() and forward_batch()
+    // the layer loop of forward(), score() (model_prompt.cpp), decode_batch() and forward_batch() (model_batch.cpp)
+    int layers_1to1(int T, int start_pos, int first, int last, const KvTarget& kv = KvTarget{0, nullptr, 0, nullptr});
+    // one layer's KV step and attention: q | k | v of `act` rotated, k | v stored where `kv` says in the cache's format, act.attn_out = the T rows' attention.
+    // fused_store: the prompt form of rotation + store (the pass runs with row maxima).  Returns the first failure; every launch goes out.
+    int attend(int layer, int T, int start_pos, const KvTarget& kv, const Views& act, bool fused_store);
+    // ---- the steps the host-driven passes share (model_prompt.cpp) ----
+    // out [n][H] = the embedding rows of the device ids.  A table format without a kernel is said on stderr and is NOT an error (as the reference).
+    int embed_rows(float* out, const int* ids_dev, int n);
+    // positions_[0, T) = start_pos, start_pos + 1, ...: queued from host_positions_, which the caller's next synchronisation releases
+    int upload_positions(int T, int start_pos);
+    // the final RMSNorm of n rows, src -> dst, in the form the LM head wants: returns the rows' largest |x| (in row_max_) where the FP16 GEMM reads the
+    // head, null otherwise
+    const float* final_norm(float* dst, const float* src, int n, PassStatus& ok);
+    // the end of every pass: synchronise, take over what raw_of() could not report through its pointer, and leave `failed` + the status in err_ unless
+    // a launcher's own message about a launch failure is already there.  Returns the pass's status.
+    int finish_pass(const char* failed, int rc);
+    // ntk_gemv over w's raw blocks wp; NTK_E_DTYPE is said on stderr (gemm.cu:801-803) and returned like any status
+    int gemv_logged(float* y, const DevTensor& w, const void* wp, const float* x);
     // logits [n][vocab] of the final-normed rows X [n][H] (row_max: their largest |x| or null): one pass over the LM head, in the form score() takes
     int lm_head(float* logits, const float* X, int n, const float* row_max);
     bool lm_head_f16() const;         // ... is the FP16 GEMM
@@ -328,6 +347,12 @@ private:
     int batch_logits(const int* slots, const int* tokens, const int* positions, int B);   // decode_batch / _sample up to batch_logits_ (queued)
     int batch_sample_buffers();       // ... and what decode_batch_sample() needs beside them (windows, sampler scratch, pinned mirrors): the same rule
     int score_buffers();              // the buffers of score(), on its first call (and again when score_rows grew)
+    // ---- device memory this object owns (model.cpp): freed by free_all() or, one at a time, by dev_release ----
+    void* dev_alloc(size_t bytes, bool zero);   // `bytes` + 256 of tail (kernels may read a last 16-byte chunk whole), remembered in allocs_; zero: the `bytes` cleared.  Null: no memory
+    void dev_free(void* p);                     // out of allocs_ and back to the device (null: nothing)
+    template <class T> void dev_release(T*& p) { dev_free(p); p = nullptr; }
+    // a buffer an earlier, failed call obtained is kept: only what is missing is allocated
+    template <class T> bool dev_need(T*& p, size_t bytes, bool zero) { if (!p) p = static_cast<T*>(dev_alloc(bytes, zero)); return p != nullptr; }
     void prof_mark(int cls, bool begin);
 
     ModelConfig cfg_;
@@ -378,6 +403,7 @@ private:
     void* score_ws_ = nullptr;      // the FP16 GEMM's workspace for the LM head where gemm_ws_ is too small for vocab rows
     size_t score_ws_bytes_ = 0;
     int* positions_ = nullptr;      // [max_seq]
+    std::vector<int> host_positions_;   // upload_positions()' host image between its H2D copy and the caller's synchronisation
     int* tokens_dev_ = nullptr;     // [max_seq]
     int* d_pos_ = nullptr;          // device scalar: position of the token being decoded
     int* d_token_ = nullptr;        // device scalar: id of the token being decoded

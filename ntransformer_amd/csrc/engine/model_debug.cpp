@@ -20,9 +20,7 @@ int Model::debug_run_layers(const float* hidden_in, int T, int start_pos, int fi
     NT_TRY(ntk_memcpy_h2d_async(hid, hidden_in, bytes, s));
     int rc;
     if (mode == 0) {
-        std::vector<int> pos(T);
-        for (int i = 0; i < T; ++i) pos[i] = start_pos + i;
-        NT_TRY(ntk_memcpy_h2d_async(positions_, pos.data(), (size_t)T * 4, s));
+        NT_TRY(upload_positions(T, start_pos));
         NT_TRY(ntk_stream_synchronize(s));
         rc = layers_1to1(T, start_pos, first, first + count);
     } else {
@@ -106,9 +104,8 @@ int Model::debug_kv_inputs_capture(int layer) {
     kv_capture_T_ = 0;
     if (layer >= 0 && !kv_capture_) {
         const size_t bytes = 2 * (size_t)cfg_.max_seq_len * cfg_.n_kv_heads * cfg_.head_dim * 4;
-        kv_capture_ = (float*)nt_hip_malloc(bytes);
+        kv_capture_ = (float*)dev_alloc(bytes, false);
         if (!kv_capture_) { err_ = "debug_kv_inputs_capture: out of device memory"; return NTK_E_NOMEM; }
-        allocs_.push_back(kv_capture_);
     }
     return NTK_OK;
 }

@@ -17,6 +17,12 @@ namespace nt {
         if (st__ != NTK_OK) return st__;   \
     } while (0)
 
+// The status of a pass that queues launch after launch: the FIRST failure is the pass's, the calls behind it still go out.  ok(st) folds one in.
+struct PassStatus {
+    int rc = NTK_OK;
+    void operator()(int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; }
+};
+
 inline bool is_quant(int dt) {
     return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K;
 }

@@ -4,9 +4,8 @@
 namespace nt {
 
 int Model::upload(DevTensor& dst, const void* host, int dtype, int64_t in_f, int64_t out_f, size_t nbytes) {
-    void* d = nt_hip_malloc(padded_bytes(nbytes));
+    void* d = dev_alloc(padded_bytes(nbytes), false);
     if (!d) { err_ = "out of device memory"; return NTK_E_NOMEM; }
-    allocs_.push_back(d);
     if (host && nbytes) {   // a failed upload must not leave silently garbage weights behind
         if (hipMemcpy(d, host, nbytes, hipMemcpyHostToDevice) != hipSuccess) { err_ = "weight upload (H2D copy) failed"; return NTK_E_LAUNCH; }
     }
@@ -206,9 +205,8 @@ int Model::repack_one(DevTensor& t) {
     const bool q8 = t.dtype == NTK_DT_Q8_0;   // (its own form and entry points: the lane-major rows)
     const size_t n = q8 ? ntk_q8l_bytes((int)t.out_f, (int)t.in_f) : ntk_rp_bytes(t.dtype, (int)t.out_f, (int)t.in_f);
     if (n == 0 || n > 0xFFFFFFF0ull) return NTK_OK;   // formats / shapes without a repacked form keep the raw path
-    void* d = nt_hip_malloc(n + 256);
+    void* d = dev_alloc(n, false);
     if (!d) return NTK_E_NOMEM;   // (the caller keeps the tensors that did fit and lets the raw path take the rest)
-    allocs_.push_back(d);
     const int st = q8 ? ntk_q8l_pack(d, t.ptr, (int)t.out_f, (int)t.in_f, stream_) : ntk_rp_pack(d, t.ptr, (int)t.out_f, (int)t.in_f, t.dtype, stream_);
     if (st != NTK_OK) { err_ = std::string("decode repack failed: ") + ntk_status_string(st); return st; }
     t.rp = d;
@@ -245,17 +243,13 @@ int Model::drop_raw_all() {
     grp({&output_});
     if (need == 0) return NTK_OK;
     if (!raw_scratch_ || raw_scratch_bytes_ < need) {
-        void* d = nt_hip_malloc(need);
+        void* d = dev_alloc(need, false);
         if (!d) { fprintf(stderr, "warning: no device memory for the unpack scratch: the GGUF bytes stay resident beside the repack\n"); repack_ = 1; return NTK_OK; }
-        allocs_.push_back(d);
         raw_scratch_ = d; raw_scratch_bytes_ = need;
     }
     auto drop = [&](DevTensor& t) {
         if (!t.ptr || !goes(t)) return;
-        auto it = std::find(allocs_.begin(), allocs_.end(), t.ptr);
-        if (it != allocs_.end()) allocs_.erase(it);
-        nt_hip_free(t.ptr);
-        t.ptr = nullptr;
+        dev_release(t.ptr);
         raw_freed_bytes_ += t.nbytes;
     };
     NT_TRY(ntk_stream_synchronize(stream_));
@@ -267,11 +261,10 @@ int Model::restore_raw_all() {
     int rc = NTK_OK;
     auto back = [&](DevTensor& t) {
         if (t.ptr || !t.rp || rc != NTK_OK) return;
-        void* d = nt_hip_malloc(padded_bytes(t.nbytes));
+        void* d = dev_alloc(padded_bytes(t.nbytes), false);
         if (!d) { rc = NTK_E_NOMEM; return; }
         const int st = ntk_rp_unpack(d, t.rp, (int)t.out_f, (int)t.in_f, t.dtype, stream_);
-        if (st != NTK_OK) { nt_hip_free(d); rc = st; return; }
-        allocs_.push_back(d);
+        if (st != NTK_OK) { dev_free(d); rc = st; return; }
         t.ptr = d;
         raw_freed_bytes_ -= t.nbytes;
     };
@@ -298,11 +291,6 @@ const void* Model::raw_of(const DevTensor& t) {
 int Model::alloc_buffers() {   // transformer.cpp:330-391
     const size_t S = (size_t)cfg_.max_seq_len, H = (size_t)cfg_.hidden_size;
     const size_t per = (size_t)cfg_.n_kv_heads * cfg_.head_dim;
-    auto dev = [&](size_t bytes, bool zero) -> void* {
-        void* p = nt_hip_malloc(bytes + 256);
-        if (p) { allocs_.push_back(p); if (zero) nt_hip_memset(p, 0, bytes); }
-        return p;
-    };
     // the attention kernels address a layer's cache rows with 32-bit byte offsets (attention.hip): a context whose per-layer cache reaches
     // 3.75 GiB is refused here, at load, rather than as NTK_E_SHAPE from the first decode step (8 KV heads of 128: 1.9 M positions)
     if (S * per * sizeof(uint16_t) >= 0xF0000000ull) { err_ = "context too long: one layer's K cache must stay below 3.75 GiB (32-bit row offsets)"; return NTK_E_SHAPE; }
@@ -320,26 +308,26 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         // a batched step is a prompt pass of up to `sequences` rows through buffers of max_seq rows (hidden_, residual_, workspace_, row_max_, kv_capture_)
         if ((size_t)sequences_ > S) { err_ = "sequences = " + std::to_string(sequences_) + " needs a context of at least as many positions (this load: " + std::to_string(S) + ")"; return NTK_E_SHAPE; }
     }
-    NT_TRY(kv_.allocate(KvGeom{cfg_.n_layers, cfg_.max_seq_len, cfg_.n_kv_heads, cfg_.head_dim}, kv_q8_, sequences_, dev, &err_));
-    hidden_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
-    residual_ = (float*)dev(std::max<size_t>(S, 2) * H * 4, false);
-    logits_ = (float*)dev((size_t)cfg_.vocab_size * 4, false);
+    NT_TRY(kv_.allocate(KvGeom{cfg_.n_layers, cfg_.max_seq_len, cfg_.n_kv_heads, cfg_.head_dim}, kv_q8_, sequences_, [&](size_t bytes, bool zero) { return dev_alloc(bytes, zero); }, &err_));
+    hidden_ = (float*)dev_alloc(std::max<size_t>(S, 2) * H * 4, false);
+    residual_ = (float*)dev_alloc(std::max<size_t>(S, 2) * H * 4, false);
+    logits_ = (float*)dev_alloc((size_t)cfg_.vocab_size * 4, false);
     const size_t attn_ws = S * (size_t)(2 * cfg_.n_heads + 2 * cfg_.n_kv_heads) * cfg_.head_dim;
     const size_t ffn_ws = 2 * S * (size_t)cfg_.intermediate_size;
     workspace_floats_ = std::max(attn_ws, ffn_ws);
-    workspace_ = (float*)dev(workspace_floats_ * 4, false);
-    positions_ = (int*)dev(S * 4, false);
-    tokens_dev_ = (int*)dev(S * 4, false);
-    d_pos_ = (int*)dev(64, true);
-    d_token_ = (int*)dev(64, true);
-    argmax_scratch_ = (float*)dev(2 * 1024 * 4, false);
-    rope_inv_freq_ = (float*)dev((size_t)cfg_.head_dim / 2 * 4 + 64, false);
-    row_max_ = (float*)dev((size_t)S * 2 * 4, true);
-    attn_scratch_ = (float*)dev(ntk_attention_split_scratch_bytes(cfg_.n_heads, cfg_.head_dim, kMaxAttnSplits), true);   // (zeroed: the arrival counters in front)
+    workspace_ = (float*)dev_alloc(workspace_floats_ * 4, false);
+    positions_ = (int*)dev_alloc(S * 4, false);
+    tokens_dev_ = (int*)dev_alloc(S * 4, false);
+    d_pos_ = (int*)dev_alloc(64, true);
+    d_token_ = (int*)dev_alloc(64, true);
+    argmax_scratch_ = (float*)dev_alloc(2 * 1024 * 4, false);
+    rope_inv_freq_ = (float*)dev_alloc((size_t)cfg_.head_dim / 2 * 4 + 64, false);
+    row_max_ = (float*)dev_alloc((size_t)S * 2 * 4, true);
+    attn_scratch_ = (float*)dev_alloc(ntk_attention_split_scratch_bytes(cfg_.n_heads, cfg_.head_dim, kMaxAttnSplits), true);   // (zeroed: the arrival counters in front)
     h_token_ = (int*)nt_hip_malloc_host(64);
     h_ring_ = (unsigned long long*)nt_hip_malloc_host(64);
     if (h_ring_) memset(h_ring_, 0, 64);
-    sample_scratch_ = dev(ntk_sample_scratch_bytes(cfg_.vocab_size), false);
+    sample_scratch_ = dev_alloc(ntk_sample_scratch_bytes(cfg_.vocab_size), false);
     {   // one workspace for every projection: the largest need over the launches the prompt pass makes (Q|K|V and gate|up go out as one)
         const int H = cfg_.hidden_size, I = cfg_.intermediate_size, qkv = (cfg_.n_heads + 2 * cfg_.n_kv_heads) * cfg_.head_dim;
         const int shapes[][2] = {{H, qkv}, {H, cfg_.n_heads * cfg_.head_dim}, {H, cfg_.n_kv_heads * cfg_.head_dim}, {cfg_.n_heads * cfg_.head_dim, H},
@@ -347,15 +335,15 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         gemm_ws_bytes_ = 0;
         for (const auto& sh : shapes) gemm_ws_bytes_ = std::max(gemm_ws_bytes_, ntk_gemm_quant_workspace_bytes(sh[0], sh[1]));
     }
-    gemm_ws_ = dev(gemm_ws_bytes_, false);
-    gemm_ws2_ = dev(gemm_ws_bytes_, false);
+    gemm_ws_ = dev_alloc(gemm_ws_bytes_, false);
+    gemm_ws2_ = dev_alloc(gemm_ws_bytes_, false);
     if (tp_world_ > 1) {   // communication buffer: flags + two slots of one prompt's worth of hidden vectors
         tp_max_floats_ = S * H;
         tp_comm_ = ntk_tp_comm_alloc(ntk_tp_comm_bytes(tp_max_floats_));   // fine-grained: csrc/tp.hip
         if (tp_comm_) allocs_.push_back(tp_comm_);
         if (!tp_comm_ || ntk_tp_comm_reset(tp_comm_, nullptr) != NTK_OK || ntk_device_synchronize() != NTK_OK) { err_ = "communication buffer allocation failed"; return NTK_E_NOMEM; }
     }
-    d_recent_ = (int*)dev(kRecentCap * 4, false);
+    d_recent_ = (int*)dev_alloc(kRecentCap * 4, false);
     h_recent_ = (int*)nt_hip_malloc_host(kRecentCap * 4);
     if (!kv_.k(0) || !kv_.v(0) || !hidden_ || !residual_ || !logits_ || !workspace_ || !positions_ || !tokens_dev_ ||
         !d_pos_ || !d_token_ || !argmax_scratch_ || !h_token_ || !h_ring_) {

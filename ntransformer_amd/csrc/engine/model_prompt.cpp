@@ -1,6 +1,5 @@
-// engine/model_prompt.cpp -- the prompt pass (see model.h)
+// engine/model_prompt.cpp -- the prompt pass of one sequence: forward, its layer loop, the LM head, scoring; the steps every host-driven pass shares (see model.h)
 #include "model_impl.h"
-#include <type_traits>
 
 namespace nt {
 
@@ -18,31 +17,59 @@ float* Model::forward(const int* tokens, int T, int start_pos, int slot) {
     tp_call_ = 0;
     // embedding rows are dequantised on the device (the reference does it on the host and uploads, :419-599)
     if (ntk_memcpy_h2d_async(tokens_dev_, tokens, (size_t)T * 4, s) != NTK_OK) return nullptr;
-    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, tokens_dev_, T, H, token_embd_.dtype, s);
-    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
-    else if (est != NTK_OK) return nullptr;
-    std::vector<int> pos(T);
-    for (int i = 0; i < T; ++i) pos[i] = start_pos + i;
-    if (ntk_memcpy_h2d_async(positions_, pos.data(), (size_t)T * 4, s) != NTK_OK) return nullptr;
-    if (ntk_stream_synchronize(s) != NTK_OK) return nullptr;   // `pos` / `tokens` are host temporaries
+    if (embed_rows(hidden_, tokens_dev_, T) != NTK_OK) return nullptr;
+    if (upload_positions(T, start_pos) != NTK_OK) return nullptr;
+    if (ntk_stream_synchronize(s) != NTK_OK) return nullptr;   // the positions' image / `tokens` are host temporaries
 
     const KvTarget kv{slot, nullptr, 0};
-    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers, kv);
-    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
+    PassStatus ok{layers_1to1(T, start_pos, 0, cfg_.n_layers, kv)};
     float* last = hidden_ + (size_t)(T - 1) * H;
     ok(ntk_rmsnorm(last, last, (const float*)output_norm_.ptr, 1, H, cfg_.norm_eps, s));   // in place, :658-659
-    {
-        raw_begin();
-        const int st = ntk_gemv(logits_, raw_of(output_), last, (int)output_.out_f, (int)output_.in_f, output_.dtype, s);
-        if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(output_.dtype));   // gemm.cu:801-803
-        else ok(st);
-    }
+    raw_begin();
+    const int st = gemv_logged(logits_, output_, raw_of(output_), last);
+    if (st != NTK_E_DTYPE) ok(st);
     if (tp_world_ > 1) ok(ntk_tp_advance_epoch(tp_comm_, s));
-    ok(ntk_stream_synchronize(s));
+    int rc = finish_pass("forward failed: ", ok.rc);
+    if (rc == NTK_OK) rc = check_tp();   // (it leaves its own message)
+    return rc == NTK_OK ? logits_ : nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// What the host-driven passes share: head (tokens' embedding, positions), tail (final norm, the end of the pass), the logged GEMV
+// ---------------------------------------------------------------------------------------------------
+int Model::embed_rows(float* out, const int* ids_dev, int n) {
+    const int st = ntk_embed_rows(out, token_embd_.ptr, ids_dev, n, cfg_.hidden_size, token_embd_.dtype, stream_);
+    if (st != NTK_E_DTYPE) return st;
+    fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
+    return NTK_OK;
+}
+
+int Model::upload_positions(int T, int start_pos) {
+    host_positions_.resize((size_t)T);
+    for (int i = 0; i < T; ++i) host_positions_[i] = start_pos + i;
+    return ntk_memcpy_h2d_async(positions_, host_positions_.data(), (size_t)T * 4, stream_);
+}
+
+const float* Model::final_norm(float* dst, const float* src, int n, PassStatus& ok) {
+    const float* nw = (const float*)output_norm_.ptr;
+    const float* rm = lm_head_f16() && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
+    if (rm) ok(ntk_rmsnorm_rowmax(dst, src, nw, n, cfg_.hidden_size, cfg_.norm_eps, row_max_, nullptr, stream_));
+    else ok(ntk_rmsnorm(dst, src, nw, n, cfg_.hidden_size, cfg_.norm_eps, stream_));
+    return rm;
+}
+
+int Model::finish_pass(const char* failed, int rc) {
+    const int sy = ntk_stream_synchronize(stream_);
+    if (rc == NTK_OK) rc = sy;
     if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
-    if (rc == NTK_OK) rc = check_tp();
-    if (rc != NTK_OK) { if (err_.empty() || rc != NTK_E_LAUNCH) err_ = std::string("forward failed: ") + ntk_status_string(rc); return nullptr; }
-    return logits_;
+    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string(failed) + ntk_status_string(rc);
+    return rc;
+}
+
+int Model::gemv_logged(float* y, const DevTensor& w, const void* wp, const float* x) {
+    const int st = ntk_gemv(y, wp, x, (int)w.out_f, (int)w.in_f, w.dtype, stream_);
+    if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
+    return st;
 }
 
 // The prompt pass's operand planes: the FP16 GEMM reads X split into FP16 planes, written into a workspace by its own pre-pass or by the launch that
@@ -73,19 +100,10 @@ static bool rp_only(const DevTensor& w) {
 
 // layers [first, last) of the 1:1 path on hidden_[T][H] at positions start_pos.. (positions_ already on the device)
 int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const KvTarget& kv) {
-    const int H = cfg_.hidden_size, I = cfg_.intermediate_size, hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads;
-    const int qd = nh * hd, kvd = nkv * hd;
+    const int H = cfg_.hidden_size, I = cfg_.intermediate_size, qd = cfg_.n_heads * cfg_.head_dim, kvd = cfg_.n_kv_heads * cfg_.head_dim;
     void* s = stream_;
-    const float scale = 1.0f / sqrtf((float)hd);
     const Views act = views(T);
-    int rc = NTK_OK;
-    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
-    // (wp: the tensor's raw GGUF blocks -- resident, or unpacked from the repack by raw_of() once per projection, not per token)
-    auto gemv = [&](float* y, const DevTensor& w, const void* wp, const float* x) {
-        const int st = ntk_gemv(y, wp, x, (int)w.out_f, (int)w.in_f, w.dtype, s);
-        if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
-        else ok(st);
-    };
+    PassStatus ok;
     // Y[t] = W . X[t] for the T tokens: one pass over W per 16 tokens on the matrix cores, or the reference's loop
     const bool batched = batched_prefill_ && T > 1;
     // the FP16 GEMM takes every prompt of 2 tokens or more (its weight-streaming form up to 32); it also reads a matrix that exists only as its decode
@@ -138,15 +156,26 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         *wp = raw_of(w);
         return bf16_now ? gemm_group(&Y, &one, 1, X, resid, rm, pt, wp) : (int)NTK_E_DTYPE;
     };
+    // Y = W . X (+ resid, which may be Y) for all T tokens on the matrix cores: the FP16 GEMM, else the F32-MFMA form.  false: a shape only the per-token
+    // loop takes (NTK_E_ALIGN / NTK_E_SHAPE: nothing launched; *wp holds the GGUF bytes for it)
+    auto gemm_mfma = [&](float* Y, const DevTensor& w, const float* X, const float* resid, const float* rm, const void** wp) {
+        int st = gemm_f16(Y, w, X, resid, rm, nullptr, wp);
+        if (not_taken(st)) st = ntk_gemm_quant(Y, *wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, resid, s);
+        if (st == NTK_E_ALIGN || st == NTK_E_SHAPE) return false;
+        ok(st);
+        return true;
+    };
+    // (wp: the tensor's raw GGUF blocks -- resident, or unpacked from the repack by raw_of() once per projection, not per token)
     auto project = [&](float* Y, const DevTensor& w, const float* X, size_t ystride, size_t xstride, const float* rm) {
         const bool dense = ystride == (size_t)w.out_f && xstride == (size_t)w.in_f;
         const void* wp = nullptr;
         if (batched && is_quant(w.dtype) && dense) {
-            int st = gemm_f16(Y, w, X, nullptr, rm, nullptr, &wp);
-            if (not_taken(st)) st = ntk_gemm_quant(Y, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, nullptr, s);
-            if (st != NTK_E_ALIGN && st != NTK_E_SHAPE) { ok(st); return; }   // those two: shapes only the per-token loop takes
+            if (gemm_mfma(Y, w, X, nullptr, rm, &wp)) return;
         } else { raw_begin(); wp = raw_of(w); }
-        for (int t = 0; t < T; ++t) gemv(Y + (size_t)t * ystride, w, wp, X + (size_t)t * xstride);
+        for (int t = 0; t < T; ++t) {
+            const int st = gemv_logged(Y + (size_t)t * ystride, w, wp, X + (size_t)t * xstride);
+            if (st != NTK_E_DTYPE) ok(st);
+        }
     };
     // matrices that share X (Q | K | V, gate | up): those of one format go out as ONE launch of the FP16 GEMM, the rest one by one
     auto project_many = [&](float* const* Ys, const DevTensor* const* Ws, int n, const float* X, const float* rm) {
@@ -181,12 +210,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         }
         const bool dense = batched && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f;
         if (dense && bf16_now) prepare_x(X, w);
-        if (dense && is_quant(w.dtype)) {
-            const void* wp = nullptr;
-            int st = gemm_f16(hidden_, w, X, hidden_, rm, nullptr, &wp);
-            if (not_taken(st)) st = ntk_gemm_quant(hidden_, wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, hidden_, s);
-            if (st != NTK_E_ALIGN && st != NTK_E_SHAPE) { ok(st); return; }
-        }
+        const void* wp = nullptr;   // (unused: project() below obtains the bytes again)
+        if (dense && is_quant(w.dtype) && gemm_mfma(hidden_, w, X, hidden_, rm, &wp)) return;
         project(residual_, w, X, H, xstride, rm);
         ok(ntk_add_inplace(hidden_, residual_, T * H, s));
     };
@@ -245,8 +270,6 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     bool normed_ahead = false;   // residual_ (with its maxima or planes) already holds this layer's normalised input, written with the previous layer's down projection
     for (int i = first; i < last_layer; ++i) {
         const LayerWeights& L = layers_[i];
-        uint16_t* const kc = kv_.attend_k(kv.slot, i);   // (q8_0: the one-layer F16 image, rebuilt below)
-        uint16_t* const vc = kv_.attend_v(kv.slot, i);
         if (!normed_ahead) norm(L.attn_norm, true, L.wq);
         normed_ahead = false;
         float* const qkv_out[3] = {act.q, act.k, act.v};
@@ -257,46 +280,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));
             kv_capture_T_ = T;
         }
-        // (every rotation below takes rope_tab(): the frequency table when the model carries frequency divisors, NULL -- the in-kernel frequency -- otherwise)
-        if (kv.segs) {   // a packed prompt pass: every segment rotated, stored and attended on its own slot's cache from its own start position, one launch each
-            ntk_kv_segments segs = *kv.segs;
-            kv_.fill(segs, kv.slots, i);
-            ok(ntk_rope_kv_store_segments_tab(act.q, act.k, act.v, &segs, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
-                                              cfg_.max_seq_len, rope_tab(), s));
-            ok(ntk_attention_prefill_segments(act.attn_out, act.q, &segs, nh, nkv, hd, cfg_.max_seq_len, scale, s));
-        } else if (kv.slots && kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
-            ntk_kv_batch caches{};
-            kv_.fill(caches, kv.slots, T, i);
-            ok(ntk_attention_decode_q8_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len,
-                                             scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attention_regime(kv.max_pos, hd)), batch_attn_scratch_, s));
-        } else if (kv.slots) {   // a batch of sequences: rope / store / attention of every row on its own cache at its own position, one launch
-            ntk_kv_batch caches{};
-            kv_.fill(caches, kv.slots, T, i);
-            const bool splits_ok = batch_attn_scratch_ && (hd == 64 || hd == 128 || hd == 256);   // (pick_attention_regime's rule)
-            const int regime = splits_ok ? attention_regime(kv.max_pos, hd) : 0;
-            ok(ntk_attention_decode_batch(act.attn_out, act.q, act.k, act.v, &caches, batch_in_ + kMaxSequences, T, rope_inv_freq_, nh, nkv, hd, cfg_.max_seq_len, scale,
-                                          cfg_.rope_theta, cfg_.rope_freq_scale, regime == 0 ? 1 : attention_splits(regime, hd), batch_attn_scratch_, s));
-        } else if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
-            void* kc8 = kv_.k(kv.slot, i);   // (kc / vc: the image, shared by all slots: rebuilt here, for this slot, every pass)
-            void* vc8 = kv_.v(kv.slot, i);
-            if (T >= 4) {
-                ok(ntk_rope_kv_store_q8_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved,
-                                            kc8, vc8, start_pos, cfg_.max_seq_len, rope_tab(), s));
-            } else {
-                ok(ntk_rope_tab(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, rope_tab(), s));
-                ok(ntk_kv_store_q8(kc8, vc8, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
-            }
-            ok(ntk_kv_dequant_q8_f16(kc, vc, kc8, vc8, start_pos + T, nkv, hd, cfg_.max_seq_len, s));
-        } else if (with_max && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
-            ok(ntk_rope_kv_store_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, kc, vc,
-                                     start_pos, cfg_.max_seq_len, rope_tab(), s));
-        } else {
-            ok(ntk_rope_tab(act.q, act.k, positions_, 1, T, nh, nkv, hd, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, rope_tab(), s));
-            ok(ntk_copy_to_kv_cache(kc, vc, act.k, act.v, T, nkv, hd, start_pos, cfg_.max_seq_len, s));
-        }
-        if (kv.slots) {}   // (attended above)
-        else if (T == 1) ok(ntk_attention_decode(act.attn_out, act.q, kc, vc, start_pos + T, nh, nkv, hd, cfg_.max_seq_len, scale, s));
-        else ok(ntk_attention_prefill(act.attn_out, act.q, kc, vc, T, start_pos, nh, nkv, hd, cfg_.max_seq_len, scale, s));
+        ok(attend(i, T, start_pos, kv, act, with_max));
         if (!project_add_norm(L.wo, act.attn_out, nullptr, L.ffn_norm, false, L.w_gate)) {
             project_add(L.wo, act.attn_out, qd, nullptr);
             norm(L.ffn_norm, false, L.w_gate);
@@ -310,10 +294,60 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         // down projection + residual, and the NEXT layer's first RMSNorm in the same consumer launch when there is a next layer in this pass
         if (i + 1 < last_layer && project_add_norm(L.w_down, act.gate, rm_b, layers_[i + 1].attn_norm, true, layers_[i + 1].wq)) normed_ahead = true;
         else project_add(L.w_down, act.gate, I, rm_b);
-        if (rc != NTK_OK) break;
+        if (ok.rc != NTK_OK) break;
     }
-    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }   // what raw_of() could not report through its pointer (it precedes the consumer's NTK_E_NULL)
-    return rc;
+    if (raw_err_ != NTK_OK) { ok.rc = raw_err_; raw_err_ = NTK_OK; }   // what raw_of() could not report through its pointer (it precedes the consumer's NTK_E_NULL)
+    return ok.rc;
+}
+
+// One layer's KV step and attention, by what `kv` names and the cache's format (see model.h).  Every rotation takes rope_tab(): the frequency table when
+// the model carries frequency divisors, NULL -- the in-kernel frequency -- otherwise.
+int Model::attend(int layer, int T, int start_pos, const KvTarget& kv, const Views& act, bool fused_store) {
+    const int hd = cfg_.head_dim, nh = cfg_.n_heads, nkv = cfg_.n_kv_heads, S = cfg_.max_seq_len;
+    const float scale = 1.0f / sqrtf((float)hd), theta = cfg_.rope_theta, fscale = cfg_.rope_freq_scale;
+    void* s = stream_;
+    PassStatus ok;
+    if (kv.segs) {   // a packed prompt pass: every segment rotated, stored and attended on its own slot's cache from its own start position, one launch each
+        ntk_kv_segments segs = *kv.segs;
+        kv_.fill(segs, kv.slots, layer);
+        ok(ntk_rope_kv_store_segments_tab(act.q, act.k, act.v, &segs, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, S, rope_tab(), s));
+        ok(ntk_attention_prefill_segments(act.attn_out, act.q, &segs, nh, nkv, hd, S, scale, s));
+        return ok.rc;
+    }
+    if (kv.slots) {   // a batch of sequences: rope / store / attention of every row on its own cache at its own position, one launch
+        ntk_kv_batch caches{};
+        kv_.fill(caches, kv.slots, T, layer);
+        const int* const positions = batch_in_ + kMaxSequences;
+        if (kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
+            return ntk_attention_decode_q8_batch(act.attn_out, act.q, act.k, act.v, &caches, positions, T, rope_inv_freq_, nh, nkv, hd, S, scale, theta, fscale,
+                                                 kv_q8_splits(attention_regime(kv.max_pos, hd)), batch_attn_scratch_, s);
+        }
+        const bool splits_ok = batch_attn_scratch_ && (hd == 64 || hd == 128 || hd == 256);   // (pick_attention_regime's rule)
+        const int regime = splits_ok ? attention_regime(kv.max_pos, hd) : 0;
+        return ntk_attention_decode_batch(act.attn_out, act.q, act.k, act.v, &caches, positions, T, rope_inv_freq_, nh, nkv, hd, S, scale, theta, fscale,
+                                          regime == 0 ? 1 : attention_splits(regime, hd), batch_attn_scratch_, s);
+    }
+    uint16_t* const kc = kv_.attend_k(kv.slot, layer);   // (q8_0: the one-layer F16 image, shared by all slots: rebuilt below, for this slot, every pass)
+    uint16_t* const vc = kv_.attend_v(kv.slot, layer);
+    if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
+        void* kc8 = kv_.k(kv.slot, layer);
+        void* vc8 = kv_.v(kv.slot, layer);
+        if (T >= 4) {
+            ok(ntk_rope_kv_store_q8_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, kc8, vc8, start_pos, S, rope_tab(), s));
+        } else {
+            ok(ntk_rope_tab(act.q, act.k, positions_, 1, T, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, rope_tab(), s));
+            ok(ntk_kv_store_q8(kc8, vc8, act.k, act.v, T, nkv, hd, start_pos, S, s));
+        }
+        ok(ntk_kv_dequant_q8_f16(kc, vc, kc8, vc8, start_pos + T, nkv, hd, S, s));
+    } else if (fused_store && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
+        ok(ntk_rope_kv_store_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, kc, vc, start_pos, S, rope_tab(), s));
+    } else {
+        ok(ntk_rope_tab(act.q, act.k, positions_, 1, T, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, rope_tab(), s));
+        ok(ntk_copy_to_kv_cache(kc, vc, act.k, act.v, T, nkv, hd, start_pos, S, s));
+    }
+    if (T == 1) ok(ntk_attention_decode(act.attn_out, act.q, kc, vc, start_pos + T, nh, nkv, hd, S, scale, s));
+    else ok(ntk_attention_prefill(act.attn_out, act.q, kc, vc, T, start_pos, nh, nkv, hd, S, scale, s));
+    return ok.rc;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -327,26 +361,15 @@ int Model::set_score_rows(int rows) {
 
 int Model::score_buffers() {
     const size_t S = (size_t)cfg_.max_seq_len, V = (size_t)cfg_.vocab_size;
-    auto dev = [&](size_t bytes) -> void* {
-        void* p = nt_hip_malloc(bytes + 256);
-        if (p) allocs_.push_back(p);
-        return p;
-    };
-    auto release = [&](auto*& p) {
-        if (!p) return;
-        allocs_.erase(std::remove(allocs_.begin(), allocs_.end(), (void*)p), allocs_.end());
-        nt_hip_free(p);
-        p = nullptr;
-    };
     auto fail = [&](const char* what) { err_ = std::string("score: no device memory for ") + what; return NTK_E_NOMEM; };
-    if (!score_targets_ && !(score_targets_ = (int*)dev(S * 4))) return fail("the targets");
-    if (!score_logprob_ && !(score_logprob_ = (float*)dev(S * 4))) return fail("the results");
-    if (!score_top1_ && !(score_top1_ = (int*)dev(S * 4))) return fail("the results");
+    if (!dev_need(score_targets_, S * 4, false)) return fail("the targets");
+    if (!dev_need(score_logprob_, S * 4, false)) return fail("the results");
+    if (!dev_need(score_top1_, S * 4, false)) return fail("the results");
     if (score_cap_ < score_rows_) {
         NT_TRY(sync());   // (an earlier call's launches may still read the smaller buffer)
-        release(score_logits_);
+        dev_release(score_logits_);
         score_cap_ = 0;
-        if (!(score_logits_ = (float*)dev((size_t)score_rows_ * V * 4))) return fail("the chunk of logits (score_rows x vocab floats)");
+        if (!dev_need(score_logits_, (size_t)score_rows_ * V * 4, false)) return fail("the chunk of logits (score_rows x vocab floats)");
         score_cap_ = score_rows_;
     }
     return lm_head_workspace("score");
@@ -358,13 +381,10 @@ int Model::lm_head_workspace(const char* who) {
     if (!(gemm_ws_ && bf16_prefill_ && f16_ok(output_) && need > gemm_ws_bytes_ && need > score_ws_bytes_)) return NTK_OK;
     if (score_ws_) {
         NT_TRY(sync());
-        allocs_.erase(std::remove(allocs_.begin(), allocs_.end(), score_ws_), allocs_.end());
-        nt_hip_free(score_ws_);
-        score_ws_ = nullptr;
+        dev_release(score_ws_);
     }
     score_ws_bytes_ = 0;
-    if (!(score_ws_ = nt_hip_malloc(need + 256))) { err_ = std::string(who) + ": no device memory for the LM head's GEMM workspace"; return NTK_E_NOMEM; }
-    allocs_.push_back(score_ws_);
+    if (!dev_need(score_ws_, need, false)) { err_ = std::string(who) + ": no device memory for the LM head's GEMM workspace"; return NTK_E_NOMEM; }
     score_ws_bytes_ = need;
     return NTK_OK;
 }
@@ -395,8 +415,7 @@ int Model::lm_head(float* logits, const float* X, int n, const float* chunk_max)
     raw_begin();   // dense heads and shapes the matrix-core forms do not take: the reference's GEMV, row by row
     const void* wp = raw_of(w);
     for (int t = 0; t < n; ++t) {
-        st = ntk_gemv(logits + (size_t)t * V, wp, X + (size_t)t * H, V, H, w.dtype, s);
-        if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
+        st = gemv_logged(logits + (size_t)t * V, w, wp, X + (size_t)t * H);
         if (st != NTK_OK) return st;
     }
     return NTK_OK;
@@ -419,243 +438,21 @@ int Model::score(const int* tokens, const int* targets, int T, int start_pos, fl
     // embedding and positions as forward() has them
     NT_TRY(ntk_memcpy_h2d_async(tokens_dev_, tokens, (size_t)T * 4, s));
     NT_TRY(ntk_memcpy_h2d_async(score_targets_, targets, (size_t)T * 4, s));
-    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, tokens_dev_, T, H, token_embd_.dtype, s);
-    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
-    else if (est != NTK_OK) return est;
-    std::vector<int> pos(T);
-    for (int i = 0; i < T; ++i) pos[i] = start_pos + i;
-    NT_TRY(ntk_memcpy_h2d_async(positions_, pos.data(), (size_t)T * 4, s));
-    NT_TRY(ntk_stream_synchronize(s));   // `pos` / `tokens` / `targets` are host memory of the caller
+    NT_TRY(embed_rows(hidden_, tokens_dev_, T));
+    NT_TRY(upload_positions(T, start_pos));
+    NT_TRY(ntk_stream_synchronize(s));   // the positions' image / `tokens` / `targets` are host temporaries
 
     const KvTarget kv{slot, nullptr, 0};
-    int rc = layers_1to1(T, start_pos, 0, cfg_.n_layers, kv);
-    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
-    // the final RMSNorm of every row, beside hidden_ (with the rows' largest |x| where the FP16 GEMM reads the head)
-    const float* rm = lm_head_f16() && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
-    if (rm) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)output_norm_.ptr, T, H, cfg_.norm_eps, row_max_, nullptr, s));
-    else ok(ntk_rmsnorm(residual_, hidden_, (const float*)output_norm_.ptr, T, H, cfg_.norm_eps, s));
-    for (int t0 = 0; t0 < T && rc == NTK_OK; t0 += score_rows_) {
+    PassStatus ok{layers_1to1(T, start_pos, 0, cfg_.n_layers, kv)};
+    const float* rm = final_norm(residual_, hidden_, T, ok);   // of every row, beside hidden_
+    for (int t0 = 0; t0 < T && ok.rc == NTK_OK; t0 += score_rows_) {
         const int n = std::min(score_rows_, T - t0);
         ok(lm_head(score_logits_, residual_ + (size_t)t0 * H, n, rm ? rm + t0 : nullptr));
         ok(ntk_logprob_rows(score_logits_, n, V, V, score_targets_ + t0, score_logprob_ + t0, top1_out ? score_top1_ + t0 : nullptr, s));
     }
-    if (rc == NTK_OK) ok(ntk_memcpy_d2h_async(logprob_out, score_logprob_, (size_t)T * 4, s));
-    if (rc == NTK_OK && top1_out) ok(ntk_memcpy_d2h_async(top1_out, score_top1_, (size_t)T * 4, s));
-    ok(ntk_stream_synchronize(s));
-    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
-    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("score failed: ") + ntk_status_string(rc);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Sequence slots: one decode step of B sequences in one pass over the weights (see model.h)
-// ---------------------------------------------------------------------------------------------------
-int Model::batch_buffers() {
-    const size_t V = (size_t)cfg_.vocab_size, N = kMaxSequences;
-    // (a buffer an earlier, failed call obtained is kept: only what is missing is allocated)
-    auto need = [&](auto*& p, size_t bytes) {
-        if (p) return true;
-        void* d = nt_hip_malloc(bytes + 256);
-        if (!d) return false;
-        allocs_.push_back(d);
-        nt_hip_memset(d, 0, bytes);
-        p = static_cast<std::remove_reference_t<decltype(p)>>(d);
-        return true;
-    };
-    if (!need(batch_in_, 3 * N * 4) || !need(batch_logprob_, N * 4) || !need(batch_next_, N * 4) ||
-        !need(batch_attn_scratch_, N * ntk_attention_split_scratch_bytes(cfg_.n_heads, cfg_.head_dim, kMaxAttnSplits)) || !need(batch_logits_, N * V * 4)) {
-        err_ = "decode_batch: no device memory for the batch buffers (16 x vocab floats of logits)";
-        return NTK_E_NOMEM;
-    }
-    return lm_head_workspace("decode_batch");   // (nothing to do once the workspace is large enough)
-}
-
-int Model::validate_batch(const int* slots, const int* tokens, const int* positions, int B, int sequences, int max_seq, int vocab, std::string* why) {
-    auto fail = [&](int rc, const char* msg) { if (why) *why = msg; return rc; };
-    if (!slots || !tokens || !positions) return fail(NTK_E_NULL, "decode_batch: null argument");
-    if (B < 1 || B > sequences || B > kMaxSequences) return fail(NTK_E_SHAPE, "decode_batch: the batch must hold 1 .. `sequences` rows");
-    unsigned seen = 0;
-    for (int b = 0; b < B; ++b) {
-        if (slots[b] < 0 || slots[b] >= sequences || slots[b] >= kMaxSequences) return fail(NTK_E_SHAPE, "decode_batch: no such sequence slot");
-        if (seen & (1u << slots[b])) return fail(NTK_E_SHAPE, "decode_batch: the same sequence slot twice in one batch");
-        seen |= 1u << slots[b];
-        if (positions[b] < 0 || positions[b] >= max_seq) return fail(NTK_E_SHAPE, "decode_batch: position outside the context");
-        if (tokens[b] < 0 || tokens[b] >= vocab) return fail(NTK_E_SHAPE, "decode_batch: token id out of range");
-    }
-    return NTK_OK;
-}
-
-// the step up to its logits: tokens | positions up, embedding, the layer loop in batch mode, final RMSNorm, LM head into batch_logits_ (all queued, no wait)
-int Model::batch_logits(const int* slots, const int* tokens, const int* positions, int B) {
-    const int H = cfg_.hidden_size, N = kMaxSequences;
-    void* s = stream_;
-    tp_call_ = 0;
-    int* const host = batch_host_;   // tokens | positions | "no target": ONE copy (a member: the copy may read it until the caller's synchronisation)
-    KvTarget kv{0, slots, 0};
-    for (int b = 0; b < N; ++b) {
-        host[b] = b < B ? tokens[b] : 0;
-        host[N + b] = b < B ? positions[b] : 0;
-        host[2 * N + b] = -1;
-        if (b < B) kv.max_pos = std::max(kv.max_pos, positions[b]);
-    }
-    NT_TRY(ntk_memcpy_h2d_async(batch_in_, host, sizeof batch_host_, s));
-    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, batch_in_, B, H, token_embd_.dtype, s);
-    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
-    else if (est != NTK_OK) return est;
-
-    int rc = layers_1to1(B, 0, 0, cfg_.n_layers, kv);
-    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
-    const float* rm = lm_head_f16() && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
-    if (rm) ok(ntk_rmsnorm_rowmax(residual_, hidden_, (const float*)output_norm_.ptr, B, H, cfg_.norm_eps, row_max_, nullptr, s));
-    else ok(ntk_rmsnorm(residual_, hidden_, (const float*)output_norm_.ptr, B, H, cfg_.norm_eps, s));
-    ok(lm_head(batch_logits_, residual_, B, rm));
-    return rc;
-}
-
-int Model::decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out) {
-    NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
-    if ((kv_q8_ && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
-    NT_TRY(batch_buffers());
-    const int V = cfg_.vocab_size, N = kMaxSequences;
-    void* s = stream_;
-    int rc = batch_logits(slots, tokens, positions, B);
-    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
-    if (next_out) ok(ntk_logprob_rows(batch_logits_, B, V, V, batch_in_ + 2 * N, batch_logprob_, batch_next_, s));
-    if (rc == NTK_OK && logits_out) ok(ntk_memcpy_d2h_async(logits_out, batch_logits_, (size_t)B * V * 4, s));
-    if (rc == NTK_OK && next_out) ok(ntk_memcpy_d2h_async(next_out, batch_next_, (size_t)B * 4, s));
-    ok(ntk_stream_synchronize(s));
-    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
-    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("decode_batch failed: ") + ntk_status_string(rc);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The packed prompt pass: the tokens of several sequences in one pass over the weights (see model.h)
-// ---------------------------------------------------------------------------------------------------
-int Model::validate_forward_batch(const int* slots, const int* lens, const int* start_pos, int n, int sequences, int max_seq, std::string* why) {
-    auto fail = [&](int rc, const char* msg) { if (why) *why = msg; return rc; };
-    if (!slots || !lens || !start_pos) return fail(NTK_E_NULL, "forward_batch: null argument");
-    if (n < 1 || n > sequences || n > kMaxSequences) return fail(NTK_E_SHAPE, "forward_batch: the pass must hold 1 .. `sequences` segments");
-    unsigned seen = 0;
-    long long total = 0;
-    for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= sequences || slots[i] >= kMaxSequences) return fail(NTK_E_SHAPE, "forward_batch: no such sequence slot");
-        if (seen & (1u << slots[i])) return fail(NTK_E_SHAPE, "forward_batch: the same sequence slot twice in one pass");
-        seen |= 1u << slots[i];
-        if (lens[i] < 1) return fail(NTK_E_SHAPE, "forward_batch: an empty segment");
-        if (start_pos[i] < 0 || (long long)start_pos[i] + lens[i] > max_seq) return fail(NTK_E_SHAPE, "forward_batch: a segment exceeds the context");
-        total += lens[i];
-    }
-    if (total > max_seq) return fail(NTK_E_SHAPE, "forward_batch: more rows than the context holds (the pass runs through the context-sized activation buffers)");
-    return NTK_OK;
-}
-
-int Model::forward_batch(const int* slots, const int* tokens, const int* lens, const int* start_pos, int n, float* logits_out, int* next_out) {
-    NT_TRY(validate_forward_batch(slots, lens, start_pos, n, sequences_, cfg_.max_seq_len, &err_));
-    if (!tokens) { err_ = "forward_batch: null argument"; return NTK_E_NULL; }
-    if (kv_q8_ || tp_world_ > 1) { err_ = "forward_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
-    const int H = cfg_.hidden_size, V = cfg_.vocab_size, N = kMaxSequences;
-    ntk_kv_segments segs{};   // rows, lengths and first positions; layers_1to1 fills in each layer's caches
-    segs.n_seg = n;
-    int T = 0;
-    for (int i = 0; i < n; ++i) { segs.row0[i] = T; segs.n_rows[i] = lens[i]; segs.start_pos[i] = start_pos[i]; T += lens[i]; }
-    for (int t = 0; t < T; ++t)   // the embedding gather indexes the table with these on the device
-        if (tokens[t] < 0 || tokens[t] >= V) { err_ = "forward_batch: token id out of range"; return NTK_E_SHAPE; }
-    NT_TRY(batch_buffers());
-    void* s = stream_;
-    tp_call_ = 0;
-    packed_tokens_.assign(tokens, tokens + T);
-    int* const host = batch_host_;   // the segments' last rows | unused | "no target": ONE copy, as batch_logits()
-    for (int b = 0; b < N; ++b) {
-        host[b] = b < n ? segs.row0[b] + segs.n_rows[b] - 1 : 0;
-        host[N + b] = 0;
-        host[2 * N + b] = -1;
-    }
-    NT_TRY(ntk_memcpy_h2d_async(tokens_dev_, packed_tokens_.data(), (size_t)T * 4, s));
-    NT_TRY(ntk_memcpy_h2d_async(batch_in_, host, sizeof batch_host_, s));
-    const int est = ntk_embed_rows(hidden_, token_embd_.ptr, tokens_dev_, T, H, token_embd_.dtype, s);
-    if (est == NTK_E_DTYPE) fprintf(stderr, "Error: Unsupported embedding dtype: %s\n", dtype_name(token_embd_.dtype));
-    else if (est != NTK_OK) return est;
-
-    KvTarget kv{0, slots, 0};
-    kv.segs = &segs;
-    int rc = layers_1to1(T, 0, 0, cfg_.n_layers, kv);
-    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
-    // the last row of every segment, gathered (hidden_ read as an F32 table) into n contiguous rows; the final RMSNorm and the LM head over those alone
-    ok(ntk_embed_rows(residual_, hidden_, batch_in_, n, H, NTK_DT_F32, s));
-    const float* rm = lm_head_f16() && row_max_ && prefill_row_max_ ? row_max_ : nullptr;
-    if (rm) ok(ntk_rmsnorm_rowmax(hidden_, residual_, (const float*)output_norm_.ptr, n, H, cfg_.norm_eps, row_max_, nullptr, s));
-    else ok(ntk_rmsnorm(hidden_, residual_, (const float*)output_norm_.ptr, n, H, cfg_.norm_eps, s));
-    ok(lm_head(batch_logits_, hidden_, n, rm));
-    if (next_out) ok(ntk_logprob_rows(batch_logits_, n, V, V, batch_in_ + 2 * N, batch_logprob_, batch_next_, s));
-    if (rc == NTK_OK && logits_out) ok(ntk_memcpy_d2h_async(logits_out, batch_logits_, (size_t)n * V * 4, s));
-    if (rc == NTK_OK && next_out) ok(ntk_memcpy_d2h_async(next_out, batch_next_, (size_t)n * 4, s));
-    ok(ntk_stream_synchronize(s));
-    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
-    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("forward_batch failed: ") + ntk_status_string(rc);
-    return rc;
-}
-
-int Model::batch_sample_buffers() {
-    const size_t N = kMaxSequences;
-    auto need = [&](auto*& p, size_t bytes) {
-        if (p) return true;
-        void* d = nt_hip_malloc(bytes + 256);
-        if (!d) return false;
-        allocs_.push_back(d);
-        p = static_cast<std::remove_reference_t<decltype(p)>>(d);
-        return true;
-    };
-    if (!need(batch_recent_, N * kRecentCap * 4) || !need(batch_sample_scratch_, ntk_sample_rows_scratch_bytes((int)N, cfg_.vocab_size))) {
-        err_ = "decode_batch_sample: no device memory for the rows' windows and the sampler's scratch";
-        return NTK_E_NOMEM;
-    }
-    if (!h_batch_recent_) h_batch_recent_ = (int*)nt_hip_malloc_host(N * kRecentCap * 4);
-    if (!h_batch_next_) h_batch_next_ = (int*)nt_hip_malloc_host(N * 4);
-    if (!h_batch_recent_ || !h_batch_next_) { err_ = "decode_batch_sample: no pinned host memory for the windows and the sampled tokens"; return NTK_E_NOMEM; }
-    return NTK_OK;
-}
-
-int Model::decode_batch_sample(const int* slots, const int* tokens, const int* positions, int B, const ntk_sample_rows& rows, const int* const* recent,
-                               float* logits_out, float* const* row_logits, int* next_out) {
-    NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
-    if ((kv_q8_ && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch_sample: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
-    if (!next_out) { err_ = "decode_batch_sample: null argument"; return NTK_E_NULL; }
-    const int V = cfg_.vocab_size;
-    int pitch = 0;   // of this step's windows: the longest one a penalty reads
-    for (int b = 0; b < B; ++b) {
-        if (V > 131072 || !device_sampler_supports(rows.temperature[b], rows.top_k[b], V)) {
-            err_ = "decode_batch_sample: a row the device sampler does not take (temperature > 0 needs 0 < top_k <= 64, top_k < vocab <= 131072)";
-            return NTK_E_SHAPE;
-        }
-        if (rows.n_recent[b] < 0 || rows.n_recent[b] > kMaxRecent) { err_ = "decode_batch_sample: a window of 0 .. 4096 tokens per row"; return NTK_E_SHAPE; }
-        if (rows.repeat_penalty[b] > 1.0f && rows.n_recent[b] > 0) {
-            if (!recent || !recent[b]) { err_ = "decode_batch_sample: null window"; return NTK_E_NULL; }
-            pitch = std::max(pitch, rows.n_recent[b]);
-        }
-    }
-    NT_TRY(batch_buffers());
-    NT_TRY(batch_sample_buffers());
-    void* s = stream_;
-    ntk_sample_rows dev = rows;   // rows without a penalty to apply read no window
-    for (int b = 0; b < B; ++b) {
-        if (rows.repeat_penalty[b] > 1.0f && rows.n_recent[b] > 0) memcpy(h_batch_recent_ + (size_t)b * pitch, recent[b], (size_t)rows.n_recent[b] * 4);
-        else dev.n_recent[b] = 0;
-    }
-    // (the previous step's copy out of the pinned staging has completed: that step synchronised)
-    if (pitch > 0) NT_TRY(ntk_memcpy_h2d_async(batch_recent_, h_batch_recent_, (size_t)B * pitch * 4, s));
-    int rc = batch_logits(slots, tokens, positions, B);
-    auto ok = [&](int st) { if (st != NTK_OK && rc == NTK_OK) rc = st; };
-    // the logits as the step computed them: queued AHEAD of the sampler, whose penalty rewrites batch_logits_ in place
-    if (rc == NTK_OK && logits_out) ok(ntk_memcpy_d2h_async(logits_out, batch_logits_, (size_t)B * V * 4, s));
-    for (int b = 0; b < B && rc == NTK_OK && row_logits; ++b)
-        if (row_logits[b]) ok(ntk_memcpy_d2h_async(row_logits[b], batch_logits_ + (size_t)b * V, (size_t)V * 4, s));
-    if (rc == NTK_OK) ok(ntk_sample_rows_top_k(batch_logits_, B, V, V, batch_recent_, pitch, &dev, batch_next_, h_batch_next_, batch_sample_scratch_, s));
-    ok(ntk_stream_synchronize(s));
-    if (raw_err_ != NTK_OK) { rc = raw_err_; raw_err_ = NTK_OK; }
-    if (rc == NTK_OK) for (int b = 0; b < B; ++b) next_out[b] = h_batch_next_[b];
-    if (rc != NTK_OK && (err_.empty() || rc != NTK_E_LAUNCH)) err_ = std::string("decode_batch_sample failed: ") + ntk_status_string(rc);
-    return rc;
+    if (ok.rc == NTK_OK) ok(ntk_memcpy_d2h_async(logprob_out, score_logprob_, (size_t)T * 4, s));
+    if (ok.rc == NTK_OK && top1_out) ok(ntk_memcpy_d2h_async(top1_out, score_top1_, (size_t)T * 4, s));
+    return finish_pass("score failed: ", ok.rc);
 }
 
 }  // namespace nt

@@ -1,5 +1,5 @@
 """GPU tests of the engine on models whose widths are NOT multiples of 256 columns: the tensor-by-tensor fallbacks (Model::repack_one; not_taken() in
-model_prompt.cpp / model_decode.cpp) that no other test forces.
+model_prompt.cpp (layers_1to1, lm_head) / model_decode.cpp) that no other test forces.
 
   model   shape                                             what it forces
   w320    hidden 320, inter 864, 2 layers, 5 / 1 heads      every projection and the LM head refused by the FP16 prompt GEMM -> the ragged-tail
