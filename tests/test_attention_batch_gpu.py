@@ -14,7 +14,7 @@ from oracle import oracle as O
 pytestmark = pytest.mark.gpu
 
 THETA = 500000.0
-GEOMETRIES = [(32, 8, 128), (64, 8, 128), (4, 2, 64), (6, 3, 80)]
+GEOMETRIES = [(32, 8, 128), (64, 8, 128), (4, 2, 64), (6, 3, 80), (8, 2, 256)]
 # per batch size: positions mixed inside one batch; B >= 2 always has position 0 beside the batch's largest
 POSITIONS = {1: [543], 2: [0, 4095], 3: [33, 0, 2047], 16: [0, 1, 15, 16, 31, 32, 33, 543, 544, 1023, 2047, 4095, 0, 32, 544, 1]}
 JUNK = np.array([0x7E00, 0xFE00, 0x7C00, 0xFC00, 0x7BFF, 0xFBFF, 0x0001, 0x8000], np.uint16)   # NaN, -NaN, +-inf, +-65504, denormal, -0
@@ -131,7 +131,7 @@ def test_attention_decode_batch_rows_equal_the_oracle_and_the_single_row_launch(
         assert np.array_equal(kcd.numpy(np.uint16), got_k) and np.array_equal(vcd.numpy(np.uint16), got_v), (b, pos)
 
 
-@pytest.mark.parametrize("nh,nkv,hd,B,nsplit", [(nh, nkv, hd, B, ns) for nh, nkv, hd, B in [(32, 8, 128, 16), (32, 8, 128, 3), (4, 2, 64, 16)]
+@pytest.mark.parametrize("nh,nkv,hd,B,nsplit", [(nh, nkv, hd, B, ns) for nh, nkv, hd, B in [(32, 8, 128, 16), (32, 8, 128, 3), (4, 2, 64, 16), (8, 2, 256, 16)]
                                                 for ns in (1, 8, 32, 3)] + [(6, 3, 80, 3, 1)])   # (head_dim 80 does not split)
 def test_attention_decode_batch_permuting_the_rows_permutes_the_results(nh, nkv, hd, B, nsplit):
     """A row's result depends on nothing but that row: the same rows in another order (other companions on every side, other slots of the
