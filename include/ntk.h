@@ -48,7 +48,8 @@ extern "C" {
 /* nt::DType numeric values (reference src/core/types.h:24-35) */
 enum {
     NTK_DT_F32 = 0, NTK_DT_F16 = 1, NTK_DT_Q8_0 = 2, NTK_DT_Q4_0 = 3, NTK_DT_Q4_K = 4,
-    NTK_DT_Q6_K = 5, NTK_DT_Q5_K = 6, NTK_DT_Q2_K = 7, NTK_DT_I32 = 8
+    NTK_DT_Q6_K = 5, NTK_DT_Q5_K = 6, NTK_DT_Q2_K = 7, NTK_DT_I32 = 8,
+    NTK_DT_BF16 = 9   /* not in the reference (GGML type 30): appended, its values above stay */
 };
 
 int         ntk_abi_version(void);

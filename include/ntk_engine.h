@@ -43,13 +43,16 @@ typedef struct ntk_gemv_seg {
     const void* W;      /* raw GGUF blocks [rows][in]              */
     float*      y;      /* output [rows]                            */
     int         rows;
-    int         dtype;  /* one format per call, or two for the plain (no resid / SiLU) form: Q4_K with Q6_K or Q5_K */
+    int         dtype;  /* one format per call, or two for the plain (no resid / SiLU) form: Q4_K with Q6_K or Q5_K;
+                           NTK_DT_F16 / NTK_DT_BF16 (unquantised rows of 16-bit words): one of them per call */
 } ntk_gemv_seg;
 
 /* y_s = W_s . f(x) for up to 3 row segments sharing x (fused Q|K|V or gate|up):
  *   norm_w != NULL : f(x) = rmsnorm(x, norm_w, eps)           (launch_rmsnorm + launch_gemv ...)
  *   resid  != NULL : y_0[r] = resid[r] + (W_0 . f(x))[r]      (launch_gemv + launch_add_inplace); resid may == y_0
- *   silu_pair != 0 : nseg == 2, y_0[r] = silu(W_0.f(x))[r] * (W_1.f(x))[r]   (2 x launch_gemv + launch_silu_mul) */
+ *   silu_pair != 0 : nseg == 2, y_0[r] = silu(W_0.f(x))[r] * (W_1.f(x))[r]   (2 x launch_gemv + launch_silu_mul)
+ * F16 / BF16 segments (csrc/gemv_dense16.hip): every form above; in_features a multiple of 8 (<= 32768) and W, x, norm_w 16-byte aligned, NTK_E_ALIGN
+ * otherwise -- nothing is launched, y is untouched, the caller runs ntk_rmsnorm / ntk_gemv / ntk_add; F16 mixed with BF16 is NTK_E_DTYPE. */
 int ntk_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in_features, const float* norm_w,
                    float eps, const float* resid, int silu_pair, void* stream);
 
@@ -292,8 +295,9 @@ int      ntk_ipc_close(void* devptr);
 
 /* Batched prompt projection on the matrix cores (replaces the per-token launch_gemv loops of
  * attention.cpp:144-162,200-210 and ffn.cpp:96-133):  Y[t,:] = W . X[t,:] (+ resid[t,:]) for t < n_tokens.
- * X [n_tokens][in] and Y/resid [n_tokens][out] are F32, token-major; W raw GGUF blocks [out][in] (quantised dtypes
- * only); X 16-byte aligned.  W is streamed once per 16 tokens; F32 activations, F32 MFMA accumulate.  resid may == Y. */
+ * X [n_tokens][in] and Y/resid [n_tokens][out] are F32, token-major; W raw GGUF blocks [out][in] (the quantised dtypes, and
+ * NTK_DT_F16 / NTK_DT_BF16 rows of 16-bit words: those with W 16-byte aligned and in_features a multiple of 32, widened exactly);
+ * X 16-byte aligned.  W is streamed once per 16 tokens; F32 activations, F32 MFMA accumulate.  resid may == Y. */
 int ntk_gemm_quant(float* Y, const void* W, const float* X, int n_tokens, int out_features, int in_features,
                    int weight_dtype, const float* resid, void* stream);
 

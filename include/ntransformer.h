@@ -69,7 +69,9 @@ int  nt_engine_load_synthetic(nt_engine_t e, const nt_synth_spec* spec, int max_
  * can decode two requests on one GPU at once (bench.py: 8b_q8_0_x2_per_gpu).  `src` must outlive `e` and must not be re-loaded or change its
  * "repack" level meanwhile; a tensor-parallel source is refused (NTK_E_SHAPE). */
 int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
-/* "fused" / "graph" / "device_sampling" / "batched_prefill" / "f16_prefill" (alias "bf16_prefill") = "0" | "1"; "persistent" / "fuse_attention" are accepted
+/* "fused" / "graph" / "device_sampling" / "batched_prefill" / "f16_prefill" (alias "bf16_prefill") = "0" | "1"; "dense_fused" = "1" (default) | "0", any time: the
+ * matrices of an unquantised model (F16, BF16) on the fused decode GEMV (five launches per layer, as a quantised model) and on the batched prompt GEMM, or
+ * ("0") on the 1:1 launcher sequence -- one GEMV per matrix and token; the A/B switch of profiles/dense16.txt; "persistent" / "fuse_attention" are accepted
  * and do nothing (the structures they selected lost to the fused launches and were removed: profiles/NEGATIVE_RESULTS.md); "repack" = "0" raw-GGUF decode GEMVs | "1" load-time repack with the GGUF
  * bytes kept resident (K-quant weights twice in HBM) | "2" one resident copy: the GGUF bytes of a repacked matrix are freed and unpacked into a scratch
  * for the launches that read raw blocks (prompt GEMM, 1:1 sequence; a fixed cost per prompt pass) | "3" (default) "2" when both copies would leave less than

@@ -34,6 +34,7 @@ static void usage(const char* prog) {
             "  -h, --help               Show this help\n"
             "  --no-fuse / --no-graph   Use the 15-launch/layer sequence / launch eagerly\n"
             "  --no-batched-prefill     Prompt tokens one by one (the reference's GEMV loops) instead of 16 per weight pass\n"
+            "  --no-dense-fuse          F16 / BF16 matrices on the 1:1 launchers instead of the fused 16-bit GEMV and the batched prompt GEMM (A/B switch)\n"
             "  --kv-cache <f16|q8_0>    KV cache format (default: f16; q8_0 = 8-bit Q8_0 blocks, 1.0625 bytes per element)\n"
             "  --rope-scaling <s>       file (default: the GGUF's rope_freqs.weight and linear scaling) | none | linear:<factor> |\n"
             "                           llama3:<factor>,<low>,<high>,<orig_ctx> (Llama-3.1 frequency factors computed by the engine)\n"
@@ -41,7 +42,7 @@ static void usage(const char* prog) {
             "  --rope-freq-scale <float> RoPE linear position scale, overriding the model's\n"
             "  --context-shift          At the end of the context drop half of the oldest positions and go on (default: stop there)\n"
             "  --keep <int>             Leading positions a context shift never drops (default: 1, the BOS)\n"
-            "  --synthetic <shape:mix>  8b|70b|tiny : Q8_0|Q4_K_M|Q6_K|...  seeded synthetic weights, no file\n"
+            "  --synthetic <shape:mix>  8b|70b|tiny : Q8_0|Q4_K_M|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
             "Accepted for CLI compatibility, no effect on the output (weights are always resident in 288 GB HBM;\n"
             "speculative decoding only changes speed, and plain decode is what runs):\n"
             "  --streaming --draft-model <p> --draft-k <n> --self-spec\n"
@@ -126,6 +127,7 @@ int main(int argc, char** argv) {
         else if (a == "--no-fuse") { engine.options().fused = false; engine.options().batched_prefill = false; }
         else if (a == "--no-batched-prefill") engine.options().batched_prefill = false;
         else if (a == "--no-graph") engine.options().graph = false;
+        else if (a == "--no-dense-fuse") (void)engine.model().set_dense_fused(false);
         else if (a == "--synthetic") { if (auto v = val()) synthetic = v; }
         else if (a == "--kv-cache") {
             const char* v = val();

@@ -29,6 +29,9 @@ int         last_launch_status();      // hipGetLastError -> NTK_OK / NTK_E_LAUN
 // gemv.hip: the GEMV over the lane-major repack of Q8_0 (ntk_q8l_pack; gemv_core.hip.h: q8l_layout) behind ntk_gemv_rp_fused (gemv_rp.hip)
 int         q8l_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in, const float* norm_w, float eps, const float* resid,
                            int silu_pair, hipStream_t st);
+// gemv_dense16.hip: the fused decode GEMV over unquantised 16-bit rows (segments of ONE dtype, NTK_DT_F16 or NTK_DT_BF16) behind ntk_gemv_fused (gemv.hip)
+int         dense16_gemv_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in, const float* norm_w, float eps, const float* resid,
+                               int silu_pair, hipStream_t st);
 
 // ---- fp16 <-> fp32: v_cvt_f32_f16 / v_cvt_f16_f32 (RNE, denormals preserved: hipcc default mode) ----
 __device__ __forceinline__ float h2f(uint16_t bits) {

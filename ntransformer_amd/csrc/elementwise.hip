@@ -88,6 +88,7 @@ __device__ float embed_elem(const uint8_t* __restrict__ table, int tok, int hidd
     switch (dt) {
         case NTK_DT_F32: return reinterpret_cast<const float*>(table)[(size_t)tok * hidden + e];
         case NTK_DT_F16: return h2f(reinterpret_cast<const uint16_t*>(table)[(size_t)tok * hidden + e]);
+        case NTK_DT_BF16: return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(table)[(size_t)tok * hidden + e] << 16);   // exact
         case NTK_DT_Q8_0: {
             const uint8_t* b = table + ((size_t)tok * (hidden / 32) + e / 32) * 34;
             const float d = h2f((uint16_t)(b[0] | (b[1] << 8)));
@@ -312,7 +313,7 @@ int ntk_embed_rows(float* out, const void* table, const int* tokens, int n_token
     const int st = last_launch_status();
     if (st != NTK_OK) return st;
     switch (dtype) {   // rows were zero-filled for anything the reference host path has no branch for
-        case NTK_DT_F32: case NTK_DT_F16: case NTK_DT_Q8_0: case NTK_DT_Q4_0: case NTK_DT_Q4_K: case NTK_DT_Q6_K: return NTK_OK;
+        case NTK_DT_F32: case NTK_DT_F16: case NTK_DT_BF16: case NTK_DT_Q8_0: case NTK_DT_Q4_0: case NTK_DT_Q4_K: case NTK_DT_Q6_K: return NTK_OK;
         default: return NTK_E_DTYPE;
     }
 }

@@ -66,6 +66,11 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
     else if (k == "batched_prefill") { E(e)->options().batched_prefill = on; E(e)->model().set_batched_prefill(on); }
     else if (k == "device_sampling") E(e)->options().device_sampling = on;
     else if (k == "f16_prefill" || k == "bf16_prefill") E(e)->model().set_bf16_prefill(on);   // (the round-2 name stays accepted)
+    else if (k == "dense_fused") {   // "1" (default) | "0": F16 / BF16 matrices on the fused decode GEMV and the batched prompt GEMM, or the 1:1 launchers; any time
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("dense_fused must be 0 or 1"); return NTK_E_SHAPE; }
+        return E(e)->model().set_dense_fused(on);
+    }
     else if (k == "persistent" || k == "fuse_attention") {   // accepted and without effect: the structures they selected were retired
         if (on) fprintf(stderr, "note: \"%s\" selected an experiment that lost to the fused launches and was removed (profiles/NEGATIVE_RESULTS.md); the option does nothing\n", key);
     }
@@ -442,8 +447,8 @@ int nt_gguf_describe(const char* path, char* out, int cap) {
             first = false;
             j += "{\"name\":\""; json_escape(j, t.name); j += "\",\"dims\":[";
             for (size_t d = 0; d < t.dims.size(); ++d) { if (d) j += ","; j += std::to_string(t.dims[d]); }
-            snprintf(b, sizeof b, "],\"ggml_type\":%u,\"dtype\":%d,\"offset\":%llu,\"nbytes\":%zu}", t.ggml_type, t.dtype,
-                     (unsigned long long)t.offset, t.nbytes);
+            snprintf(b, sizeof b, "],\"ggml_type\":%u,\"dtype\":%d,\"type\":\"%s\",\"offset\":%llu,\"nbytes\":%zu}", t.ggml_type, t.dtype,
+                     t.known_type ? nt::dtype_name(t.dtype) : "UNKNOWN", (unsigned long long)t.offset, t.nbytes);
             j += b;
         }
         j += "]}";

@@ -26,17 +26,18 @@ int ggml_type_to_dtype(uint32_t t) {
         case 13: return NTK_DT_Q5_K;
         case 14: return NTK_DT_Q6_K;
         case 26: return NTK_DT_I32;
+        case 30: return NTK_DT_BF16;   // not in the reference
         default: return NTK_DT_F32;   // the reference's fallback
     }
 }
 
 bool ggml_type_known(uint32_t t) {
-    switch (t) { case 0: case 1: case 2: case 8: case 10: case 12: case 13: case 14: case 26: return true; default: return false; }
+    switch (t) { case 0: case 1: case 2: case 8: case 10: case 12: case 13: case 14: case 26: case 30: return true; default: return false; }
 }
 
 const char* dtype_name(int dt) {
-    static const char* n[] = {"F32", "F16", "Q8_0", "Q4_0", "Q4_K_M", "Q6_K", "Q5_K", "Q2_K", "I32"};
-    return dt >= 0 && dt <= 8 ? n[dt] : "UNKNOWN";
+    static const char* n[] = {"F32", "F16", "Q8_0", "Q4_0", "Q4_K_M", "Q6_K", "Q5_K", "Q2_K", "I32", "BF16"};
+    return dt >= 0 && dt <= 9 ? n[dt] : "UNKNOWN";
 }
 
 void ModelConfig::print() const {   // same fields the reference prints (config.cpp:52-65)

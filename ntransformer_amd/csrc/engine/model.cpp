@@ -111,6 +111,18 @@ int Model::set_attention_merge(bool on) {
     return NTK_OK;
 }
 
+int Model::set_dense_fused(bool on) {
+    if (on == dense_fused_) return NTK_OK;
+    if (!layers_.empty()) {
+        NT_TRY(sync());
+        drop_graphs();
+    }
+    dense_fused_ = on;
+    return NTK_OK;
+}
+
+bool Model::fusable(int dt) const { return is_quant(dt) || (dense_fused_ && is_dense16(dt)); }
+
 int Model::set_repack(int level) {
     level = level < 0 ? 0 : level > 3 ? 3 : level;
     if (shares_weights_) { err_ = "set_repack: this sequence shares another model's tensors"; return NTK_E_SHAPE; }

@@ -253,6 +253,12 @@ public:
     int repack_level() const { return repack_; }
     uint64_t repack_bytes() const { return repack_bytes_; }
     uint64_t resident_weight_bytes() const { return weight_bytes_ - raw_freed_bytes_ + repack_bytes_ + raw_scratch_bytes_; }
+    // F16 / BF16 matrices on the fused launches (1, default): the decode pass groups them like quantised ones (ntk_gemv_fused -> gemv_dense16.hip: five
+    // launches per layer, norm + LM head in one) and the prompt pass sends them to the F32-MFMA GEMM ahead of the per-token loop.  0: the 1:1 launcher
+    // sequence both passes had before (ntk_rmsnorm / ntk_gemv / ntk_add per matrix; one GEMV per token and projection) -- the A/B switch.  Any time;
+    // captured graphs are dropped when the setting changes.
+    int set_dense_fused(bool on);
+    bool fusable(int dt) const;   // a matrix of this dtype goes out on the fused decode launches / the batched prompt GEMM
     void set_bf16_prefill(bool on) { bf16_prefill_ = on; }   // batched prompt: FP16-MFMA (gemm_f16.hip; the option keeps its round-2 name) or the F32-MFMA form (16)
     // which form decode_step_fused(…) emits at the current position: the fused launches of its attention regime
     const char* decode_path() const;
@@ -438,6 +444,7 @@ private:
     bool prefill_fused_split_ = true;   // (A/B switch of that: 0 = the FP16 GEMM's own pre-pass launches)
     size_t gemm_ws_bytes_ = 0;
     bool bf16_prefill_ = true;
+    bool dense_fused_ = true;
     int repack_ = 3;                 // EFFECTIVE level: 0 raw path, 1 repack + raw resident, 2 repack only (one resident copy); 3 only before a load
     int repack_wanted_ = 3;          // the level as ASKED (3 = the default: resolves to 2 at load): re-evaluated by every load
     bool repack_done_ = false;       // repack_all() ran on the loaded tensors

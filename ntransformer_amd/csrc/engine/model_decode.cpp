@@ -33,9 +33,9 @@ int Model::enqueue_token(bool greedy) {
     prof_mark(2, false);
     if (est != NTK_OK && est != NTK_E_DTYPE) return est;
     NT_TRY(enqueue_layers(0, cfg_.n_layers));
-    // final RMSNorm + LM head: one launch for a quantised output matrix (timed as one interval whichever form takes it), two 1:1 launches for a dense one
+    // final RMSNorm + LM head: one launch for a quantised or fused 16-bit output matrix (timed as one interval whichever form takes it), two 1:1 launches otherwise
     const DevTensor* const w = &output_;
-    const bool timed = is_quant(w->dtype);
+    const bool timed = fusable(w->dtype);
     if (timed) prof_mark(0, true);
     NT_TRY(decode_project(&w, &logits_, 1, hidden1_, &output_norm_, nullptr, 16, 0, false));
     if (timed) prof_mark(0, false);
@@ -48,9 +48,10 @@ int Model::enqueue_token(bool greedy) {
     return NTK_OK;
 }
 
-// y_k = W_k . f(x) for n <= 3 matrices sharing x.  Matrices with one quantised dtype go out as one fused launch (RMSNorm prologue when `norm`, residual
-// epilogue when `resid`, n == 1; silu_pair: y_0 = SiLU(y_0) x y_1 in the epilogue, two matrices of one format); dense F16/F32 tensors take the 1:1
-// launchers.  Scratch: residual_[0,H) = dense output before the residual add, residual_[H,2H) = norm(x).  kind: the call site's rp_mask() bit.  timed: every
+// y_k = W_k . f(x) for n <= 3 matrices sharing x.  Matrices with one fusable dtype (quantised; F16 / BF16 unless dense_fused = 0) go out as one fused launch
+// (RMSNorm prologue when `norm`, residual epilogue when `resid`, n == 1; silu_pair: y_0 = SiLU(y_0) x y_1 in the epilogue, two matrices of one format); the
+// other dense tensors, and a 16-bit group whose shape or alignment the fused kernel does not take (NTK_E_ALIGN / NTK_E_SHAPE), take the 1:1 launchers.
+// Scratch: residual_[0,H) = dense output before the residual add, residual_[H,2H) = norm(x).  kind: the call site's rp_mask() bit.  timed: every
 // launch is a profiler interval of its own (false: the caller times the whole call as one).
 int Model::decode_project(const DevTensor* const* ws, float* const* ys, int n, const float* x, const DevTensor* norm, const float* resid, int kind,
                           int silu_pair, bool timed) {
@@ -84,33 +85,42 @@ int Model::decode_project(const DevTensor* const* ws, float* const* ys, int n, c
         if (!not_taken(st)) return st;
     }
     bool done[3] = {false, false, false};
+    auto one_to_one = [&](int a) -> int {   // matrix a through the reference's launchers
+        const DevTensor& w = *ws[a];
+        const float* xin = x;
+        if (nw) {
+            NT_TRY(ntk_rmsnorm(residual_ + H, x, nw, 1, (int)w.in_f, cfg_.norm_eps, s));
+            xin = residual_ + H;
+        }
+        float* y = resid ? residual_ : ys[a];
+        raw_begin();
+        NT_TRY(ntk_gemv(y, raw_of(w), xin, (int)w.out_f, (int)w.in_f, w.dtype, s));
+        if (resid) NT_TRY(ntk_add(ys[a], resid, residual_, (int)w.out_f, s));
+        done[a] = true;
+        return NTK_OK;
+    };
     for (int a = 0; a < n; ++a) {
         if (done[a]) continue;
         const DevTensor& w = *ws[a];
-        if (!is_quant(w.dtype)) {
-            const float* xin = x;
-            if (nw) {
-                NT_TRY(ntk_rmsnorm(residual_ + H, x, nw, 1, (int)w.in_f, cfg_.norm_eps, s));
-                xin = residual_ + H;
-            }
-            float* y = resid ? residual_ : ys[a];
-            raw_begin();
-            NT_TRY(ntk_gemv(y, raw_of(w), xin, (int)w.out_f, (int)w.in_f, w.dtype, s));
-            if (resid) NT_TRY(ntk_add(ys[a], resid, residual_, (int)w.out_f, s));
-            done[a] = true;
-            continue;
-        }
+        if (!fusable(w.dtype)) { NT_TRY(one_to_one(a)); continue; }
         ntk_gemv_seg segs[3];
-        int m = 0;
+        int idx[3], m = 0;
         raw_begin();
         for (int b = a; b < n; ++b) {
             if (done[b] || ws[b]->dtype != w.dtype) continue;
+            idx[m] = b;
             segs[m++] = {raw_of(*ws[b]), ys[b], (int)ws[b]->out_f, ws[b]->dtype};
-            done[b] = true;
         }
         mark(true);
-        NT_TRY(ntk_gemv_fused(segs, m, x, (int)w.in_f, nw, cfg_.norm_eps, resid, silu_pair, s));
+        const int st = ntk_gemv_fused(segs, m, x, (int)w.in_f, nw, cfg_.norm_eps, resid, silu_pair, s);
         mark(false);
+        if (is_dense16(w.dtype) && (st == NTK_E_ALIGN || st == NTK_E_SHAPE)) {   // nothing was launched: the group one by one, and the epilogue the launch would have run
+            for (int k = 0; k < m; ++k) NT_TRY(one_to_one(idx[k]));
+            if (silu_pair) NT_TRY(ntk_silu_mul(ys[idx[0]], ys[idx[0]], ys[idx[1]], (int)w.out_f, s));
+            continue;
+        }
+        NT_TRY(st);
+        for (int k = 0; k < m; ++k) done[idx[k]] = true;
     }
     return NTK_OK;
 }
@@ -148,8 +158,8 @@ int Model::enqueue_layers(int first, int last_layer) {
         NT_TRY(project_add(L.wo, act.attn_out, 2));
         const DevTensor* const ffn[2] = {&L.w_gate, &L.w_up};
         float* const ffn_out[2] = {act.gate, act.up};
-        // one quantised format: SiLU x up in the launch's epilogue, one profiler interval whichever form takes it; otherwise a launch of its own
-        const bool pair = is_quant(L.w_gate.dtype) && L.w_gate.dtype == L.w_up.dtype;
+        // one fusable format: SiLU x up in the launch's epilogue, one profiler interval whichever form takes it; otherwise a launch of its own
+        const bool pair = fusable(L.w_gate.dtype) && L.w_gate.dtype == L.w_up.dtype;
         if (pair) prof_mark(0, true);
         NT_TRY(decode_project(ffn, ffn_out, 2, hidden1_, &L.ffn_norm, nullptr, 4, pair, !pair));
         if (pair) prof_mark(0, false);

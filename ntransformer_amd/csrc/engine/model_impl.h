@@ -27,6 +27,9 @@ inline bool is_quant(int dt) {
     return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K;
 }
 
+// unquantised rows of 16-bit words: the fused decode GEMV (gemv_dense16.hip) and the F32-MFMA prompt GEMM take them beside the quantised formats
+inline bool is_dense16(int dt) { return dt == NTK_DT_F16 || dt == NTK_DT_BF16; }
+
 // the three statuses with which a launcher says "nothing was launched: try the next form"
 inline bool not_taken(int st) { return st == NTK_E_DTYPE || st == NTK_E_SHAPE || st == NTK_E_ALIGN; }
 

@@ -194,6 +194,9 @@ int Model::finish_load() {
             (weight_bytes_ - raw_freed_bytes_) / 1073741824.0, repack_bytes_ ? (" + " + std::to_string(repack_bytes_ / 1073741824.0).substr(0, 5) + " GB repacked for decode").c_str() : "",
             q8_twice ? (", of which " + std::to_string(q8_twice / 1073741824.0).substr(0, 5) + " GB extra: Q8_0 matrices keep their GGUF bytes beside the repack").c_str() : "",
             fr / 1073741824.0);
+    if (!layers_.empty())   // the formats a user chose the file for: an unquantised model says so
+        fprintf(stderr, "Weight types: attn_q %s, ffn_down %s, output %s, token_embd %s\n", dtype_name(layers_[0].wq.dtype), dtype_name(layers_[0].w_down.dtype),
+                dtype_name(output_.dtype), dtype_name(token_embd_.dtype));
     return NTK_OK;
 }
 

@@ -159,7 +159,9 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     // Y = W . X (+ resid, which may be Y) for all T tokens on the matrix cores: the FP16 GEMM, else the F32-MFMA form.  false: a shape only the per-token
     // loop takes (NTK_E_ALIGN / NTK_E_SHAPE: nothing launched; *wp holds the GGUF bytes for it)
     auto gemm_mfma = [&](float* Y, const DevTensor& w, const float* X, const float* resid, const float* rm, const void** wp) {
-        int st = gemm_f16(Y, w, X, resid, rm, nullptr, wp);
+        int st = NTK_E_DTYPE;
+        if (is_dense16(w.dtype)) { raw_begin(); *wp = raw_of(w); }   // 16-bit rows: the F32-MFMA form alone (the FP16 GEMM has no decoder for them)
+        else st = gemm_f16(Y, w, X, resid, rm, nullptr, wp);
         if (not_taken(st)) st = ntk_gemm_quant(Y, *wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, resid, s);
         if (st == NTK_E_ALIGN || st == NTK_E_SHAPE) return false;
         ok(st);
@@ -169,7 +171,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     auto project = [&](float* Y, const DevTensor& w, const float* X, size_t ystride, size_t xstride, const float* rm) {
         const bool dense = ystride == (size_t)w.out_f && xstride == (size_t)w.in_f;
         const void* wp = nullptr;
-        if (batched && is_quant(w.dtype) && dense) {
+        if (batched && fusable(w.dtype) && dense) {
             if (gemm_mfma(Y, w, X, nullptr, rm, &wp)) return;
         } else { raw_begin(); wp = raw_of(w); }
         for (int t = 0; t < T; ++t) {
@@ -211,7 +213,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         const bool dense = batched && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f;
         if (dense && bf16_now) prepare_x(X, w);
         const void* wp = nullptr;   // (unused: project() below obtains the bytes again)
-        if (dense && is_quant(w.dtype) && gemm_mfma(hidden_, w, X, hidden_, rm, &wp)) return;
+        if (dense && fusable(w.dtype) && gemm_mfma(hidden_, w, X, hidden_, rm, &wp)) return;
         project(residual_, w, X, H, xstride, rm);
         ok(ntk_add_inplace(hidden_, residual_, T * H, s));
     };
@@ -396,7 +398,7 @@ int Model::lm_head(float* logits, const float* X, int n, const float* chunk_max)
     const DevTensor& w = output_;
     const int H = cfg_.hidden_size, V = cfg_.vocab_size;
     void* s = stream_;
-    const bool batched = batched_prefill_ && is_quant(w.dtype);
+    const bool batched = batched_prefill_ && fusable(w.dtype) && (is_quant(w.dtype) || n > 1);   // (one row of a 16-bit head: the GEMV reads as many bytes)
     void* const ws = score_ws_ ? score_ws_ : gemm_ws_;
     const size_t ws_bytes = score_ws_ ? score_ws_bytes_ : gemm_ws_bytes_;
     int st = NTK_E_DTYPE;

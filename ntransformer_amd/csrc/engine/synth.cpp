@@ -29,6 +29,14 @@ inline uint16_t f2h(float f) {
     memcpy(&b, &h, 2);
     return b;
 }
+// F32 -> bfloat16: round to nearest even on the 16 dropped bits; subnormals are kept (no flush), +-inf is kept, NaN stays NaN with the quiet bit
+// set (the rounding add would carry some payloads into infinity).  gguf.py's f32_to_bf16 is the same statement in numpy.
+inline uint16_t f2bf(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x0040u);
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
 inline void put16(uint8_t* p, uint16_t v) { memcpy(p, &v, 2); }
 
 struct BlockInfo { int bw, bb; };
@@ -41,6 +49,7 @@ BlockInfo block_of(int gt) {
         case 12: return {256, 144};
         case 13: return {256, 176};
         case 14: return {256, 210};
+        case 30: return {1, 2};   // BF16
         default: return {0, 0};
     }
 }
@@ -97,7 +106,7 @@ void fill_dense(uint8_t* dst, int gt, uint64_t key, int64_t e0, int64_t n, doubl
             v = (float)((a - 2.0) * 1.7320508 * tgt);
         }
         if (gt == 0) memcpy(dst + 4 * e, &v, 4);
-        else put16(dst + 2 * e, f2h(v));
+        else put16(dst + 2 * e, gt == 30 ? f2bf(v) : f2h(v));
     }
 }
 
@@ -108,6 +117,7 @@ int mix_type(const std::string& mix) {
     if (mix == "Q5_K") return 13;
     if (mix == "Q6_K") return 14;
     if (mix == "F16") return 1;
+    if (mix == "BF16") return 30;
     if (mix == "F32") return 0;
     return -1;
 }

@@ -66,6 +66,13 @@ template <> struct GFmt<NTK_DT_Q4_0> { static constexpr int BW = 32, BB = 18, SB
 template <> struct GFmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, SB = 144; };
 template <> struct GFmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, SB = 176; };
 template <> struct GFmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, SB = 210; };
+// Unquantised 16-bit rows (IEEE half, bfloat16): a "block" is 32 consecutive weights in 64 bytes, no scale.  A chunk of a row is then 8 KiB, and
+// sixteen of them with the padded pitch would not fit the CU's 160 KiB beside the reduction buffers; these formats require 16-byte-aligned rows
+// instead (W aligned; a row is a multiple of 64 bytes), stage exactly 8 KiB per row at a pitch of 8 KiB and keep the reads conflict-free by
+// XOR-ing the 16-byte piece index with the row (SWZ: kernel stage + Deq16 below) -- 160 KiB to the byte.
+template <> struct GFmt<NTK_DT_F16>  { static constexpr int BW = 32, BB = 64, SB = 512; };
+template <> struct GFmt<NTK_DT_BF16> { static constexpr int BW = 32, BB = 64, SB = 512; };
+template <int DT> constexpr bool GSWZ = (DT == NTK_DT_F16 || DT == NTK_DT_BF16);
 
 struct GemmParams {
     const uint8_t* W;     // 16-byte-aligned-down base
@@ -180,14 +187,31 @@ template <> struct Deq<NTK_DT_Q6_K> {   // gemm.cu:421-459: sub-block s = 4 half
     }
 };
 
+// 16-bit rows: the lane's 8 weights are ONE 16-byte piece of the swizzled row image (piece index ^ row, row = lane % 16 -- the kernel's r), widened
+// exactly: half by v_cvt_f32_f16, bfloat16 as the high half of the float
+template <bool BF> struct Deq16 {
+    __device__ static void run(const uint8_t* st, int shift, int s, int g, float (&a)[8]) {
+        const int piece = ((shift + 64 * s + 16 * g) >> 4) ^ ((int)threadIdx.x & 15);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(st + 16 * piece);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (BF) { a[2 * j] = __uint_as_float(w[j] << 16); a[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u); }
+            else { a[2 * j] = h2f((uint16_t)(w[j] & 0xFFFFu)); a[2 * j + 1] = h2f((uint16_t)(w[j] >> 16)); }
+        }
+    }
+};
+template <> struct Deq<NTK_DT_F16> : Deq16<false> {};
+template <> struct Deq<NTK_DT_BF16> : Deq16<true> {};
+
 // FULL: in % 256 == 0, every slice has its eight sub-blocks (no per-sub-block branches: the compiler can then move the
 // next sub-block's LDS reads above the current MFMAs)
 template <int DT, bool FULL>
 __global__ __launch_bounds__(64 * GM_WAVES) void gemm_quant_mfma_kernel(const GemmParams p) {
     using F = GFmt<DT>;
     constexpr int CB = GM_WAVES * F::SB;                          // bytes of one row inside a K chunk (GM_WAVES slices)
-    constexpr int NLR = (CB + 15 + 1023) / 1024;                  // 1 KiB wave loads that cover them at any alignment
-    constexpr int RPITCH = NLR * 1024 + 16;                       // LDS bytes per staged row (+16: rows start on different banks)
+    constexpr int NLR = GSWZ<DT> ? CB / 1024 : (CB + 15 + 1023) / 1024;   // 1 KiB wave loads that cover them at any alignment (16-bit rows: aligned)
+    constexpr int RPITCH = GSWZ<DT> ? NLR * 1024 : NLR * 1024 + 16;       // LDS bytes per staged row (+16: rows start on different banks; 16-bit rows: swizzled)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,7 +272,8 @@ __global__ __launch_bounds__(64 * GM_WAVES) void gemm_quant_mfma_kernel(const Ge
             for (int q = 0; q < GM_RPW; ++q)
 #pragma unroll
                 for (int j = 0; j < NLR; ++j)
-                    *reinterpret_cast<u32x4*>(tile_img + (wave + GM_WAVES * q) * RPITCH + 16 * (lane + 64 * j)) = pf[q][j];
+                    *reinterpret_cast<u32x4*>(tile_img + (wave + GM_WAVES * q) * RPITCH +
+                                              16 * (GSWZ<DT> ? (lane + 64 * j) ^ ((wave + GM_WAVES * q) & 15) : lane + 64 * j)) = pf[q][j];
             GM_STAMP();                                            // rows landed + staged
             __syncthreads();                                       // B1: the tile image is complete
             GM_STAMP();                                            // past B1
@@ -317,7 +342,7 @@ static int launch_gemm(float* Y, const void* W, const float* X, int T, int out, 
     using F = GFmt<DT>;
     if (in <= 0 || in % F::BW != 0 || in % 32 != 0) return NTK_E_SHAPE;
     const uintptr_t w = reinterpret_cast<uintptr_t>(W);
-    if (w & 1) return NTK_E_ALIGN;
+    if (w & (GSWZ<DT> ? 15 : 1)) return NTK_E_ALIGN;
     if ((reinterpret_cast<uintptr_t>(X) & 15) != 0 || (in % 4) != 0) return NTK_E_ALIGN;
     GemmParams p{};
     p.W = reinterpret_cast<const uint8_t*>(w & ~(uintptr_t)15);
@@ -329,8 +354,8 @@ static int launch_gemm(float* Y, const void* W, const float* X, int T, int out, 
     p.row_bytes = (unsigned)row_bytes;
     p.nslices = (in + GM_SLICE - 1) / GM_SLICE;
     constexpr int CB = GM_WAVES * F::SB;
-    constexpr int NLR = (CB + 15 + 1023) / 1024;
-    constexpr int RPITCH = NLR * 1024 + 16;
+    constexpr int NLR = GSWZ<DT> ? CB / 1024 : (CB + 15 + 1023) / 1024;
+    constexpr int RPITCH = GSWZ<DT> ? NLR * 1024 : NLR * 1024 + 16;
     const size_t lds = (size_t)GM_ROWS * RPITCH + (size_t)2 * GM_WAVES * 256 * sizeof(float);
     static bool once = [] {
         return hipFuncSetAttribute((const void*)gemm_quant_mfma_kernel<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -372,6 +397,8 @@ extern "C" int ntk_gemm_quant(float* Y, const void* W, const float* X, int n_tok
             case NTK_DT_Q4_K: rc = ntk::launch_gemm<NTK_DT_Q4_K>(y, W, x, T, out_features, in_features, rs, st); break;
             case NTK_DT_Q5_K: rc = ntk::launch_gemm<NTK_DT_Q5_K>(y, W, x, T, out_features, in_features, rs, st); break;
             case NTK_DT_Q6_K: rc = ntk::launch_gemm<NTK_DT_Q6_K>(y, W, x, T, out_features, in_features, rs, st); break;
+            case NTK_DT_F16: rc = ntk::launch_gemm<NTK_DT_F16>(y, W, x, T, out_features, in_features, rs, st); break;
+            case NTK_DT_BF16: rc = ntk::launch_gemm<NTK_DT_BF16>(y, W, x, T, out_features, in_features, rs, st); break;
             default: return NTK_E_DTYPE;
         }
         if (rc != NTK_OK) return rc;

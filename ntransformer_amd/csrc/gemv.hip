@@ -699,10 +699,14 @@ __global__ __launch_bounds__(512, 4) void gemv_quant_pair_kernel(const GemvParam
 }
 
 // ------------------------------------------------------------------------------------------------
-// Dense F16 / F32 rows (reference gemm.cu:476-671): one wave per row, 16-byte lane loads when the row
-// is aligned, scalar otherwise (the reference's own F32 test uses in = 3).  Not on any target config.
+// Dense F16 / BF16 / F32 rows (reference gemm.cu:476-671; BF: the 16-bit words are bfloat16, widened exactly by bits << 16): one wave per row,
+// 16-byte lane loads when the row is aligned, scalar otherwise (the reference's own F32 test uses in = 3).  The 1:1 launcher: the engine's
+// 16-bit models run on gemv_dense16.hip and come here only with dense_fused = 0 or with shapes that kernel does not take.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool ADD>
+template <bool BF> __device__ __forceinline__ float w16f(uint16_t bits) {
+    if constexpr (BF) return __uint_as_float((uint32_t)bits << 16); else return h2f(bits);
+}
+template <typename T, bool ADD, bool BF = false>
 __global__ __launch_bounds__(256) void gemv_dense_kernel(float* __restrict__ y, const T* __restrict__ W,
                                                          const float* __restrict__ x, int out, int in) {
     const int lane = threadIdx.x & 63;
@@ -724,17 +728,17 @@ __global__ __launch_bounds__(256) void gemv_dense_kernel(float* __restrict__ y, 
                 } else {
                     const float4 x0 = *reinterpret_cast<const float4*>(x + 8 * i);
                     const float4 x1 = *reinterpret_cast<const float4*>(x + 8 * i + 4);
-                    acc = fmaf(h2f((uint16_t)(raw.x & 0xFFFF)), x0.x, acc); acc = fmaf(h2f((uint16_t)(raw.x >> 16)), x0.y, acc);
-                    acc = fmaf(h2f((uint16_t)(raw.y & 0xFFFF)), x0.z, acc); acc = fmaf(h2f((uint16_t)(raw.y >> 16)), x0.w, acc);
-                    acc = fmaf(h2f((uint16_t)(raw.z & 0xFFFF)), x1.x, acc); acc = fmaf(h2f((uint16_t)(raw.z >> 16)), x1.y, acc);
-                    acc = fmaf(h2f((uint16_t)(raw.w & 0xFFFF)), x1.z, acc); acc = fmaf(h2f((uint16_t)(raw.w >> 16)), x1.w, acc);
+                    acc = fmaf(w16f<BF>((uint16_t)(raw.x & 0xFFFF)), x0.x, acc); acc = fmaf(w16f<BF>((uint16_t)(raw.x >> 16)), x0.y, acc);
+                    acc = fmaf(w16f<BF>((uint16_t)(raw.y & 0xFFFF)), x0.z, acc); acc = fmaf(w16f<BF>((uint16_t)(raw.y >> 16)), x0.w, acc);
+                    acc = fmaf(w16f<BF>((uint16_t)(raw.z & 0xFFFF)), x1.x, acc); acc = fmaf(w16f<BF>((uint16_t)(raw.z >> 16)), x1.y, acc);
+                    acc = fmaf(w16f<BF>((uint16_t)(raw.w & 0xFFFF)), x1.z, acc); acc = fmaf(w16f<BF>((uint16_t)(raw.w >> 16)), x1.w, acc);
                 }
             }
             done = nv * V;
         }
         for (int i = done + lane; i < in; i += 64) {
             float wv;
-            if constexpr (sizeof(T) == 4) wv = (float)w[i]; else wv = h2f((uint16_t)w[i]);
+            if constexpr (sizeof(T) == 4) wv = (float)w[i]; else wv = w16f<BF>((uint16_t)w[i]);
             acc = fmaf(wv, x[i], acc);
         }
         acc = wave_sum(acc);
@@ -1047,6 +1051,8 @@ static int launch_dense(float* y, const void* W, const float* x, int out, int in
     const int grid = std::min((out + 3) / 4, 2048);
     if (dt == NTK_DT_F32)
         hipLaunchKernelGGL((gemv_dense_kernel<float, ADD>), dim3(grid), dim3(256), 0, st, y, (const float*)W, x, out, in);
+    else if (dt == NTK_DT_BF16)
+        hipLaunchKernelGGL((gemv_dense_kernel<uint16_t, ADD, true>), dim3(grid), dim3(256), 0, st, y, (const uint16_t*)W, x, out, in);
     else
         hipLaunchKernelGGL((gemv_dense_kernel<uint16_t, ADD>), dim3(grid), dim3(256), 0, st, y, (const uint16_t*)W, x, out, in);
     return last_launch_status();
@@ -1090,7 +1096,7 @@ int ntk_gemv(float* y, const void* W, const float* x, int out_features, int in_f
     if (!y || !W || !x) return NTK_E_NULL;
     if (out_features < 0 || in_features <= 0) return NTK_E_SHAPE;
     hipStream_t st = ntk::resolve_stream(stream);
-    if (weight_dtype == NTK_DT_F32 || weight_dtype == NTK_DT_F16)
+    if (weight_dtype == NTK_DT_F32 || weight_dtype == NTK_DT_F16 || weight_dtype == NTK_DT_BF16)
         return ntk::launch_dense<false>(y, W, x, out_features, in_features, weight_dtype, st);
     if (!ntk::is_quant(weight_dtype)) return NTK_E_DTYPE;
     ntk_gemv_seg seg{W, y, out_features, weight_dtype};
@@ -1109,6 +1115,11 @@ static int gemv_fused_form(const ntk_gemv_seg* segs, int nseg, const float* x, i
                            const float* resid, int silu_pair, void* stream, int xi_mode) {
     if (!segs || !x) return NTK_E_NULL;
     if (nseg < 1 || nseg > ntk::MAX_SEG) return NTK_E_SHAPE;
+    if (segs[0].dtype == NTK_DT_F16 || segs[0].dtype == NTK_DT_BF16) {   // unquantised 16-bit rows: gemv_dense16.hip, segments of one dtype
+        for (int i = 1; i < nseg; ++i)
+            if (segs[i].dtype != segs[0].dtype) return NTK_E_DTYPE;
+        return ntk::dense16_gemv_fused(segs, nseg, x, in_features, norm_w, eps, resid, silu_pair, ntk::resolve_stream(stream));
+    }
     ntk_gemv_seg a[3], b[3];
     int na = 0, nb = 0;
     for (int i = 0; i < nseg; ++i) {

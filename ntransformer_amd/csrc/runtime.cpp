@@ -87,7 +87,7 @@ size_t ntk_row_bytes(int dtype, int64_t n) {
     if (n < 0) return 0;
     switch (dtype) {   // reference src/core/types.h:37-88
         case NTK_DT_F32: case NTK_DT_I32: return (size_t)n * 4;
-        case NTK_DT_F16: return (size_t)n * 2;
+        case NTK_DT_F16: case NTK_DT_BF16: return (size_t)n * 2;
         case NTK_DT_Q8_0: return n % 32 ? 0 : (size_t)(n / 32) * 34;
         case NTK_DT_Q4_0: return n % 32 ? 0 : (size_t)(n / 32) * 18;
         case NTK_DT_Q4_K: return n % 256 ? 0 : (size_t)(n / 256) * 144;

@@ -31,21 +31,37 @@ T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I6
 
 # ggml tensor types the reference maps (types.h:173-215)
 GGML_F32, GGML_F16, GGML_Q4_0, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K = 0, 1, 2, 8, 12, 13, 14
+GGML_BF16 = 30   # not in the reference: bfloat16, the format checkpoints are published in
 
 # nt::DType numeric values (types.h:24-35) -- the C ABI contract
 DT_F32, DT_F16, DT_Q8_0, DT_Q4_0, DT_Q4_K, DT_Q6_K, DT_Q5_K, DT_Q2_K, DT_I32 = range(9)
+DT_BF16 = 9   # NTK_DT_BF16: appended behind the reference's values
 
 GGML_TO_DT = {GGML_F32: DT_F32, GGML_F16: DT_F16, GGML_Q4_0: DT_Q4_0, GGML_Q8_0: DT_Q8_0,
-              GGML_Q4_K: DT_Q4_K, GGML_Q5_K: DT_Q5_K, GGML_Q6_K: DT_Q6_K}
+              GGML_Q4_K: DT_Q4_K, GGML_Q5_K: DT_Q5_K, GGML_Q6_K: DT_Q6_K, GGML_BF16: DT_BF16}
 DT_TO_GGML = {v: k for k, v in GGML_TO_DT.items()}
 DT_NAME = {DT_F32: "F32", DT_F16: "F16", DT_Q8_0: "Q8_0", DT_Q4_0: "Q4_0", DT_Q4_K: "Q4_K",
-           DT_Q6_K: "Q6_K", DT_Q5_K: "Q5_K"}
+           DT_Q6_K: "Q6_K", DT_Q5_K: "Q5_K", DT_BF16: "BF16"}
 NAME_TO_GGML = {"F32": GGML_F32, "F16": GGML_F16, "Q4_0": GGML_Q4_0, "Q8_0": GGML_Q8_0,
-                "Q4_K": GGML_Q4_K, "Q5_K": GGML_Q5_K, "Q6_K": GGML_Q6_K}
+                "Q4_K": GGML_Q4_K, "Q5_K": GGML_Q5_K, "Q6_K": GGML_Q6_K, "BF16": GGML_BF16}
 
 # (elements per block, bytes per block)
 BLOCK = {GGML_F32: (1, 4), GGML_F16: (1, 2), GGML_Q4_0: (32, 18), GGML_Q8_0: (32, 34),
-         GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176), GGML_Q6_K: (256, 210)}
+         GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176), GGML_Q6_K: (256, 210), GGML_BF16: (1, 2)}
+
+
+def f32_to_bf16(x: np.ndarray) -> np.ndarray:
+    """float32 -> bfloat16 bit patterns (uint16, same shape): round to nearest even on the 16 dropped bits, subnormals kept (no flush), +-inf kept,
+    NaN stays NaN with the quiet bit set (the rounding add could otherwise carry a NaN's payload into infinity)."""
+    u = np.ascontiguousarray(x, dtype="<f4").view(np.uint32)
+    rounded = (u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, (u >> np.uint32(16)) | np.uint32(0x0040), rounded).astype(np.uint16)
+
+
+def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
+    """bfloat16 bit patterns -> float32: the bits become the high half, exactly."""
+    return (np.ascontiguousarray(bits).view("<u2").astype(np.uint32) << np.uint32(16)).view("<f4")
 
 
 def row_bytes(ggml_type: int, n: int) -> int:
@@ -143,6 +159,7 @@ class GGUFFile:
     data_offset: int
     _mm: Optional[mmap.mmap] = field(default=None, repr=False)
     _buf: Optional[np.ndarray] = field(default=None, repr=False)
+    kv_span: Tuple[int, int] = (0, 0)   # file bytes [a, b) of the metadata entries, as written (write_f32_twin copies them)
 
     def raw(self, name: str) -> np.ndarray:
         ti = self.tensors[name]
@@ -153,6 +170,8 @@ class GGUFFile:
         return GGML_TO_DT[self.tensors[name].ggml_type]
 
     def f32(self, name: str) -> np.ndarray:
+        if self.tensors[name].ggml_type == GGML_BF16:   # widened exactly (a copy: the file holds 16-bit words)
+            return bf16_to_f32(self.raw(name).view("<u2"))
         assert self.tensors[name].ggml_type == GGML_F32
         return self.raw(name).view("<f4")
 
@@ -200,10 +219,12 @@ def read_gguf(path: str) -> GGUFFile:
         raise ValueError("unsupported GGUF version %d" % version)
     n_tensors, n_kv = rd("Q"), rd("Q")
     meta: Dict[str, object] = {}
+    kv_begin = pos
     for _ in range(n_kv):
         k = rstr().decode("utf-8")
         t = rd("I")
         meta[k] = rval(t)
+    kv_end = pos
     tensors: Dict[str, TensorInfo] = {}
     for _ in range(n_tensors):
         name = rstr().decode("utf-8")
@@ -216,7 +237,27 @@ def read_gguf(path: str) -> GGUFFile:
         tensors[name] = TensorInfo(name, dims, gt, off, row_bytes(gt, n))
     align = int(meta.get("general.alignment", 32))
     data_offset = (pos + align - 1) // align * align
-    return GGUFFile(path, version, meta, tensors, data_offset, mm, buf)
+    return GGUFFile(path, version, meta, tensors, data_offset, mm, buf, (kv_begin, kv_end))
+
+
+def write_f32_twin(src: str, dst: str, widen: Sequence[int] = (GGML_BF16,)) -> None:
+    """`src` again with every tensor whose type is in `widen` stored as F32 holding the same VALUES (exact: a bfloat16 or half value is a float), the
+    other tensors and the metadata copied byte for byte: the file a reader without BF16 -- the oracle -- computes the model's reference from, with no
+    quantiser in between."""
+    f = read_gguf(src)
+    n_kv = len(f.meta)
+    kvs = [bytes(f._buf[f.kv_span[0]:f.kv_span[1]])] + [b""] * (n_kv - 1)   # (write_gguf counts the entries and joins them)
+    specs = []
+    for name, ti in f.tensors.items():
+        n = 1
+        for d in ti.dims:
+            n *= d
+        if ti.ggml_type in widen:
+            specs.append(TensorSpec(name, ti.dims, GGML_F32, dequantize(np.array(f.raw(name)), ti.ggml_type, n).astype("<f4").tobytes()))
+        else:
+            specs.append(TensorSpec(name, ti.dims, ti.ggml_type, bytes(f.raw(name))))
+    f.close()
+    write_gguf(dst, kvs, specs)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -236,6 +277,8 @@ def synth_tensor(rng: np.random.Generator, ggml_type: int, out_f: int, in_f: int
         return (rng.standard_normal(out_f * in_f) * tgt).astype("<f4").tobytes()
     if ggml_type == GGML_F16:
         return (rng.standard_normal(out_f * in_f) * tgt).astype("<f2").tobytes()
+    if ggml_type == GGML_BF16:
+        return f32_to_bf16((rng.standard_normal(out_f * in_f) * tgt).astype("<f4")).astype("<u2").tobytes()
     blk = np.empty((nb, bb), np.uint8)
     if ggml_type == GGML_Q8_0:
         blk[:, 0:2] = _f16_bytes(tgt / 73.3 * jit)
@@ -285,6 +328,8 @@ def dequantize(raw: np.ndarray | bytes, ggml_type: int, n: int) -> np.ndarray:
         return raw.view("<f4").astype(np.float32)
     if ggml_type == GGML_F16:
         return raw.view("<f2").astype(np.float32)
+    if ggml_type == GGML_BF16:
+        return bf16_to_f32(raw[: 2 * n].view("<u2"))
     b = raw[: nb * bb].reshape(nb, bb)
     if ggml_type == GGML_Q8_0:
         d = b[:, 0:2].copy().view("<f2").astype(np.float32)

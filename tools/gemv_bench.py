@@ -2,7 +2,8 @@
 """Micro-benchmark of the dequant-fused GEMV launches at the real Llama-3.1 8B / 70B shapes: achieved HBM GB/s
 per shape (algorithmic bytes = rows * row_bytes).  Successive launches walk a >1 GB pool of weight bytes so
 the 256 MiB Infinity Cache cannot serve them (in decode every token streams the whole model).
-usage: python tools/gemv_bench.py [--dtypes Q8_0,Q4_K,Q6_K] [--json out.json]"""
+F16 / BF16 (unquantised rows, csrc/gemv_dense16.hip): every shape goes through ntk_gemv_fused, the plain ones included.
+usage: python tools/gemv_bench.py [--dtypes Q8_0,Q4_K,Q6_K,F16,BF16] [--json out.json]"""
 import argparse
 import ctypes as C
 import json
@@ -18,11 +19,12 @@ from ntransformer_amd.ops import DeviceBuffer as DB  # noqa: E402
 SHAPES = {  # name: (kind, rows..., in)
     "8b.q": ("plain", 4096, 4096), "8b.kv": ("plain", 1024, 4096), "8b.qkv_fused": ("qkv", (4096, 1024, 1024), 4096),
     "8b.o+res": ("resid", 4096, 4096), "8b.gate|up+silu": ("silu", 14336, 4096), "8b.down+res": ("resid", 4096, 14336),
-    "lm_head": ("plain", 128256, 4096),
+    "lm_head": ("plain", 128256, 4096), "lm_head+norm": ("norm", 128256, 4096),
     "70b.qkv_fused": ("qkv", (8192, 1024, 1024), 8192), "70b.o+res": ("resid", 8192, 8192),
     "70b.gate|up+silu": ("silu", 28672, 8192), "70b.down+res": ("resid", 8192, 28672),
 }
-GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K}
+GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K, "F16": G.GGML_F16, "BF16": G.GGML_BF16}
+DENSE16 = (G.GGML_F16, G.GGML_BF16)
 
 
 def main():
@@ -45,7 +47,16 @@ def main():
     HIP = C.CDLL("libamdhip64.so")
     if a.nw:
         L.ntk_tune_rp_waves(a.nw)
-    pool_bytes = a.pool_mb << 20
+    # a launch walks at least two slots of the pool: the pool holds two of the largest launch asked for (an F16 LM head is 1.05 GB)
+    def launch_bytes(dname, sname):
+        kind, rows, in_f = SHAPES[sname]
+        rlist = list(rows) if isinstance(rows, tuple) else [rows]
+        if a.rp and GT[dname] in (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K):
+            rpb = [(ops.rp_bytes(G.GGML_TO_DT[GT[dname]], r, in_f) + 255) // 256 * 256 for r in (rlist if kind != "silu" else [rlist[0], rlist[0]])]
+            return (sum(rpb) + 4095) // 4096 * 4096
+        per = G.row_bytes(GT[dname], in_f) * (sum(rlist) if kind != "silu" else 2 * rlist[0])
+        return (per + 4095) // 4096 * 4096
+    pool_bytes = max(a.pool_mb << 20, 2 * max(launch_bytes(d, s) for d in a.dtypes.split(",") for s in a.shapes.split(",")))
     rng = np.random.default_rng(0)
     # valid-looking blocks are irrelevant for timing; small-magnitude bytes keep fp16 scales finite
     pool = DB.from_numpy(rng.integers(0, 60, pool_bytes, dtype=np.uint8))
@@ -68,6 +79,7 @@ def main():
                 rpb = [(b + 255) // 256 * 256 for b in rpb]
                 per_launch_al = (sum(rpb) + 4095) // 4096 * 4096
             nslots = max(2, pool_bytes // per_launch_al)
+            assert nslots * per_launch_al <= pool_bytes, "a launch would read past the pool"
             x = DB.from_numpy(rng.standard_normal(in_f).astype(np.float32))
             nw = DB.from_numpy(np.ones(in_f, np.float32))
             ys = [DB.zeros(max(r, 1) * 4) for r in (rlist if kind != "silu" else [rlist[0], rlist[0]])]
@@ -82,8 +94,10 @@ def main():
                     ops.gemv_rp_fused(segs, x, in_f, norm_w=nw if kind in ("qkv", "silu") else None, eps=1e-5,
                                       resid=ys[0] if kind == "resid" else None, silu_pair=kind == "silu")
                     return
-                if kind == "plain" and a.lm:
+                if kind == "plain" and (a.lm or gt in DENSE16):
                     fused([(base, ys[0], rlist[0], dt)], x, in_f)
+                elif kind == "norm":
+                    fused([(base, ys[0], rlist[0], dt)], x, in_f, norm_w=nw, eps=1e-5)
                 elif kind == "plain":
                     ops.launch_gemv(ys[0], base, x, rlist[0], in_f, dt)
                 elif kind == "resid":

@@ -17,7 +17,7 @@ from ntransformer_amd.ops import DeviceBuffer as DB  # noqa: E402
 
 SHAPES = {"8b.q/o": (4096, 4096), "8b.kv": (1024, 4096), "8b.gate/up": (14336, 4096), "8b.down": (4096, 14336),
           "70b.q/o": (8192, 8192), "70b.gate/up": (28672, 8192), "70b.down": (8192, 28672)}
-GT = {"Q8_0": G.GGML_Q8_0, "Q4_K": G.GGML_Q4_K, "Q6_K": G.GGML_Q6_K}
+GT = {"Q8_0": G.GGML_Q8_0, "Q4_K": G.GGML_Q4_K, "Q6_K": G.GGML_Q6_K, "F16": G.GGML_F16, "BF16": G.GGML_BF16}   # (F16 / BF16: the F32-MFMA form only)
 
 
 def timed(fn, reps):
