@@ -384,6 +384,24 @@ int ntk_reduce_rmsnorm_prepare_x(float* hidden, const ntk_gemm_partials* partial
 int ntk_silu_mul_prepare_x(float* output, const float* gate, const float* up, int n_tokens, int width, void* workspace, void* stream);
 int ntk_reduce_silu_mul_prepare_x(float* output, const ntk_gemm_partials* partials, void* workspace, void* stream);
 
+/* The same projection over UNQUANTISED 16-bit rows on the 16-bit matrix cores (csrc/gemm_dense16.hip; plan: csrc/gemm_dense16_plan.h): the descriptor of
+ * ntk_gemm_quant_f16 with segs[i].dtype NTK_DT_F16 or NTK_DT_BF16 -- one of them per call -- and segs[i].W the matrix as it lies in the file, [rows_i][in]
+ * 16-bit words.  The weights reach the matrix instructions without a conversion; products are exact, sums F32.
+ *   F16   v_mfma_f32_16x16x32_f16 over the FP16 GEMM's own operand planes (two FP16 pieces of x s, 1 / s on the finished sum: the bound above).  The
+ *         workspace has the layout ntk_gemm_prepare_x and the other ntk_*_prepare_x producers write: with reuse_x != 0 their planes are read as they lie.
+ *   BF16  v_mfma_f32_16x16x32_bf16 over THREE bfloat16 pieces of x and no token scale: p1 = rn(x), p2 = rn(x - p1), p3 = rn(x - p1 - p2), rn to nearest
+ *         even and never from a finite x to infinity; p1 + p2 + p3 == x for every x whose last bit is >= 2^-133, |x - sum| <= 2^-134 below.  Its planes are
+ *         a layout of their own in the same workspace (a workspace holds ONE kind of planes at a time); reuse_x != 0 reads those of the previous BF16 call.
+ * A token's outputs do not depend on the other tokens, on n_tokens or on the segments sharing the launch: full_form has nothing to select and is ignored,
+ * as is row_max (the F16 pre-pass is one launch either way).  K is never split: partials, if given, reports nsplit = 1 and Y is written with the residual.
+ * Limits: rows_i % 16 == 0, in_features % 32 == 0, 1..3 segments, weights_repacked == 0 (NTK_E_SHAPE); dtypes other than F16 / BF16 or two kinds in one
+ * call (NTK_E_DTYPE); W_i, Y_i, X, resid, workspace 16-byte aligned (NTK_E_ALIGN) -- a refused call launches nothing and leaves Y as it was.  Rows of Y
+ * behind n_tokens are never written.  resid: one segment only, may alias Y.  More than 1024 tokens run as passes of 1024 (reuse_x is then ignored).
+ * workspace: ntk_gemm_dense16_workspace_bytes(in_features, rows, dtype) bytes (0: not a 16-bit dtype); for F16 never more than
+ * ntk_gemm_quant_workspace_bytes of the same shape.  Stream ordered, no allocation, the same bits on every launch. */
+size_t ntk_gemm_dense16_workspace_bytes(int in_features, int out_features, int dtype);
+int ntk_gemm_dense16(const ntk_gemm_desc* desc, void* stream);
+
 /* Dequantise rows of a (quantised) embedding table on the device: out[t,:] = table[tokens[t],:].
  * Same arithmetic as the host loop in reference src/model/transformer.cpp:419-599; Q5_K is zero-filled
  * exactly as the reference does (:595-598).  tokens is a DEVICE int array. */

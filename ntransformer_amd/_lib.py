@@ -127,6 +127,8 @@ def lib() -> C.CDLL:
         "ntk_debug_rp_prologue": (i, [vp, vp, vp, f, i, i, i, vp]),
         "ntk_debug_mfma_i8_probe": (i, [vp, vp, vp, vp]),
         "ntk_gemm_quant": (i, [vp, vp, vp, i, i, i, i, vp, vp]),
+        "ntk_gemm_dense16_workspace_bytes": (sz, [i, i, i]),
+        "ntk_gemm_dense16": (i, [C.POINTER(GemmDesc), vp]),
         "ntk_attention_decode_split": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_attention_split_scratch_bytes": (C.c_size_t, [i, i, i]),
         "ntk_attention_split_scratch_init": (i, [vp, i, vp]),

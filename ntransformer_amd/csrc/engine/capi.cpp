@@ -71,6 +71,11 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (v != "0" && v != "1") { E(e)->set_error("dense_fused must be 0 or 1"); return NTK_E_SHAPE; }
         return E(e)->model().set_dense_fused(on);
     }
+    else if (k == "dense_mfma16") {   // "1" (default) | "0": the prompt pass's F16 / BF16 matrices on the 16-bit matrix cores, or the F32-MFMA form; any time (the A/B switch)
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("dense_mfma16 must be 0 or 1"); return NTK_E_SHAPE; }
+        E(e)->model().set_dense_mfma16(on);
+    }
     else if (k == "persistent" || k == "fuse_attention") {   // accepted and without effect: the structures they selected were retired
         if (on) fprintf(stderr, "note: \"%s\" selected an experiment that lost to the fused launches and was removed (profiles/NEGATIVE_RESULTS.md); the option does nothing\n", key);
     }

@@ -258,6 +258,7 @@ public:
     // sequence both passes had before (ntk_rmsnorm / ntk_gemv / ntk_add per matrix; one GEMV per token and projection) -- the A/B switch.  Any time;
     // captured graphs are dropped when the setting changes.
     int set_dense_fused(bool on);
+    void set_dense_mfma16(bool on) { dense_mfma16_ = on; }   // F16 / BF16 matrices of the batched prompt pass: the 16-bit matrix cores (gemm_dense16.hip) or the F32-MFMA form; any time
     bool fusable(int dt) const;   // a matrix of this dtype goes out on the fused decode launches / the batched prompt GEMM
     void set_bf16_prefill(bool on) { bf16_prefill_ = on; }   // batched prompt: FP16-MFMA (gemm_f16.hip; the option keeps its round-2 name) or the F32-MFMA form (16)
     // which form decode_step_fused(…) emits at the current position: the fused launches of its attention regime
@@ -445,6 +446,7 @@ private:
     size_t gemm_ws_bytes_ = 0;
     bool bf16_prefill_ = true;
     bool dense_fused_ = true;
+    bool dense_mfma16_ = true;
     int repack_ = 3;                 // EFFECTIVE level: 0 raw path, 1 repack + raw resident, 2 repack only (one resident copy); 3 only before a load
     int repack_wanted_ = 3;          // the level as ASKED (3 = the default: resolves to 2 at load): re-evaluated by every load
     bool repack_done_ = false;       // repack_all() ran on the loaded tensors

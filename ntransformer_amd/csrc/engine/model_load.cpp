@@ -337,6 +337,12 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
                                  {H, 2 * I}, {H, I}, {I, H}};
         gemm_ws_bytes_ = 0;
         for (const auto& sh : shapes) gemm_ws_bytes_ = std::max(gemm_ws_bytes_, ntk_gemm_quant_workspace_bytes(sh[0], sh[1]));
+        // ... and the planes of the 16-bit GEMM where the model has an F16 / BF16 matrix (a quantised-only model: not a byte more)
+        auto dense16_need = [&](const DevTensor& t) {
+            if (is_dense16(t.dtype)) gemm_ws_bytes_ = std::max(gemm_ws_bytes_, ntk_gemm_dense16_workspace_bytes((int)t.in_f, (int)t.out_f, t.dtype));
+        };
+        for (const auto& L : layers_) for (auto m : kLayerMatrices) dense16_need(L.*m);
+        dense16_need(output_);
     }
     gemm_ws_ = dev_alloc(gemm_ws_bytes_, false);
     gemm_ws2_ = dev_alloc(gemm_ws_bytes_, false);

@@ -1,5 +1,6 @@
 // engine/model_prompt.cpp -- the prompt pass of one sequence: forward, its layer loop, the LM head, scoring; the steps every host-driven pass shares (see model.h)
 #include "model_impl.h"
+#include "../gemm_dense16_plan.h"   // (ntk::gd_worth: the token counts the 16-bit GEMM is measured to win at)
 
 namespace nt {
 
@@ -75,16 +76,19 @@ int Model::gemv_logged(float* y, const DevTensor& w, const void* wp, const float
 // The prompt pass's operand planes: the FP16 GEMM reads X split into FP16 planes, written into a workspace by its own pre-pass or by the launch that
 // produced X (ntk_*_prepare_x: the projection then needs no pre-pass launch at all).  Two workspaces are used alternately.  The invariant: a producer
 // never writes planes into the workspace whose partial sums it is reading -- a projection's deferred K splits lie in the workspace of its own planes, so
-// the producer that consumes them takes other().
+// the producer that consumes them takes other().  Planes come in two KINDS: the FP16 pieces the FP16 GEMM and the F16 matrices of the 16-bit GEMM read (what
+// every producer writes), and the three bfloat16 pieces of a BF16 matrix (ntk_gemm_dense16's own pre-pass only); a workspace holds one kind at a time.
 struct OperandPlanes {
+    enum Kind { fp16, bf16 };
     void* ws[2];
     int cur = 0;
     const float* of = nullptr;   // the X whose planes lie in ws[cur] (Q, K, V and gate, up share one X)
+    Kind kind = fp16;            // ... and which planes they are
     void* current() const { return ws[cur]; }
-    bool hold(const float* X) const { return X == of; }
+    bool hold(const float* X, Kind k = fp16) const { return X == of && k == kind; }
     void* other() { cur ^= 1; of = nullptr; return ws[cur]; }                // a producer is about to write planes: the workspace the last projection did NOT use
-    void written(const float* X, bool split) { of = split ? X : nullptr; }   // X has new contents: planes are stale unless its producer just split it
-    void in_current(const float* X) { of = X; }                              // a projection's pre-pass (or such a producer) has left X's planes in ws[cur]
+    void written(const float* X, bool split) { of = split ? X : nullptr; kind = fp16; }   // X has new contents: planes are stale unless its producer just split it
+    void in_current(const float* X, Kind k = fp16) { of = X; kind = k; }     // a projection's pre-pass (or such a producer) has left X's planes in ws[cur]
 };
 
 // the formats and shapes ntk_gemm_quant_f16 takes
@@ -94,6 +98,8 @@ static bool f16_ok(const DevTensor& w) {
 }
 // a K-quant matrix whose GGUF bytes were freed after the load-time repack (one resident copy): the FP16 GEMM reads it FROM THE REPACK
 // (ntk_gemm_desc.weights_repacked: identical bits) -- no unpack in front of the prompt launches
+// the 16-bit matrices and shapes ntk_gemm_dense16 takes
+static bool dense16_ok(const DevTensor& w) { return is_dense16(w.dtype) && w.in_f % 32 == 0 && w.out_f % 16 == 0 && w.ptr; }
 static bool rp_only(const DevTensor& w) {
     return !w.ptr && w.rp && (w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K) && w.out_f % 16 == 0;
 }
@@ -122,7 +128,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     // in the array that only ntk_rmsnorm_rowmax zeroes.
     enum class XForm { plain, row_max, split };
     auto x_form = [&](int width, const DevTensor& next_w) {
-        if (with_max && prefill_fused_split_ && gemm_ws2_ != nullptr && T <= 64 && tp_world_ == 1 && f16_ok(next_w) && (int)next_w.in_f == width) return XForm::split;
+        const bool f16_planes = f16_ok(next_w) || (dense_mfma16_ && fusable(next_w.dtype) && next_w.dtype == NTK_DT_F16 && dense16_ok(next_w) && ntk::gd_worth(T));   // (BF16 matrices read planes of their own kind)
+        if (with_max && prefill_fused_split_ && gemm_ws2_ != nullptr && T <= 64 && tp_world_ == 1 && f16_planes && (int)next_w.in_f == width) return XForm::split;
         return with_max ? XForm::row_max : XForm::plain;
     };
     // The FP16 GEMM behind its descriptor (ntk_engine.h): 1..3 matrices of one format sharing X, ONE launch.  `raw`: the matrices' GGUF bytes where the
@@ -144,6 +151,24 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         if (st == NTK_OK) planes.in_current(X);
         return st;
     };
+    // 1..3 F16 / BF16 matrices of one dtype sharing X on the 16-bit matrix cores (ntk_gemm_dense16), ONE launch; X's planes of that kind are reused when they
+    // lie in the current workspace, and lie there after the launch.  Option dense_mfma16 = 0, or fewer tokens than the form is measured to win at
+    // (gemm_dense16_plan.h: gd_worth): not taken (NTK_E_DTYPE), the caller runs the F32-MFMA form.
+    auto dense16_group = [&](float* const* Ys, const DevTensor* const* Ws, int n, const float* X, const float* resid) {
+        if (!dense_mfma16_ || !gemm_ws_ || !ntk::gd_worth(T)) return (int)NTK_E_DTYPE;
+        ntk_gemv_seg segs[3];
+        for (int k = 0; k < n; ++k) {
+            if (!dense16_ok(*Ws[k])) return (int)NTK_E_SHAPE;
+            segs[k] = {Ws[k]->ptr, Ys[k], (int)Ws[k]->out_f, Ws[k]->dtype};
+        }
+        const OperandPlanes::Kind kind = Ws[0]->dtype == NTK_DT_BF16 ? OperandPlanes::bf16 : OperandPlanes::fp16;
+        ntk_gemm_desc d{};
+        d.segs = segs; d.nseg = n; d.X = X; d.n_tokens = T; d.in_features = (int)Ws[0]->in_f; d.resid = resid;
+        d.workspace = planes.current(); d.workspace_bytes = gemm_ws_bytes_; d.reuse_x = planes.hold(X, kind) ? 1 : 0;
+        const int st = ntk_gemm_dense16(&d, s);
+        if (st == NTK_OK) planes.in_current(X, kind);
+        return st;
+    };
     // One quantised matrix on the FP16 matrix cores (up to 1024 tokens per pass): straight from the repack where it exists only there; otherwise, or when that form
     // is not taken, from its GGUF bytes -- *wp, obtained here for the caller's F32-MFMA / per-token fallbacks too (without the FP16 option: NTK_E_DTYPE, no launch).
     auto gemm_f16 = [&](float* Y, const DevTensor& w, const float* X, const float* resid, const float* rm, ntk_gemm_partials* pt, const void** wp) {
@@ -160,7 +185,11 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     // loop takes (NTK_E_ALIGN / NTK_E_SHAPE: nothing launched; *wp holds the GGUF bytes for it)
     auto gemm_mfma = [&](float* Y, const DevTensor& w, const float* X, const float* resid, const float* rm, const void** wp) {
         int st = NTK_E_DTYPE;
-        if (is_dense16(w.dtype)) { raw_begin(); *wp = raw_of(w); }   // 16-bit rows: the F32-MFMA form alone (the FP16 GEMM has no decoder for them)
+        if (is_dense16(w.dtype)) {   // 16-bit rows: the 16-bit matrix cores, else the F32-MFMA form (the FP16 GEMM has no decoder for them)
+            raw_begin(); *wp = raw_of(w);
+            const DevTensor* const one = &w;
+            st = dense16_group(&Y, &one, 1, X, resid);
+        }
         else st = gemm_f16(Y, w, X, resid, rm, nullptr, wp);
         if (not_taken(st)) st = ntk_gemm_quant(Y, *wp, X, T, (int)w.out_f, (int)w.in_f, w.dtype, resid, s);
         if (st == NTK_E_ALIGN || st == NTK_E_SHAPE) return false;
@@ -182,15 +211,17 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     // matrices that share X (Q | K | V, gate | up): those of one format go out as ONE launch of the FP16 GEMM, the rest one by one
     auto project_many = [&](float* const* Ys, const DevTensor* const* Ws, int n, const float* X, const float* rm) {
         bool done[3] = {false, false, false};
-        for (int a = 0; a < n && batched && bf16_now; ++a) {
+        for (int a = 0; a < n && batched && (bf16_now || is_dense16(Ws[a]->dtype)); ++a) {
             if (done[a]) continue;
+            const bool d16 = is_dense16(Ws[a]->dtype);
+            if (d16 ? !(fusable(Ws[a]->dtype) && dense_mfma16_) : !bf16_now) continue;
             float* ys[3];
             const DevTensor* ws[3];
             int idx[3], m = 0;
             for (int b = a; b < n; ++b)
                 if (!done[b] && Ws[b]->dtype == Ws[a]->dtype && Ws[b]->in_f == Ws[a]->in_f) { ys[m] = Ys[b]; ws[m] = Ws[b]; idx[m++] = b; }
             if (m < 2) continue;
-            const int st = gemm_group(ys, ws, m, X, nullptr, rm, nullptr, nullptr);
+            const int st = d16 ? dense16_group(ys, ws, m, X, nullptr) : gemm_group(ys, ws, m, X, nullptr, rm, nullptr, nullptr);
             if (st == NTK_OK) for (int k = 0; k < m; ++k) done[idx[k]] = true;
             else if (!not_taken(st)) { ok(st); return; }
         }
@@ -211,7 +242,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             return;
         }
         const bool dense = batched && (size_t)w.out_f == (size_t)H && xstride == (size_t)w.in_f;
-        if (dense && bf16_now) prepare_x(X, w);
+        if (dense && (bf16_now || is_dense16(w.dtype))) prepare_x(X, w);
         const void* wp = nullptr;   // (unused: project() below obtains the bytes again)
         if (dense && fusable(w.dtype) && gemm_mfma(hidden_, w, X, hidden_, rm, &wp)) return;
         project(residual_, w, X, H, xstride, rm);
@@ -411,6 +442,13 @@ int Model::lm_head(float* logits, const float* X, int n, const float* chunk_max)
         d.workspace = ws; d.workspace_bytes = ws_bytes; d.row_max = chunk_max; d.weights_repacked = repacked ? 1 : 0;
         d.full_form = 1;   // the same bits whatever the caller cuts the rows into (the form is otherwise chosen by the call's token count)
         st = ntk_gemm_quant_f16(&d, s);
+    }
+    if (batched && is_dense16(w.dtype) && dense_mfma16_ && ws && dense16_ok(w) && ntk::gd_worth(n)) {   // a 16-bit head over more than one row: the 16-bit matrix cores
+        const ntk_gemv_seg seg{w.ptr, logits, V, w.dtype};
+        ntk_gemm_desc d{};
+        d.segs = &seg; d.nseg = 1; d.X = X; d.n_tokens = n; d.in_features = H;
+        d.workspace = ws; d.workspace_bytes = ws_bytes;
+        st = ntk_gemm_dense16(&d, s);
     }
     if (batched && not_taken(st)) { raw_begin(); st = ntk_gemm_quant(logits, raw_of(w), X, n, V, H, w.dtype, nullptr, s); }
     if (batched && !not_taken(st)) return st;

@@ -299,6 +299,30 @@ def gemm_quant_f16_prepared(segs, X, n_tokens, in_features, resid=None, row_max=
     return call
 
 
+def gemm_dense16_workspace(in_features, rows, dtype) -> "DeviceBuffer":
+    """a workspace of ntk_gemm_dense16_workspace_bytes for F16 / BF16 matrices [rows][in_features]"""
+    n = int(_lib.lib().ntk_gemm_dense16_workspace_bytes(in_features, rows, int(dtype)))
+    if n == 0:
+        raise _lib.NtkError(-1, "ntk_gemm_dense16_workspace_bytes: not a 16-bit dtype")
+    return DeviceBuffer(n)
+
+
+def gemm_dense16(segs, X, n_tokens, in_features, resid=None, workspace=None, reuse_x=0, repacked=False, stream=None) -> int:
+    """ntk_gemm_dense16 (include/ntk_engine.h): segs = [(W, Y, rows, dtype), ...] F16 or BF16 matrices sharing X, on the 16-bit matrix cores.  Returns the
+    status (a refusal launches nothing); synchronises when the workspace is allocated here."""
+    ws = workspace if workspace is not None else DeviceBuffer(max(int(_lib.lib().ntk_gemm_dense16_workspace_bytes(in_features, sum(r for _, _, r, _ in segs), int(segs[0][3]))), 256))
+    arr = (GemvSeg * len(segs))()
+    for i, (W, y, rows, dt) in enumerate(segs):
+        arr[i].W, arr[i].y, arr[i].rows, arr[i].dtype = _p(W), _p(y), rows, int(dt)
+    d = _lib.GemmDesc()
+    d.segs, d.nseg, d.X, d.n_tokens, d.in_features, d.resid = arr, len(segs), _p(X), n_tokens, in_features, _p(resid)
+    d.workspace, d.workspace_bytes, d.reuse_x = _p(ws), ws.nbytes if isinstance(ws, DeviceBuffer) else (1 << 40), int(reuse_x)
+    d.weights_repacked = 1 if repacked else 0
+    st = _lib.lib().ntk_gemm_dense16(C.byref(d), stream)
+    synchronize()
+    return st
+
+
 def gemm_quant_ws_multi(segs, X, n_tokens, in_features, stream=None, repacked=False):
     """several matrices of one format sharing X as one launch of the FP16 GEMM: segs = [(W, Y, rows, dtype), ...]"""
     return _gemm_quant_f16(segs, X, n_tokens, in_features, stream=stream, repacked=repacked)

@@ -17,7 +17,7 @@ from ntransformer_amd.ops import DeviceBuffer as DB  # noqa: E402
 
 SHAPES = {"8b.q/o": (4096, 4096), "8b.kv": (1024, 4096), "8b.gate/up": (14336, 4096), "8b.down": (4096, 14336),
           "70b.q/o": (8192, 8192), "70b.gate/up": (28672, 8192), "70b.down": (8192, 28672)}
-GT = {"Q8_0": G.GGML_Q8_0, "Q4_K": G.GGML_Q4_K, "Q6_K": G.GGML_Q6_K, "F16": G.GGML_F16, "BF16": G.GGML_BF16}   # (F16 / BF16: the F32-MFMA form only)
+GT = {"Q8_0": G.GGML_Q8_0, "Q4_K": G.GGML_Q4_K, "Q6_K": G.GGML_Q6_K, "F16": G.GGML_F16, "BF16": G.GGML_BF16}   # (F16 / BF16 in the per-matrix table: the F32-MFMA form; the engine part: --ab-dense-mfma16)
 
 
 def timed(fn, reps):
@@ -47,6 +47,7 @@ def main():
     ap.add_argument("--layers", type=int, default=0, help="engine part: layers of the preset to build (0 = all)")
     ap.add_argument("--option", action="append", default=[], help="engine part: key=value engine options (e.g. prefill_fused_split=0)")
     ap.add_argument("--ab-rope-scaling", default="", help="engine part: a rope_scaling option value (e.g. llama3:8,1,4,8192): the prompt pass without and with it, two engines in this process, alternated, median of 3")
+    ap.add_argument("--ab-dense-mfma16", action="store_true", help="engine part, F16 / BF16 mixes: alternate dense_mfma16 = 1 / 0 three times per prompt length (the 16-bit matrix cores against the F32-MFMA form of the same tree), medians; then decode tokens/s once with each setting")
     ap.add_argument("--bf16-only", action="store_true", help="per-matrix table: only the FP16 GEMM launches (profiling; the flag keeps its round-2 name)")
     a = ap.parse_args()
     ops.init(0)
@@ -128,6 +129,23 @@ def main():
                         print("8B %s prompt of %4d tokens, FP16 GEMM, prefill_row_max=%d (rep %d): %9.2f ms = %9.1f tokens/s" % (a.mix, T, rm, rep, dt_ * 1e3, T / dt_), flush=True)
                 eng.set_option("prefill_row_max", 1)
                 continue
+            if a.ab_dense_mfma16:
+                eng.set_option("batched_prefill", 1); eng.set_option("bf16_prefill", 1)
+                ts = {1: [], 0: []}
+                for on in (1, 0):
+                    eng.set_option("dense_mfma16", on); eng.forward(prompt, 0)      # (warm-up of both forms)
+                for rep in range(3):
+                    for on in (1, 0):
+                        eng.set_option("dense_mfma16", on)
+                        t0 = time.perf_counter(); eng.forward(prompt, 0); ts[on].append(time.perf_counter() - t0)
+                med = {on: sorted(ts[on])[1] for on in ts}
+                res["engine"].append({"mix": a.mix, "prompt_tokens": T, "dense_mfma16_ms": {str(on): [round(t * 1e3, 2) for t in ts[on]] for on in ts}})
+                print("%s %s prompt of %4d tokens: dense_mfma16=1 %9.2f ms [%s]   dense_mfma16=0 %9.2f ms [%s]   x %.2f" %
+                      (a.model.upper(), a.mix, T, med[1] * 1e3, " ".join("%.2f" % (t * 1e3) for t in ts[1]), med[0] * 1e3,
+                       " ".join("%.2f" % (t * 1e3) for t in ts[0]), med[0] / med[1]), flush=True)
+                print("    shader clock right behind these runs: %.0f MHz" % ops.sclk_mhz(), flush=True)
+                eng.set_option("dense_mfma16", 1)
+                continue
             for batched in modes:   # 2: FP16 MFMA, 64-token chunks; 1: F32 MFMA, 16 per pass; 0: the reference's per-token loop
                 eng.set_option("batched_prefill", batched > 0)
                 eng.set_option("bf16_prefill", batched == 2)
@@ -138,6 +156,16 @@ def main():
                 dt_ = sorted(ts)[len(ts) // 2]
                 res["engine"].append({"mix": a.mix, "prompt_tokens": T, "batched": batched, "ms": round(dt_ * 1e3, 2), "tok_s": round(T / dt_, 1)})
                 print("%s %s prompt of %4d tokens, batched_prefill=%d: %9.2f ms = %9.1f tokens/s" % (a.model.upper(), a.mix, T, batched, dt_ * 1e3, T / dt_), flush=True)
+        if a.ab_dense_mfma16:   # the decode path does not read the option: tokens/s of 64 graph-replayed steps behind a 16-token prompt, once per setting
+            for on in (1, 0):
+                eng.set_option("dense_mfma16", on)
+                eng.forward(prompt[:16], 0)
+                for i in range(8): eng.decode_fused(5, 16 + i, True)
+                t0 = time.perf_counter()
+                for i in range(64): eng.decode_fused(5, 24 + i, True)
+                dt_ = (time.perf_counter() - t0) / 64
+                print("%s %s decode, dense_mfma16=%d: %.1f tokens/s (%.3f ms per token)" % (a.model.upper(), a.mix, on, 1.0 / dt_, dt_ * 1e3), flush=True)
+            eng.set_option("dense_mfma16", 1)
         eng.close()
     if a.json: json.dump(res, open(a.json, "w"), indent=1)
 
