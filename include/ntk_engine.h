@@ -479,6 +479,14 @@ void ntk_debug_malloc_budget(long long bytes);
 /* *d_pos += 1 (one thread); keeps positions on the device across graph replays */
 int ntk_advance_pos(int* d_pos, void* stream);
 
+/* The Q | K | V projection bias of Qwen2-family models (csrc/qkv_bias.hip), in place and in ONE launch for the three buffers and all rows:
+ * q[r][c] += bq[c] (q: [n_rows][q_dim], contiguous), k[r][c] += bk[c], v[r][c] += bv[c] (k, v: [n_rows][kv_dim]).  Every element is one F32 add.
+ * A bias pointer may be NULL: that buffer is left untouched (and need not exist); all three NULL: NTK_OK, nothing launched.  A buffer is walked in
+ * 16-byte pieces when its base and bias are 16-byte aligned and its dimension is a multiple of 4, element by element otherwise: no alignment is
+ * assumed.  NTK_E_NULL: a bias without its buffer; NTK_E_SHAPE: n_rows < 0 or a dimension <= 0, or a row of more than 65535 x 256 work items over
+ * the three buffers (a work item is one 16-byte piece or one element: 16.7 M elements per row at the least); n_rows == 0: NTK_OK, nothing launched. */
+int ntk_qkv_bias(float* q, float* k, float* v, const float* bq, const float* bk, const float* bv, int n_rows, int q_dim, int kv_dim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

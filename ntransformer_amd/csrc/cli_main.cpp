@@ -42,7 +42,7 @@ static void usage(const char* prog) {
             "  --rope-freq-scale <float> RoPE linear position scale, overriding the model's\n"
             "  --context-shift          At the end of the context drop half of the oldest positions and go on (default: stop there)\n"
             "  --keep <int>             Leading positions a context shift never drops (default: 1, the BOS)\n"
-            "  --synthetic <shape:mix>  8b|70b|tiny : Q8_0|Q4_K_M|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
+            "  --synthetic <shape:mix>  8b|70b|tiny|qwen2.5-7b : Q8_0|Q4_K_M|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
             "Accepted for CLI compatibility, no effect on the output (weights are always resident in 288 GB HBM;\n"
             "speculative decoding only changes speed, and plain decode is what runs):\n"
             "  --streaming --draft-model <p> --draft-k <n> --self-spec\n"
@@ -162,6 +162,11 @@ int main(int argc, char** argv) {
         if (c != std::string::npos) s.mix = synthetic.substr(c + 1);
         if (shape == "70b") { s.hidden = 8192; s.inter = 28672; s.layers = 80; s.heads = 64; }
         else if (shape == "tiny") { s.hidden = 256; s.inter = 512; s.layers = 2; s.heads = 4; s.kv_heads = 2; s.vocab = 512; s.bos = 256; s.eos = 257; s.ctx = 256; }
+        else if (shape == "qwen2.5-7b" || shape == "qwen2.5-7b-nobias") {   // Qwen2.5-7B's geometry with a tied head; -nobias: the same model without the three bias vectors (the A/B twin)
+            s.hidden = 3584; s.inter = 18944; s.layers = 28; s.heads = 28; s.kv_heads = 4; s.vocab = 152064; s.ctx = 32768;
+            s.eps = 1e-6f; s.theta = 1e6f; s.bos = 151643; s.eos = 151645;
+            s.mix = (shape == "qwen2.5-7b" ? "qwen2-tied:" : "tied:") + s.mix;
+        }
         else if (shape != "8b") { fprintf(stderr, "unknown synthetic shape %s\n", shape.c_str()); return 1; }
         st = engine.load_synthetic(s, max_context);
     } else {

@@ -35,6 +35,8 @@ struct PassStatus;   // model_impl.h
 
 struct LayerWeights {
     DevTensor attn_norm, wq, wk, wv, wo, ffn_norm, w_gate, w_up, w_down;
+    DevTensor bq, bk, bv;   // the Q | K | V projection biases of a Qwen2-family file (F32 [out]; each optional: ptr == nullptr without one)
+    bool has_qkv_bias() const { return bq.ptr || bk.ptr || bv.ptr; }
 };
 // the seven projection matrices of a layer, for whoever visits them all: for (auto m : kLayerMatrices) use(L.*m);
 inline constexpr std::array<DevTensor LayerWeights::*, 7> kLayerMatrices = {&LayerWeights::wq, &LayerWeights::wk, &LayerWeights::wv, &LayerWeights::wo,
@@ -221,6 +223,12 @@ public:
     int set_rope_freq_base(const std::string& text);
     int set_rope_freq_scale(const std::string& text);
     int rope_factor_count() const { return (int)rope_factors_.size(); }
+    // Q | K | V projection biases (blk.N.attn_{q,k,v}.bias; Qwen2, optional under any architecture): each F32 with one value per output row, a rank's
+    // slice under tensor parallelism.  A layer that carries one gets ONE more launch behind its Q | K | V projection in both layer loops (ntk_qkv_bias:
+    // layers_1to1 ahead of the KV capture, enqueue_layers as a node of the captured graph); a layer without issues the launches it always has.
+    // Refused at load, ahead of the device and naming the tensor: a bias of another type or size, and the tensors the engine would silently ignore
+    // (attn_q_norm / attn_k_norm.weight, attn_output.bias, ffn_gate / ffn_up / ffn_down.bias).
+    int qkv_bias_layers() const { int n = 0; for (const auto& L : layers_) n += L.has_qkv_bias() ? 1 : 0; return n; }
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
     uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included
@@ -291,6 +299,7 @@ private:
     int load_impl(const std::string& gguf_path, int max_context);
     int finish_load();
     int resolve_rope(const GgufFile* f);   // the rope options + the file (null: synthetic) -> cfg_.rope_theta / rope_freq_scale / rope_scaling_type / rope_orig_ctx / rope_factors, rope_factors_
+    int check_layer_extras(const GgufFile& f);   // the bias tensors' type and size, and the per-layer tensors the engine has no kernel for: refusals that name the tensor
     int init_device();               // the GPU NTK_DEVICE names (default 0)
     int own_stream();                 // a private non-blocking stream: sequences and ranks that share a process must not queue behind each other
     int alloc_buffers();

@@ -143,6 +143,11 @@ int Model::enqueue_layers(int first, int last_layer) {
         const DevTensor* const qkv[3] = {&L.wq, &L.wk, &L.wv};
         float* const qkv_out[3] = {act.q, act.k, act.v};
         NT_TRY(decode_project(qkv, qkv_out, 3, hidden1_, &L.attn_norm, nullptr, 1));
+        if (L.has_qkv_bias()) {   // a Qwen2 layer: its projection biases, one launch (a node of the captured token); a layer without: nothing
+            prof_mark(2, true);
+            NT_TRY(ntk_qkv_bias(act.q, act.k, act.v, (const float*)L.bq.ptr, (const float*)L.bk.ptr, (const float*)L.bv.ptr, 1, nh * hd, nkv * hd, s));
+            prof_mark(2, false);
+        }
         prof_mark(1, true);
         if (kv_q8_)
             NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, kv_.k(0, i), kv_.v(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,

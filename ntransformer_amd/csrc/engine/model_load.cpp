@@ -55,6 +55,36 @@ static const struct { const char* name; DevTensor LayerWeights::* member; Shard 
     {"ffn_up.weight", &LayerWeights::w_up, ROWS, 'h', 'i'},
     {"ffn_down.weight", &LayerWeights::w_down, COLS, 'i', 'h'},
 };
+// ... and the optional ones, "blk.<i>.<name>": the Q | K | V projection biases (Qwen2; llama.cpp takes them under `llama` too) -- F32, one value per output
+// row, so a rank's whole heads are a contiguous slice (ROWS)
+static const struct { const char* name; DevTensor LayerWeights::* member; char out; } kLayerBiases[] = {
+    {"attn_q.bias", &LayerWeights::bq, 'q'},
+    {"attn_k.bias", &LayerWeights::bk, 'k'},
+    {"attn_v.bias", &LayerWeights::bv, 'k'},
+};
+// per-layer tensors of neighbouring architectures that this engine has no kernel for: a file that carries one is refused rather than run without it
+static const char* const kLayerUnsupported[] = {"attn_q_norm.weight", "attn_k_norm.weight", "attn_output.bias", "ffn_gate.bias", "ffn_up.bias", "ffn_down.bias"};
+
+int Model::check_layer_extras(const GgufFile& f) {
+    const int64_t qd = (int64_t)cfg_.n_heads * cfg_.head_dim, kvd = (int64_t)cfg_.n_kv_heads * cfg_.head_dim;
+    for (const GgufTensor& t : f.tensors()) {   // every "blk.<i>.<name>" of the file, whatever its index: a tensor behind the last layer is not passed over either
+        int li = -1, at = 0;
+        if (sscanf(t.name.c_str(), "blk.%d.%n", &li, &at) != 1 || at == 0) continue;
+        const char* const rest = t.name.c_str() + at;
+        for (const char* u : kLayerUnsupported)
+            if (strcmp(rest, u) == 0) { err_ = "Unsupported tensor " + t.name + ": this engine runs Llama and Qwen2 layers (no per-head Q/K norm, no output or FFN bias)"; return NTK_E_FORMAT; }
+        for (const auto& e : kLayerBiases) {
+            if (strcmp(rest, e.name) != 0) continue;
+            const int64_t want = e.out == 'q' ? qd : kvd;
+            if (t.dtype != NTK_DT_F32 || !t.known_type) { err_ = t.name + " must be F32"; return NTK_E_DTYPE; }
+            if (t.numel() != want) {
+                err_ = t.name + " holds " + std::to_string(t.numel()) + " values, " + std::to_string(want) + " (one per output row) are needed";
+                return NTK_E_SHAPE;
+            }
+        }
+    }
+    return NTK_OK;
+}
 
 int Model::load(const std::string& path, int max_context) {
     const int st = load_impl(path, max_context);
@@ -75,6 +105,8 @@ int Model::load_impl(const std::string& path, int max_context) {
         cfg_.max_seq_len = max_context;
     }
     st = resolve_rope(&f);   // (before anything is allocated: a bad rope_freqs.weight refuses the load)
+    if (st != NTK_OK) { fprintf(stderr, "%s\n", err_.c_str()); return st; }
+    st = check_layer_extras(f);   // (likewise: a bias of the wrong type or size, a tensor the layer loop would ignore)
     if (st != NTK_OK) { fprintf(stderr, "%s\n", err_.c_str()); return st; }
     cfg_.print();
     f.print_info();
@@ -105,8 +137,18 @@ int Model::load_impl(const std::string& path, int max_context) {
         output_tied_ = true;
     }
     NT_TRY(take("output_norm.weight"));
-    for (int i = 0; i < cfg_.n_layers; ++i)   // transformer.cpp:286-328
+    for (int i = 0; i < cfg_.n_layers; ++i) {   // transformer.cpp:286-328
         for (const auto& e : kLayerTensors) NT_TRY(take("blk." + std::to_string(i) + "." + e.name));
+        // the optional biases.  take()'s checks do not run here: check_layer_extras() -- called above, ahead of the device -- has held every bias of the
+        // file to F32 and to its slot's element count, and a loader that gets here another way must do the same before it uploads one
+        for (const auto& e : kLayerBiases) {
+            const std::string name = "blk." + std::to_string(i) + "." + e.name;
+            const GgufTensor* t = f.find(name);
+            TensorSlot sl;
+            if (!t || !slot_of(name, &sl)) continue;
+            NT_TRY(upload_shard(*sl.dst, f.data(*t), t->dtype, sl.in_f, sl.out_f, t->nbytes, sl.how));
+        }
+    }
     return finish_load();
 }
 
@@ -120,6 +162,8 @@ bool Model::slot_of(const std::string& name, TensorSlot* sl) {
     if (sscanf(name.c_str(), "blk.%d.%n", &li, &at) != 1 || at == 0 || li < 0 || li >= (int)layers_.size()) return false;
     for (const auto& e : kLayerTensors)
         if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), e.how, extent(e.in), extent(e.out)}; return true; }
+    for (const auto& e : kLayerBiases)   // [out] values: `out` rows of one element
+        if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), ROWS, 1, extent(e.out)}; return true; }
     return false;
 }
 
@@ -129,6 +173,7 @@ int Model::load_synthetic(const SynthSpec& spec, int max_context, int nthreads) 
     if (!synth_plan(spec, plan)) { err_ = "bad synthetic spec"; return NTK_E_SHAPE; }
     cfg_ = ModelConfig();
     cfg_.model_name = "synthetic-" + spec.mix;
+    if (synth_flavour(spec.mix).qwen2) cfg_.architecture = "qwen2";
     cfg_.vocab_size = spec.vocab; cfg_.hidden_size = spec.hidden; cfg_.intermediate_size = spec.inter;
     cfg_.n_layers = spec.layers; cfg_.n_heads = spec.heads; cfg_.n_kv_heads = spec.kv_heads;
     cfg_.head_dim = spec.hidden / spec.heads;
@@ -154,6 +199,10 @@ int Model::load_synthetic(const SynthSpec& spec, int max_context, int nthreads) 
         if (rc != NTK_OK) break;
     }
     nt_hip_free_host(stage);
+    if (rc == NTK_OK && !output_.ptr) {   // a plan without output.weight (the Qwen2 flavour's tied head): as load_impl
+        output_ = token_embd_;
+        output_tied_ = true;
+    }
     if (rc == NTK_OK) rc = finish_load();
     if (rc != NTK_OK) free_all();
     return rc;

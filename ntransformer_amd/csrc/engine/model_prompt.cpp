@@ -308,6 +308,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         float* const qkv_out[3] = {act.q, act.k, act.v};
         const DevTensor* const qkv[3] = {&L.wq, &L.wk, &L.wv};
         project_many(qkv_out, qkv, 3, residual_, rm_a);
+        // a Qwen2 layer's projection biases: one launch over the T rows of q | k | v, ahead of the capture and the rotation (a layer without: no launch)
+        if (L.has_qkv_bias()) ok(ntk_qkv_bias(act.q, act.k, act.v, (const float*)L.bq.ptr, (const float*)L.bk.ptr, (const float*)L.bv.ptr, T, qd, kvd, s));
         if (i == kv_capture_layer_ && kv_capture_) {   // parity instrumentation: the F32 projections the store launches are about to read
             ok(ntk_copy(kv_capture_, act.k, T * kvd, s));
             ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));

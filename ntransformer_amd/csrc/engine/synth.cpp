@@ -147,13 +147,21 @@ static bool parse_layer_sample(const std::string& mix, int layers, int& of, std:
     return true;
 }
 
+SynthFlavour synth_flavour(const std::string& mix) {
+    if (mix.compare(0, 6, "qwen2:") == 0) return {true, false, mix.substr(6)};
+    if (mix.compare(0, 11, "qwen2-tied:") == 0) return {true, true, mix.substr(11)};
+    if (mix.compare(0, 5, "tied:") == 0) return {false, true, mix.substr(5)};
+    return {false, false, mix};
+}
+
 bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     out.clear();
     int sample_of = 0;
     std::vector<int> sample;
-    if (!parse_layer_sample(s.mix, s.layers, sample_of, sample)) return false;
-    const bool km = s.mix == "Q4_K_M" || sample_of > 0;
-    const int base = km ? 12 : mix_type(s.mix);
+    const SynthFlavour fl = synth_flavour(s.mix);
+    if (!parse_layer_sample(fl.mix, s.layers, sample_of, sample)) return false;
+    const bool km = fl.mix == "Q4_K_M" || sample_of > 0;
+    const int base = km ? 12 : mix_type(fl.mix);
     if (base < 0 || s.heads <= 0 || s.kv_heads <= 0 || s.hidden % s.heads) return false;
     const int hd = s.hidden / s.heads;
     const int64_t q_dim = (int64_t)s.heads * hd, kv_dim = (int64_t)s.kv_heads * hd;
@@ -172,6 +180,11 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
         add(p + "attn_q.weight", base, s.hidden, q_dim, 1);
         add(p + "attn_k.weight", base, s.hidden, kv_dim, 1);
         add(p + "attn_v.weight", v_t, s.hidden, kv_dim, 1);
+        if (fl.qwen2) {   // the projection biases: F32 [out], values of the size of the projections' own outputs
+            add(p + "attn_q.bias", 0, 1, q_dim, 0.5);
+            add(p + "attn_k.bias", 0, 1, kv_dim, 0.5);
+            add(p + "attn_v.bias", 0, 1, kv_dim, 0.5);
+        }
         add(p + "attn_output.weight", base, q_dim, s.hidden, 1);
         add(p + "ffn_norm.weight", 0, s.hidden, 1, 0);
         add(p + "ffn_gate.weight", base, s.hidden, s.inter, 1);
@@ -179,7 +192,7 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
         add(p + "ffn_down.weight", down_t, s.inter, s.hidden, 1);
     }
     add("output_norm.weight", 0, s.hidden, 1, 0);
-    add("output.weight", km ? 14 : base, s.hidden, s.vocab, 2.0);
+    if (!fl.tied) add("output.weight", km ? 14 : base, s.hidden, s.vocab, 2.0);
     return true;
 }
 
@@ -253,18 +266,20 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
     auto kv_f32 = [&](const char* k, float v) { str(k); u32(6); f32(v); };
     auto kv_str = [&](const char* k, const std::string& v) { str(k); u32(8); str(v); };
     u32(0x46554747u); u32(3); u64(plan.size()); u64(16);
-    kv_str("general.architecture", "llama");
+    const std::string arch = synth_flavour(s.mix).qwen2 ? "qwen2" : "llama";   // (the hyper-parameters live under the architecture's own prefix)
+    const auto key = [&](const char* k) { return arch + "." + k; };
+    kv_str("general.architecture", arch);
     kv_str("general.name", "synthetic-" + s.mix);
     kv_u32("general.alignment", 32);
-    kv_u32("llama.vocab_size", (uint32_t)s.vocab);
-    kv_u32("llama.embedding_length", (uint32_t)s.hidden);
-    kv_u32("llama.feed_forward_length", (uint32_t)s.inter);
-    kv_u32("llama.block_count", (uint32_t)s.layers);
-    kv_u32("llama.attention.head_count", (uint32_t)s.heads);
-    kv_u32("llama.attention.head_count_kv", (uint32_t)s.kv_heads);
-    kv_u32("llama.context_length", (uint32_t)s.ctx);
-    kv_f32("llama.attention.layer_norm_rms_epsilon", s.eps);
-    kv_f32("llama.rope.freq_base", s.theta);
+    kv_u32(key("vocab_size").c_str(), (uint32_t)s.vocab);
+    kv_u32(key("embedding_length").c_str(), (uint32_t)s.hidden);
+    kv_u32(key("feed_forward_length").c_str(), (uint32_t)s.inter);
+    kv_u32(key("block_count").c_str(), (uint32_t)s.layers);
+    kv_u32(key("attention.head_count").c_str(), (uint32_t)s.heads);
+    kv_u32(key("attention.head_count_kv").c_str(), (uint32_t)s.kv_heads);
+    kv_u32(key("context_length").c_str(), (uint32_t)s.ctx);
+    kv_f32(key("attention.layer_norm_rms_epsilon").c_str(), s.eps);
+    kv_f32(key("rope.freq_base").c_str(), s.theta);
     str("tokenizer.ggml.tokens"); u32(9); u32(8); u64(toks.size());
     for (const auto& t : toks) str(t);
     str("tokenizer.ggml.token_type"); u32(9); u32(5); u64(types.size());
@@ -275,6 +290,7 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
     for (const auto& t : plan) {
         str(t.name);
         if (t.out_f == 1 && t.sigma == 0) { u32(1); u64((uint64_t)t.in_f); }
+        else if (t.in_f == 1) { u32(1); u64((uint64_t)t.out_f); }   // a bias vector
         else { u32(2); u64((uint64_t)t.in_f); u64((uint64_t)t.out_f); }
         u32((uint32_t)t.ggml_type);
         u64(off);

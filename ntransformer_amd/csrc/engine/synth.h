@@ -13,7 +13,7 @@ namespace nt {
 struct SynthTensor {
     std::string name;
     int ggml_type;
-    int64_t in_f, out_f;   // vectors: in_f = n, out_f = 1
+    int64_t in_f, out_f;   // norm vectors: in_f = n, out_f = 1; bias vectors: in_f = 1, out_f = n
     double sigma;
     size_t nbytes;
 };
@@ -23,11 +23,17 @@ struct SynthSpec {
     int ctx = 131072;
     float eps = 1e-5f, theta = 500000.0f;
     int bos = 128000, eos = 128009;
-    std::string mix = "Q8_0";   // Q8_0 | Q4_0 | Q4_K | Q5_K | Q6_K | F16 | F32 | Q4_K_M
+    std::string mix = "Q8_0";   // Q8_0 | Q4_0 | Q4_K | Q5_K | Q6_K | F16 | F32 | Q4_K_M, optionally behind a flavour prefix (synth_flavour)
     uint64_t seed = 20260925;
 };
 
-// tensor list in file order (token_embd, per-layer 9 tensors, output_norm, output); false if `mix` is unknown
+// The architecture flavour rides in front of the mix (nt_synth_spec keeps its layout): "qwen2:<mix>" = a Qwen2 model -- architecture string and
+// hyper-parameter keys "qwen2", three F32 bias vectors per layer (blk.N.attn_{q,k,v}.bias, behind attn_v.weight, seeded like every other tensor);
+// "qwen2-tied:<mix>" = the same without output.weight (the LM head is token_embd.weight); "tied:<mix>" = the Llama model without output.weight (the
+// bias-free twin of a tied Qwen2 model).  No prefix: the Llama model.
+struct SynthFlavour { bool qwen2, tied; std::string mix; };
+SynthFlavour synth_flavour(const std::string& mix);
+// tensor list in file order (token_embd, per-layer 9 tensors -- 12 in the Qwen2 flavour --, output_norm, output); false if `mix` is unknown
 bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out);
 // deterministic in (seed, name, element index); multi-threaded
 void synth_fill(void* dst, const SynthTensor& t, uint64_t seed, int nthreads);

@@ -33,6 +33,11 @@ PRESETS = {
     "small": dict(hidden=1024, inter=2048, layers=4, heads=8, kv_heads=2, vocab=2048, ctx=2048, bos=256, eos=257),
     "8b": dict(hidden=4096, inter=14336, layers=32, heads=32, kv_heads=8, vocab=128256, ctx=131072, bos=128000, eos=128009),
     "70b": dict(hidden=8192, inter=28672, layers=80, heads=64, kv_heads=8, vocab=128256, ctx=131072, bos=128000, eos=128009),
+    # Qwen2.5-7B's geometry with a tied head; the flavour rides in front of the mix (csrc/engine/synth.h: synth_flavour): three F32 bias vectors per layer
+    "qwen2.5-7b": dict(hidden=3584, inter=18944, layers=28, heads=28, kv_heads=4, vocab=152064, ctx=32768, bos=151643, eos=151645, eps=1e-6, theta=1e6,
+                       flavour="qwen2-tied"),
+    "qwen2.5-7b-nobias": dict(hidden=3584, inter=18944, layers=28, heads=28, kv_heads=4, vocab=152064, ctx=32768, bos=151643, eos=151645, eps=1e-6, theta=1e6,
+                              flavour="tied"),   # its bias-free twin (the A/B of tools/prefill_bench.py --ab-qkv-bias)
 }
 
 
@@ -40,7 +45,9 @@ def synth_spec(preset: str, mix: str = "Q8_0", seed: int = 20260925, layers: Opt
     p = dict(PRESETS[preset])
     if layers is not None:
         p["layers"] = layers
-    return SynthSpec(p["hidden"], p["inter"], p["layers"], p["heads"], p["kv_heads"], p["vocab"], p["ctx"], 1e-5, 500000.0,
+    if p.get("flavour"):
+        mix = p["flavour"] + ":" + mix
+    return SynthSpec(p["hidden"], p["inter"], p["layers"], p["heads"], p["kv_heads"], p["vocab"], p["ctx"], p.get("eps", 1e-5), p.get("theta", 500000.0),
                      p["bos"], p["eos"], mix.encode(), seed)
 
 
@@ -122,6 +129,7 @@ def _bind():
     L.nt_rope_build_table.argtypes = [i, f, vp, vp]
     L.nt_engine_rope_info.argtypes = [vp, C.c_char_p, i]
     L.nt_gguf_describe.argtypes = [C.c_char_p, C.c_char_p, i]
+    L.nt_engine_qkv_bias.argtypes = [vp]
     L._engine_bound = True
     return L
 
@@ -217,6 +225,11 @@ class Engine:
     def rope_factors(self) -> int: return int(self.rope_info()["rope_factors"])
     @property
     def rope_orig_ctx(self) -> int: return int(self.rope_info()["rope_orig_ctx"])
+
+    @property
+    def qkv_bias(self) -> int:
+        """in how many layers the loaded model adds a Q | K | V projection bias (nt_engine_qkv_bias): 0 for a Llama model"""
+        return int(self.L.nt_engine_qkv_bias(self.h))
 
     @property
     def vocab_size(self): return self.L.nt_engine_vocab_size(self.h)

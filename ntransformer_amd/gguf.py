@@ -397,6 +397,11 @@ TINY = LlamaShape("tiny", 256, 512, 2, 4, 2, 512, ctx=256, bos=256, eos=257)
 SMALL = LlamaShape("small", 1024, 2048, 4, 8, 2, 2048, ctx=2048, bos=256, eos=257)       # hd=128, GQA 4
 LLAMA_8B = LlamaShape("llama3.1-8b", 4096, 14336, 32, 32, 8, 128256, bos=128000, eos=128009)
 LLAMA_70B = LlamaShape("llama3.1-70b", 8192, 28672, 80, 64, 8, 128256, bos=128000, eos=128009)
+# Qwen2 (make_synthetic_llama(..., arch="qwen2", qkv_bias=<scale>)): the published geometry, and the two-layer shapes of the engine tests
+QWEN25_7B = LlamaShape("qwen2.5-7b", 3584, 18944, 28, 28, 4, 152064, ctx=32768, eps=1e-6, theta=1e6, bos=151643, eos=151645)
+QWEN_T64 = LlamaShape("qt64", 256, 512, 2, 4, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)        # the TINY shape: head_dim 64
+QWEN_T128 = LlamaShape("qt128", 256, 512, 2, 2, 1, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)      # head_dim 128
+QWEN_7 = LlamaShape("q7", 1792, 512, 2, 14, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)          # head_dim 128, 7 query heads per KV head (Qwen2.5-7B's ratio)
 
 
 def use_more_bits(i: int, n: int) -> bool:
@@ -501,8 +506,13 @@ def llama3_rope_factors(head_dim: int, theta: float, factor: float = 8.0, low_fr
 
 def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: int = 20260925,
                          with_scores: bool = False, overrides: Optional[Dict[str, str]] = None,
-                         rope_freqs: Optional[np.ndarray] = None, rope_scaling: Optional[Dict[str, object]] = None) -> Dict[str, int]:
+                         rope_freqs: Optional[np.ndarray] = None, rope_scaling: Optional[Dict[str, object]] = None,
+                         arch: str = "llama", qkv_bias=None, tied: bool = False, extra_tensors: Sequence[TensorSpec] = ()) -> Dict[str, int]:
     """Write a seeded synthetic Llama-architecture GGUF; returns {tensor name: ggml type}.
+    arch: general.architecture and the prefix of the hyper-parameter keys ("llama", "qwen2").  qkv_bias: None (no bias tensors) or the scale of the
+    seeded blk.N.attn_{q,k,v}.bias vectors (F32 [out], normal values times the scale, written behind attn_v.weight as llama.cpp's converter orders them);
+    a dict {"q": s, "k": s, "v": s} writes only the named ones.  tied: no output.weight (the LM head is token_embd.weight).  extra_tensors: appended as
+    given (the loader's refusals: a bias of another type or size, tensors of architectures the engine does not run).
     overrides: per-matrix types on top of the mix, in every layer ({"ffn_up": "Q4_K"}).
     rope_freqs: the per-pair frequency divisors, appended as the tensor rope_freqs.weight (float32; a float16 array is written as F16, any length is
     written as given: the loader's refusals).  rope_scaling: {"type": "linear" | "yarn" | ..., "factor": F, "original_context_length": N,
@@ -538,28 +548,36 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
     for i in range(shape.layers):
         p = "blk.%d." % i
         specs.append(TensorSpec(p + "attn_norm.weight", (shape.hidden,), GGML_F32, norm_w(p + "attn_norm.weight")))
-        for m in ("attn_q", "attn_k", "attn_v", "attn_output"):
+        for m in ("attn_q", "attn_k", "attn_v"):
             mat(p + m + ".weight", *dims[m])
+        for m, key in (("attn_q", "q"), ("attn_k", "k"), ("attn_v", "v")):
+            scale = qkv_bias.get(key) if isinstance(qkv_bias, dict) else qkv_bias
+            if scale is not None:
+                name = p + m + ".bias"
+                specs.append(TensorSpec(name, (dims[m][1],), GGML_F32, (float(scale) * rng_for(name).standard_normal(dims[m][1])).astype("<f4").tobytes()))
+        mat(p + "attn_output.weight", *dims["attn_output"])
         specs.append(TensorSpec(p + "ffn_norm.weight", (shape.hidden,), GGML_F32, norm_w(p + "ffn_norm.weight")))
         for m in ("ffn_gate", "ffn_up", "ffn_down"):
             mat(p + m + ".weight", *dims[m])
     specs.append(TensorSpec("output_norm.weight", (shape.hidden,), GGML_F32, norm_w("output_norm.weight")))
-    mat("output.weight", shape.hidden, shape.vocab, sigma=2.0)
+    if not tied:
+        mat("output.weight", shape.hidden, shape.vocab, sigma=2.0)
+    specs.extend(extra_tensors)
 
     toks, ttypes = synth_vocab(shape, np.random.Generator(np.random.Philox(key=[seed, 7])))
     kvs = [
-        kv_str("general.architecture", "llama"),
+        kv_str("general.architecture", arch),
         kv_str("general.name", "synthetic-%s-%s" % (shape.name, mix)),
         kv_u32("general.alignment", 32),
-        kv_u32("llama.vocab_size", shape.vocab),
-        kv_u32("llama.embedding_length", shape.hidden),
-        kv_u32("llama.feed_forward_length", shape.inter),
-        kv_u32("llama.block_count", shape.layers),
-        kv_u32("llama.attention.head_count", shape.heads),
-        kv_u32("llama.attention.head_count_kv", shape.kv_heads),
-        kv_u32("llama.context_length", shape.ctx),
-        kv_f32("llama.attention.layer_norm_rms_epsilon", shape.eps),
-        kv_f32("llama.rope.freq_base", shape.theta),
+        kv_u32(arch + ".vocab_size", shape.vocab),
+        kv_u32(arch + ".embedding_length", shape.hidden),
+        kv_u32(arch + ".feed_forward_length", shape.inter),
+        kv_u32(arch + ".block_count", shape.layers),
+        kv_u32(arch + ".attention.head_count", shape.heads),
+        kv_u32(arch + ".attention.head_count_kv", shape.kv_heads),
+        kv_u32(arch + ".context_length", shape.ctx),
+        kv_f32(arch + ".attention.layer_norm_rms_epsilon", shape.eps),
+        kv_f32(arch + ".rope.freq_base", shape.theta),
         kv_arr_str("tokenizer.ggml.tokens", toks),
         kv_arr_i32("tokenizer.ggml.token_type", ttypes),
         kv_u32("tokenizer.ggml.bos_token_id", shape.bos),
@@ -570,13 +588,13 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
         kvs.append(kv_arr_f32("tokenizer.ggml.scores", sc))
     if rope_scaling:
         if "type" in rope_scaling:
-            kvs.append(kv_str("llama.rope.scaling.type", str(rope_scaling["type"])))
+            kvs.append(kv_str(arch + ".rope.scaling.type", str(rope_scaling["type"])))
         if "factor" in rope_scaling:
-            kvs.append(kv_f32("llama.rope.scaling.factor", float(rope_scaling["factor"])))
+            kvs.append(kv_f32(arch + ".rope.scaling.factor", float(rope_scaling["factor"])))
         if "original_context_length" in rope_scaling:
-            kvs.append(kv_u32("llama.rope.scaling.original_context_length", int(rope_scaling["original_context_length"])))
+            kvs.append(kv_u32(arch + ".rope.scaling.original_context_length", int(rope_scaling["original_context_length"])))
         if "scale_linear" in rope_scaling:
-            kvs.append(kv_f32("llama.rope.scale_linear", float(rope_scaling["scale_linear"])))
+            kvs.append(kv_f32(arch + ".rope.scale_linear", float(rope_scaling["scale_linear"])))
     if rope_freqs is not None:
         rf = np.asarray(rope_freqs)
         f16 = rf.dtype == np.float16

@@ -178,6 +178,11 @@ def gemv_fused(segs: Sequence[tuple], x, in_features, norm_w=None, eps=0.0, resi
                                                    1 if integer_activations else 0, stream), "gemv_fused_form")
 
 
+def qkv_bias(q, k, v, bq, bk, bv, n_rows, q_dim, kv_dim, stream=None):
+    """ntk_qkv_bias: q [n_rows][q_dim] += bq, k / v [n_rows][kv_dim] += bk / bv, in place, one launch; a bias of None leaves its buffer untouched"""
+    check(_lib.lib().ntk_qkv_bias(_p(q), _p(k), _p(v), _p(bq), _p(bk), _p(bv), n_rows, q_dim, kv_dim, stream), "qkv_bias")
+
+
 def q8l_bytes(rows, in_features) -> int:
     return int(_lib.lib().ntk_q8l_bytes(rows, in_features))
 

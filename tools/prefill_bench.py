@@ -48,6 +48,7 @@ def main():
     ap.add_argument("--option", action="append", default=[], help="engine part: key=value engine options (e.g. prefill_fused_split=0)")
     ap.add_argument("--ab-rope-scaling", default="", help="engine part: a rope_scaling option value (e.g. llama3:8,1,4,8192): the prompt pass without and with it, two engines in this process, alternated, median of 3")
     ap.add_argument("--ab-dense-mfma16", action="store_true", help="engine part, F16 / BF16 mixes: alternate dense_mfma16 = 1 / 0 three times per prompt length (the 16-bit matrix cores against the F32-MFMA form of the same tree), medians; then decode tokens/s once with each setting")
+    ap.add_argument("--ab-qkv-bias", action="store_true", help="engine part: the prompt pass of the qwen2.5-7b preset (three bias vectors per layer) and of its bias-free twin, two engines in this process, alternated, median of 3")
     ap.add_argument("--bf16-only", action="store_true", help="per-matrix table: only the FP16 GEMM launches (profiling; the flag keeps its round-2 name)")
     a = ap.parse_args()
     ops.init(0)
@@ -107,6 +108,29 @@ def main():
                                       "all_ms": [round(t * 1e3, 2) for t in ts[name]]})
                 print("%s %s prompt of %4d tokens, rope_scaling %-22s (%2d factors): median of 3 %9.2f ms = %9.1f tokens/s   [%s]" %
                       (a.model.upper(), a.mix, T, name, eng.rope_factors, med * 1e3, T / med, " ".join("%.2f" % (t * 1e3) for t in ts[name])), flush=True)
+        for _, eng in engines: eng.close()
+    elif not a.no_engine and a.ab_qkv_bias:
+        # two engines in this process: the Qwen2.5-7B shape with its three bias vectors per layer and its bias-free twin (the same seeded matrices), their
+        # prompt passes alternated -- the difference is one ntk_qkv_bias launch per layer
+        engines = []
+        for preset in ("qwen2.5-7b-nobias", "qwen2.5-7b"):
+            eng = E.Engine()
+            eng.load_synthetic(E.synth_spec(preset, a.mix, layers=a.layers) if a.layers else E.synth_spec(preset, a.mix), 4096)
+            engines.append((preset, eng))
+        r = np.random.Generator(np.random.Philox(key=[20260925, 98]))
+        for T in [int(t) for t in a.tokens.split(',')]:
+            prompt = [151643] + [int(t) for t in r.integers(0, 151000, T - 1)]
+            ts = {name: [] for name, _ in engines}
+            for name, eng in engines: eng.forward(prompt, 0)
+            for rep in range(3):
+                for name, eng in engines:
+                    t0 = time.perf_counter(); eng.forward(prompt, 0); ts[name].append(time.perf_counter() - t0)
+            for name, eng in engines:
+                med = sorted(ts[name])[1]
+                res["engine"].append({"mix": a.mix, "prompt_tokens": T, "model": name, "qkv_bias_layers": eng.qkv_bias, "ms": round(med * 1e3, 2),
+                                      "all_ms": [round(t * 1e3, 2) for t in ts[name]]})
+                print("%-18s %s prompt of %4d tokens (%2d biased layers): median of 3 %9.2f ms = %9.1f tokens/s   [%s]" %
+                      (name, a.mix, T, eng.qkv_bias, med * 1e3, T / med, " ".join("%.2f" % (t * 1e3) for t in ts[name])), flush=True)
         for _, eng in engines: eng.close()
     elif not a.no_engine:
         eng = E.Engine()
