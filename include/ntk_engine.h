@@ -487,6 +487,14 @@ int ntk_advance_pos(int* d_pos, void* stream);
  * the three buffers (a work item is one 16-byte piece or one element: 16.7 M elements per row at the least); n_rows == 0: NTK_OK, nothing launched. */
 int ntk_qkv_bias(float* q, float* k, float* v, const float* bq, const float* bk, const float* bv, int n_rows, int q_dim, int kv_dim, void* stream);
 
+/* The per-head RMSNorm of Q and K of Qwen3-family models (csrc/qk_norm.hip), in place and in ONE launch for both buffers and all rows: every head of
+ * q [n_rows][n_heads * head_dim] becomes x * (1 / sqrtf(sum(x^2) / head_dim + eps)) * wq[head_dim], every head of k [n_rows][n_kv_heads * head_dim] the
+ * same with wk; one weight vector serves all heads of its buffer.  One wave per (row, head), the head in registers: a float2 per lane at head_dim 128
+ * (buffer and weight 8-byte aligned), a float4 at 256 (16-byte aligned), lane-strided elements for every other even head_dim or base.  The order of the
+ * sum depends on head_dim and alignment alone: a row of a T-row launch has the bits of its one-row launch.  NTK_E_NULL: any NULL pointer; NTK_E_SHAPE:
+ * head_dim <= 0 or odd, n_heads <= 0, n_kv_heads <= 0, n_rows < 0 (the buffers untouched); n_rows == 0: NTK_OK, nothing launched. */
+int ntk_qk_norm(float* q, float* k, const float* wq, const float* wk, int n_rows, int n_heads, int n_kv_heads, int head_dim, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -301,11 +301,16 @@ int64_t nt_synth_tensor(const nt_synth_spec* spec, const char* name, void* dst, 
 /* JSON description of a GGUF file: config, tensor table, vocab size. Returns bytes needed (excl. NUL) or negative.  RoPE scaling as the FILE states it:
  * "rope_scaling_type" (<arch>.rope.scaling.type; "linear" for a bare legacy rope.scale_linear; "none" without either), "rope_freq_scale" (1 / factor for
  * linear, else 1), "rope_factors" (elements of rope_freqs.weight, 0 without the tensor), "rope_orig_ctx" (.original_context_length, 0 when absent).
- * "qkv_bias_tensors": how many blk.*.attn_{q,k,v}.bias tensors the file carries (3 per layer in a Qwen2 file, 0 in a Llama file). */
+ * "qkv_bias_tensors": how many blk.*.attn_{q,k,v}.bias tensors the file carries (3 per layer in a Qwen2 file, 0 in a Llama file); "qk_norm_tensors": how
+ * many blk.*.attn_{q,k}_norm.weight (2 per layer in a Qwen3 file).  "head_dim" is <arch>.attention.key_length where the file has the key (Qwen3,
+ * Mistral-Nemo: heads x head_dim differs from the hidden size), hidden_size / n_heads otherwise. */
 int   nt_gguf_describe(const char* path, char* json_out, int cap);
 /* In how many layers the LOADED engine adds a Q | K | V projection bias (blk.N.attn_{q,k,v}.bias, each optional, F32, one value per output row, added
  * ahead of the rotation: ntk_qkv_bias); 0 for a Llama model, whose launches are unchanged; -1 without a loaded engine. */
 int   nt_engine_qkv_bias(nt_engine_t e);
+/* In how many layers the LOADED engine normalises every head of Q and K (blk.N.attn_q_norm.weight + attn_k_norm.weight, F32 [head_dim], a pair per layer;
+ * RMSNorm behind the bias and ahead of the rotation: ntk_qk_norm); 0 for a Llama or Qwen2 model, whose launches are unchanged; -1 without a loaded engine. */
+int   nt_engine_qk_norm(nt_engine_t e);
 /* The rotation a LOADED engine runs with, as JSON: "rope_theta", "rope_scaling_type" ("none" | "linear" | "llama3"; a file's "yarn" / unknown type is
  * reported as it is named, and is not applied), "rope_freq_scale", "rope_factors" (per-pair divisors folded into the frequency table: 0 or head_dim / 2),
  * "rope_orig_ctx".  Returns bytes needed (excl. NUL) or negative. */

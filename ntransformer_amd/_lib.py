@@ -157,6 +157,7 @@ def lib() -> C.CDLL:
         "ntk_sample_rows_top_k": (i, [vp, i, i, i, vp, i, C.POINTER(SampleRows), vp, vp, vp, vp]),
         "ntk_advance_pos": (i, [vp, vp]),
         "ntk_qkv_bias": (i, [vp, vp, vp, vp, vp, vp, i, i, i, vp]),
+        "ntk_qk_norm": (i, [vp, vp, vp, vp, i, i, i, i, f, vp]),
         "ntk_debug_sclk": (i, [vp, vp]),
         "ntk_debug_sclk_begin": (i, [vp, vp, vp]),
         "ntk_debug_sclk_end": (i, [vp, vp]),

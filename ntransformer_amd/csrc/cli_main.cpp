@@ -42,7 +42,7 @@ static void usage(const char* prog) {
             "  --rope-freq-scale <float> RoPE linear position scale, overriding the model's\n"
             "  --context-shift          At the end of the context drop half of the oldest positions and go on (default: stop there)\n"
             "  --keep <int>             Leading positions a context shift never drops (default: 1, the BOS)\n"
-            "  --synthetic <shape:mix>  8b|70b|tiny|qwen2.5-7b : Q8_0|Q4_K_M|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
+            "  --synthetic <shape:mix>  8b|70b|tiny|qwen2.5-7b|qwen3-8b|qwen3-4b : Q8_0|Q4_K_M|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
             "Accepted for CLI compatibility, no effect on the output (weights are always resident in 288 GB HBM;\n"
             "speculative decoding only changes speed, and plain decode is what runs):\n"
             "  --streaming --draft-model <p> --draft-k <n> --self-spec\n"
@@ -166,6 +166,13 @@ int main(int argc, char** argv) {
             s.hidden = 3584; s.inter = 18944; s.layers = 28; s.heads = 28; s.kv_heads = 4; s.vocab = 152064; s.ctx = 32768;
             s.eps = 1e-6f; s.theta = 1e6f; s.bos = 151643; s.eos = 151645;
             s.mix = (shape == "qwen2.5-7b" ? "qwen2-tied:" : "tied:") + s.mix;
+        }
+        else if (shape == "qwen3-8b" || shape == "qwen3-8b-nonorm" || shape == "qwen3-4b" || shape == "qwen3-4b-nonorm") {
+            // Qwen3-8B (untied head) and Qwen3-4B (32 heads of 128 over a hidden size of 2560, tied head); -nonorm: the same model without the Q / K norm vectors (the A/B twin)
+            const bool b8 = shape.compare(0, 8, "qwen3-8b") == 0, norm = shape.find("-nonorm") == std::string::npos;
+            s.hidden = b8 ? 4096 : 2560; s.inter = b8 ? 12288 : 9728; s.layers = 36; s.heads = 32; s.kv_heads = 8; s.vocab = 151936; s.ctx = 40960;
+            s.eps = 1e-6f; s.theta = 1e6f; s.bos = 151643; s.eos = 151645;
+            s.mix = std::string(norm ? "qwen3-" : "") + "hd128" + (b8 ? ":" : "-tied:") + s.mix;
         }
         else if (shape != "8b") { fprintf(stderr, "unknown synthetic shape %s\n", shape.c_str()); return 1; }
         st = engine.load_synthetic(s, max_context);

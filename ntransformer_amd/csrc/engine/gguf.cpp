@@ -204,6 +204,21 @@ int GgufFile::parse() {   // reference loader.cpp:56-187
     m.n_kv_heads = geti(pre + "attention.head_count_kv", m.n_heads);
     if (m.n_heads <= 0 || m.n_kv_heads <= 0 || m.hidden_size <= 0) { err_ = "Bad model dimensions"; return NTK_E_FORMAT; }
     m.head_dim = m.hidden_size / m.n_heads;
+    // a head size of its own (<arch>.attention.key_length: Qwen3's heads x 128 > hidden, Mistral-Nemo's < hidden); without the key, hidden / heads
+    if (auto kl = meta_.find(pre + "attention.key_length"); kl != meta_.end()) {
+        const std::string kname = pre + "attention.key_length", vname = pre + "attention.value_length";
+        const int64_t hd = kl->second.kind == GgufValue::INT ? (int64_t)kl->second.i : -1;
+        if (hd <= 0 || (hd & 1)) { err_ = kname + " = " + (kl->second.kind == GgufValue::INT ? std::to_string(hd) : std::string("(not an integer)")) + ": the head size must be positive and even"; return NTK_E_FORMAT; }
+        if (auto vl = meta_.find(vname); vl != meta_.end() && (vl->second.kind != GgufValue::INT || (int64_t)vl->second.i != hd)) {
+            err_ = vname + " differs from " + kname + " = " + std::to_string(hd) + ": keys and values of different sizes are not supported";
+            return NTK_E_FORMAT;
+        }
+        if (hd > 0x7FFFFFFF / (int64_t)m.n_heads || hd > 0x7FFFFFFF / (int64_t)m.n_kv_heads) {
+            err_ = kname + " = " + std::to_string(hd) + ": heads x head size overflows";
+            return NTK_E_FORMAT;
+        }
+        m.head_dim = (int)hd;
+    }
     m.max_seq_len = geti(pre + "context_length", m.max_seq_len);
     m.norm_eps = getf(pre + "attention.layer_norm_rms_epsilon", m.norm_eps);
     m.rope_theta = getf(pre + "rope.freq_base", m.rope_theta);

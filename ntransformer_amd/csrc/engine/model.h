@@ -37,6 +37,8 @@ struct LayerWeights {
     DevTensor attn_norm, wq, wk, wv, wo, ffn_norm, w_gate, w_up, w_down;
     DevTensor bq, bk, bv;   // the Q | K | V projection biases of a Qwen2-family file (F32 [out]; each optional: ptr == nullptr without one)
     bool has_qkv_bias() const { return bq.ptr || bk.ptr || bv.ptr; }
+    DevTensor q_norm, k_norm;   // the per-head RMSNorm weights of Q and K of a Qwen3-family file (F32 [head_dim], whole on every rank; a pair or neither)
+    bool has_qk_norm() const { return q_norm.ptr && k_norm.ptr; }
 };
 // the seven projection matrices of a layer, for whoever visits them all: for (auto m : kLayerMatrices) use(L.*m);
 inline constexpr std::array<DevTensor LayerWeights::*, 7> kLayerMatrices = {&LayerWeights::wq, &LayerWeights::wk, &LayerWeights::wv, &LayerWeights::wo,
@@ -227,8 +229,13 @@ public:
     // slice under tensor parallelism.  A layer that carries one gets ONE more launch behind its Q | K | V projection in both layer loops (ntk_qkv_bias:
     // layers_1to1 ahead of the KV capture, enqueue_layers as a node of the captured graph); a layer without issues the launches it always has.
     // Refused at load, ahead of the device and naming the tensor: a bias of another type or size, and the tensors the engine would silently ignore
-    // (attn_q_norm / attn_k_norm.weight, attn_output.bias, ffn_gate / ffn_up / ffn_down.bias).
+    // (attn_output.bias, ffn_gate / ffn_up / ffn_down.bias).
     int qkv_bias_layers() const { int n = 0; for (const auto& L : layers_) n += L.has_qkv_bias() ? 1 : 0; return n; }
+    // Per-head RMSNorm of Q and K (blk.N.attn_q_norm.weight / attn_k_norm.weight; Qwen3, optional under any architecture): F32, head_dim values each, one
+    // vector for all heads of the layer, whole on every tensor-parallel rank.  A layer that carries the pair gets ONE more launch (ntk_qk_norm) behind
+    // the bias launch and ahead of the rotation in both layer loops; a layer without issues the launches it always has.  Refused at load, ahead of the
+    // device and naming the tensor: a norm of another type or size, one without its partner, one on a layer the model does not have.
+    int qk_norm_layers() const { int n = 0; for (const auto& L : layers_) n += L.has_qk_norm() ? 1 : 0; return n; }
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
     uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included

@@ -148,6 +148,11 @@ int Model::enqueue_layers(int first, int last_layer) {
             NT_TRY(ntk_qkv_bias(act.q, act.k, act.v, (const float*)L.bq.ptr, (const float*)L.bk.ptr, (const float*)L.bv.ptr, 1, nh * hd, nkv * hd, s));
             prof_mark(2, false);
         }
+        if (L.has_qk_norm()) {   // a Qwen3 layer: the per-head RMSNorm of q and k, one launch (a node of the captured token); a layer without: nothing
+            prof_mark(2, true);
+            NT_TRY(ntk_qk_norm(act.q, act.k, (const float*)L.q_norm.ptr, (const float*)L.k_norm.ptr, 1, nh, nkv, hd, cfg_.norm_eps, s));
+            prof_mark(2, false);
+        }
         prof_mark(1, true);
         if (kv_q8_)
             NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, kv_.k(0, i), kv_.v(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,

@@ -62,17 +62,37 @@ static const struct { const char* name; DevTensor LayerWeights::* member; char o
     {"attn_k.bias", &LayerWeights::bk, 'k'},
     {"attn_v.bias", &LayerWeights::bv, 'k'},
 };
+// the per-head RMSNorm weights of Q and K (Qwen3): F32 [head_dim], one vector for all heads of the layer, so every rank holds it WHOLE; a pair per layer
+static const struct { const char* name; DevTensor LayerWeights::* member; } kLayerQkNorms[] = {
+    {"attn_q_norm.weight", &LayerWeights::q_norm},
+    {"attn_k_norm.weight", &LayerWeights::k_norm},
+};
 // per-layer tensors of neighbouring architectures that this engine has no kernel for: a file that carries one is refused rather than run without it
-static const char* const kLayerUnsupported[] = {"attn_q_norm.weight", "attn_k_norm.weight", "attn_output.bias", "ffn_gate.bias", "ffn_up.bias", "ffn_down.bias"};
+static const char* const kLayerUnsupported[] = {"attn_output.bias", "ffn_gate.bias", "ffn_up.bias", "ffn_down.bias"};
 
 int Model::check_layer_extras(const GgufFile& f) {
     const int64_t qd = (int64_t)cfg_.n_heads * cfg_.head_dim, kvd = (int64_t)cfg_.n_kv_heads * cfg_.head_dim;
+    std::vector<const GgufTensor*> norms[2];   // the layer's q / k norm by layer index, for the pair rule below
+    for (auto& v : norms) v.assign((size_t)std::max(cfg_.n_layers, 0), nullptr);
     for (const GgufTensor& t : f.tensors()) {   // every "blk.<i>.<name>" of the file, whatever its index: a tensor behind the last layer is not passed over either
         int li = -1, at = 0;
         if (sscanf(t.name.c_str(), "blk.%d.%n", &li, &at) != 1 || at == 0) continue;
         const char* const rest = t.name.c_str() + at;
         for (const char* u : kLayerUnsupported)
-            if (strcmp(rest, u) == 0) { err_ = "Unsupported tensor " + t.name + ": this engine runs Llama and Qwen2 layers (no per-head Q/K norm, no output or FFN bias)"; return NTK_E_FORMAT; }
+            if (strcmp(rest, u) == 0) { err_ = "Unsupported tensor " + t.name + ": this engine runs Llama, Qwen2 and Qwen3 layers (no attention-output or FFN bias)"; return NTK_E_FORMAT; }
+        for (int w = 0; w < 2; ++w) {
+            if (strcmp(rest, kLayerQkNorms[w].name) != 0) continue;
+            if (li < 0 || li >= cfg_.n_layers) {
+                err_ = "Unsupported tensor " + t.name + ": the model has " + std::to_string(cfg_.n_layers) + " layers";
+                return NTK_E_FORMAT;
+            }
+            if (t.dtype != NTK_DT_F32 || !t.known_type) { err_ = t.name + " must be F32"; return NTK_E_DTYPE; }
+            if (t.numel() != cfg_.head_dim) {
+                err_ = t.name + " holds " + std::to_string(t.numel()) + " values, " + std::to_string(cfg_.head_dim) + " (head_dim: one vector for all heads) are needed";
+                return NTK_E_SHAPE;
+            }
+            norms[w][(size_t)li] = &t;
+        }
         for (const auto& e : kLayerBiases) {
             if (strcmp(rest, e.name) != 0) continue;
             const int64_t want = e.out == 'q' ? qd : kvd;
@@ -81,6 +101,13 @@ int Model::check_layer_extras(const GgufFile& f) {
                 err_ = t.name + " holds " + std::to_string(t.numel()) + " values, " + std::to_string(want) + " (one per output row) are needed";
                 return NTK_E_SHAPE;
             }
+        }
+    }
+    for (size_t i = 0; i < norms[0].size(); ++i) {   // a pair per layer: Q normalised against unnormalised K (or the reverse) is no model anyone trained
+        const GgufTensor* const lone = norms[0][i] && !norms[1][i] ? norms[0][i] : norms[1][i] && !norms[0][i] ? norms[1][i] : nullptr;
+        if (lone) {
+            err_ = "Unsupported tensor " + lone->name + ": layer " + std::to_string(i) + " carries it without its partner (attn_q_norm.weight and attn_k_norm.weight come as a pair)";
+            return NTK_E_FORMAT;
         }
     }
     return NTK_OK;
@@ -148,6 +175,13 @@ int Model::load_impl(const std::string& path, int max_context) {
             if (!t || !slot_of(name, &sl)) continue;
             NT_TRY(upload_shard(*sl.dst, f.data(*t), t->dtype, sl.in_f, sl.out_f, t->nbytes, sl.how));
         }
+        for (const auto& e : kLayerQkNorms) {   // ... and the optional Q / K norm pair, held to F32, head_dim values and a pair per layer by the same pre-pass
+            const std::string name = "blk." + std::to_string(i) + "." + e.name;
+            const GgufTensor* t = f.find(name);
+            TensorSlot sl;
+            if (!t || !slot_of(name, &sl)) continue;
+            NT_TRY(upload_shard(*sl.dst, f.data(*t), t->dtype, sl.in_f, sl.out_f, t->nbytes, sl.how));
+        }
     }
     return finish_load();
 }
@@ -164,6 +198,8 @@ bool Model::slot_of(const std::string& name, TensorSlot* sl) {
         if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), e.how, extent(e.in), extent(e.out)}; return true; }
     for (const auto& e : kLayerBiases)   // [out] values: `out` rows of one element
         if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), ROWS, 1, extent(e.out)}; return true; }
+    for (const auto& e : kLayerQkNorms)   // [head_dim] values, whole on every rank
+        if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), WHOLE, hd, 1}; return true; }
     return false;
 }
 
@@ -173,10 +209,11 @@ int Model::load_synthetic(const SynthSpec& spec, int max_context, int nthreads) 
     if (!synth_plan(spec, plan)) { err_ = "bad synthetic spec"; return NTK_E_SHAPE; }
     cfg_ = ModelConfig();
     cfg_.model_name = "synthetic-" + spec.mix;
-    if (synth_flavour(spec.mix).qwen2) cfg_.architecture = "qwen2";
+    const SynthFlavour fl = synth_flavour(spec.mix);
+    if (fl.qwen2 || fl.qwen3) cfg_.architecture = fl.qwen3 ? "qwen3" : "qwen2";
     cfg_.vocab_size = spec.vocab; cfg_.hidden_size = spec.hidden; cfg_.intermediate_size = spec.inter;
     cfg_.n_layers = spec.layers; cfg_.n_heads = spec.heads; cfg_.n_kv_heads = spec.kv_heads;
-    cfg_.head_dim = spec.hidden / spec.heads;
+    cfg_.head_dim = fl.head_dim ? fl.head_dim : spec.hidden / spec.heads;   // (synth_plan has held it to a positive even value)
     cfg_.norm_eps = spec.eps; cfg_.rope_theta = spec.theta;
     cfg_.max_seq_len = std::min(spec.ctx, max_context);
     cfg_.bos_token_id = spec.bos; cfg_.eos_token_id = spec.eos;

@@ -310,6 +310,8 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         project_many(qkv_out, qkv, 3, residual_, rm_a);
         // a Qwen2 layer's projection biases: one launch over the T rows of q | k | v, ahead of the capture and the rotation (a layer without: no launch)
         if (L.has_qkv_bias()) ok(ntk_qkv_bias(act.q, act.k, act.v, (const float*)L.bq.ptr, (const float*)L.bk.ptr, (const float*)L.bv.ptr, T, qd, kvd, s));
+        // a Qwen3 layer's per-head RMSNorm of Q and K: one launch over every head of the T rows, behind the bias and ahead of the capture and the rotation
+        if (L.has_qk_norm()) ok(ntk_qk_norm(act.q, act.k, (const float*)L.q_norm.ptr, (const float*)L.k_norm.ptr, T, cfg_.n_heads, cfg_.n_kv_heads, cfg_.head_dim, cfg_.norm_eps, s));
         if (i == kv_capture_layer_ && kv_capture_) {   // parity instrumentation: the F32 projections the store launches are about to read
             ok(ntk_copy(kv_capture_, act.k, T * kvd, s));
             ok(ntk_copy(kv_capture_ + (size_t)cfg_.max_seq_len * kvd, act.v, T * kvd, s));

@@ -98,8 +98,8 @@ void fill_dense(uint8_t* dst, int gt, uint64_t key, int64_t e0, int64_t n, doubl
     for (int64_t e = 0; e < n; ++e) {
         uint64_t st = key ^ ((uint64_t)(e0 + e) * 0xD1342543DE82EF95ull + 0x632BE59BD9B4E019ull);
         float v;
-        if (norm_vec) {
-            v = (float)(1.0 + 0.05 * (2.0 * u01(splitmix(st)) - 1.0));
+        if (norm_vec) {   // (tgt: the amplitude)
+            v = (float)(1.0 + tgt * (2.0 * u01(splitmix(st)) - 1.0));
         } else {   // ~N(0,1) via sum of 4 uniforms, scaled
             double a = 0;
             for (int k = 0; k < 4; ++k) a += u01(splitmix(st));
@@ -148,10 +148,25 @@ static bool parse_layer_sample(const std::string& mix, int layers, int& of, std:
 }
 
 SynthFlavour synth_flavour(const std::string& mix) {
-    if (mix.compare(0, 6, "qwen2:") == 0) return {true, false, mix.substr(6)};
-    if (mix.compare(0, 11, "qwen2-tied:") == 0) return {true, true, mix.substr(11)};
-    if (mix.compare(0, 5, "tied:") == 0) return {false, true, mix.substr(5)};
-    return {false, false, mix};
+    const SynthFlavour plain{false, false, mix};
+    const size_t colon = mix.find(':');
+    if (colon == std::string::npos || colon == 0 || mix.compare(0, 7, "Q4_K_M@") == 0) return plain;
+    SynthFlavour fl{false, false, mix.substr(colon + 1)};
+    const std::string pre = mix.substr(0, colon);
+    for (size_t at = 0, n = 0; at <= pre.size(); ++n) {
+        const size_t dash = pre.find('-', at);
+        const std::string tok = pre.substr(at, dash == std::string::npos ? std::string::npos : dash - at);
+        if (tok == "qwen2" && n == 0) fl.qwen2 = true;
+        else if (tok == "qwen3" && n == 0) fl.qwen3 = true;
+        else if (tok == "tied" && !fl.tied) fl.tied = true;
+        else if (tok.size() > 2 && tok.size() <= 8 && tok.compare(0, 2, "hd") == 0 && tok.find_first_not_of("0123456789", 2) == std::string::npos && !fl.head_dim)
+            fl.head_dim = atoi(tok.c_str() + 2);   // (0 or odd: synth_plan refuses)
+        else return plain;   // not a flavour: the whole string is the mix (which synth_plan does not know)
+        if (tok.compare(0, 2, "hd") == 0 && fl.head_dim <= 0) fl.head_dim = -1;
+        if (dash == std::string::npos) break;
+        at = dash + 1;
+    }
+    return fl;
 }
 
 bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
@@ -162,8 +177,8 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     if (!parse_layer_sample(fl.mix, s.layers, sample_of, sample)) return false;
     const bool km = fl.mix == "Q4_K_M" || sample_of > 0;
     const int base = km ? 12 : mix_type(fl.mix);
-    if (base < 0 || s.heads <= 0 || s.kv_heads <= 0 || s.hidden % s.heads) return false;
-    const int hd = s.hidden / s.heads;
+    if (base < 0 || s.heads <= 0 || s.kv_heads <= 0 || (fl.head_dim ? fl.head_dim < 0 || (fl.head_dim & 1) : s.hidden % s.heads)) return false;
+    const int hd = fl.head_dim ? fl.head_dim : s.hidden / s.heads;
     const int64_t q_dim = (int64_t)s.heads * hd, kv_dim = (int64_t)s.kv_heads * hd;
     auto add = [&](const std::string& name, int gt, int64_t in_f, int64_t out_f, double sigma) {
         const BlockInfo b = block_of(gt);
@@ -185,6 +200,10 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
             add(p + "attn_k.bias", 0, 1, kv_dim, 0.5);
             add(p + "attn_v.bias", 0, 1, kv_dim, 0.5);
         }
+        if (fl.qwen3) {   // the per-head norm weights: F32 [head_dim], 1 + 0.5 u -- far enough from 1, and q from k, that dropping or swapping them shows
+            add(p + "attn_q_norm.weight", 0, hd, 1, -0.5);
+            add(p + "attn_k_norm.weight", 0, hd, 1, -0.5);
+        }
         add(p + "attn_output.weight", base, q_dim, s.hidden, 1);
         add(p + "ffn_norm.weight", 0, s.hidden, 1, 0);
         add(p + "ffn_gate.weight", base, s.hidden, s.inter, 1);
@@ -199,8 +218,8 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
 void synth_fill(void* dst, const SynthTensor& t, uint64_t seed, int nthreads) {
     const BlockInfo b = block_of(t.ggml_type);
     const uint64_t key = seed * 0x9E3779B97F4A7C15ull ^ fnv1a(t.name);
-    const bool norm_vec = t.sigma == 0;
-    const double tgt = norm_vec ? 0 : t.sigma / std::sqrt((double)t.in_f);
+    const bool norm_vec = t.sigma <= 0;
+    const double tgt = norm_vec ? (t.sigma < 0 ? -t.sigma : 0.05) : t.sigma / std::sqrt((double)t.in_f);
     const int64_t n_el = t.in_f * t.out_f;
     const int64_t units = b.bw > 1 ? n_el / b.bw : (n_el + 255) / 256;
     nthreads = std::max(1, std::min<int>(nthreads, (int)std::min<int64_t>(units, 256)));
@@ -265,8 +284,9 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
     auto kv_u32 = [&](const char* k, uint32_t v) { str(k); u32(4); u32(v); };
     auto kv_f32 = [&](const char* k, float v) { str(k); u32(6); f32(v); };
     auto kv_str = [&](const char* k, const std::string& v) { str(k); u32(8); str(v); };
-    u32(0x46554747u); u32(3); u64(plan.size()); u64(16);
-    const std::string arch = synth_flavour(s.mix).qwen2 ? "qwen2" : "llama";   // (the hyper-parameters live under the architecture's own prefix)
+    const SynthFlavour fl = synth_flavour(s.mix);
+    u32(0x46554747u); u32(3); u64(plan.size()); u64(fl.head_dim > 0 ? 18 : 16);   // (metadata entries: key_length and value_length with a head size of its own)
+    const std::string arch = fl.qwen3 ? "qwen3" : fl.qwen2 ? "qwen2" : "llama";   // (the hyper-parameters live under the architecture's own prefix)
     const auto key = [&](const char* k) { return arch + "." + k; };
     kv_str("general.architecture", arch);
     kv_str("general.name", "synthetic-" + s.mix);
@@ -277,6 +297,10 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
     kv_u32(key("block_count").c_str(), (uint32_t)s.layers);
     kv_u32(key("attention.head_count").c_str(), (uint32_t)s.heads);
     kv_u32(key("attention.head_count_kv").c_str(), (uint32_t)s.kv_heads);
+    if (fl.head_dim > 0) {   // a head size of its own
+        kv_u32(key("attention.key_length").c_str(), (uint32_t)fl.head_dim);
+        kv_u32(key("attention.value_length").c_str(), (uint32_t)fl.head_dim);
+    }
     kv_u32(key("context_length").c_str(), (uint32_t)s.ctx);
     kv_f32(key("attention.layer_norm_rms_epsilon").c_str(), s.eps);
     kv_f32(key("rope.freq_base").c_str(), s.theta);
@@ -289,7 +313,7 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
     uint64_t off = 0;
     for (const auto& t : plan) {
         str(t.name);
-        if (t.out_f == 1 && t.sigma == 0) { u32(1); u64((uint64_t)t.in_f); }
+        if (t.out_f == 1 && t.sigma <= 0) { u32(1); u64((uint64_t)t.in_f); }
         else if (t.in_f == 1) { u32(1); u64((uint64_t)t.out_f); }   // a bias vector
         else { u32(2); u64((uint64_t)t.in_f); u64((uint64_t)t.out_f); }
         u32((uint32_t)t.ggml_type);

@@ -14,7 +14,7 @@ struct SynthTensor {
     std::string name;
     int ggml_type;
     int64_t in_f, out_f;   // norm vectors: in_f = n, out_f = 1; bias vectors: in_f = 1, out_f = n
-    double sigma;
+    double sigma;          // matrices and biases: the scale of the values; norm vectors: 0 = 1 + 0.05 u, negative = 1 + |sigma| u, u uniform in [-1, 1)
     size_t nbytes;
 };
 
@@ -31,9 +31,14 @@ struct SynthSpec {
 // hyper-parameter keys "qwen2", three F32 bias vectors per layer (blk.N.attn_{q,k,v}.bias, behind attn_v.weight, seeded like every other tensor);
 // "qwen2-tied:<mix>" = the same without output.weight (the LM head is token_embd.weight); "tied:<mix>" = the Llama model without output.weight (the
 // bias-free twin of a tied Qwen2 model).  No prefix: the Llama model.
-struct SynthFlavour { bool qwen2, tied; std::string mix; };
+// "qwen3[-hd<N>][-tied]:<mix>" = a Qwen3 model -- architecture and keys "qwen3", no biases, two F32 norm vectors of head_dim values per layer
+// (blk.N.attn_q_norm.weight, attn_k_norm.weight, behind attn_v.weight, seeded by name, values 1 + 0.5 u with u uniform in [-1, 1)); -hd<N> gives the
+// heads a size of their own: <arch>.attention.key_length = value_length = N and projections of heads x N rows, whatever the hidden size.
+// "hd<N>[-tied]:<mix>" = the Llama model with such a head size (Mistral-Nemo's kind; the norm-free twin of a qwen3-hd<N> model).
+// The general form is a '-'-separated list in front of the ':' -- qwen2 | qwen3 first, then hd<N>, tied in any order.
+struct SynthFlavour { bool qwen2, tied; std::string mix; bool qwen3 = false; int head_dim = 0; };
 SynthFlavour synth_flavour(const std::string& mix);
-// tensor list in file order (token_embd, per-layer 9 tensors -- 12 in the Qwen2 flavour --, output_norm, output); false if `mix` is unknown
+// tensor list in file order (token_embd, per-layer 9 tensors -- 12 in the Qwen2, 11 in the Qwen3 flavour --, output_norm, output); false if `mix` is unknown
 bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out);
 // deterministic in (seed, name, element index); multi-threaded
 void synth_fill(void* dst, const SynthTensor& t, uint64_t seed, int nthreads);

@@ -38,6 +38,16 @@ PRESETS = {
                        flavour="qwen2-tied"),
     "qwen2.5-7b-nobias": dict(hidden=3584, inter=18944, layers=28, heads=28, kv_heads=4, vocab=152064, ctx=32768, bos=151643, eos=151645, eps=1e-6, theta=1e6,
                               flavour="tied"),   # its bias-free twin (the A/B of tools/prefill_bench.py --ab-qkv-bias)
+    # Qwen3-8B (untied head) and Qwen3-4B (32 heads of 128 over a hidden size of 2560: heads x head_dim = 4096, tied head): two F32 norm vectors of
+    # head_dim values per layer; -nonorm: the same seeded matrices without them (the A/B of tools/prefill_bench.py --ab-qk-norm)
+    "qwen3-8b": dict(hidden=4096, inter=12288, layers=36, heads=32, kv_heads=8, vocab=151936, ctx=40960, bos=151643, eos=151645, eps=1e-6, theta=1e6,
+                     flavour="qwen3-hd128"),
+    "qwen3-8b-nonorm": dict(hidden=4096, inter=12288, layers=36, heads=32, kv_heads=8, vocab=151936, ctx=40960, bos=151643, eos=151645, eps=1e-6, theta=1e6,
+                            flavour="hd128"),
+    "qwen3-4b": dict(hidden=2560, inter=9728, layers=36, heads=32, kv_heads=8, vocab=151936, ctx=40960, bos=151643, eos=151645, eps=1e-6, theta=1e6,
+                     flavour="qwen3-hd128-tied"),
+    "qwen3-4b-nonorm": dict(hidden=2560, inter=9728, layers=36, heads=32, kv_heads=8, vocab=151936, ctx=40960, bos=151643, eos=151645, eps=1e-6, theta=1e6,
+                            flavour="hd128-tied"),
 }
 
 
@@ -130,6 +140,7 @@ def _bind():
     L.nt_engine_rope_info.argtypes = [vp, C.c_char_p, i]
     L.nt_gguf_describe.argtypes = [C.c_char_p, C.c_char_p, i]
     L.nt_engine_qkv_bias.argtypes = [vp]
+    L.nt_engine_qk_norm.argtypes = [vp]
     L._engine_bound = True
     return L
 
@@ -230,6 +241,11 @@ class Engine:
     def qkv_bias(self) -> int:
         """in how many layers the loaded model adds a Q | K | V projection bias (nt_engine_qkv_bias): 0 for a Llama model"""
         return int(self.L.nt_engine_qkv_bias(self.h))
+
+    @property
+    def qk_norm(self) -> int:
+        """in how many layers the loaded model normalises every head of Q and K (nt_engine_qk_norm): 0 for a Llama or Qwen2 model"""
+        return int(self.L.nt_engine_qk_norm(self.h))
 
     @property
     def vocab_size(self): return self.L.nt_engine_vocab_size(self.h)

@@ -391,6 +391,11 @@ class LlamaShape:
     theta: float = 500000.0
     bos: int = 1
     eos: int = 2
+    head_dim: int = 0     # 0: hidden / heads; else a head size of its own, written as <arch>.attention.key_length / value_length
+
+    @property
+    def hd(self) -> int:
+        return self.head_dim or self.hidden // self.heads
 
 
 TINY = LlamaShape("tiny", 256, 512, 2, 4, 2, 512, ctx=256, bos=256, eos=257)
@@ -402,6 +407,30 @@ QWEN25_7B = LlamaShape("qwen2.5-7b", 3584, 18944, 28, 28, 4, 152064, ctx=32768, 
 QWEN_T64 = LlamaShape("qt64", 256, 512, 2, 4, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)        # the TINY shape: head_dim 64
 QWEN_T128 = LlamaShape("qt128", 256, 512, 2, 2, 1, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)      # head_dim 128
 QWEN_7 = LlamaShape("q7", 1792, 512, 2, 14, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)          # head_dim 128, 7 query heads per KV head (Qwen2.5-7B's ratio)
+# Qwen3 (make_synthetic_llama(..., arch="qwen3", qk_norm=<scale>)): the published geometries -- Qwen3-4B's 32 heads of 128 over a hidden size of 2560 --
+# and the two-layer shapes of the engine tests; NEMO_128: Mistral-Nemo's kind under `llama`, heads x head_dim BELOW the hidden size and no norm tensors
+QWEN3_8B = LlamaShape("qwen3-8b", 4096, 12288, 36, 32, 8, 151936, ctx=40960, eps=1e-6, theta=1e6, bos=151643, eos=151645, head_dim=128)
+QWEN3_4B = LlamaShape("qwen3-4b", 2560, 9728, 36, 32, 8, 151936, ctx=40960, eps=1e-6, theta=1e6, bos=151643, eos=151645, head_dim=128)
+QWEN3_N64 = LlamaShape("q3n64", 256, 512, 2, 4, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)                   # head_dim 64 = hidden / heads
+QWEN3_W128 = LlamaShape("q3w128", 256, 512, 2, 4, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257, head_dim=128)   # 4 x 128 = 512 > hidden
+QWEN3_G128 = LlamaShape("q3g128", 1024, 512, 2, 8, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)               # head_dim 128, 4 query heads per KV head
+NEMO_128 = LlamaShape("nemo128", 512, 512, 2, 2, 1, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257, head_dim=128)    # 2 x 128 = 256 < hidden
+
+
+def model_head_dim(meta: Dict[str, object]) -> int:
+    """The head size a file's metadata states: <arch>.attention.key_length where the key is there (Qwen3, Mistral-Nemo), else embedding_length / head_count.
+    ValueError names the key when key_length is not a positive even number or value_length differs from it (the engine refuses the same files)."""
+    arch = meta.get("general.architecture", b"llama")
+    arch = arch.decode() if isinstance(arch, bytes) else arch
+    kname, vname = arch + ".attention.key_length", arch + ".attention.value_length"
+    if kname not in meta:
+        return int(meta[arch + ".embedding_length"]) // int(meta[arch + ".attention.head_count"])
+    hd = int(meta[kname])
+    if hd <= 0 or hd % 2:
+        raise ValueError("%s = %d: the head size must be positive and even" % (kname, hd))
+    if vname in meta and int(meta[vname]) != hd:
+        raise ValueError("%s = %d differs from %s = %d" % (vname, int(meta[vname]), kname, hd))
+    return hd
 
 
 def use_more_bits(i: int, n: int) -> bool:
@@ -507,12 +536,17 @@ def llama3_rope_factors(head_dim: int, theta: float, factor: float = 8.0, low_fr
 def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: int = 20260925,
                          with_scores: bool = False, overrides: Optional[Dict[str, str]] = None,
                          rope_freqs: Optional[np.ndarray] = None, rope_scaling: Optional[Dict[str, object]] = None,
-                         arch: str = "llama", qkv_bias=None, tied: bool = False, extra_tensors: Sequence[TensorSpec] = ()) -> Dict[str, int]:
+                         arch: str = "llama", qkv_bias=None, tied: bool = False, extra_tensors: Sequence[TensorSpec] = (),
+                         qk_norm=None, extra_kvs: Sequence[bytes] = ()) -> Dict[str, int]:
     """Write a seeded synthetic Llama-architecture GGUF; returns {tensor name: ggml type}.
     arch: general.architecture and the prefix of the hyper-parameter keys ("llama", "qwen2").  qkv_bias: None (no bias tensors) or the scale of the
     seeded blk.N.attn_{q,k,v}.bias vectors (F32 [out], normal values times the scale, written behind attn_v.weight as llama.cpp's converter orders them);
     a dict {"q": s, "k": s, "v": s} writes only the named ones.  tied: no output.weight (the LM head is token_embd.weight).  extra_tensors: appended as
     given (the loader's refusals: a bias of another type or size, tensors of architectures the engine does not run).
+    qk_norm: None (no norm tensors) or the amplitude s of the seeded blk.N.attn_q_norm.weight / attn_k_norm.weight vectors (F32 [head_dim], 1 + s u with u
+    uniform in [-1, 1), written behind attn_v.weight and any bias); a dict {"q": s, "k": s} writes only the named ones (the loader's pair rule).  A shape
+    with head_dim != 0 gets <arch>.attention.key_length = value_length = head_dim and projections of heads x head_dim rows.  extra_kvs: metadata entries
+    (kv_u32(...) ...) appended as given.  Without qk_norm, extra_kvs and shape.head_dim the file is byte for byte what it always was.
     overrides: per-matrix types on top of the mix, in every layer ({"ffn_up": "Q4_K"}).
     rope_freqs: the per-pair frequency divisors, appended as the tensor rope_freqs.weight (float32; a float16 array is written as F16, any length is
     written as given: the loader's refusals).  rope_scaling: {"type": "linear" | "yarn" | ..., "factor": F, "original_context_length": N,
@@ -521,7 +555,7 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
     for m, t in (overrides or {}).items():
         for i in range(shape.layers):
             types["blk.%d.%s.weight" % (i, m)] = NAME_TO_GGML[t]
-    hd = shape.hidden // shape.heads
+    hd = shape.hd
     q_dim, kv_dim = shape.heads * hd, shape.kv_heads * hd
     dims = {"attn_q": (shape.hidden, q_dim), "attn_k": (shape.hidden, kv_dim), "attn_v": (shape.hidden, kv_dim),
             "attn_output": (q_dim, shape.hidden), "ffn_gate": (shape.hidden, shape.inter),
@@ -555,6 +589,11 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
             if scale is not None:
                 name = p + m + ".bias"
                 specs.append(TensorSpec(name, (dims[m][1],), GGML_F32, (float(scale) * rng_for(name).standard_normal(dims[m][1])).astype("<f4").tobytes()))
+        for m, key in (("attn_q_norm", "q"), ("attn_k_norm", "k")):
+            amp = qk_norm.get(key) if isinstance(qk_norm, dict) else qk_norm
+            if amp is not None:
+                name = p + m + ".weight"
+                specs.append(TensorSpec(name, (hd,), GGML_F32, (1.0 + float(amp) * rng_for(name).uniform(-1, 1, hd)).astype("<f4").tobytes()))
         mat(p + "attn_output.weight", *dims["attn_output"])
         specs.append(TensorSpec(p + "ffn_norm.weight", (shape.hidden,), GGML_F32, norm_w(p + "ffn_norm.weight")))
         for m in ("ffn_gate", "ffn_up", "ffn_down"):
@@ -575,6 +614,7 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
         kv_u32(arch + ".block_count", shape.layers),
         kv_u32(arch + ".attention.head_count", shape.heads),
         kv_u32(arch + ".attention.head_count_kv", shape.kv_heads),
+    ] + ([kv_u32(arch + ".attention.key_length", shape.head_dim), kv_u32(arch + ".attention.value_length", shape.head_dim)] if shape.head_dim else []) + [
         kv_u32(arch + ".context_length", shape.ctx),
         kv_f32(arch + ".attention.layer_norm_rms_epsilon", shape.eps),
         kv_f32(arch + ".rope.freq_base", shape.theta),
@@ -595,6 +635,7 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
             kvs.append(kv_u32(arch + ".rope.scaling.original_context_length", int(rope_scaling["original_context_length"])))
         if "scale_linear" in rope_scaling:
             kvs.append(kv_f32(arch + ".rope.scale_linear", float(rope_scaling["scale_linear"])))
+    kvs.extend(extra_kvs)
     if rope_freqs is not None:
         rf = np.asarray(rope_freqs)
         f16 = rf.dtype == np.float16
@@ -617,7 +658,7 @@ def write_vocab_gguf(path: str, tokens: Sequence[bytes], scores: Optional[Sequen
 
 def algorithmic_bytes_per_token(shape: LlamaShape, types: Dict[str, int], pos: int = 0) -> int:
     """B_tok of SURVEY.md section 8(d): matrices once in GGUF encoding + norms + KV r/w + 1 embedding row."""
-    hd = shape.hidden // shape.heads
+    hd = shape.hd
     total = 0
     for name, t in types.items():
         if name == "token_embd.weight":

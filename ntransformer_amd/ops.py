@@ -183,6 +183,11 @@ def qkv_bias(q, k, v, bq, bk, bv, n_rows, q_dim, kv_dim, stream=None):
     check(_lib.lib().ntk_qkv_bias(_p(q), _p(k), _p(v), _p(bq), _p(bk), _p(bv), n_rows, q_dim, kv_dim, stream), "qkv_bias")
 
 
+def qk_norm(q, k, wq, wk, n_rows, n_heads, n_kv_heads, head_dim, eps, stream=None):
+    """ntk_qk_norm: RMSNorm of every head of q [n_rows][n_heads * head_dim] (weights wq[head_dim]) and of k [n_rows][n_kv_heads * head_dim] (wk), in place, one launch"""
+    check(_lib.lib().ntk_qk_norm(_p(q), _p(k), _p(wq), _p(wk), n_rows, n_heads, n_kv_heads, head_dim, eps, stream), "qk_norm")
+
+
 def q8l_bytes(rows, in_features) -> int:
     return int(_lib.lib().ntk_q8l_bytes(rows, in_features))
 

@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--ab-rope-scaling", default="", help="engine part: a rope_scaling option value (e.g. llama3:8,1,4,8192): the prompt pass without and with it, two engines in this process, alternated, median of 3")
     ap.add_argument("--ab-dense-mfma16", action="store_true", help="engine part, F16 / BF16 mixes: alternate dense_mfma16 = 1 / 0 three times per prompt length (the 16-bit matrix cores against the F32-MFMA form of the same tree), medians; then decode tokens/s once with each setting")
     ap.add_argument("--ab-qkv-bias", action="store_true", help="engine part: the prompt pass of the qwen2.5-7b preset (three bias vectors per layer) and of its bias-free twin, two engines in this process, alternated, median of 3")
+    ap.add_argument("--ab-qk-norm", action="store_true", help="engine part: the qwen3-8b preset (two Q / K norm vectors per layer) and its norm-free twin: the prompt pass with two engines in this process, alternated, median of 3; then decode tokens/s of 128 greedy steps, each engine loaded alone (it owns the static decode slots), alternated --decode-rounds times")
+    ap.add_argument("--decode-rounds", type=int, default=2, help="--ab-qk-norm: how often the pair of decode measurements is repeated")
     ap.add_argument("--bf16-only", action="store_true", help="per-matrix table: only the FP16 GEMM launches (profiling; the flag keeps its round-2 name)")
     a = ap.parse_args()
     ops.init(0)
@@ -132,6 +134,48 @@ def main():
                 print("%-18s %s prompt of %4d tokens (%2d biased layers): median of 3 %9.2f ms = %9.1f tokens/s   [%s]" %
                       (name, a.mix, T, eng.qkv_bias, med * 1e3, T / med, " ".join("%.2f" % (t * 1e3) for t in ts[name])), flush=True)
         for _, eng in engines: eng.close()
+    elif not a.no_engine and a.ab_qk_norm:
+        # the Qwen3-8B shape with its two norm vectors per layer and its norm-free twin (the same seeded matrices): the difference is one ntk_qk_norm launch per layer
+        presets = ("qwen3-8b-nonorm", "qwen3-8b")
+        spec_of = lambda preset: E.synth_spec(preset, a.mix, layers=a.layers) if a.layers else E.synth_spec(preset, a.mix)
+        engines = []
+        for preset in presets:
+            eng = E.Engine()
+            eng.load_synthetic(spec_of(preset), 4096)
+            engines.append((preset, eng))
+        r = np.random.Generator(np.random.Philox(key=[20260925, 97]))
+        for T in [int(t) for t in a.tokens.split(',')]:
+            prompt = [151643] + [int(t) for t in r.integers(0, 151000, T - 1)]
+            ts = {name: [] for name, _ in engines}
+            for name, eng in engines: eng.forward(prompt, 0)
+            for rep in range(3):
+                for name, eng in engines:
+                    t0 = time.perf_counter(); eng.forward(prompt, 0); ts[name].append(time.perf_counter() - t0)
+            for name, eng in engines:
+                med = sorted(ts[name])[1]
+                res["engine"].append({"mix": a.mix, "prompt_tokens": T, "model": name, "qk_norm_layers": eng.qk_norm, "ms": round(med * 1e3, 2),
+                                      "all_ms": [round(t * 1e3, 2) for t in ts[name]]})
+                print("%-16s %s prompt of %4d tokens (%2d normalising layers): median of 3 %9.2f ms = %9.1f tokens/s   [%s]" %
+                      (name, a.mix, T, eng.qk_norm, med * 1e3, T / med, " ".join("%.2f" % (t * 1e3) for t in ts[name])), flush=True)
+        for _, eng in engines: eng.close()
+        prompt = [151643] + [int(t) for t in r.integers(0, 151000, 15)]
+        for rnd in range(a.decode_rounds):
+            for preset in presets:
+                eng = E.Engine()
+                eng.load_synthetic(spec_of(preset), 4096)
+                gen = lambda n: eng.generate_tokens(prompt, n, temperature=0.0, repeat_penalty=1.0, stop_at_eos=False)
+                gen(8)
+                per = []
+                for rep in range(3):
+                    t0 = time.perf_counter(); gen(1); t1 = time.perf_counter(); gen(129); t2 = time.perf_counter()
+                    per.append(((t2 - t1) - (t1 - t0)) / 128)
+                med = sorted(per)[1]
+                res["engine"].append({"mix": a.mix, "decode": True, "model": preset, "qk_norm_layers": eng.qk_norm, "ms_per_token": round(med * 1e3, 4),
+                                      "all_ms": [round(t * 1e3, 4) for t in per]})
+                print("%-16s %s decode, round %d (%2d normalising layers, %s): median of 3 %.4f ms per token = %.1f tokens/s   [%s]" %
+                      (preset, a.mix, rnd, eng.qk_norm, eng.decode_path() if hasattr(eng, "decode_path") else "fused + graph", med * 1e3, 1.0 / med,
+                       " ".join("%.4f" % (t * 1e3) for t in per)), flush=True)
+                eng.close()
     elif not a.no_engine:
         eng = E.Engine()
         if a.repack >= 0: eng.set_option("repack", a.repack)
