@@ -495,6 +495,40 @@ int ntk_qkv_bias(float* q, float* k, float* v, const float* bq, const float* bk,
  * head_dim <= 0 or odd, n_heads <= 0, n_kv_heads <= 0, n_rows < 0 (the buffers untouched); n_rows == 0: NTK_OK, nothing launched. */
 int ntk_qk_norm(float* q, float* k, const float* wq, const float* wk, int n_rows, int n_heads, int n_kv_heads, int head_dim, float eps, void* stream);
 
+/* ---- The routed expert FFN of mixture-of-experts models (csrc/moe.hip; Qwen3-MoE, Mixtral) ---------------------------------------------------------
+ * T rows of a pass (1 .. 1024), E experts (1 .. 256), K experts per row (1 .. min(E, 16)); a PAIR is p = t K + k.  Expert e of a 3-D GGUF tensor is the
+ * contiguous block of `rows` rows at e x rows x ntk_row_bytes(dtype, columns); expert matrices are NTK_DT_Q8_0, NTK_DT_Q4_K or NTK_DT_Q6_K, each tensor
+ * its own type, rows at any even address (a Q6_K row of 768 columns is 630 bytes).  Everything about the routing -- ids, the work list -- is read from
+ * device memory by the launches: no launch parameter depends on it, so the three calls can be captured into a graph.  Nothing here allocates or
+ * synchronises.  Every call returns, with the outputs untouched: NTK_E_NULL (a required pointer is NULL), NTK_E_SHAPE (T, E or K outside the limits,
+ * K > E, a size <= 0, columns that are not whole blocks of the type, a row too long for the 64 KiB of LDS the four waves share: beyond about 16 000
+ * columns), NTK_E_DTYPE (another expert type), NTK_E_ALIGN (float rows not 16-byte aligned, weights at an odd address).
+ *
+ * ntk_moe_route: logits[t][e] = router[e] . xn[t] (router F32 [E][hidden], F32 accumulation), ids[t][0 .. K) = the K largest in descending order (equal
+ * logits: the lower expert first), w[t][k] = exp(l_k - l_0) / sum_j exp(l_j - l_0) over those K (llama.cpp's softmax -> top-K -> renormalise), and the
+ * expert-major work list: offsets[E + 1], pairs[T K] = the pair indices sorted by (expert, pair index), i.e. numpy's stable argsort of ids.ravel().
+ * logits (optional, [T][E]): the raw logits, for tests.  The same bits on every launch: no atomics.
+ * ntk_moe_gate_up: act[p][0 .. inter) = SiLU(Wg[e] . xn[t]) x (Wu[e] . xn[t]), e = ids[p] as the work list names it (w_gate / w_up: [E][inter][hidden]).
+ * ntk_moe_down: y[t][0 .. hidden) = resid[t] + sum over k ascending of w[t][k] x (Wd[e_k] . act[t K + k]) (w_down: [E][hidden][inter]); y may be resid.
+ * part: scratch of T K hidden floats (every pair's products before the sum).  A pair's result does not depend on T or on which pairs share its expert.
+ *
+ * ntk_moe_workspace_layout: byte offsets of the NTK_MOE_WS_* sections (each 256-byte aligned) of one workspace for a pass of up to T rows, and its size
+ * (0: arguments out of range); ntk_moe_workspace_bytes: the size alone. */
+enum { NTK_MOE_WS_XN = 0, NTK_MOE_WS_ACT, NTK_MOE_WS_PART, NTK_MOE_WS_W, NTK_MOE_WS_IDS, NTK_MOE_WS_PAIRS, NTK_MOE_WS_OFFSETS, NTK_MOE_WS_SECTIONS };
+size_t ntk_moe_workspace_layout(int T, int E, int K, int inter, int hidden, size_t off[NTK_MOE_WS_SECTIONS]);
+size_t ntk_moe_workspace_bytes(int T, int E, int K, int inter, int hidden);
+/* LDS bytes a launch needs for rows of `columns` columns: ntk_moe_gate_up stages a row of each of its two matrices per wave (dt_a, dt_b), ntk_moe_down one
+ * (dt_b < 0); 0: a type that is not taken or columns that are not whole blocks.  A launch beyond NTK_MOE_LDS_MAX returns NTK_E_SHAPE: the engine refuses
+ * such a file at load. */
+#define NTK_MOE_LDS_MAX 65536
+size_t ntk_moe_lds_bytes(int dt_a, int dt_b, int columns);
+int ntk_moe_route(const float* xn, const float* router, int T, int hidden, int E, int K, int* ids, float* w, int* offsets, int* pairs, float* logits,
+                  void* stream);
+int ntk_moe_gate_up(float* act, const float* xn, const void* w_gate, int dt_gate, const void* w_up, int dt_up, const int* offsets, const int* pairs,
+                    int T, int hidden, int inter, int E, int K, void* stream);
+int ntk_moe_down(float* y, const float* resid, const float* act, const void* w_down, int dt_down, const int* ids, const float* w, const int* offsets,
+                 const int* pairs, float* part, int T, int hidden, int inter, int E, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -311,6 +311,11 @@ int   nt_engine_qkv_bias(nt_engine_t e);
 /* In how many layers the LOADED engine normalises every head of Q and K (blk.N.attn_q_norm.weight + attn_k_norm.weight, F32 [head_dim], a pair per layer;
  * RMSNorm behind the bias and ahead of the rotation: ntk_qk_norm); 0 for a Llama or Qwen2 model, whose launches are unchanged; -1 without a loaded engine. */
 int   nt_engine_qk_norm(nt_engine_t e);
+/* How many layers of the loaded model are mixture-of-experts layers (blk.N.ffn_gate_inp.weight + ffn_{gate,up,down}_exps.weight: their FFN is
+ * ntk_rmsnorm -> ntk_moe_route -> ntk_moe_gate_up -> ntk_moe_down, the experts chosen on the device); *experts / *used (each optional) receive the
+ * expert count E and the experts per token K, 0 for a model without such a layer, whose launches are unchanged; -1 without a loaded engine.
+ * nt_gguf_describe reports "expert_count", "expert_used_count", "expert_feed_forward_length" (0 where the file names none) and "moe_layers". */
+int   nt_engine_moe(nt_engine_t e, int* experts, int* used);
 /* The rotation a LOADED engine runs with, as JSON: "rope_theta", "rope_scaling_type" ("none" | "linear" | "llama3"; a file's "yarn" / unknown type is
  * reported as it is named, and is not applied), "rope_freq_scale", "rope_factors" (per-pair divisors folded into the frequency table: 0 or head_dim / 2),
  * "rope_orig_ctx".  Returns bytes needed (excl. NUL) or negative. */

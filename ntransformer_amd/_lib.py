@@ -158,6 +158,12 @@ def lib() -> C.CDLL:
         "ntk_advance_pos": (i, [vp, vp]),
         "ntk_qkv_bias": (i, [vp, vp, vp, vp, vp, vp, i, i, i, vp]),
         "ntk_qk_norm": (i, [vp, vp, vp, vp, i, i, i, i, f, vp]),
+        "ntk_moe_workspace_layout": (sz, [i, i, i, i, i, C.POINTER(sz)]),
+        "ntk_moe_workspace_bytes": (sz, [i, i, i, i, i]),
+        "ntk_moe_lds_bytes": (sz, [i, i, i]),
+        "ntk_moe_route": (i, [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp]),
+        "ntk_moe_gate_up": (i, [vp, vp, vp, i, vp, i, vp, vp, i, i, i, i, i, vp]),
+        "ntk_moe_down": (i, [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
         "ntk_debug_sclk": (i, [vp, vp]),
         "ntk_debug_sclk_begin": (i, [vp, vp, vp]),
         "ntk_debug_sclk_end": (i, [vp, vp]),

@@ -42,7 +42,7 @@ static void usage(const char* prog) {
             "  --rope-freq-scale <float> RoPE linear position scale, overriding the model's\n"
             "  --context-shift          At the end of the context drop half of the oldest positions and go on (default: stop there)\n"
             "  --keep <int>             Leading positions a context shift never drops (default: 1, the BOS)\n"
-            "  --synthetic <shape:mix>  8b|70b|tiny|qwen2.5-7b|qwen3-8b|qwen3-4b : Q8_0|Q4_K_M|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
+            "  --synthetic <shape:mix>  8b|70b|tiny|qwen2.5-7b|qwen3-8b|qwen3-4b|qwen3-30b-a3b|mixtral-8x7b : Q8_0|Q4_K_M|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
             "Accepted for CLI compatibility, no effect on the output (weights are always resident in 288 GB HBM;\n"
             "speculative decoding only changes speed, and plain decode is what runs):\n"
             "  --streaming --draft-model <p> --draft-k <n> --self-spec\n"
@@ -173,6 +173,16 @@ int main(int argc, char** argv) {
             s.hidden = b8 ? 4096 : 2560; s.inter = b8 ? 12288 : 9728; s.layers = 36; s.heads = 32; s.kv_heads = 8; s.vocab = 151936; s.ctx = 40960;
             s.eps = 1e-6f; s.theta = 1e6f; s.bos = 151643; s.eos = 151645;
             s.mix = std::string(norm ? "qwen3-" : "") + "hd128" + (b8 ? ":" : "-tied:") + s.mix;
+        }
+        else if (shape == "qwen3-30b-a3b") {   // Qwen3-30B-A3B: 128 experts of width 768, 8 per token, in every layer; Q / K norms, 32 / 4 heads of 128 over a hidden size of 2048
+            s.hidden = 2048; s.inter = 6144; s.layers = 48; s.heads = 32; s.kv_heads = 4; s.vocab = 151936; s.ctx = 40960;
+            s.eps = 1e-6f; s.theta = 1e6f; s.bos = 151643; s.eos = 151645;
+            s.mix = "qwen3-hd128-moe128x8-i768:" + s.mix;
+        }
+        else if (shape == "mixtral-8x7b") {   // Mixtral 8x7B under `llama`: 8 experts of width 14336 (= feed_forward_length), 2 per token
+            s.hidden = 4096; s.inter = 14336; s.layers = 32; s.heads = 32; s.kv_heads = 8; s.vocab = 32000; s.ctx = 32768;
+            s.eps = 1e-5f; s.theta = 1e6f; s.bos = 1; s.eos = 2;
+            s.mix = "moe8x2:" + s.mix;
         }
         else if (shape != "8b") { fprintf(stderr, "unknown synthetic shape %s\n", shape.c_str()); return 1; }
         st = engine.load_synthetic(s, max_context);

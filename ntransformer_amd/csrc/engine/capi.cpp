@@ -444,14 +444,17 @@ int nt_gguf_describe(const char* path, char* out, int cap) {
         j += b;
         json_escape(j, c.rope_scaling_type);
         j += "\",";
-        int n_bias = 0, n_qk_norm = 0;   // blk.<i>.attn_{q,k,v}.bias; blk.<i>.attn_{q,k}_norm.weight
+        int n_bias = 0, n_qk_norm = 0, n_moe = 0;   // blk.<i>.attn_{q,k,v}.bias; blk.<i>.attn_{q,k}_norm.weight; blk.<i>.ffn_gate_inp.weight (the router of a mixture-of-experts layer)
         for (const auto& t : f.tensors()) {
             int li = -1, at = 0;
             if (sscanf(t.name.c_str(), "blk.%d.%n", &li, &at) != 1 || at == 0) continue;
             const std::string rest = t.name.substr((size_t)at);
             n_bias += rest == "attn_q.bias" || rest == "attn_k.bias" || rest == "attn_v.bias";
             n_qk_norm += rest == "attn_q_norm.weight" || rest == "attn_k_norm.weight";
+            n_moe += rest == "ffn_gate_inp.weight";
         }
+        j += "\"expert_count\":" + std::to_string(c.expert_count) + ",\"expert_used_count\":" + std::to_string(c.expert_used_count) + ",";
+        j += "\"expert_feed_forward_length\":" + std::to_string(c.expert_ff_length) + ",\"moe_layers\":" + std::to_string(n_moe) + ",";
         j += "\"qkv_bias_tensors\":" + std::to_string(n_bias) + ",";
         j += "\"qk_norm_tensors\":" + std::to_string(n_qk_norm) + ",";
         j += "\"architecture\":\""; json_escape(j, c.architecture); j += "\",\"name\":\""; json_escape(j, c.model_name);
@@ -497,6 +500,14 @@ int nt_engine_rope_info(nt_engine_t e, char* out, int cap) {
 
 int nt_engine_qkv_bias(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().qkv_bias_layers() : -1; }
 int nt_engine_qk_norm(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().qk_norm_layers() : -1; }
+int nt_engine_moe(nt_engine_t e, int* experts, int* used) {
+    if (!e || !E(e)->loaded()) return -1;
+    const nt::Model& m = E(e)->model();
+    const int n = m.moe_layers();
+    if (experts) *experts = n ? m.config().expert_count : 0;
+    if (used) *used = n ? m.config().expert_used_count : 0;
+    return n;
+}
 
 int nt_rope_llama3_factors(int head_dim, float theta, float factor, float low_freq_factor, float high_freq_factor, int orig_ctx, float* out) {
     return nt::rope_llama3_factors(head_dim, theta, factor, low_freq_factor, high_freq_factor, orig_ctx, out);   // host only

@@ -48,6 +48,7 @@ void ModelConfig::print() const {   // same fields the reference prints (config.
     fprintf(stderr, "RoPE theta: %.1f, GQA: %s (group=%d)\n", rope_theta, n_kv_heads < n_heads ? "yes" : "no",
             n_kv_heads > 0 ? n_heads / n_kv_heads : 0);
     fprintf(stderr, "BOS: %d, EOS: %d\n", bos_token_id, eos_token_id);
+    if (expert_count > 0) fprintf(stderr, "Experts: %d, used per token: %d, expert FFN width: %d\n", expert_count, expert_used_count, expert_ff_length);
 }
 
 namespace {
@@ -219,6 +220,10 @@ int GgufFile::parse() {   // reference loader.cpp:56-187
         }
         m.head_dim = (int)hd;
     }
+    // mixture-of-experts keys (Qwen3-MoE, Mixtral); the Model holds them to its limits where the file carries expert tensors
+    m.expert_count = geti(pre + "expert_count", 0);
+    m.expert_used_count = geti(pre + "expert_used_count", 0);
+    m.expert_ff_length = geti(pre + "expert_feed_forward_length", m.expert_count > 0 ? m.intermediate_size : 0);
     m.max_seq_len = geti(pre + "context_length", m.max_seq_len);
     m.norm_eps = getf(pre + "attention.layer_norm_rms_epsilon", m.norm_eps);
     m.rope_theta = getf(pre + "rope.freq_base", m.rope_theta);

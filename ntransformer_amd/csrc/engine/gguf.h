@@ -28,6 +28,9 @@ struct ModelConfig {   // reference src/model/config.h:16-60 (same defaults)
     int rope_orig_ctx = 0;          // <arch>.rope.scaling.original_context_length (0: absent)
     int rope_factors = 0;           // elements of the tensor rope_freqs.weight (0: absent); a loaded Model: the divisors folded into its frequency table
     bool rope_interleaved = false;  // never set by the reference (config.h:36): NeoX pairing always
+    int expert_count = 0;           // <arch>.expert_count (E; 0: absent -- a dense model)
+    int expert_used_count = 0;      // <arch>.expert_used_count (K experts per token)
+    int expert_ff_length = 0;       // <arch>.expert_feed_forward_length (I_e); absent: feed_forward_length where the file has experts (Mixtral under `llama`)
     int max_seq_len = 4096;
     int bos_token_id = 1;
     int eos_token_id = 2;

@@ -63,6 +63,7 @@ void Model::free_all() {
     rope_factors_.clear();
     batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = batch_recent_ = nullptr; batch_sample_scratch_ = nullptr;
     kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
+    moe_ws_ = nullptr; moe_rows_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;
     positions_ = tokens_dev_ = d_pos_ = d_token_ = nullptr;
     score_logits_ = score_logprob_ = nullptr; score_targets_ = score_top1_ = nullptr; score_cap_ = 0;   // (they were in allocs_)
@@ -148,6 +149,9 @@ uint64_t Model::bytes_per_token(int pos) const {
     uint64_t b = 0;
     for (const auto& L : layers_)
         for (auto m : kLayerMatrices) b += (L.*m).nbytes;
+    for (const auto& L : layers_)   // a mixture-of-experts layer: the router and the K experts a token is routed to, of E
+        if (L.is_moe() && cfg_.expert_count > 0)
+            b += L.router.nbytes + (uint64_t)(L.gate_exps.nbytes + L.up_exps.nbytes + L.down_exps.nbytes) / (uint64_t)cfg_.expert_count * (uint64_t)cfg_.expert_used_count;
     b += output_.nbytes;
     b += (uint64_t)(2 * cfg_.n_layers + 1) * cfg_.hidden_size * 4;
     const uint64_t kv_row = kv_.row_bytes();

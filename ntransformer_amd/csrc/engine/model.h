@@ -39,6 +39,10 @@ struct LayerWeights {
     bool has_qkv_bias() const { return bq.ptr || bk.ptr || bv.ptr; }
     DevTensor q_norm, k_norm;   // the per-head RMSNorm weights of Q and K of a Qwen3-family file (F32 [head_dim], whole on every rank; a pair or neither)
     bool has_qk_norm() const { return q_norm.ptr && k_norm.ptr; }
+    // the routed expert FFN of a mixture-of-experts layer (Qwen3-MoE, Mixtral) IN PLACE of w_gate / w_up / w_down: the F32 router [E][hidden] and the three
+    // 3-D expert tensors as raw GGUF bytes (expert e: the block of out_f rows at e x out_f x row bytes; in_f / out_f are ONE expert's extents).  All four or none.
+    DevTensor router, gate_exps, up_exps, down_exps;
+    bool is_moe() const { return router.ptr != nullptr; }
 };
 // the seven projection matrices of a layer, for whoever visits them all: for (auto m : kLayerMatrices) use(L.*m);
 inline constexpr std::array<DevTensor LayerWeights::*, 7> kLayerMatrices = {&LayerWeights::wq, &LayerWeights::wk, &LayerWeights::wv, &LayerWeights::wo,
@@ -236,6 +240,13 @@ public:
     // the bias launch and ahead of the rotation in both layer loops; a layer without issues the launches it always has.  Refused at load, ahead of the
     // device and naming the tensor: a norm of another type or size, one without its partner, one on a layer the model does not have.
     int qk_norm_layers() const { int n = 0; for (const auto& L : layers_) n += L.has_qk_norm() ? 1 : 0; return n; }
+    // Mixture-of-experts layers (blk.N.ffn_gate_inp.weight + ffn_{gate,up,down}_exps.weight; any architecture, a rule per layer): the FFN of such a layer is
+    // ntk_rmsnorm -> ntk_moe_route -> ntk_moe_gate_up -> ntk_moe_down (csrc/moe.hip) in both layer loops, on the expert tensors' raw GGUF bytes at every
+    // repack level; a dense layer issues the launches it always has.  Refused at load, ahead of the device and naming the tensor or key: both FFN forms
+    // on one layer or a partial quartet, a quartet on a layer the model does not have, a router that is not F32 [E][hidden], an expert tensor that is not
+    // 3-D with the model's extents or not Q8_0 / Q4_K / Q6_K, E or K outside 1 .. 256 / 1 .. min(E, 16), expert keys without a quartet, shared-expert
+    // tensors, tensor parallelism.
+    int moe_layers() const { int n = 0; for (const auto& L : layers_) n += L.is_moe() ? 1 : 0; return n; }
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
     uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included
@@ -377,6 +388,9 @@ private:
     // a buffer an earlier, failed call obtained is kept: only what is missing is allocated
     template <class T> bool dev_need(T*& p, size_t bytes, bool zero) { if (!p) p = static_cast<T*>(dev_alloc(bytes, zero)); return p != nullptr; }
     void prof_mark(int cls, bool begin);
+    // a mixture-of-experts layer's FFN on T rows: x [T][H] -> RMSNorm with ffn_norm -> route -> gate | up -> down, io = io + ... in place (model_decode.cpp).
+    // marks: profiler class marks around the launches (the fused token)
+    int moe_ffn(const LayerWeights& L, float* io, int T, bool marks);
 
     ModelConfig cfg_;
     GgufVocab vocab_;
@@ -443,6 +457,9 @@ private:
     const float* rope_tab() const { return rope_factors_.empty() ? nullptr : rope_inv_freq_; }   // the prompt-side launches' table argument
     RopeScalingOption rope_opt_;     // the options (kept across loads)
     float rope_base_opt_ = 0.0f, rope_scale_opt_ = 0.0f;   // 0: not set
+    uint8_t* moe_ws_ = nullptr;      // the routed FFN's workspace (ntk_moe_workspace_layout for max_seq rows, at most 1024); null: a model without experts
+    size_t moe_off_[8] = {};         // ... its sections' byte offsets
+    int moe_rows_ = 0;               // ... the rows it was sized for
     void* stream_ = nullptr;
     bool batched_prefill_ = true;
     struct Timed { int cls; void* a; void* b; int n; bool shared_a; };   // n launches between events a and b

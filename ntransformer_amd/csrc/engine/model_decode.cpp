@@ -166,6 +166,10 @@ int Model::enqueue_layers(int first, int last_layer) {
                 cfg_.rope_theta, cfg_.rope_freq_scale, attention_splits(attn_regime_, hd), attn_scratch_, s));
         prof_mark(1, false);
         NT_TRY(project_add(L.wo, act.attn_out, 2));
+        if (L.is_moe()) {   // a mixture-of-experts layer: norm, route, gate | up, down as four nodes of the captured token, the experts chosen on the device
+            NT_TRY(moe_ffn(L, hidden1_, 1, true));
+            continue;
+        }
         const DevTensor* const ffn[2] = {&L.w_gate, &L.w_up};
         float* const ffn_out[2] = {act.gate, act.up};
         // one fusable format: SiLU x up in the launch's epilogue, one profiler interval whichever form takes it; otherwise a launch of its own
@@ -175,6 +179,40 @@ int Model::enqueue_layers(int first, int last_layer) {
         if (pair) prof_mark(0, false);
         else NT_TRY(ntk_silu_mul(act.gate, act.gate, act.up, I, s));
         NT_TRY(project_add(L.w_down, act.gate, 8));
+    }
+    return NTK_OK;
+}
+
+// The routed expert FFN of a mixture-of-experts layer on the T rows io [T][H], in place: RMSNorm with ffn_norm into F32 rows of the workspace, the router's
+// top-K and work list, SiLU(gate) x up of every (row, expert) pair, the weighted down projections added to io.  Nothing here depends on the routing: ids,
+// weights and the list stay on the device.  A pass of more rows than the workspace holds goes in pieces (a pair's bits do not depend on the piece).
+int Model::moe_ffn(const LayerWeights& L, float* io, int T, bool marks) {
+    if (!moe_ws_ || moe_rows_ <= 0) return NTK_E_NULL;
+    const int H = cfg_.hidden_size, E = cfg_.expert_count, K = cfg_.expert_used_count, Ie = cfg_.expert_ff_length;
+    void* s = stream_;
+    float* const xn = reinterpret_cast<float*>(moe_ws_ + moe_off_[NTK_MOE_WS_XN]);
+    float* const act = reinterpret_cast<float*>(moe_ws_ + moe_off_[NTK_MOE_WS_ACT]);
+    float* const part = reinterpret_cast<float*>(moe_ws_ + moe_off_[NTK_MOE_WS_PART]);
+    float* const w = reinterpret_cast<float*>(moe_ws_ + moe_off_[NTK_MOE_WS_W]);
+    int* const ids = reinterpret_cast<int*>(moe_ws_ + moe_off_[NTK_MOE_WS_IDS]);
+    int* const pairs = reinterpret_cast<int*>(moe_ws_ + moe_off_[NTK_MOE_WS_PAIRS]);
+    int* const offsets = reinterpret_cast<int*>(moe_ws_ + moe_off_[NTK_MOE_WS_OFFSETS]);
+    auto mark = [&](int cls, bool begin) { if (marks) prof_mark(cls, begin); };
+    for (int t0 = 0; t0 < T; t0 += moe_rows_) {
+        const int n = std::min(moe_rows_, T - t0);
+        float* const x = io + (size_t)t0 * H;
+        mark(2, true);
+        NT_TRY(ntk_rmsnorm(xn, x, (const float*)L.ffn_norm.ptr, n, H, cfg_.norm_eps, s));
+        mark(2, false);
+        mark(2, true);
+        NT_TRY(ntk_moe_route(xn, (const float*)L.router.ptr, n, H, E, K, ids, w, offsets, pairs, nullptr, s));
+        mark(2, false);
+        mark(0, true);
+        NT_TRY(ntk_moe_gate_up(act, xn, L.gate_exps.ptr, L.gate_exps.dtype, L.up_exps.ptr, L.up_exps.dtype, offsets, pairs, n, H, Ie, E, K, s));
+        mark(0, false);
+        mark(0, true);
+        NT_TRY(ntk_moe_down(x, x, act, L.down_exps.ptr, L.down_exps.dtype, ids, w, offsets, pairs, part, n, H, Ie, E, K, s));
+        mark(0, false);
     }
     return NTK_OK;
 }

@@ -68,18 +68,80 @@ static const struct { const char* name; DevTensor LayerWeights::* member; } kLay
     {"attn_k_norm.weight", &LayerWeights::k_norm},
 };
 // per-layer tensors of neighbouring architectures that this engine has no kernel for: a file that carries one is refused rather than run without it
-static const char* const kLayerUnsupported[] = {"attn_output.bias", "ffn_gate.bias", "ffn_up.bias", "ffn_down.bias"};
+static const char* const kLayerUnsupported[] = {"attn_output.bias", "ffn_gate.bias", "ffn_up.bias", "ffn_down.bias",
+                                                // the shared experts of Qwen2-MoE / DeepSeek and DeepSeek's biased routing: not built
+                                                "ffn_gate_inp_shexp.weight", "ffn_gate_shexp.weight", "ffn_up_shexp.weight", "ffn_down_shexp.weight", "exp_probs_b.bias"};
+// the routed expert FFN of a mixture-of-experts layer, in place of the dense ffn_gate / ffn_up / ffn_down trio: the F32 router, ggml dims (hidden, E), and
+// three 3-D expert tensors, dims (in, out, E) -- 'h' hidden, 'e' the expert FFN width.  They stay raw GGUF bytes: no repack, never freed, shared by load_shared.
+static const struct { const char* name; DevTensor LayerWeights::* member; char in, out; } kLayerExperts[] = {
+    {"ffn_gate_inp.weight", &LayerWeights::router, 'h', 'E'},
+    {"ffn_gate_exps.weight", &LayerWeights::gate_exps, 'h', 'e'},
+    {"ffn_up_exps.weight", &LayerWeights::up_exps, 'h', 'e'},
+    {"ffn_down_exps.weight", &LayerWeights::down_exps, 'e', 'h'},
+};
+static const char* const kLayerDenseFfn[] = {"ffn_gate.weight", "ffn_up.weight", "ffn_down.weight"};
 
 int Model::check_layer_extras(const GgufFile& f) {
     const int64_t qd = (int64_t)cfg_.n_heads * cfg_.head_dim, kvd = (int64_t)cfg_.n_kv_heads * cfg_.head_dim;
     std::vector<const GgufTensor*> norms[2];   // the layer's q / k norm by layer index, for the pair rule below
     for (auto& v : norms) v.assign((size_t)std::max(cfg_.n_layers, 0), nullptr);
+    std::vector<const GgufTensor*> experts[4];   // ... and its expert quartet, for the all-or-none rule
+    for (auto& v : experts) v.assign((size_t)std::max(cfg_.n_layers, 0), nullptr);
+    std::vector<const GgufTensor*> dense_ffn((size_t)std::max(cfg_.n_layers, 0), nullptr);   // (any one of the dense trio)
+    const std::string pre = cfg_.architecture + ".";
+    const int64_t H = cfg_.hidden_size, E = cfg_.expert_count, Ie = cfg_.expert_ff_length;
+    bool any_expert = false;
     for (const GgufTensor& t : f.tensors()) {   // every "blk.<i>.<name>" of the file, whatever its index: a tensor behind the last layer is not passed over either
         int li = -1, at = 0;
         if (sscanf(t.name.c_str(), "blk.%d.%n", &li, &at) != 1 || at == 0) continue;
         const char* const rest = t.name.c_str() + at;
         for (const char* u : kLayerUnsupported)
-            if (strcmp(rest, u) == 0) { err_ = "Unsupported tensor " + t.name + ": this engine runs Llama, Qwen2 and Qwen3 layers (no attention-output or FFN bias)"; return NTK_E_FORMAT; }
+            if (strcmp(rest, u) == 0) { err_ = "Unsupported tensor " + t.name + ": this engine runs Llama, Qwen2, Qwen3 and routed mixture-of-experts layers (no attention-output or FFN bias, no shared experts or biased routing)"; return NTK_E_FORMAT; }
+        for (const char* d : kLayerDenseFfn)
+            if (strcmp(rest, d) == 0 && li >= 0 && li < cfg_.n_layers) dense_ffn[(size_t)li] = &t;
+        for (int w = 0; w < 4; ++w) {
+            if (strcmp(rest, kLayerExperts[w].name) != 0) continue;
+            if (li < 0 || li >= cfg_.n_layers) {
+                err_ = "Unsupported tensor " + t.name + ": the model has " + std::to_string(cfg_.n_layers) + " layers";
+                return NTK_E_FORMAT;
+            }
+            if (tp_world_ > 1) { err_ = "Unsupported tensor " + t.name + ": tensor parallelism over a mixture-of-experts layer is not built"; return NTK_E_SHAPE; }
+            // the keys first: every extent below is measured against them
+            if (E < 1 || E > 256) { err_ = pre + "expert_count = " + std::to_string(E) + ": 1 .. 256 experts are supported (" + t.name + ")"; return NTK_E_SHAPE; }
+            if (cfg_.expert_used_count < 1 || cfg_.expert_used_count > std::min<int64_t>(E, 16)) {
+                err_ = pre + "expert_used_count = " + std::to_string(cfg_.expert_used_count) + ": 1 .. min(expert_count, 16) experts per token are supported (" + t.name + ")";
+                return NTK_E_SHAPE;
+            }
+            if (Ie < 1) { err_ = pre + "expert_feed_forward_length is missing or not positive (" + t.name + ")"; return NTK_E_SHAPE; }
+            if (w == 0) {
+                if (t.dtype != NTK_DT_F32 || !t.known_type) { err_ = t.name + " must be F32"; return NTK_E_DTYPE; }
+                if (t.numel() != H * E || (t.dims.size() >= 1 && t.dims[0] != H)) {
+                    err_ = t.name + " holds " + std::to_string(t.numel()) + " values, hidden x expert_count = " + std::to_string(H) + " x " + std::to_string(E) + " are needed";
+                    return NTK_E_SHAPE;
+                }
+            } else {
+                const int64_t in = kLayerExperts[w].in == 'h' ? H : Ie, out = kLayerExperts[w].out == 'h' ? H : Ie;
+                if (t.dims.size() != 3 || t.dims[0] != in || t.dims[1] != out || t.dims[2] != E) {
+                    err_ = "Unexpected shape for " + t.name + ": a 3-D tensor of dims (" + std::to_string(in) + ", " + std::to_string(out) + ", " + std::to_string(E) + ") is needed";
+                    return NTK_E_SHAPE;
+                }
+                if (!t.known_type || (t.dtype != NTK_DT_Q8_0 && t.dtype != NTK_DT_Q4_K && t.dtype != NTK_DT_Q6_K)) {
+                    err_ = "Unsupported tensor type for " + t.name + ": expert matrices are Q8_0, Q4_K or Q6_K";
+                    return NTK_E_DTYPE;
+                }
+                if (ntk_row_bytes(t.dtype, in) == 0) {   // (a width the type cannot hold: Q4_K / Q6_K rows of a width that is no multiple of 256)
+                    err_ = "Unexpected shape for " + t.name + ": rows of " + std::to_string(in) + " columns are not whole blocks of " + dtype_name(t.dtype);
+                    return NTK_E_SHAPE;
+                }
+                if (ntk_moe_lds_bytes(t.dtype, -1, (int)std::min<int64_t>(in, 0x7FFFFFFF)) > NTK_MOE_LDS_MAX) {   // (one row per wave must fit the launch's LDS)
+                    err_ = "Unexpected shape for " + t.name + ": rows of " + std::to_string(in) + " " + dtype_name(t.dtype) + " columns are beyond what the expert GEMV stages (" +
+                           std::to_string(NTK_MOE_LDS_MAX) + " bytes of LDS for four rows)";
+                    return NTK_E_SHAPE;
+                }
+            }
+            experts[w][(size_t)li] = &t;
+            any_expert = true;
+        }
         for (int w = 0; w < 2; ++w) {
             if (strcmp(rest, kLayerQkNorms[w].name) != 0) continue;
             if (li < 0 || li >= cfg_.n_layers) {
@@ -109,6 +171,32 @@ int Model::check_layer_extras(const GgufFile& f) {
             err_ = "Unsupported tensor " + lone->name + ": layer " + std::to_string(i) + " carries it without its partner (attn_q_norm.weight and attn_k_norm.weight come as a pair)";
             return NTK_E_FORMAT;
         }
+    }
+    for (size_t i = 0; i < dense_ffn.size(); ++i) {   // a layer carries the dense trio or the whole quartet
+        int have = 0, missing = -1;
+        const GgufTensor* first = nullptr;
+        for (int w = 0; w < 4; ++w) {
+            if (experts[w][i]) { ++have; if (!first) first = experts[w][i]; }
+            else if (missing < 0) missing = w;
+        }
+        if (have && dense_ffn[i]) {
+            err_ = "Unsupported tensor " + first->name + ": layer " + std::to_string(i) + " also carries " + dense_ffn[i]->name + " (a layer has the dense FFN or the experts, not both)";
+            return NTK_E_FORMAT;
+        }
+        if (have == 4 && ntk_moe_lds_bytes(experts[1][i]->dtype, experts[2][i]->dtype, (int)H) > NTK_MOE_LDS_MAX) {   // gate | up stage a row of each per wave
+            err_ = "Unexpected shape for " + experts[2][i]->name + ": rows of " + std::to_string(H) + " columns of " + dtype_name(experts[1][i]->dtype) + " gate and " +
+                   dtype_name(experts[2][i]->dtype) + " up experts are beyond what the expert GEMV stages (" + std::to_string(NTK_MOE_LDS_MAX) + " bytes of LDS for four row pairs)";
+            return NTK_E_SHAPE;
+        }
+        if (have && have < 4) {
+            err_ = "Tensor not found: blk." + std::to_string(i) + "." + kLayerExperts[missing].name + " (layer " + std::to_string(i) + " carries " + first->name + ": the router and the three expert tensors come together)";
+            return NTK_E_FORMAT;
+        }
+    }
+    if (!any_expert && (cfg_.expert_count > 0 || cfg_.expert_used_count > 0)) {
+        err_ = pre + (cfg_.expert_count > 0 ? "expert_count = " + std::to_string(cfg_.expert_count) : "expert_used_count = " + std::to_string(cfg_.expert_used_count)) +
+               ": the file names experts and carries no blk.N.ffn_gate_inp.weight / ffn_*_exps.weight";
+        return NTK_E_FORMAT;
     }
     return NTK_OK;
 }
@@ -165,7 +253,19 @@ int Model::load_impl(const std::string& path, int max_context) {
     }
     NT_TRY(take("output_norm.weight"));
     for (int i = 0; i < cfg_.n_layers; ++i) {   // transformer.cpp:286-328
-        for (const auto& e : kLayerTensors) NT_TRY(take("blk." + std::to_string(i) + "." + e.name));
+        const std::string blk = "blk." + std::to_string(i) + ".";
+        const bool moe = f.find(blk + kLayerExperts[0].name) != nullptr;   // (check_layer_extras: the whole quartet and no dense trio, or the reverse)
+        for (const auto& e : kLayerTensors) {
+            if (moe && (e.member == &LayerWeights::w_gate || e.member == &LayerWeights::w_up || e.member == &LayerWeights::w_down)) continue;
+            NT_TRY(take(blk + e.name));
+        }
+        for (const auto& e : kLayerExperts) {   // held to type and extents by the pre-pass; uploaded whole, as the file has them
+            if (!moe) break;
+            const GgufTensor* t = f.find(blk + e.name);
+            TensorSlot sl;
+            if (!t || !slot_of(blk + e.name, &sl)) { err_ = "Tensor not found: " + blk + e.name; return NTK_E_FORMAT; }
+            NT_TRY(upload(*sl.dst, f.data(*t), t->dtype, sl.in_f, sl.out_f, t->nbytes));
+        }
         // the optional biases.  take()'s checks do not run here: check_layer_extras() -- called above, ahead of the device -- has held every bias of the
         // file to F32 and to its slot's element count, and a loader that gets here another way must do the same before it uploads one
         for (const auto& e : kLayerBiases) {
@@ -200,6 +300,10 @@ bool Model::slot_of(const std::string& name, TensorSlot* sl) {
         if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), ROWS, 1, extent(e.out)}; return true; }
     for (const auto& e : kLayerQkNorms)   // [head_dim] values, whole on every rank
         if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), WHOLE, hd, 1}; return true; }
+    for (const auto& e : kLayerExperts) {   // ONE expert's [out][in] (the router: [E][hidden]); the tensor holds expert_count of them back to back
+        auto ext = [&](char c) -> int64_t { return c == 'h' ? H : c == 'E' ? cfg_.expert_count : cfg_.expert_ff_length; };
+        if (name.compare(at, std::string::npos, e.name) == 0) { *sl = {&(layers_[li].*e.member), WHOLE, ext(e.in), ext(e.out)}; return true; }
+    }
     return false;
 }
 
@@ -210,7 +314,11 @@ int Model::load_synthetic(const SynthSpec& spec, int max_context, int nthreads) 
     cfg_ = ModelConfig();
     cfg_.model_name = "synthetic-" + spec.mix;
     const SynthFlavour fl = synth_flavour(spec.mix);
-    if (fl.qwen2 || fl.qwen3) cfg_.architecture = fl.qwen3 ? "qwen3" : "qwen2";
+    if (fl.qwen2 || fl.qwen3) cfg_.architecture = fl.qwen3 ? (fl.experts ? "qwen3moe" : "qwen3") : "qwen2";
+    if (fl.experts) {   // (synth_plan has held the counts to the engine's limits)
+        if (tp_world_ > 1) { err_ = "tensor parallelism over a mixture-of-experts model is not built"; return NTK_E_SHAPE; }
+        cfg_.expert_count = fl.experts; cfg_.expert_used_count = fl.used; cfg_.expert_ff_length = fl.expert_inter > 0 ? fl.expert_inter : spec.inter;
+    }
     cfg_.vocab_size = spec.vocab; cfg_.hidden_size = spec.hidden; cfg_.intermediate_size = spec.inter;
     cfg_.n_layers = spec.layers; cfg_.n_heads = spec.heads; cfg_.n_kv_heads = spec.kv_heads;
     cfg_.head_dim = fl.head_dim ? fl.head_dim : spec.hidden / spec.heads;   // (synth_plan has held it to a positive even value)
@@ -232,7 +340,9 @@ int Model::load_synthetic(const SynthSpec& spec, int max_context, int nthreads) 
         synth_fill(stage, t, spec.seed, nthreads);
         TensorSlot sl;
         if (!slot_of(t.name, &sl)) { rc = NTK_E_FORMAT; break; }
-        rc = upload_shard(*sl.dst, stage, ggml_type_to_dtype((uint32_t)t.ggml_type), t.in_f, t.out_f, t.nbytes, sl.how);
+        // (an expert tensor: ONE expert's extents, the bytes of all of them)
+        if (t.experts > 0) rc = upload(*sl.dst, stage, ggml_type_to_dtype((uint32_t)t.ggml_type), sl.in_f, sl.out_f, t.nbytes);
+        else rc = upload_shard(*sl.dst, stage, ggml_type_to_dtype((uint32_t)t.ggml_type), t.in_f, t.out_f, t.nbytes, sl.how);
         if (rc != NTK_OK) break;
     }
     nt_hip_free_host(stage);
@@ -281,8 +391,8 @@ int Model::finish_load() {
             q8_twice ? (", of which " + std::to_string(q8_twice / 1073741824.0).substr(0, 5) + " GB extra: Q8_0 matrices keep their GGUF bytes beside the repack").c_str() : "",
             fr / 1073741824.0);
     if (!layers_.empty())   // the formats a user chose the file for: an unquantised model says so
-        fprintf(stderr, "Weight types: attn_q %s, ffn_down %s, output %s, token_embd %s\n", dtype_name(layers_[0].wq.dtype), dtype_name(layers_[0].w_down.dtype),
-                dtype_name(output_.dtype), dtype_name(token_embd_.dtype));
+        fprintf(stderr, "Weight types: attn_q %s, ffn_down %s, output %s, token_embd %s\n", dtype_name(layers_[0].wq.dtype),
+                dtype_name(layers_[0].is_moe() ? layers_[0].down_exps.dtype : layers_[0].w_down.dtype), dtype_name(output_.dtype), dtype_name(token_embd_.dtype));
     return NTK_OK;
 }
 
@@ -432,6 +542,14 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     }
     gemm_ws_ = dev_alloc(gemm_ws_bytes_, false);
     gemm_ws2_ = dev_alloc(gemm_ws_bytes_, false);
+    moe_ws_ = nullptr; moe_rows_ = 0;
+    if (moe_layers() > 0) {   // the routed FFN's workspace: normed rows, act, per-pair products, w, ids, the work list -- for passes of up to 1024 rows (longer ones go in pieces)
+        moe_rows_ = (int)std::min<size_t>(S, 1024);
+        const size_t n = ntk_moe_workspace_layout(moe_rows_, cfg_.expert_count, cfg_.expert_used_count, cfg_.expert_ff_length, cfg_.hidden_size, moe_off_);
+        if (n == 0) { err_ = "mixture-of-experts workspace: expert counts out of range"; return NTK_E_SHAPE; }
+        moe_ws_ = (uint8_t*)dev_alloc(n, true);
+        if (!moe_ws_) { err_ = "buffer allocation failed (mixture-of-experts workspace)"; return NTK_E_NOMEM; }
+    }
     if (tp_world_ > 1) {   // communication buffer: flags + two slots of one prompt's worth of hidden vectors
         tp_max_floats_ = S * H;
         tp_comm_ = ntk_tp_comm_alloc(ntk_tp_comm_bytes(tp_max_floats_));   // fine-grained: csrc/tp.hip

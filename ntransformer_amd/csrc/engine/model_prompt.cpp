@@ -318,6 +318,13 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
             kv_capture_T_ = T;
         }
         ok(attend(i, T, start_pos, kv, act, with_max));
+        if (L.is_moe()) {   // a mixture-of-experts layer: the plain output projection, then an unfused RMSNorm into F32 rows (no operand planes, no row maxima) and
+            // the three routed-FFN launches on the T rows, in place on hidden_; the next layer's norm is not folded into anything (normed_ahead stays false)
+            project_add(L.wo, act.attn_out, qd, nullptr);
+            ok(moe_ffn(L, hidden_, T, false));
+            if (ok.rc != NTK_OK) break;
+            continue;
+        }
         if (!project_add_norm(L.wo, act.attn_out, nullptr, L.ffn_norm, false, L.w_gate)) {
             project_add(L.wo, act.attn_out, qd, nullptr);
             norm(L.ffn_norm, false, L.w_gate);

@@ -2,6 +2,7 @@
 #include "synth.h"
 #include "../../../include/ntk_engine.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -161,6 +162,15 @@ SynthFlavour synth_flavour(const std::string& mix) {
         else if (tok == "tied" && !fl.tied) fl.tied = true;
         else if (tok.size() > 2 && tok.size() <= 8 && tok.compare(0, 2, "hd") == 0 && tok.find_first_not_of("0123456789", 2) == std::string::npos && !fl.head_dim)
             fl.head_dim = atoi(tok.c_str() + 2);   // (0 or odd: synth_plan refuses)
+        else if (tok.size() > 3 && tok.compare(0, 3, "moe") == 0 && !fl.experts) {   // moe<E>x<K> (counts out of range: synth_plan refuses)
+            int e = 0, k = 0, used = 0;
+            if (sscanf(tok.c_str() + 3, "%dx%d%n", &e, &k, &used) != 2 || (size_t)used != tok.size() - 3) return plain;
+            fl.experts = e > 0 ? e : -1; fl.used = k;
+        }
+        else if (tok.size() > 1 && tok.size() <= 8 && tok[0] == 'i' && tok.find_first_not_of("0123456789", 1) == std::string::npos && fl.experts && !fl.expert_inter) {
+            fl.expert_inter = atoi(tok.c_str() + 1);
+            if (fl.expert_inter <= 0) fl.expert_inter = -1;
+        }
         else return plain;   // not a flavour: the whole string is the mix (which synth_plan does not know)
         if (tok.compare(0, 2, "hd") == 0 && fl.head_dim <= 0) fl.head_dim = -1;
         if (dash == std::string::npos) break;
@@ -178,6 +188,8 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     const bool km = fl.mix == "Q4_K_M" || sample_of > 0;
     const int base = km ? 12 : mix_type(fl.mix);
     if (base < 0 || s.heads <= 0 || s.kv_heads <= 0 || (fl.head_dim ? fl.head_dim < 0 || (fl.head_dim & 1) : s.hidden % s.heads)) return false;
+    if (fl.experts && (fl.experts < 1 || fl.experts > 256 || fl.used < 1 || fl.used > std::min(fl.experts, 16) || fl.expert_inter < 0)) return false;
+    const int64_t e_inter = fl.expert_inter > 0 ? fl.expert_inter : s.inter;
     const int hd = fl.head_dim ? fl.head_dim : s.hidden / s.heads;
     const int64_t q_dim = (int64_t)s.heads * hd, kv_dim = (int64_t)s.kv_heads * hd;
     auto add = [&](const std::string& name, int gt, int64_t in_f, int64_t out_f, double sigma) {
@@ -206,6 +218,13 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
         }
         add(p + "attn_output.weight", base, q_dim, s.hidden, 1);
         add(p + "ffn_norm.weight", 0, s.hidden, 1, 0);
+        if (fl.experts) {   // the routed FFN: the router and the experts' matrices, expert after expert in one tensor each
+            add(p + "ffn_gate_inp.weight", 0, s.hidden, fl.experts, 2.0);
+            add(p + "ffn_gate_exps.weight", base, s.hidden, e_inter * fl.experts, 1); out.back().experts = fl.experts;
+            add(p + "ffn_up_exps.weight", base, s.hidden, e_inter * fl.experts, 1); out.back().experts = fl.experts;
+            add(p + "ffn_down_exps.weight", down_t, e_inter, (int64_t)s.hidden * fl.experts, 1); out.back().experts = fl.experts;
+            continue;
+        }
         add(p + "ffn_gate.weight", base, s.hidden, s.inter, 1);
         add(p + "ffn_up.weight", base, s.hidden, s.inter, 1);
         add(p + "ffn_down.weight", down_t, s.inter, s.hidden, 1);
@@ -285,8 +304,9 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
     auto kv_f32 = [&](const char* k, float v) { str(k); u32(6); f32(v); };
     auto kv_str = [&](const char* k, const std::string& v) { str(k); u32(8); str(v); };
     const SynthFlavour fl = synth_flavour(s.mix);
-    u32(0x46554747u); u32(3); u64(plan.size()); u64(fl.head_dim > 0 ? 18 : 16);   // (metadata entries: key_length and value_length with a head size of its own)
-    const std::string arch = fl.qwen3 ? "qwen3" : fl.qwen2 ? "qwen2" : "llama";   // (the hyper-parameters live under the architecture's own prefix)
+    // (metadata entries: key_length and value_length with a head size of its own; the expert counts, and the experts' width where the flavour names it)
+    u32(0x46554747u); u32(3); u64(plan.size()); u64(16 + (fl.head_dim > 0 ? 2 : 0) + (fl.experts ? 2 + (fl.expert_inter > 0 ? 1 : 0) : 0));
+    const std::string arch = fl.qwen3 ? (fl.experts ? "qwen3moe" : "qwen3") : fl.qwen2 ? "qwen2" : "llama";   // (the hyper-parameters live under the architecture's own prefix)
     const auto key = [&](const char* k) { return arch + "." + k; };
     kv_str("general.architecture", arch);
     kv_str("general.name", "synthetic-" + s.mix);
@@ -300,6 +320,11 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
     if (fl.head_dim > 0) {   // a head size of its own
         kv_u32(key("attention.key_length").c_str(), (uint32_t)fl.head_dim);
         kv_u32(key("attention.value_length").c_str(), (uint32_t)fl.head_dim);
+    }
+    if (fl.experts) {
+        kv_u32(key("expert_count").c_str(), (uint32_t)fl.experts);
+        kv_u32(key("expert_used_count").c_str(), (uint32_t)fl.used);
+        if (fl.expert_inter > 0) kv_u32(key("expert_feed_forward_length").c_str(), (uint32_t)fl.expert_inter);
     }
     kv_u32(key("context_length").c_str(), (uint32_t)s.ctx);
     kv_f32(key("attention.layer_norm_rms_epsilon").c_str(), s.eps);
@@ -315,6 +340,7 @@ int synth_write_gguf(const std::string& path, const SynthSpec& s, int nthreads) 
         str(t.name);
         if (t.out_f == 1 && t.sigma <= 0) { u32(1); u64((uint64_t)t.in_f); }
         else if (t.in_f == 1) { u32(1); u64((uint64_t)t.out_f); }   // a bias vector
+        else if (t.experts > 0) { u32(3); u64((uint64_t)t.in_f); u64((uint64_t)(t.out_f / t.experts)); u64((uint64_t)t.experts); }
         else { u32(2); u64((uint64_t)t.in_f); u64((uint64_t)t.out_f); }
         u32((uint32_t)t.ggml_type);
         u64(off);

@@ -16,6 +16,7 @@ struct SynthTensor {
     int64_t in_f, out_f;   // norm vectors: in_f = n, out_f = 1; bias vectors: in_f = 1, out_f = n
     double sigma;          // matrices and biases: the scale of the values; norm vectors: 0 = 1 + 0.05 u, negative = 1 + |sigma| u, u uniform in [-1, 1)
     size_t nbytes;
+    int experts = 0;       // > 0: a 3-D expert tensor -- out_f counts the rows of ALL experts (expert e: rows e out_f / experts ..), written with dims (in_f, out_f / experts, experts)
 };
 
 struct SynthSpec {
@@ -36,7 +37,12 @@ struct SynthSpec {
 // heads a size of their own: <arch>.attention.key_length = value_length = N and projections of heads x N rows, whatever the hidden size.
 // "hd<N>[-tied]:<mix>" = the Llama model with such a head size (Mistral-Nemo's kind; the norm-free twin of a qwen3-hd<N> model).
 // The general form is a '-'-separated list in front of the ':' -- qwen2 | qwen3 first, then hd<N>, tied in any order.
-struct SynthFlavour { bool qwen2, tied; std::string mix; bool qwen3 = false; int head_dim = 0; };
+// "moe<E>x<K>[-i<I_e>]" (with or without qwen3 / hd<N> / tied in front of it) = a mixture-of-experts model: every layer carries, in place of ffn_gate / ffn_up /
+// ffn_down, the F32 router blk.N.ffn_gate_inp.weight (dims (hidden, E), values of scale 2 / sqrt(hidden)) and the 3-D expert tensors ffn_gate_exps /
+// ffn_up_exps (dims (hidden, I_e, E)) and ffn_down_exps ((I_e, hidden, E)) in the types the mix gives the dense matrices; keys <arch>.expert_count = E,
+// expert_used_count = K and -- with -i<I_e> -- expert_feed_forward_length (without it I_e = the spec's inter: Mixtral under `llama`); the architecture of a
+// qwen3 model with experts is "qwen3moe".  E in 1 .. 256, K in 1 .. min(E, 16): anything else is refused by synth_plan.
+struct SynthFlavour { bool qwen2, tied; std::string mix; bool qwen3 = false; int head_dim = 0; int experts = 0, used = 0, expert_inter = 0; };
 SynthFlavour synth_flavour(const std::string& mix);
 // tensor list in file order (token_embd, per-layer 9 tensors -- 12 in the Qwen2, 11 in the Qwen3 flavour --, output_norm, output); false if `mix` is unknown
 bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out);

@@ -48,6 +48,11 @@ PRESETS = {
                      flavour="qwen3-hd128-tied"),
     "qwen3-4b-nonorm": dict(hidden=2560, inter=9728, layers=36, heads=32, kv_heads=8, vocab=151936, ctx=40960, bos=151643, eos=151645, eps=1e-6, theta=1e6,
                             flavour="hd128-tied"),
+    # mixture-of-experts: Qwen3-30B-A3B (128 experts of width 768, 8 per token, every layer) and Mixtral 8x7B under `llama` (8 experts of width 14336, 2 per token)
+    "qwen3-30b-a3b": dict(hidden=2048, inter=6144, layers=48, heads=32, kv_heads=4, vocab=151936, ctx=40960, bos=151643, eos=151645, eps=1e-6, theta=1e6,
+                          flavour="qwen3-hd128-moe128x8-i768"),
+    "mixtral-8x7b": dict(hidden=4096, inter=14336, layers=32, heads=32, kv_heads=8, vocab=32000, ctx=32768, bos=1, eos=2, eps=1e-5, theta=1e6,
+                         flavour="moe8x2"),
 }
 
 
@@ -141,6 +146,7 @@ def _bind():
     L.nt_gguf_describe.argtypes = [C.c_char_p, C.c_char_p, i]
     L.nt_engine_qkv_bias.argtypes = [vp]
     L.nt_engine_qk_norm.argtypes = [vp]
+    L.nt_engine_moe.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L._engine_bound = True
     return L
 
@@ -246,6 +252,16 @@ class Engine:
     def qk_norm(self) -> int:
         """in how many layers the loaded model normalises every head of Q and K (nt_engine_qk_norm): 0 for a Llama or Qwen2 model"""
         return int(self.L.nt_engine_qk_norm(self.h))
+
+    def moe(self) -> int:
+        """how many layers of the loaded model are mixture-of-experts layers (nt_engine_moe): 0 for a dense model; moe_experts() gives (E, K)"""
+        return int(self.L.nt_engine_moe(self.h, None, None))
+
+    def moe_experts(self):
+        """(expert count E, experts per token K) of the loaded model; (0, 0) for a dense model"""
+        e, k = C.c_int(0), C.c_int(0)
+        self.L.nt_engine_moe(self.h, C.byref(e), C.byref(k))
+        return int(e.value), int(k.value)
 
     @property
     def vocab_size(self): return self.L.nt_engine_vocab_size(self.h)

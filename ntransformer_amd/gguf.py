@@ -417,6 +417,15 @@ QWEN3_G128 = LlamaShape("q3g128", 1024, 512, 2, 8, 2, 512, ctx=1024, eps=1e-6, t
 NEMO_128 = LlamaShape("nemo128", 512, 512, 2, 2, 1, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257, head_dim=128)    # 2 x 128 = 256 < hidden
 
 
+# Mixture-of-experts (make_synthetic_llama(..., experts=E, experts_used=K, expert_inter=I_e)): the published geometries and the two-layer shapes of the
+# engine tests.  Qwen3-30B-A3B: 128 experts of width 768, 8 per token; Mixtral 8x7B (architecture `llama`): 8 experts of width 14336, 2 per token
+QWEN3_30B_A3B = LlamaShape("qwen3-30b-a3b", 2048, 6144, 48, 32, 4, 151936, ctx=40960, eps=1e-6, theta=1e6, bos=151643, eos=151645, head_dim=128)
+MIXTRAL_8X7B = LlamaShape("mixtral-8x7b", 4096, 14336, 32, 32, 8, 32000, ctx=32768, eps=1e-5, theta=1e6, bos=1, eos=2)
+MOE_8Q8 = LlamaShape("moe8q8", 256, 512, 2, 4, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257)                    # heads of 64
+MOE_4K = LlamaShape("moe4k", 256, 512, 2, 4, 2, 512, ctx=1024, eps=1e-6, theta=1e6, bos=256, eos=257, head_dim=128)        # heads of 128, key_length
+MIXTRAL_4 = LlamaShape("mixtral4", 512, 256, 2, 4, 2, 512, ctx=1024, eps=1e-5, theta=1e6, bos=256, eos=257)                # I_e = feed_forward_length
+
+
 def model_head_dim(meta: Dict[str, object]) -> int:
     """The head size a file's metadata states: <arch>.attention.key_length where the key is there (Qwen3, Mistral-Nemo), else embedding_length / head_count.
     ValueError names the key when key_length is not a positive even number or value_length differs from it (the engine refuses the same files)."""
@@ -537,7 +546,8 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
                          with_scores: bool = False, overrides: Optional[Dict[str, str]] = None,
                          rope_freqs: Optional[np.ndarray] = None, rope_scaling: Optional[Dict[str, object]] = None,
                          arch: str = "llama", qkv_bias=None, tied: bool = False, extra_tensors: Sequence[TensorSpec] = (),
-                         qk_norm=None, extra_kvs: Sequence[bytes] = ()) -> Dict[str, int]:
+                         qk_norm=None, extra_kvs: Sequence[bytes] = (), experts: Optional[int] = None, experts_used: Optional[int] = None,
+                         expert_inter: Optional[int] = None, router_scale: float = 1.0, moe_layers: Optional[Sequence[int]] = None) -> Dict[str, int]:
     """Write a seeded synthetic Llama-architecture GGUF; returns {tensor name: ggml type}.
     arch: general.architecture and the prefix of the hyper-parameter keys ("llama", "qwen2").  qkv_bias: None (no bias tensors) or the scale of the
     seeded blk.N.attn_{q,k,v}.bias vectors (F32 [out], normal values times the scale, written behind attn_v.weight as llama.cpp's converter orders them);
@@ -547,14 +557,29 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
     uniform in [-1, 1), written behind attn_v.weight and any bias); a dict {"q": s, "k": s} writes only the named ones (the loader's pair rule).  A shape
     with head_dim != 0 gets <arch>.attention.key_length = value_length = head_dim and projections of heads x head_dim rows.  extra_kvs: metadata entries
     (kv_u32(...) ...) appended as given.  Without qk_norm, extra_kvs and shape.head_dim the file is byte for byte what it always was.
+    experts: None (dense layers) or E -- the layers named by moe_layers (None: all of them) carry, in place of ffn_gate / ffn_up / ffn_down, the router
+    blk.N.ffn_gate_inp.weight (F32, dims (hidden, E), normal values times router_scale / sqrt(hidden): logits of about that scale) and the 3-D expert
+    tensors ffn_gate_exps / ffn_up_exps (dims (hidden, I_e, E)) and ffn_down_exps ((I_e, hidden, E)), expert e the contiguous block of rows e I_e .. (e + 1) I_e
+    (hidden for down), in the types the mix gives ffn_gate / ffn_up / ffn_down of that layer (overrides: {"ffn_down_exps": "Q6_K"}); the keys
+    <arch>.expert_count = E, <arch>.expert_used_count = experts_used and -- only where expert_inter is given -- <arch>.expert_feed_forward_length =
+    expert_inter (without it I_e = shape.inter, what Mixtral files under `llama` carry).  Without `experts` the file is byte for byte what it always was.
     overrides: per-matrix types on top of the mix, in every layer ({"ffn_up": "Q4_K"}).
     rope_freqs: the per-pair frequency divisors, appended as the tensor rope_freqs.weight (float32; a float16 array is written as F16, any length is
     written as given: the loader's refusals).  rope_scaling: {"type": "linear" | "yarn" | ..., "factor": F, "original_context_length": N,
     "scale_linear": F (the legacy key)} -> the llama.rope.scaling.* / llama.rope.scale_linear keys that are named.  Both None: nothing is appended."""
     types = tensor_types(shape, mix)
+    moe_at = set(range(shape.layers) if moe_layers is None else moe_layers) if experts else set()
+    for i in sorted(moe_at):          # an expert tensor takes the type the mix gives the dense matrix in its place
+        for m in ("ffn_gate", "ffn_up", "ffn_down"):
+            types["blk.%d.%s_exps.weight" % (i, m)] = types.pop("blk.%d.%s.weight" % (i, m))
     for m, t in (overrides or {}).items():
         for i in range(shape.layers):
+            if m.endswith("_exps") and i not in moe_at:
+                continue
+            if not m.endswith("_exps") and m.startswith("ffn_") and i in moe_at:
+                continue
             types["blk.%d.%s.weight" % (i, m)] = NAME_TO_GGML[t]
+    e_inter = int(expert_inter) if expert_inter else shape.inter
     hd = shape.hd
     q_dim, kv_dim = shape.heads * hd, shape.kv_heads * hd
     dims = {"attn_q": (shape.hidden, q_dim), "attn_k": (shape.hidden, kv_dim), "attn_v": (shape.hidden, kv_dim),
@@ -596,6 +621,15 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
                 specs.append(TensorSpec(name, (hd,), GGML_F32, (1.0 + float(amp) * rng_for(name).uniform(-1, 1, hd)).astype("<f4").tobytes()))
         mat(p + "attn_output.weight", *dims["attn_output"])
         specs.append(TensorSpec(p + "ffn_norm.weight", (shape.hidden,), GGML_F32, norm_w(p + "ffn_norm.weight")))
+        if i in moe_at:
+            name = p + "ffn_gate_inp.weight"
+            specs.append(TensorSpec(name, (shape.hidden, experts), GGML_F32,
+                                    (float(router_scale) / np.sqrt(shape.hidden) * rng_for(name).standard_normal(experts * shape.hidden)).astype("<f4").tobytes()))
+            for m, (in_f, out_f) in (("ffn_gate_exps", (shape.hidden, e_inter)), ("ffn_up_exps", (shape.hidden, e_inter)), ("ffn_down_exps", (e_inter, shape.hidden))):
+                name, t = p + m + ".weight", types[p + m + ".weight"]
+                specs.append(TensorSpec(name, (in_f, out_f, experts), t,
+                                        (lambda n=name, tt=t, o=out_f, ii=in_f: synth_tensor(rng_for(n), tt, o * experts, ii, 1.0))))
+            continue
         for m in ("ffn_gate", "ffn_up", "ffn_down"):
             mat(p + m + ".weight", *dims[m])
     specs.append(TensorSpec("output_norm.weight", (shape.hidden,), GGML_F32, norm_w("output_norm.weight")))
@@ -635,6 +669,11 @@ def make_synthetic_llama(path: str, shape: LlamaShape, mix: str = "Q8_0", seed: 
             kvs.append(kv_u32(arch + ".rope.scaling.original_context_length", int(rope_scaling["original_context_length"])))
         if "scale_linear" in rope_scaling:
             kvs.append(kv_f32(arch + ".rope.scale_linear", float(rope_scaling["scale_linear"])))
+    if experts:
+        kvs.append(kv_u32(arch + ".expert_count", int(experts)))
+        kvs.append(kv_u32(arch + ".expert_used_count", int(experts_used if experts_used is not None else 2)))
+        if expert_inter:
+            kvs.append(kv_u32(arch + ".expert_feed_forward_length", int(expert_inter)))
     kvs.extend(extra_kvs)
     if rope_freqs is not None:
         rf = np.asarray(rope_freqs)

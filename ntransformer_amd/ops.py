@@ -188,6 +188,38 @@ def qk_norm(q, k, wq, wk, n_rows, n_heads, n_kv_heads, head_dim, eps, stream=Non
     check(_lib.lib().ntk_qk_norm(_p(q), _p(k), _p(wq), _p(wk), n_rows, n_heads, n_kv_heads, head_dim, eps, stream), "qk_norm")
 
 
+MOE_WS_SECTIONS = ("xn", "act", "part", "w", "ids", "pairs", "offsets")   # NTK_MOE_WS_*, in order
+
+
+def moe_workspace_layout(T, E, K, inter, hidden):
+    """ntk_moe_workspace_layout: ({section: byte offset}, total bytes) of one routed-FFN workspace for passes of up to T rows; (None, 0) out of range"""
+    off = (C.c_size_t * len(MOE_WS_SECTIONS))()
+    total = int(_lib.lib().ntk_moe_workspace_layout(T, E, K, inter, hidden, off))
+    return (dict(zip(MOE_WS_SECTIONS, [int(o) for o in off])) if total else None), total
+
+
+def moe_workspace_bytes(T, E, K, inter, hidden) -> int:
+    return int(_lib.lib().ntk_moe_workspace_bytes(T, E, K, inter, hidden))
+
+
+def moe_route(xn, router, T, hidden, E, K, ids, w, offsets, pairs, logits=None, stream=None):
+    """ntk_moe_route: the K largest router logits of each of the T rows (ids int32 [T][K], descending, ties to the lower expert), w = softmax over them,
+    and the expert-major work list offsets [E + 1] / pairs [T K]; logits (optional): the raw [T][E] logits"""
+    check(_lib.lib().ntk_moe_route(_p(xn), _p(router), T, hidden, E, K, _p(ids), _p(w), _p(offsets), _p(pairs), _p(logits), stream), "moe_route")
+
+
+def moe_gate_up(act, xn, w_gate, dt_gate, w_up, dt_up, offsets, pairs, T, hidden, inter, E, K, stream=None):
+    """ntk_moe_gate_up: act [T K][inter] = SiLU(Wg[e] . xn[t]) x (Wu[e] . xn[t]) for every pair of the work list"""
+    check(_lib.lib().ntk_moe_gate_up(_p(act), _p(xn), _p(w_gate), int(dt_gate), _p(w_up), int(dt_up), _p(offsets), _p(pairs), T, hidden, inter, E, K, stream),
+          "moe_gate_up")
+
+
+def moe_down(y, resid, act, w_down, dt_down, ids, w, offsets, pairs, part, T, hidden, inter, E, K, stream=None):
+    """ntk_moe_down: y [T][hidden] = resid + sum over k ascending of w[t][k] x (Wd[e_k] . act[t K + k]); y may be resid; part: T K hidden floats of scratch"""
+    check(_lib.lib().ntk_moe_down(_p(y), _p(resid), _p(act), _p(w_down), int(dt_down), _p(ids), _p(w), _p(offsets), _p(pairs), _p(part), T, hidden, inter, E, K,
+                                  stream), "moe_down")
+
+
 def q8l_bytes(rows, in_features) -> int:
     return int(_lib.lib().ntk_q8l_bytes(rows, in_features))
 
