@@ -528,6 +528,22 @@ int ntk_moe_gate_up(float* act, const float* xn, const void* w_gate, int dt_gate
                     int T, int hidden, int inter, int E, int K, void* stream);
 int ntk_moe_down(float* y, const float* resid, const float* act, const void* w_down, int dt_down, const int* ids, const float* w, const int* offsets,
                  const int* pairs, float* part, int T, int hidden, int inter, int E, int K, void* stream);
+/* The PROMPT forms of ntk_moe_gate_up / ntk_moe_down (csrc/moe_gemm.hip): a grouped GEMM on the F32 matrix cores.  Every argument means what it means
+ * above -- the same work list, the same act / part / y layouts, y may be resid -- so either form runs on the same buffers; the limits, the expert types
+ * and every refusal (code for code, outputs untouched) are the GEMV form's, except that no row is too long.  Weights are dequantised to F32 as the dense
+ * prompt GEMM does (csrc/gemm_deq.hip.h) and multiplied with the unrounded F32 activations by v_mfma_f32_16x16x4_f32 with F32 accumulation: results
+ * within the GEMV bar of the GEMV form, in another summation order.  A TILE is up to 16 consecutive work-list entries of one expert; the grid holds
+ * ceil(T K / 16) + E tile slots and each workgroup finds its tile from the offsets on the device (csrc/moe_tiles.h), so no launch parameter depends on
+ * the routing and nothing is atomic.  Offsets are clamped to the list and a pair index outside [0, T K) is skipped, as in the GEMV form.  A pair's bits
+ * do not depend on T, on the pairs it shares a tile with, on its tile or column, or on the launch; a NaN row stays in its own pairs.
+ * ntk_moe_gemm_gate_up: two launches, the gate products waiting in act for the up launch's SiLU(g) x u epilogue, g / (1 + expf(-g)) * u as above;
+ * scratch / scratch_bytes: at least ntk_moe_gemm_scratch_bytes (today 0 for every shape: scratch may then be NULL; fewer bytes: NTK_E_SHAPE).
+ * ntk_moe_gemm_down: the products into part, then the GEMV form's combine, resid[t] + sum_k fmaf(w[p], part[p], s): the same bits for the same part. */
+size_t ntk_moe_gemm_scratch_bytes(int T, int E, int K, int inter, int hidden);   /* may be 0; 0 also for counts out of range */
+int ntk_moe_gemm_gate_up(float* act, const float* xn, const void* w_gate, int dt_gate, const void* w_up, int dt_up, const int* offsets, const int* pairs,
+                         void* scratch, size_t scratch_bytes, int T, int hidden, int inter, int E, int K, void* stream);
+int ntk_moe_gemm_down(float* y, const float* resid, const float* act, const void* w_down, int dt_down, const int* ids, const float* w, const int* offsets,
+                      const int* pairs, float* part, int T, int hidden, int inter, int E, int K, void* stream);
 
 #ifdef __cplusplus
 }

@@ -164,6 +164,9 @@ def lib() -> C.CDLL:
         "ntk_moe_route": (i, [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp]),
         "ntk_moe_gate_up": (i, [vp, vp, vp, i, vp, i, vp, vp, i, i, i, i, i, vp]),
         "ntk_moe_down": (i, [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "ntk_moe_gemm_scratch_bytes": (sz, [i, i, i, i, i]),
+        "ntk_moe_gemm_gate_up": (i, [vp, vp, vp, i, vp, i, vp, vp, vp, sz, i, i, i, i, i, vp]),
+        "ntk_moe_gemm_down": (i, [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
         "ntk_debug_sclk": (i, [vp, vp]),
         "ntk_debug_sclk_begin": (i, [vp, vp, vp]),
         "ntk_debug_sclk_end": (i, [vp, vp]),

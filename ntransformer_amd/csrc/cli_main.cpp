@@ -35,6 +35,7 @@ static void usage(const char* prog) {
             "  --no-fuse / --no-graph   Use the 15-launch/layer sequence / launch eagerly\n"
             "  --no-batched-prefill     Prompt tokens one by one (the reference's GEMV loops) instead of 16 per weight pass\n"
             "  --no-dense-fuse          F16 / BF16 matrices on the 1:1 launchers instead of the fused 16-bit GEMV and the batched prompt GEMM (A/B switch)\n"
+            "  --no-moe-gemm            Prompt passes over mixture-of-experts layers on the expert GEMV instead of the grouped matrix-core GEMM (A/B switch)\n"
             "  --kv-cache <f16|q8_0>    KV cache format (default: f16; q8_0 = 8-bit Q8_0 blocks, 1.0625 bytes per element)\n"
             "  --rope-scaling <s>       file (default: the GGUF's rope_freqs.weight and linear scaling) | none | linear:<factor> |\n"
             "                           llama3:<factor>,<low>,<high>,<orig_ctx> (Llama-3.1 frequency factors computed by the engine)\n"
@@ -128,6 +129,7 @@ int main(int argc, char** argv) {
         else if (a == "--no-batched-prefill") engine.options().batched_prefill = false;
         else if (a == "--no-graph") engine.options().graph = false;
         else if (a == "--no-dense-fuse") (void)engine.model().set_dense_fused(false);
+        else if (a == "--no-moe-gemm") engine.model().set_moe_gemm(false);
         else if (a == "--synthetic") { if (auto v = val()) synthetic = v; }
         else if (a == "--kv-cache") {
             const char* v = val();

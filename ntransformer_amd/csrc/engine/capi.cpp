@@ -76,6 +76,17 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (v != "0" && v != "1") { E(e)->set_error("dense_mfma16 must be 0 or 1"); return NTK_E_SHAPE; }
         E(e)->model().set_dense_mfma16(on);
     }
+    else if (k == "moe_gemm") {   // "1" (default) | "0": prompt passes over mixture-of-experts layers on the grouped matrix-core GEMM, or the expert GEMV at every row count; any time (the A/B switch)
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("moe_gemm must be 0 or 1"); return NTK_E_SHAPE; }
+        E(e)->model().set_moe_gemm(on);
+    }
+    else if (k == "moe_gemm_min_rows") {   // 1 .. 1024: the rows of a pass from which the grouped GEMM is taken (default: the measured threshold, Model::kMoeGemmMinRows); any time
+        char* end = nullptr;
+        const long n = strtol(value, &end, 10);
+        if (end == value || *end != 0 || n < 1 || n > 1024) { E(e)->set_error("moe_gemm_min_rows must be an integer 1 .. 1024"); return NTK_E_SHAPE; }
+        return E(e)->model().set_moe_gemm_min_rows((int)n);
+    }
     else if (k == "persistent" || k == "fuse_attention") {   // accepted and without effect: the structures they selected were retired
         if (on) fprintf(stderr, "note: \"%s\" selected an experiment that lost to the fused launches and was removed (profiles/NEGATIVE_RESULTS.md); the option does nothing\n", key);
     }

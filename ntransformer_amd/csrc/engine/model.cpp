@@ -63,7 +63,7 @@ void Model::free_all() {
     rope_factors_.clear();
     batch_logits_ = batch_logprob_ = batch_attn_scratch_ = nullptr; batch_in_ = batch_next_ = batch_recent_ = nullptr; batch_sample_scratch_ = nullptr;
     kv_capture_ = nullptr; kv_capture_layer_ = -1; kv_capture_T_ = 0;
-    moe_ws_ = nullptr; moe_rows_ = 0;
+    moe_ws_ = nullptr; moe_rows_ = 0; moe_gemm_scratch_ = nullptr; moe_gemm_scratch_bytes_ = 0;
     hidden_ = residual_ = workspace_ = logits_ = argmax_scratch_ = rope_inv_freq_ = attn_scratch_ = row_max_ = nullptr;
     positions_ = tokens_dev_ = d_pos_ = d_token_ = nullptr;
     score_logits_ = score_logprob_ = nullptr; score_targets_ = score_top1_ = nullptr; score_cap_ = 0;   // (they were in allocs_)

@@ -43,6 +43,7 @@ struct LayerWeights {
     // 3-D expert tensors as raw GGUF bytes (expert e: the block of out_f rows at e x out_f x row bytes; in_f / out_f are ONE expert's extents).  All four or none.
     DevTensor router, gate_exps, up_exps, down_exps;
     bool is_moe() const { return router.ptr != nullptr; }
+    bool moe_gemm_ok = false;   // decided at load: the three expert tensors are types, shapes and addresses the grouped prompt GEMM (csrc/moe_gemm.hip) takes
 };
 // the seven projection matrices of a layer, for whoever visits them all: for (auto m : kLayerMatrices) use(L.*m);
 inline constexpr std::array<DevTensor LayerWeights::*, 7> kLayerMatrices = {&LayerWeights::wq, &LayerWeights::wk, &LayerWeights::wv, &LayerWeights::wo,
@@ -247,6 +248,17 @@ public:
     // 3-D with the model's extents or not Q8_0 / Q4_K / Q6_K, E or K outside 1 .. 256 / 1 .. min(E, 16), expert keys without a quartet, shared-expert
     // tensors, tensor parallelism.
     int moe_layers() const { int n = 0; for (const auto& L : layers_) n += L.is_moe() ? 1 : 0; return n; }
+    // A pass of at least moe_gemm_min_rows_ rows over such a layer takes ntk_moe_gemm_gate_up -> ntk_moe_gemm_down (csrc/moe_gemm.hip: the grouped GEMM on the
+    // matrix cores) in place of the two GEMV launches, on the same workspace sections, where option moe_gemm is on and the layer's tensors are ones the GEMM
+    // takes (LayerWeights::moe_gemm_ok; a layer it does not take stays on the GEMV without a word).  The threshold is above 1 whatever is set: the decode
+    // step and its captured graph stay on the GEMV launches, bit for bit.  Both options may be set at any time (the A/B switch).
+    static constexpr int kMoeGemmMinRows = 2;   // profiles/moe_gemm.txt: the smallest measured row count (2 / 4 / .. / 1024) from which the GEMM form wins at that and every larger one, on both shapes
+    void set_moe_gemm(bool on) { moe_gemm_ = on; }
+    int set_moe_gemm_min_rows(int n) {
+        if (n < 1 || n > 1024) { err_ = "moe_gemm_min_rows must be 1 .. 1024"; return NTK_E_SHAPE; }
+        moe_gemm_min_rows_ = n;
+        return NTK_OK;
+    }
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
     uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included
@@ -460,6 +472,10 @@ private:
     uint8_t* moe_ws_ = nullptr;      // the routed FFN's workspace (ntk_moe_workspace_layout for max_seq rows, at most 1024); null: a model without experts
     size_t moe_off_[8] = {};         // ... its sections' byte offsets
     int moe_rows_ = 0;               // ... the rows it was sized for
+    void* moe_gemm_scratch_ = nullptr;   // ntk_moe_gemm_scratch_bytes for moe_rows_ rows (null where that is 0)
+    size_t moe_gemm_scratch_bytes_ = 0;
+    bool moe_gemm_ = true;           // option moe_gemm
+    int moe_gemm_min_rows_ = kMoeGemmMinRows;   // option moe_gemm_min_rows (1 is accepted and means 2: a one-row pass never takes the GEMM)
     void* stream_ = nullptr;
     bool batched_prefill_ = true;
     struct Timed { int cls; void* a; void* b; int n; bool shared_a; };   // n launches between events a and b

@@ -207,11 +207,15 @@ int Model::moe_ffn(const LayerWeights& L, float* io, int T, bool marks) {
         mark(2, true);
         NT_TRY(ntk_moe_route(xn, (const float*)L.router.ptr, n, H, E, K, ids, w, offsets, pairs, nullptr, s));
         mark(2, false);
+        const bool gemm = moe_gemm_ && L.moe_gemm_ok && n >= std::max(2, moe_gemm_min_rows_);   // (one row: always the GEMV launches, the captured token's)
         mark(0, true);
-        NT_TRY(ntk_moe_gate_up(act, xn, L.gate_exps.ptr, L.gate_exps.dtype, L.up_exps.ptr, L.up_exps.dtype, offsets, pairs, n, H, Ie, E, K, s));
+        if (gemm) NT_TRY(ntk_moe_gemm_gate_up(act, xn, L.gate_exps.ptr, L.gate_exps.dtype, L.up_exps.ptr, L.up_exps.dtype, offsets, pairs, moe_gemm_scratch_,
+                                              moe_gemm_scratch_bytes_, n, H, Ie, E, K, s));
+        else NT_TRY(ntk_moe_gate_up(act, xn, L.gate_exps.ptr, L.gate_exps.dtype, L.up_exps.ptr, L.up_exps.dtype, offsets, pairs, n, H, Ie, E, K, s));
         mark(0, false);
         mark(0, true);
-        NT_TRY(ntk_moe_down(x, x, act, L.down_exps.ptr, L.down_exps.dtype, ids, w, offsets, pairs, part, n, H, Ie, E, K, s));
+        if (gemm) NT_TRY(ntk_moe_gemm_down(x, x, act, L.down_exps.ptr, L.down_exps.dtype, ids, w, offsets, pairs, part, n, H, Ie, E, K, s));
+        else NT_TRY(ntk_moe_down(x, x, act, L.down_exps.ptr, L.down_exps.dtype, ids, w, offsets, pairs, part, n, H, Ie, E, K, s));
         mark(0, false);
     }
     return NTK_OK;

@@ -549,6 +549,19 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         if (n == 0) { err_ = "mixture-of-experts workspace: expert counts out of range"; return NTK_E_SHAPE; }
         moe_ws_ = (uint8_t*)dev_alloc(n, true);
         if (!moe_ws_) { err_ = "buffer allocation failed (mixture-of-experts workspace)"; return NTK_E_NOMEM; }
+        moe_gemm_scratch_ = nullptr;
+        moe_gemm_scratch_bytes_ = ntk_moe_gemm_scratch_bytes(moe_rows_, cfg_.expert_count, cfg_.expert_used_count, cfg_.expert_ff_length, cfg_.hidden_size);
+        if (moe_gemm_scratch_bytes_) {
+            moe_gemm_scratch_ = dev_alloc(moe_gemm_scratch_bytes_, false);
+            if (!moe_gemm_scratch_) { err_ = "buffer allocation failed (mixture-of-experts GEMM scratch)"; return NTK_E_NOMEM; }
+        }
+        for (auto& L : layers_) {   // which layers the grouped prompt GEMM takes: the expert types, whole blocks per row, rows at even addresses
+            auto takes = [](const DevTensor& t) {
+                return (t.dtype == NTK_DT_Q8_0 || t.dtype == NTK_DT_Q4_K || t.dtype == NTK_DT_Q6_K) && t.in_f > 0 && t.in_f <= 0x7FFFFFFF &&
+                       ntk_row_bytes(t.dtype, (int)t.in_f) != 0 && (uintptr_t)t.ptr % 2 == 0;
+            };
+            L.moe_gemm_ok = L.is_moe() && takes(L.gate_exps) && takes(L.up_exps) && takes(L.down_exps);
+        }
     }
     if (tp_world_ > 1) {   // communication buffer: flags + two slots of one prompt's worth of hidden vectors
         tp_max_floats_ = S * H;

@@ -220,6 +220,23 @@ def moe_down(y, resid, act, w_down, dt_down, ids, w, offsets, pairs, part, T, hi
                                   stream), "moe_down")
 
 
+def moe_gemm_scratch_bytes(T, E, K, inter, hidden) -> int:
+    """ntk_moe_gemm_scratch_bytes: the scratch ntk_moe_gemm_gate_up wants for a pass of up to T rows (may be 0; 0 also for counts out of range)"""
+    return int(_lib.lib().ntk_moe_gemm_scratch_bytes(T, E, K, inter, hidden))
+
+
+def moe_gemm_gate_up(act, xn, w_gate, dt_gate, w_up, dt_up, offsets, pairs, T, hidden, inter, E, K, scratch=None, scratch_bytes=0, stream=None):
+    """ntk_moe_gemm_gate_up: moe_gate_up's result on the matrix cores (the grouped prompt GEMM); scratch: at least moe_gemm_scratch_bytes bytes, None for 0"""
+    check(_lib.lib().ntk_moe_gemm_gate_up(_p(act), _p(xn), _p(w_gate), int(dt_gate), _p(w_up), int(dt_up), _p(offsets), _p(pairs), _p(scratch),
+                                          int(scratch_bytes), T, hidden, inter, E, K, stream), "moe_gemm_gate_up")
+
+
+def moe_gemm_down(y, resid, act, w_down, dt_down, ids, w, offsets, pairs, part, T, hidden, inter, E, K, stream=None):
+    """ntk_moe_gemm_down: moe_down's result on the matrix cores, the same combine over part; y may be resid"""
+    check(_lib.lib().ntk_moe_gemm_down(_p(y), _p(resid), _p(act), _p(w_down), int(dt_down), _p(ids), _p(w), _p(offsets), _p(pairs), _p(part), T, hidden,
+                                       inter, E, K, stream), "moe_gemm_down")
+
+
 def q8l_bytes(rows, in_features) -> int:
     return int(_lib.lib().ntk_q8l_bytes(rows, in_features))
 
