@@ -43,7 +43,7 @@ typedef struct ntk_gemv_seg {
     const void* W;      /* raw GGUF blocks [rows][in]              */
     float*      y;      /* output [rows]                            */
     int         rows;
-    int         dtype;  /* one format per call, or two for the plain (no resid / SiLU) form: Q4_K with Q6_K or Q5_K;
+    int         dtype;  /* one format per call, or two for the plain (no resid / SiLU) form: Q4_K with Q6_K or Q5_K, Q3_K with Q4_K or Q5_K;
                            NTK_DT_F16 / NTK_DT_BF16 (unquantised rows of 16-bit words): one of them per call */
 } ntk_gemv_seg;
 
@@ -67,7 +67,7 @@ int ntk_q8l_unpack(void* raw, const void* packed, int rows, int in_features, voi
 
 /* Engine-owned load-time repack of a K-quant matrix and the decode GEMV on the int8 matrix cores that reads it (csrc/gemv_rp.hip; SURVEY
  * 7.1 step 7 / 8(b) "Ownership": repack buffers belong to the engine object, the 1:1 ntk_gemv above keeps taking raw GGUF).  Q4_K, Q5_K,
- * Q6_K; in_features % 256 == 0 and <= 32768; rows padded to tiles of 16 inside the buffer.  Same integers, same scales (ntk_rp_dequant gives
+ * Q6_K, Q3_K (three bits per weight as a 2-bit and a 1-bit plane: 1824 bytes per 16 rows x 256 columns, 1.036 x GGUF); in_features % 256 == 0 and <= 32768; rows padded to tiles of 16 inside the buffer.  Same integers, same scales (ntk_rp_dequant gives
  * the GGUF dequantisation bit for bit), 1.028 x / 1.023 x / 1.000 x the GGUF bytes.  Arithmetic: x -> per 256-column super-block three
  * signed base-256 digit planes of rint(x 2^(22-e)) (e = exponent of the block's largest |x|: <= 2^-22 of it per term), exact integer dot
  * products per sub-block on v_mfma_i32_16x16x64_i8, the reference's factorisation (gemm.cu:190-244, 297-354, 421-459) around them.
@@ -80,7 +80,7 @@ size_t ntk_rp_bytes(int dtype, int rows, int in_features);
 int ntk_rp_pack(void* dst, const void* raw, int rows, int in_features, int dtype, void* stream);
 int ntk_rp_dequant(float* out, const void* rp, int rows, int in_features, int dtype, void* stream);
 /* the raw GGUF blocks [rows][in] back from the repacked form, byte for byte (the engine keeps ONE resident copy of a K-quant matrix and unpacks into
- * a scratch in front of the launches that read raw blocks); raw: 4-byte aligned (Q6_K: 2); stream ordered */
+ * a scratch in front of the launches that read raw blocks); raw: 4-byte aligned (Q6_K, Q3_K: 2); stream ordered */
 int ntk_rp_unpack(void* raw, const void* rp, int rows, int in_features, int dtype, void* stream);
 int ntk_gemv_rp(float* y, const void* rp, const float* x, int out_features, int in_features, int weight_dtype, void* stream);
 int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in_features, const float* norm_w, float eps,
@@ -107,7 +107,7 @@ float* ntk_decode_arena_slot(int slot);
 int ntk_debug_gemv_static_x(void);
 
 /* parity instrumentation of the above: the LDS image its prologue builds from x (4 in + 68 in/256 bytes: three digit planes, a zero plane,
- * 64 bytes of sub-block-sum digits and one 2^(e-22) per super-block; nsub = 8: 32-column sub-blocks (Q4_K / Q5_K), 16: Q6_K), and
+ * 64 bytes of sub-block-sum digits and one 2^(e-22) per super-block; nsub = 8: 32-column sub-blocks (Q4_K / Q5_K), 16: Q6_K / Q3_K), and
  * D[16][16] = A[16][64] . B[64][16] on the matrix instruction under the lane maps the kernel assumes */
 int ntk_debug_rp_prologue(uint8_t* out, const float* x, const float* norm_w, float eps, int in_features, int nsub, int nwaves, void* stream);
 int ntk_debug_mfma_i8_probe(int* D, const int8_t* A, const int8_t* B, void* stream);

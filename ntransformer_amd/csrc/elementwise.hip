@@ -125,6 +125,15 @@ __device__ float embed_elem(const uint8_t* __restrict__ table, int tok, int hidd
             const int q = (lo | (((qh[l] >> (2 * g)) & 3) << 4)) - 32;
             return __fmul_rn(__fmul_rn(d, (float)sc), (float)q);
         }
+        case NTK_DT_Q3_K: {   // ggml block_q3_K (not in the reference): w = (d (s - 32)) (q - 4)
+            const uint8_t* b = table + ((size_t)tok * (hidden / 256) + e / 256) * 110;
+            const float d = h2f((uint16_t)(b[108] | (b[109] << 8)));
+            const int w = e & 255, n = w >> 7, j = (w >> 5) & 3, l = w & 31, is = w >> 4, grp = is >> 2, k = is & 3;
+            const uint8_t* a = b + 96;
+            const int sc = (int)(((a[4 * (grp & 1) + k] >> (4 * (grp >> 1))) & 15) | (((a[8 + k] >> (2 * grp)) & 3) << 4)) - 32;
+            const int q = (int)(((b[32 + 32 * n + l] >> (2 * j)) & 3) | (((b[l] >> (4 * n + j)) & 1) << 2)) - 4;
+            return __fmul_rn(__fmul_rn(d, (float)sc), (float)q);
+        }
         default: return 0.0f;   // Q5_K and anything else: the reference zero-fills (transformer.cpp:595-598)
     }
 }
@@ -313,7 +322,7 @@ int ntk_embed_rows(float* out, const void* table, const int* tokens, int n_token
     const int st = last_launch_status();
     if (st != NTK_OK) return st;
     switch (dtype) {   // rows were zero-filled for anything the reference host path has no branch for
-        case NTK_DT_F32: case NTK_DT_F16: case NTK_DT_BF16: case NTK_DT_Q8_0: case NTK_DT_Q4_0: case NTK_DT_Q4_K: case NTK_DT_Q6_K: return NTK_OK;
+        case NTK_DT_F32: case NTK_DT_F16: case NTK_DT_BF16: case NTK_DT_Q8_0: case NTK_DT_Q4_0: case NTK_DT_Q4_K: case NTK_DT_Q6_K: case NTK_DT_Q3_K: return NTK_OK;
         default: return NTK_E_DTYPE;
     }
 }

@@ -22,6 +22,7 @@ int ggml_type_to_dtype(uint32_t t) {
         case 2: return NTK_DT_Q4_0;
         case 8: return NTK_DT_Q8_0;
         case 10: return NTK_DT_Q2_K;
+        case 11: return NTK_DT_Q3_K;   // not in the reference
         case 12: return NTK_DT_Q4_K;
         case 13: return NTK_DT_Q5_K;
         case 14: return NTK_DT_Q6_K;
@@ -32,12 +33,12 @@ int ggml_type_to_dtype(uint32_t t) {
 }
 
 bool ggml_type_known(uint32_t t) {
-    switch (t) { case 0: case 1: case 2: case 8: case 10: case 12: case 13: case 14: case 26: case 30: return true; default: return false; }
+    switch (t) { case 0: case 1: case 2: case 8: case 10: case 11: case 12: case 13: case 14: case 26: case 30: return true; default: return false; }
 }
 
 const char* dtype_name(int dt) {
-    static const char* n[] = {"F32", "F16", "Q8_0", "Q4_0", "Q4_K_M", "Q6_K", "Q5_K", "Q2_K", "I32", "BF16"};
-    return dt >= 0 && dt <= 9 ? n[dt] : "UNKNOWN";
+    static const char* n[] = {"F32", "F16", "Q8_0", "Q4_0", "Q4_K_M", "Q6_K", "Q5_K", "Q2_K", "I32", "BF16", "Q3_K"};
+    return dt >= 0 && dt <= 10 ? n[dt] : "UNKNOWN";
 }
 
 void ModelConfig::print() const {   // same fields the reference prints (config.cpp:52-65)

@@ -91,7 +91,8 @@ struct OperandPlanes {
     void in_current(const float* X, Kind k = fp16) { of = X; kind = k; }     // a projection's pre-pass (or such a producer) has left X's planes in ws[cur]
 };
 
-// the formats and shapes ntk_gemm_quant_f16 takes
+// the formats ntk_gemm_quant_f16 has a decoder for (Q3_K has none: its prompts run on the F32 matrix cores), and the shapes it takes
+static bool f16_fmt(int dt) { return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K; }
 static bool f16_ok(const DevTensor& w) {
     const bool kq = w.dtype == NTK_DT_Q4_0 || w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K;
     return (w.dtype == NTK_DT_Q8_0 || kq) && w.in_f % (kq ? 256 : 128) == 0 && w.out_f % 16 == 0 && (w.ptr || w.rp);
@@ -179,7 +180,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         }
         raw_begin();
         *wp = raw_of(w);
-        return bf16_now ? gemm_group(&Y, &one, 1, X, resid, rm, pt, wp) : (int)NTK_E_DTYPE;
+        return bf16_now && f16_fmt(w.dtype) ? gemm_group(&Y, &one, 1, X, resid, rm, pt, wp) : (int)NTK_E_DTYPE;
     };
     // Y = W . X (+ resid, which may be Y) for all T tokens on the matrix cores: the FP16 GEMM, else the F32-MFMA form.  false: a shape only the per-token
     // loop takes (NTK_E_ALIGN / NTK_E_SHAPE: nothing launched; *wp holds the GGUF bytes for it)
@@ -214,7 +215,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
         for (int a = 0; a < n && batched && (bf16_now || is_dense16(Ws[a]->dtype)); ++a) {
             if (done[a]) continue;
             const bool d16 = is_dense16(Ws[a]->dtype);
-            if (d16 ? !(fusable(Ws[a]->dtype) && dense_mfma16_) : !bf16_now) continue;
+            if (d16 ? !(fusable(Ws[a]->dtype) && dense_mfma16_) : !(bf16_now && f16_fmt(Ws[a]->dtype))) continue;   // (a format without an FP16 decoder: no unpack for a launch that would be refused)
             float* ys[3];
             const DevTensor* ws[3];
             int idx[3], m = 0;
@@ -259,7 +260,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     // hidden += W . X followed by the NEXT RMSNorm (nw; into residual_) as one consumer launch of the projection's K splits (ntk_gemm_quant_f16 with
     // `partials` + ntk_reduce_rmsnorm_*); false = not this shape / format: the caller runs project_add + norm
     auto project_add_norm = [&](const DevTensor& w, const float* X, const float* rm, const DevTensor& nw, bool zero_b, const DevTensor& next_w) -> bool {
-        if (!with_max || tp_world_ > 1 || !is_quant(w.dtype) || (size_t)w.out_f != (size_t)H) return false;
+        if (!with_max || tp_world_ > 1 || !is_quant(w.dtype) || !f16_fmt(w.dtype) || (size_t)w.out_f != (size_t)H) return false;
         ntk_gemm_partials pt;
         prepare_x(X, w);
         // (a launch that does not split K adds the residual in its own epilogue, in place, as project_add does: nothing is deferred then)
@@ -276,7 +277,7 @@ int Model::layers_1to1(int T, int start_pos, int first, int last_layer, const Kv
     // gate | up and SiLU x up (per token in the reference, ffn.cpp:127: the same elementwise op) with the gate | up launch's K splits summed by the SiLU
     // launch itself (ntk_gemm_quant_f16 with `partials` + ntk_reduce_silu_mul_*); false = not this shape / format: the caller takes the separate launches
     auto gate_up_silu = [&](const LayerWeights& L) -> bool {
-        if (!with_max || !rm_b || tp_world_ > 1 || L.w_gate.dtype != L.w_up.dtype || !is_quant(L.w_gate.dtype) || L.w_gate.in_f != L.w_up.in_f ||
+        if (!with_max || !rm_b || tp_world_ > 1 || L.w_gate.dtype != L.w_up.dtype || !is_quant(L.w_gate.dtype) || !f16_fmt(L.w_gate.dtype) || L.w_gate.in_f != L.w_up.in_f ||
             (size_t)L.w_gate.out_f != (size_t)I || (size_t)L.w_up.out_f != (size_t)I || I % 4 != 0) return false;
         float* const ys[2] = {act.gate, act.up};
         const DevTensor* const ws[2] = {&L.w_gate, &L.w_up};

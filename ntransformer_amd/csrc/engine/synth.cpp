@@ -47,6 +47,7 @@ BlockInfo block_of(int gt) {
         case 1: return {1, 2};
         case 2: return {32, 18};
         case 8: return {32, 34};
+        case 11: return {256, 110};
         case 12: return {256, 144};
         case 13: return {256, 176};
         case 14: return {256, 210};
@@ -91,6 +92,11 @@ void fill_unit(uint8_t* dst, int gt, uint64_t key, uint64_t unit, double tgt) {
             put16(dst + 208, f2h((float)(tgt / (37.0 * 18.5) * jit)));
             break;
         }
+        case 11: {  // Q3_K: hmask[32], qs[64], scales[12], d; RMS of (q - 4) 2.35, of (s - 32) 18.5
+            fill_random(dst, 108, st);
+            put16(dst + 108, f2h((float)(tgt / (2.35 * 18.5) * jit)));
+            break;
+        }
         default: break;
     }
 }
@@ -117,6 +123,7 @@ int mix_type(const std::string& mix) {
     if (mix == "Q4_K") return 12;
     if (mix == "Q5_K") return 13;
     if (mix == "Q6_K") return 14;
+    if (mix == "Q3_K" || mix == "Q3_K_M") return 11;
     if (mix == "F16") return 1;
     if (mix == "BF16") return 30;
     if (mix == "F32") return 0;
@@ -186,6 +193,9 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     const SynthFlavour fl = synth_flavour(s.mix);
     if (!parse_layer_sample(fl.mix, s.layers, sample_of, sample)) return false;
     const bool km = fl.mix == "Q4_K_M" || sample_of > 0;
+    // Q3_K_M: llama.cpp's rule as remembered (its source is not at hand; gguf.py tensor_types states the same): Q3_K beside Q4_K, Q5_K and Q6_K
+    // where real files put it.  Plain Q3_K keeps a Q6_K LM head, as those files do.
+    const bool k3m = fl.mix == "Q3_K_M";
     const int base = km ? 12 : mix_type(fl.mix);
     if (base < 0 || s.heads <= 0 || s.kv_heads <= 0 || (fl.head_dim ? fl.head_dim < 0 || (fl.head_dim & 1) : s.hidden % s.heads)) return false;
     if (fl.experts && (fl.experts < 1 || fl.experts > 256 || fl.used < 1 || fl.used > std::min(fl.experts, 16) || fl.expert_inter < 0)) return false;
@@ -201,8 +211,8 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     for (int i = 0; i < s.layers; ++i) {
         const std::string p = "blk." + std::to_string(i) + ".";
         const bool more = km && (sample_of > 0 ? use_more_bits(sample[i], sample_of) : use_more_bits(i, s.layers));
-        const int v_t = more ? 14 : (km && s.heads / s.kv_heads >= 4 && s.hidden >= 8192 ? 13 : base);
-        const int down_t = more ? 14 : base;
+        const int v_t = k3m ? (i < 2 ? 13 : 12) : more ? 14 : (km && s.heads / s.kv_heads >= 4 && s.hidden >= 8192 ? 13 : base);
+        const int down_t = k3m ? (i < s.layers / 16 ? 13 : use_more_bits(i, s.layers) ? 12 : 11) : more ? 14 : base;
         add(p + "attn_norm.weight", 0, s.hidden, 1, 0);
         add(p + "attn_q.weight", base, s.hidden, q_dim, 1);
         add(p + "attn_k.weight", base, s.hidden, kv_dim, 1);
@@ -216,7 +226,7 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
             add(p + "attn_q_norm.weight", 0, hd, 1, -0.5);
             add(p + "attn_k_norm.weight", 0, hd, 1, -0.5);
         }
-        add(p + "attn_output.weight", base, q_dim, s.hidden, 1);
+        add(p + "attn_output.weight", k3m ? 12 : base, q_dim, s.hidden, 1);
         add(p + "ffn_norm.weight", 0, s.hidden, 1, 0);
         if (fl.experts) {   // the routed FFN: the router and the experts' matrices, expert after expert in one tensor each
             add(p + "ffn_gate_inp.weight", 0, s.hidden, fl.experts, 2.0);
@@ -230,7 +240,7 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
         add(p + "ffn_down.weight", down_t, s.inter, s.hidden, 1);
     }
     add("output_norm.weight", 0, s.hidden, 1, 0);
-    if (!fl.tied) add("output.weight", km ? 14 : base, s.hidden, s.vocab, 2.0);
+    if (!fl.tied) add("output.weight", km || base == 11 ? 14 : base, s.hidden, s.vocab, 2.0);
     return true;
 }
 

@@ -17,6 +17,7 @@ template <> struct GFmt<NTK_DT_Q4_0> { static constexpr int BW = 32, BB = 18, SB
 template <> struct GFmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, SB = 144; };
 template <> struct GFmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, SB = 176; };
 template <> struct GFmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, SB = 210; };
+template <> struct GFmt<NTK_DT_Q3_K> { static constexpr int BW = 256, BB = 110, SB = 110; };
 // Unquantised 16-bit rows (IEEE half, bfloat16): a "block" is 32 consecutive weights in 64 bytes, no scale.  A chunk of a row is then 8 KiB, and
 // sixteen of them with the padded pitch would not fit the CU's 160 KiB beside the reduction buffers; these formats require 16-byte-aligned rows
 // instead (W aligned; a row is a multiple of 64 bytes), stage exactly 8 KiB per row at a pitch of 8 KiB and keep the reads conflict-free by
@@ -124,6 +125,26 @@ template <> struct Deq<NTK_DT_Q6_K> {   // gemm.cu:421-459: sub-block s = 4 half
                       ((q[1] >> sh) & 0x0F0F0F0Fu) | (((h[1] >> (2 * ty)) & 0x03030303u) << 4), n);
 #pragma unroll
         for (int j = 0; j < 8; ++j) a[j] = sc * (n[j] - 32.0f);
+    }
+};
+
+template <> struct Deq<NTK_DT_Q3_K> {   // ggml block_q3_K (not in the reference): sub-block s = 4 n + j; w = d (sc[2 s + l/16] - 32) (q - 4)
+    __device__ static void run(const uint8_t* st, int shift, int s, int g, float (&a)[8]) {
+        uint32_t q[2], h[2], sa[3];
+        lds_read_dwords<2>(q, st, shift + 32 + 32 * (s >> 2) + 8 * g);
+        lds_read_dwords<2>(h, st, shift + 8 * g);
+        lds_read_dwords<3>(sa, st, shift + 96);
+        const float d = h2f(lds_u16_at(st, shift + 108));
+        // scale is = 2 s + g / 2 = 4 grp + k: low nibble of byte 4 (grp & 1) + k (high one for grp >= 2), bits 2 grp of byte 8 + k on top
+        const int is = 2 * s + (g >> 1), grp = is >> 2, k = is & 3;
+        const uint32_t lo4 = (((grp & 1) ? sa[1] : sa[0]) >> (8 * k + 4 * (grp >> 1))) & 15u, hi2 = (sa[2] >> (8 * k + 2 * grp)) & 3u;
+        const float sc = d * (float)((int)(lo4 | (hi2 << 4)) - 32);
+        const int sh = 2 * (s & 3);
+        float n[8];
+        bytes8_to_f32(((q[0] >> sh) & 0x03030303u) | (((h[0] >> s) & 0x01010101u) << 2),
+                      ((q[1] >> sh) & 0x03030303u) | (((h[1] >> s) & 0x01010101u) << 2), n);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = sc * (n[j] - 4.0f);
     }
 };
 

@@ -40,6 +40,7 @@ template <> struct Fmt<NTK_DT_Q4_0> { static constexpr int BW = 32, BB = 18, NL 
 template <> struct Fmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, NL = 3, MINW = 4; };
 template <> struct Fmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, NL = 3, MINW = 4; };
 template <> struct Fmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, NL = 4, MINW = 4; };
+template <> struct Fmt<NTK_DT_Q3_K> { static constexpr int BW = 256, BB = 110, NL = 2, MINW = 4; };   // 16 blocks of 110 bytes + 15: two chunks
 // (Round 3 also built the row stream of gemv.hip on an LDS-DMA ring -- two or three row slices in flight per wave instead of one -- and measured
 // NOTHING: Q4_K gate|up 16.7 -> 16.3 us, LM head 52.8 -> 52.7, 70B gate|up 48.7 -> 49.1 (profiles/r03_gemv_lds_dma_ring_experiment.txt):
 // the long K-quant launches were bound by VALU issue, not by bytes in flight.  That form was removed in round 4, when the matrix-core
@@ -419,5 +420,47 @@ template <bool A16> struct Dot<NTK_DT_Q6_K, A16> {
     }
 };
 
+// Q3_K (ggml block_q3_K: hmask[32] qs[64] scales[12] d, 110 bytes, any even alignment; not in the reference).  lane = (block, c): columns 64 c + [0, 64) of
+// the block, in order.  Column 128 n + 32 j + l keeps its two low bits in bits 2 j of qs[32 n + l] and its third in bit 4 n + j of hmask[l]: with
+// n = c >> 1 and j = 2 (c & 1) + {0, 1} the lane's two 32-column groups are bit pairs 4 (c & 1) and 4 (c & 1) + 2 of the SAME 32 qs bytes, and bits
+// 2 c, 2 c + 1 of the 32 hmask bytes (one rotation puts them on bits 2 and 3, as Dot<Q5_K> does with its fifth bits).  The four 16-column runs are
+// sub-blocks 4 c .. 4 c + 3: their 6-bit scales come out of the 12 bytes as the bytes of ONE dword.  w = d (s - 32) (q - 4); the 4 leaves through sx16.
+template <bool A16> struct Dot<NTK_DT_Q3_K, A16> {
+    __device__ static float run(const uint8_t* st, int shift, int lane, int ncols, const f32x2 (&x2)[32],
+                                const float (&sx16)[4], const float (&)[2]) {
+        if (ncols <= 0) return 0.0f;
+        const int c = lane & 3, ob = shift + 110 * (lane >> 2);
+        uint32_t a[3];
+        lds_read_dwords<3>(a, st, ob + 96);
+        const float d = h2f(lds_u16_at(st, ob + 108));
+        const uint32_t sc = ((((c & 1) ? a[1] : a[0]) >> (4 * (c >> 1))) & 0x0F0F0F0Fu) | (((a[2] >> (2 * c)) & 0x03030303u) << 4);
+        float S[4];   // [2 group + run]
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {   // the two 16-column runs of each group
+            uint32_t q[4], hm[4];
+            lds_read_dwords<4>(q, st, ob + 32 + 32 * (c >> 1) + 16 * hh);
+            lds_read_dwords<4>(hm, st, ob + 16 * hh);
+            float l0 = 0.0f, l1 = 0.0f, h0 = 0.0f, h1 = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t qs = q[i] >> (4 * (c & 1));
+                const uint32_t r = __builtin_amdgcn_alignbit(hm[i], hm[i], (uint32_t)((2 * c + 30) & 31));   // rotate right by 2 c - 2
+                const uint32_t lo = opaque((qs & 0x03030303u) | (r & 0x04040404u));
+                const uint32_t hi = opaque(((qs >> 2) & 0x03030303u) | ((r >> 1) & 0x04040404u));
+                const f32x2 xa = x2[8 * hh + 2 * i], xb = x2[8 * hh + 2 * i + 1], xc = x2[16 + 8 * hh + 2 * i], xd = x2[16 + 8 * hh + 2 * i + 1];
+                l0 = fmaf(ub2f(lo, 0), xa.x, l0); l1 = fmaf(ub2f(lo, 1), xa.y, l1); l0 = fmaf(ub2f(lo, 2), xb.x, l0); l1 = fmaf(ub2f(lo, 3), xb.y, l1);
+                h0 = fmaf(ub2f(hi, 0), xc.x, h0); h1 = fmaf(ub2f(hi, 1), xc.y, h1); h0 = fmaf(ub2f(hi, 2), xd.x, h0); h1 = fmaf(ub2f(hi, 3), xd.y, h1);
+            }
+            S[hh] = l0 + l1;
+            S[2 + hh] = h0 + h1;
+        }
+        // sum (q - 4) x = sum q x - 4 sum x, per 16-column run, times the run's scale less 32
+        float bs = (ub2f(sc, 0) - 32.0f) * fmaf(-4.0f, sx16[0], S[0]);
+        bs = fmaf(ub2f(sc, 1) - 32.0f, fmaf(-4.0f, sx16[1], S[1]), bs);
+        bs = fmaf(ub2f(sc, 2) - 32.0f, fmaf(-4.0f, sx16[2], S[2]), bs);
+        bs = fmaf(ub2f(sc, 3) - 32.0f, fmaf(-4.0f, sx16[3], S[3]), bs);
+        return d * bs;
+    }
+};
 
 }  // namespace ntk

@@ -20,8 +20,12 @@
 //        Q5_K: + 256 bytes, dword l: bit 8 y + 4 h + v = bit 4 of the quant of column 128 s + 64 h + 16 kg + 4 v + y
 //        Q6_K: + 512 bytes, dwords 2 l + h: bits 8 y + 2 v (+1) = bits 4..5 of the quant of that column
 //   P2 [tile][sb][S2 bytes]   16 rows x 16 bytes: Q4_K / Q5_K {sc[8], m[8]} (the 6-bit values as bytes), Q6_K sc[16] (int8);
-//        then 16 x {d, dmin} (FP16 pairs; Q6_K: 16 x d).
-//   Bytes: Q4_K 2368 per item (GGUF 2304: 1.028 x), Q5_K 2880 (2816: 1.023 x), Q6_K 3360 (3360: 1.000 x).
+//        then 16 x {d, dmin} (FP16 pairs; Q6_K: 16 x d).  Q3_K: Q6_K's record -- its sixteen 6-bit scales as int8 already reduced by 32, 16 x d.
+//        Q3_K: NO nibble chunk -- three bits per weight as two bit planes, 768 bytes per step:
+//              [0, 512)   dwords 2 l + h: bits 8 y + 2 v (+1) = bits 0..1 of the quant of column 128 s + 64 h + 16 kg + 4 v + y   (Q6_K's top-bit plane, one level down)
+//              [512, 768) dword l: bit 8 y + 2 + v (h = 0) / 8 y + ((6 + v) & 7) (h = 1) = bit 2 of the quant of that column -- positions from which every one of
+//              the eight operand dwords takes its bit with ONE shift (none for h = 0, v = 0) into bit 2 of each byte
+//   Bytes: Q4_K 2368 per item (GGUF 2304: 1.028 x), Q5_K 2880 (2816: 1.023 x), Q6_K 3360 (3360: 1.000 x), Q3_K 1824 (1760: 1.036 x).
 //   Rows are padded to whole tiles with zero weights.
 //
 // MFMA roles: first operand (M = 16) = digit planes of x from LDS, entry m = 4 jj + p (sub-block jj of the 64 columns, digit p; p = 3
@@ -45,10 +49,15 @@ template <int DT> struct Rp;
 template <> struct Rp<NTK_DT_Q4_K> { static constexpr int S1 = 1024, S2 = 320, BB = 144, NSUB = 8; };
 template <> struct Rp<NTK_DT_Q5_K> { static constexpr int S1 = 1280, S2 = 320, BB = 176, NSUB = 8; };
 template <> struct Rp<NTK_DT_Q6_K> { static constexpr int S1 = 1536, S2 = 288, BB = 210, NSUB = 16; };
+template <> struct Rp<NTK_DT_Q3_K> { static constexpr int S1 = 768, S2 = 288, BB = 110, NSUB = 16; };
+// (the format exists for its bytes: the repack may cost 4 % over the GGUF blocks of a whole tile, no more)
+static_assert(25 * (2 * Rp<NTK_DT_Q3_K>::S1 + Rp<NTK_DT_Q3_K>::S2) <= 26 * 16 * Rp<NTK_DT_Q3_K>::BB, "Q3_K repack: at most 1.04 x the GGUF bytes");
+// bit of the Q3_K third-bit plane that holds (half h, dword v) of byte y's column
+__host__ __device__ constexpr int q3_hpos(int h, int v) { return h ? ((6 + v) & 7) : 2 + v; }
 
-static bool rp_supported(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K; }
-static size_t rp_s1(int dt) { return dt == NTK_DT_Q4_K ? 1024 : dt == NTK_DT_Q5_K ? 1280 : 1536; }
-static size_t rp_s2(int dt) { return dt == NTK_DT_Q6_K ? 288 : 320; }
+static bool rp_supported(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K; }
+static size_t rp_s1(int dt) { return dt == NTK_DT_Q4_K ? 1024 : dt == NTK_DT_Q5_K ? 1280 : dt == NTK_DT_Q3_K ? 768 : 1536; }
+static size_t rp_s2(int dt) { return dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K ? 288 : 320; }
 
 // ------------------------------------------------------------------------------------------------------------------
 // raw GGUF accessors (reference src/core/types.h:112-137): the quant integer of column cc of a super-block
@@ -61,6 +70,9 @@ template <int DT> __device__ __forceinline__ int raw_q(const uint8_t* blk, int c
         int q = hi ? (by >> 4) : (by & 15);
         if constexpr (DT == NTK_DT_Q5_K) q |= ((blk[16 + l] >> (2 * chunk + hi)) & 1) << 4;
         return q;
+    } else if constexpr (DT == NTK_DT_Q3_K) {   // ggml block_q3_K: hmask[32] qs[64] scales[12] d
+        const int n = cc >> 7, j = (cc >> 5) & 3, l = cc & 31;
+        return ((blk[32 + 32 * n + l] >> (2 * j)) & 3) | (((blk[l] >> (4 * n + j)) & 1) << 2);
     } else {
         const int n = cc >> 7, quarter = (cc >> 5) & 3, l = cc & 31;
         const int by = blk[64 * n + l + ((quarter & 1) ? 32 : 0)];
@@ -91,9 +103,18 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
             const int v = b >> 2, y = b & 3;
             if constexpr (DT == NTK_DT_Q5_K) hb |= (uint32_t)((q0 >> 4) & 1) << (8 * y + v) | (uint32_t)((q1 >> 4) & 1) << (8 * y + 4 + v);
             if constexpr (DT == NTK_DT_Q6_K) { hh[0] |= (uint32_t)((q0 >> 4) & 3) << (8 * y + 2 * v); hh[1] |= (uint32_t)((q1 >> 4) & 3) << (8 * y + 2 * v); }
+            if constexpr (DT == NTK_DT_Q3_K) {
+                hh[0] |= (uint32_t)(q0 & 3) << (8 * y + 2 * v); hh[1] |= (uint32_t)(q1 & 3) << (8 * y + 2 * v);
+                hb |= (uint32_t)((q0 >> 2) & 1) << (8 * y + q3_hpos(0, v)) | (uint32_t)((q1 >> 2) & 1) << (8 * y + q3_hpos(1, v));
+            }
         }
     }
-    *reinterpret_cast<u4*>(p1 + 16 * l) = u4{w[0], w[1], w[2], w[3]};
+    if constexpr (DT == NTK_DT_Q3_K) {   // the two bit planes, no nibble chunk
+        *reinterpret_cast<u2*>(p1 + 8 * l) = u2{hh[0], hh[1]};
+        *reinterpret_cast<uint32_t*>(p1 + 512 + 4 * l) = hb;
+    } else {
+        *reinterpret_cast<u4*>(p1 + 16 * l) = u4{w[0], w[1], w[2], w[3]};
+    }
     if constexpr (DT == NTK_DT_Q5_K) *reinterpret_cast<uint32_t*>(p1 + 1024 + 4 * l) = hb;
     if constexpr (DT == NTK_DT_Q6_K) *reinterpret_cast<u2*>(p1 + 1024 + 8 * l) = u2{hh[0], hh[1]};
     if (t < 16) {   // row record of row t
@@ -105,7 +126,16 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
         uint16_t d = 0, dmin = 0;
         for (int k = 0; k < 16; ++k) rec[k] = 0;
         if (lv) {
-            if constexpr (DT == NTK_DT_Q6_K) {
+            if constexpr (DT == NTK_DT_Q3_K) {   // the sixteen 6-bit scales as ggml unpacks its 12 bytes, reduced by 32
+                const uint8_t* a = b2 + 96;
+                for (int k = 0; k < 4; ++k) {
+                    rec[k] = (uint8_t)(((a[k] & 15) | (((a[8 + k] >> 0) & 3) << 4)) - 32);
+                    rec[4 + k] = (uint8_t)(((a[4 + k] & 15) | (((a[8 + k] >> 2) & 3) << 4)) - 32);
+                    rec[8 + k] = (uint8_t)(((a[k] >> 4) | (((a[8 + k] >> 4) & 3) << 4)) - 32);
+                    rec[12 + k] = (uint8_t)(((a[4 + k] >> 4) | (((a[8 + k] >> 6) & 3) << 4)) - 32);
+                }
+                d = (uint16_t)(b2[108] | (b2[109] << 8));
+            } else if constexpr (DT == NTK_DT_Q6_K) {
                 for (int k = 0; k < 16; ++k) rec[k] = b2[192 + k];
                 d = (uint16_t)(b2[208] | (b2[209] << 8));
             } else {
@@ -120,7 +150,7 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
             }
         }
         for (int k = 0; k < 16; ++k) p2[16 * t + k] = rec[k];
-        if constexpr (DT == NTK_DT_Q6_K) *reinterpret_cast<uint16_t*>(p2 + 256 + 2 * t) = d;
+        if constexpr (F::NSUB == 16) *reinterpret_cast<uint16_t*>(p2 + 256 + 2 * t) = d;
         else *reinterpret_cast<uint32_t*>(p2 + 256 + 4 * t) = (uint32_t)d | ((uint32_t)dmin << 16);
     }
 }
@@ -201,7 +231,39 @@ __global__ __launch_bounds__(256) void rp_unpack_kernel(uint8_t* __restrict__ ra
     const int i = t & 15;
     uint8_t* row = outb + i * PITCH;
     auto ld32 = [&](const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); };
-    if constexpr (DT == NTK_DT_Q6_K) {   // ql[128] qh[64] scales[16] d   (types.h:132-137)
+    if constexpr (DT == NTK_DT_Q3_K) {   // hmask[32] qs[64] scales[12] d   (ggml block_q3_K)
+        {                                // qs[32 n + 4 w ..+3]: two bits of each of the four 32-column quarters of half n (as Q6_K's qh, from the 2-bit plane)
+            const int w = (t >> 4) & 7, n = t >> 7;
+            uint32_t v = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {   // quarter j: lanes kg = 2 (j & 1) + (w >> 2), plane dword j >> 1, dword v = w & 3 of the lane's sixteen columns
+                const uint32_t src = ld32(p1 + (size_t)n * F::S1 + 8 * (16 * (2 * (j & 1) + (w >> 2)) + i) + 4 * (j >> 1));
+                v |= ((src >> (2 * (w & 3))) & 0x03030303u) << (2 * j);
+            }
+            *reinterpret_cast<uint32_t*>(row + 32 + 32 * n + 4 * w) = v;
+        }
+        if (t < 128) {                   // hmask[4 w ..+3]: bit 4 n + j of a byte <- the third-bit plane of step n, the same lanes
+            const int w = t >> 4;
+            uint32_t v = 0;
+#pragma unroll
+            for (int nj = 0; nj < 8; ++nj) {
+                const int n = nj >> 2, j = nj & 3;
+                const uint32_t src = ld32(p1 + (size_t)n * F::S1 + 512 + 4 * (16 * (2 * (j & 1) + (w >> 2)) + i));
+                v |= ((src >> q3_hpos(j >> 1, w & 3)) & 0x01010101u) << nj;
+            }
+            *reinterpret_cast<uint32_t*>(row + 4 * w) = v;
+        }
+        if (t < 48) {                    // the 12 scale bytes: s - 32 keeps the low six bits of s with bit 5 flipped
+            const uint32_t S0 = (ld32(p2 + 16 * i) ^ 0x20202020u) & 0x3F3F3F3Fu, S1 = (ld32(p2 + 16 * i + 4) ^ 0x20202020u) & 0x3F3F3F3Fu;
+            const uint32_t S2 = (ld32(p2 + 16 * i + 8) ^ 0x20202020u) & 0x3F3F3F3Fu, S3 = (ld32(p2 + 16 * i + 12) ^ 0x20202020u) & 0x3F3F3F3Fu;
+            const int u = t >> 4;
+            const uint32_t a = u == 0 ? (S0 & 0x0F0F0F0Fu) | ((S2 & 0x0F0F0F0Fu) << 4)
+                             : u == 1 ? (S1 & 0x0F0F0F0Fu) | ((S3 & 0x0F0F0F0Fu) << 4)
+                                      : ((S0 >> 4) & 0x03030303u) | (((S1 >> 4) & 0x03030303u) << 2) | (((S2 >> 4) & 0x03030303u) << 4) | (((S3 >> 4) & 0x03030303u) << 6);
+            *reinterpret_cast<uint32_t*>(row + 96 + 4 * u) = a;
+        }
+        if (t < 16) *reinterpret_cast<uint16_t*>(row + 108) = *reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i);
+    } else if constexpr (DT == NTK_DT_Q6_K) {   // ql[128] qh[64] scales[16] d   (types.h:132-137)
         if (t < 128) {                   // ql[64 s + 16 kg ..]: the lane's 16-byte chunk of step s
             const int kg = (t >> 4) & 3, s = t >> 6;
             *reinterpret_cast<u4*>(row + 64 * s + 16 * kg) = *reinterpret_cast<const u4*>(p1 + (size_t)s * F::S1 + 16 * (16 * kg + i));
@@ -252,7 +314,7 @@ __global__ __launch_bounds__(256) void rp_unpack_kernel(uint8_t* __restrict__ ra
         }
     }
     __syncthreads();
-    constexpr int UB = DT == NTK_DT_Q6_K ? 2 : 4, U = F::BB / UB;   // Q6_K blocks are 210 bytes at 2-byte alignment: halfword stores
+    constexpr int UB = F::BB % 4 ? 2 : 4, U = F::BB / UB;   // Q6_K / Q3_K blocks are 210 / 110 bytes at 2-byte alignment: halfword stores
     for (int k = t; k < 16 * U; k += 256) {
         const int r = k / U, u = k - r * U, grow = 16 * tile + r;
         if (grow >= rows) continue;
@@ -274,13 +336,23 @@ __global__ __launch_bounds__(256) void rp_dequant_kernel(float* __restrict__ out
         const size_t item = (size_t)tile * nsb + sb;
         const uint8_t* p1 = rp + item * (2 * F::S1) + (size_t)s * F::S1;
         const uint8_t* p2 = rp + p2_off + item * F::S2;
-        const int by = p1[16 * l + b];
-        int q = h ? (by >> 4) : (by & 15);
         const int v = b >> 2, y = b & 3;
+        int q;
+        if constexpr (DT == NTK_DT_Q3_K) {
+            q = (int)((*reinterpret_cast<const uint32_t*>(p1 + 8 * l + 4 * h) >> (8 * y + 2 * v)) & 3u) |
+                (int)((*reinterpret_cast<const uint32_t*>(p1 + 512 + 4 * l) >> (8 * y + q3_hpos(h, v))) & 1u) << 2;
+        } else {
+            const int by = p1[16 * l + b];
+            q = h ? (by >> 4) : (by & 15);
+        }
         if constexpr (DT == NTK_DT_Q5_K) q |= (int)((*reinterpret_cast<const uint32_t*>(p1 + 1024 + 4 * l) >> (8 * y + 4 * h + v)) & 1u) << 4;
         if constexpr (DT == NTK_DT_Q6_K) q |= (int)((*reinterpret_cast<const uint32_t*>(p1 + 1024 + 8 * l + 4 * h) >> (8 * y + 2 * v)) & 3u) << 4;
         float w;
-        if constexpr (DT == NTK_DT_Q6_K) {
+        if constexpr (DT == NTK_DT_Q3_K) {   // w = (d (s - 32)) (q - 4)
+            const float d = h2f(*reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i));
+            const float sc = (float)(int)(int8_t)p2[16 * i + (c >> 4)];
+            w = __fmul_rn(__fmul_rn(d, sc), (float)(q - 4));
+        } else if constexpr (DT == NTK_DT_Q6_K) {
             const float d = h2f(*reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i));
             const float sc = (float)(int)(int8_t)p2[16 * i + (c >> 4)];
             w = __fmul_rn(__fmul_rn(d, sc), (float)(q - 32));
@@ -395,8 +467,8 @@ template <int DT> struct RpItem {
     u4 n0, n1;      // the two step records' nibble chunks
     u4 rec;         // the row record
     uint32_t dd;    // d | dmin << 16  (Q6_K: d)
-    uint32_t hb0, hb1;   // Q5_K
-    u2 hh0, hh1;         // Q6_K
+    uint32_t hb0, hb1;   // Q5_K; Q3_K: the third-bit plane
+    u2 hh0, hh1;         // Q6_K; Q3_K: the 2-bit plane (n0 / n1 stay unused)
 };
 
 template <int DT, bool NORM>
@@ -453,8 +525,15 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         const unsigned off = (unsigned)tile * (unsigned)nsb + (unsigned)(li - l_v * nsb);
         const uint8_t* p1 = base + (size_t)off * (2 * F::S1);
         const uint8_t* p2 = base + sg.p2_off + (size_t)off * F::S2;
-        it.n0 = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p1 + 16 * lane));
-        it.n1 = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p1 + F::S1 + 16 * lane));
+        if constexpr (DT == NTK_DT_Q3_K) {   // 12 bytes per lane and step: the 2-bit plane, the third-bit plane
+            it.hh0 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p1 + 8 * lane));
+            it.hh1 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p1 + F::S1 + 8 * lane));
+            it.hb0 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p1 + 512 + 4 * lane));
+            it.hb1 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p1 + F::S1 + 512 + 4 * lane));
+        } else {
+            it.n0 = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p1 + 16 * lane));
+            it.n1 = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p1 + F::S1 + 16 * lane));
+        }
         if constexpr (DT == NTK_DT_Q5_K) {
             it.hb0 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p1 + 1024 + 4 * lane));
             it.hb1 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p1 + F::S1 + 1024 + 4 * lane));
@@ -465,7 +544,7 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         }
         // (non-temporal like the rest of the weight stream: 12 % of the bytes must not push the KV cache and the activations out of L2)
         it.rec = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p2 + 16 * i16));
-        if constexpr (DT == NTK_DT_Q6_K) it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i16));
+        if constexpr (NSUB == 16) it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i16));
         else it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p2 + 256 + 4 * i16));
         l_idx += NW;
     };
@@ -569,7 +648,8 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         v4i b[4];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const u4 raw = s ? it.n1 : it.n0;
+            u4 raw = {0u, 0u, 0u, 0u};   // the step's nibble chunk (Q3_K has none: its items leave n0 / n1 unloaded)
+            if constexpr (DT != NTK_DT_Q3_K) raw = s ? it.n1 : it.n0;
             v4i& b0 = b[2 * s];
             v4i& b1 = b[2 * s + 1];
             if constexpr (DT == NTK_DT_Q4_K) {
@@ -582,6 +662,17 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
                     b0[k] = (int)(((hb << (4 - k)) & 0x10101010u) | (raw[k] & 0x0F0F0F0Fu));
                     b1[k] = (int)(((hb >> k) & 0x10101010u) | ((raw[k] >> 4) & 0x0F0F0F0Fu));
                 }
+            } else if constexpr (DT == NTK_DT_Q3_K) {
+                // bit planes -> int8 operands: shift + and for the two low bits, shift + and-or for the third: 4 per dword, less the three shifts by
+                // zero -- 29 vector instructions per 32 weights (7.25 per 8; Q4_K 3, Q6_K 6.5: DESIGN 3.1)
+                const u2 lo = s ? it.hh1 : it.hh0;         // byte y, bits 2 v .. 2 v + 1
+                const uint32_t hb = s ? it.hb1 : it.hb0;   // byte y, bit q3_hpos(h, v)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t t1 = k < 2 ? (hb >> (4 + k)) : (hb << (4 - k));   // bit (6 + k) & 7 -> bit 2
+                    b0[k] = (int)(((hb >> k) & 0x04040404u) | ((lo[0] >> (2 * k)) & 0x03030303u));
+                    b1[k] = (int)((t1 & 0x04040404u) | ((lo[1] >> (2 * k)) & 0x03030303u));
+                }
             } else {
                 const u2 hh = s ? it.hh1 : it.hh0;         // byte y, bits 2 v .. 2 v + 1
 #pragma unroll
@@ -593,7 +684,7 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
                 }
             }
         }
-        // minimum (Q4_K / Q5_K: dmin sum_j m_j sum x) / offset (Q6_K: 32 d sum_j sc_j sum x) term: the row's bytes x the digits of the sums
+        // minimum (Q4_K / Q5_K: dmin sum_j m_j sum x) / offset (Q6_K: 32 d sum_j sc_j sum x, Q3_K: 4 d sum_j (s_j - 32) sum x) term: the row's bytes x the digits of the sums
         v4i bc;
         if constexpr (NSUB == 8) bc = v4i{kg == 0 ? (int)it.rec[2] : 0, kg == 0 ? (int)it.rec[3] : 0, 0, 0};
         else bc = v4i{kg == 0 ? (int)it.rec[0] : 0, kg == 0 ? (int)it.rec[1] : 0, kg == 0 ? (int)it.rec[2] : 0, kg == 0 ? (int)it.rec[3] : 0};
@@ -623,7 +714,7 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         racc = fmaf(S, d * inv, racc);
         const float corr = fmaf(fmaf(fmaf((float)cc[3], 256.0f, (float)cc[2]), 256.0f, (float)cc[1]), 256.0f, (float)cc[0]);
         float fneg;
-        if constexpr (NSUB == 8) fneg = -h2f((uint16_t)(it.dd >> 16)) * inv; else fneg = -32.0f * d * inv;
+        if constexpr (NSUB == 8) fneg = -h2f((uint16_t)(it.dd >> 16)) * inv; else fneg = (DT == NTK_DT_Q3_K ? -4.0f : -32.0f) * d * inv;
         racc = fmaf(corr, fneg, racc);
     };
 
@@ -882,6 +973,7 @@ int ntk_rp_pack(void* dst, const void* raw, int rows, int in_features, int dtype
     const uint8_t* r = static_cast<const uint8_t*>(raw);
     if (dtype == NTK_DT_Q4_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q4_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q5_K>, g, b, 0, st, d, r, rows, nsb, p2);
+    else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q3_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q6_K>, g, b, 0, st, d, r, rows, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -890,7 +982,7 @@ int ntk_rp_unpack(void* raw, const void* rp, int rows, int in_features, int dtyp
     if (!raw || !rp) return NTK_E_NULL;
     if (!ntk::rp_supported(dtype)) return NTK_E_DTYPE;
     if (rows <= 0 || in_features <= 0 || in_features % 256 != 0) return NTK_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(rp) & 15) || (reinterpret_cast<uintptr_t>(raw) & (dtype == NTK_DT_Q6_K ? 1 : 3))) return NTK_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(rp) & 15) || (reinterpret_cast<uintptr_t>(raw) & (dtype == NTK_DT_Q6_K || dtype == NTK_DT_Q3_K ? 1 : 3))) return NTK_E_ALIGN;
     const int tiles = (rows + 15) / 16, nsb = in_features / 256;
     if ((long)tiles * nsb > 0x7FFFFFFFl) return NTK_E_SHAPE;
     const size_t p2 = (size_t)tiles * nsb * 2 * ntk::rp_s1(dtype);
@@ -900,6 +992,7 @@ int ntk_rp_unpack(void* raw, const void* rp, int rows, int in_features, int dtyp
     const uint8_t* r = static_cast<const uint8_t*>(rp);
     if (dtype == NTK_DT_Q4_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q4_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q5_K>, g, b, 0, st, d, r, rows, nsb, p2);
+    else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q3_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q6_K>, g, b, 0, st, d, r, rows, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -915,6 +1008,7 @@ int ntk_rp_dequant(float* out, const void* rp, int rows, int in_features, int dt
     const uint8_t* r = static_cast<const uint8_t*>(rp);
     if (dtype == NTK_DT_Q4_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q4_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q5_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
+    else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q3_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q6_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -982,11 +1076,16 @@ int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in
     RpFn fn = nullptr;
     const bool nm = norm_w != nullptr;
     if (dta == dtb) {
-        fn = dta == NTK_DT_Q4_K ? rp_fn<NTK_DT_Q4_K, NTK_DT_Q4_K>(nm) : dta == NTK_DT_Q5_K ? rp_fn<NTK_DT_Q5_K, NTK_DT_Q5_K>(nm) : rp_fn<NTK_DT_Q6_K, NTK_DT_Q6_K>(nm);
+        fn = dta == NTK_DT_Q4_K ? rp_fn<NTK_DT_Q4_K, NTK_DT_Q4_K>(nm) : dta == NTK_DT_Q5_K ? rp_fn<NTK_DT_Q5_K, NTK_DT_Q5_K>(nm)
+           : dta == NTK_DT_Q3_K ? rp_fn<NTK_DT_Q3_K, NTK_DT_Q3_K>(nm) : rp_fn<NTK_DT_Q6_K, NTK_DT_Q6_K>(nm);
     } else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q6_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q6_K>(nm);
     else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q5_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q5_K>(nm);
     else if (dta == NTK_DT_Q6_K && dtb == NTK_DT_Q4_K) fn = rp_fn<NTK_DT_Q6_K, NTK_DT_Q4_K>(nm);
     else if (dta == NTK_DT_Q5_K && dtb == NTK_DT_Q4_K) fn = rp_fn<NTK_DT_Q5_K, NTK_DT_Q4_K>(nm);
+    else if (dta == NTK_DT_Q3_K && dtb == NTK_DT_Q4_K) fn = rp_fn<NTK_DT_Q3_K, NTK_DT_Q4_K>(nm);   // the Q | K | V launches of Q3_K_S / _M / _L files
+    else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q3_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q3_K>(nm);
+    else if (dta == NTK_DT_Q3_K && dtb == NTK_DT_Q5_K) fn = rp_fn<NTK_DT_Q3_K, NTK_DT_Q5_K>(nm);
+    else if (dta == NTK_DT_Q5_K && dtb == NTK_DT_Q3_K) fn = rp_fn<NTK_DT_Q5_K, NTK_DT_Q3_K>(nm);
     else return NTK_E_DTYPE;
     if (!fn) return NTK_E_LAUNCH;
 #ifdef NTK_TUNE

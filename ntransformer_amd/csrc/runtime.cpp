@@ -93,6 +93,7 @@ size_t ntk_row_bytes(int dtype, int64_t n) {
         case NTK_DT_Q4_K: return n % 256 ? 0 : (size_t)(n / 256) * 144;
         case NTK_DT_Q5_K: return n % 256 ? 0 : (size_t)(n / 256) * 176;
         case NTK_DT_Q6_K: return n % 256 ? 0 : (size_t)(n / 256) * 210;
+        case NTK_DT_Q3_K: return n % 256 ? 0 : (size_t)(n / 256) * 110;
         case NTK_DT_Q2_K: return n % 256 ? 0 : (size_t)(n / 256) * 84;
         default: return 0;
     }

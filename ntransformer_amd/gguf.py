@@ -32,22 +32,24 @@ T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I6
 # ggml tensor types the reference maps (types.h:173-215)
 GGML_F32, GGML_F16, GGML_Q4_0, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K = 0, 1, 2, 8, 12, 13, 14
 GGML_BF16 = 30   # not in the reference: bfloat16, the format checkpoints are published in
+GGML_Q3_K = 11   # not in the reference: the 3-bit K-quant of llama.cpp's Q3_K_S / _M / _L files
 
 # nt::DType numeric values (types.h:24-35) -- the C ABI contract
 DT_F32, DT_F16, DT_Q8_0, DT_Q4_0, DT_Q4_K, DT_Q6_K, DT_Q5_K, DT_Q2_K, DT_I32 = range(9)
 DT_BF16 = 9   # NTK_DT_BF16: appended behind the reference's values
+DT_Q3_K = 10  # NTK_DT_Q3_K: likewise
 
 GGML_TO_DT = {GGML_F32: DT_F32, GGML_F16: DT_F16, GGML_Q4_0: DT_Q4_0, GGML_Q8_0: DT_Q8_0,
-              GGML_Q4_K: DT_Q4_K, GGML_Q5_K: DT_Q5_K, GGML_Q6_K: DT_Q6_K, GGML_BF16: DT_BF16}
+              GGML_Q4_K: DT_Q4_K, GGML_Q5_K: DT_Q5_K, GGML_Q6_K: DT_Q6_K, GGML_BF16: DT_BF16, GGML_Q3_K: DT_Q3_K}
 DT_TO_GGML = {v: k for k, v in GGML_TO_DT.items()}
 DT_NAME = {DT_F32: "F32", DT_F16: "F16", DT_Q8_0: "Q8_0", DT_Q4_0: "Q4_0", DT_Q4_K: "Q4_K",
-           DT_Q6_K: "Q6_K", DT_Q5_K: "Q5_K", DT_BF16: "BF16"}
+           DT_Q6_K: "Q6_K", DT_Q5_K: "Q5_K", DT_BF16: "BF16", DT_Q3_K: "Q3_K"}
 NAME_TO_GGML = {"F32": GGML_F32, "F16": GGML_F16, "Q4_0": GGML_Q4_0, "Q8_0": GGML_Q8_0,
-                "Q4_K": GGML_Q4_K, "Q5_K": GGML_Q5_K, "Q6_K": GGML_Q6_K, "BF16": GGML_BF16}
+                "Q4_K": GGML_Q4_K, "Q5_K": GGML_Q5_K, "Q6_K": GGML_Q6_K, "BF16": GGML_BF16, "Q3_K": GGML_Q3_K}
 
 # (elements per block, bytes per block)
 BLOCK = {GGML_F32: (1, 4), GGML_F16: (1, 2), GGML_Q4_0: (32, 18), GGML_Q8_0: (32, 34),
-         GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176), GGML_Q6_K: (256, 210), GGML_BF16: (1, 2)}
+         GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176), GGML_Q6_K: (256, 210), GGML_BF16: (1, 2), GGML_Q3_K: (256, 110)}
 
 
 def f32_to_bf16(x: np.ndarray) -> np.ndarray:
@@ -298,6 +300,9 @@ def synth_tensor(rng: np.random.Generator, ggml_type: int, out_f: int, in_f: int
         blk[:, 0:192] = rng.integers(0, 256, (nb, 192), dtype=np.uint8)
         blk[:, 192:208] = rng.integers(-64, 64, (nb, 16), dtype=np.int8).view(np.uint8)
         blk[:, 208:210] = _f16_bytes(tgt / (37.0 * 18.5) * jit)
+    elif ggml_type == GGML_Q3_K:                         # hmask[32] qs[64] scales[12] d: RMS of (q - 4) 2.35, of (s - 32) 18.5
+        blk[:, 0:108] = rng.integers(0, 256, (nb, 108), dtype=np.uint8)
+        blk[:, 108:110] = _f16_bytes(tgt / (2.35 * 18.5) * jit)
     else:
         raise ValueError(ggml_type)
     return blk.tobytes()
@@ -370,6 +375,20 @@ def dequantize(raw: np.ndarray | bytes, ggml_type: int, n: int) -> np.ndarray:
         isx = np.arange(32) // 16
         scl = np.stack([sc[:, :, isx + 2 * g] for g in range(4)], 2)  # [nb, 2, 4, 32]
         w = d[:, :, None, None] * scl * q
+        return w.reshape(-1).astype(np.float32)
+    if ggml_type == GGML_Q3_K:
+        # ggml block_q3_K: column 128 n + 32 j + l has its two low bits in bits 2 j of qs[32 n + l], its third in bit 4 n + j of hmask[l], and
+        # the 6-bit scale 8 n + 2 j + l // 16 of the sixteen that the 12 scale bytes hold; w = (d (s - 32)) (q - 4)
+        hm = b[:, 0:32].astype(np.int32)[:, None, None, :]
+        qs = b[:, 32:96].reshape(nb, 2, 1, 32).astype(np.int32)
+        a = b[:, 96:108].astype(np.int32)
+        d = b[:, 108:110].copy().view("<f2").astype(np.float32)
+        nn, jj = np.arange(2)[None, :, None, None], np.arange(4)[None, None, :, None]
+        q = (((qs >> (2 * jj)) & 3) | (((hm >> (4 * nn + jj)) & 1) << 2)) - 4           # [nb, 2, 4, 32]
+        hi = a[:, 8:12]
+        s = np.concatenate([(a[:, 0:4] & 15) | ((hi & 3) << 4), (a[:, 4:8] & 15) | (((hi >> 2) & 3) << 4),
+                            (a[:, 0:4] >> 4) | (((hi >> 4) & 3) << 4), (a[:, 4:8] >> 4) | (((hi >> 6) & 3) << 4)], 1) - 32   # [nb, 16]
+        w = (d * s.astype(np.float32)).reshape(nb, 2, 4, 2, 1) * q.astype(np.float32).reshape(nb, 2, 4, 2, 16)
         return w.reshape(-1).astype(np.float32)
     raise ValueError(ggml_type)
 
@@ -448,7 +467,7 @@ def use_more_bits(i: int, n: int) -> bool:
 
 
 def tensor_types(shape: LlamaShape, mix: str) -> Dict[str, int]:
-    """name -> ggml type for a quantisation mix: a plain type name or 'Q4_K_M'."""
+    """name -> ggml type for a quantisation mix: a plain type name, 'Q4_K_M' or 'Q3_K_M'."""
     L = shape.layers
     out: Dict[str, int] = {}
     mats = ["attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down"]
@@ -464,6 +483,21 @@ def tensor_types(shape: LlamaShape, mix: str) -> Dict[str, int]:
                 elif m == "attn_v" and gqa >= 4 and shape.hidden >= 8192:
                     t = GGML_Q5_K  # 70B-class GQA: remaining attn_v -> Q5_K
                 out["blk.%d.%s.weight" % (i, m)] = t
+    elif mix == "Q3_K_M":
+        # llama.cpp's Q3_K_M rule as remembered -- its source is not at hand, so this may differ from it in detail; what it has to do here is put Q3_K
+        # beside Q4_K, Q5_K and Q6_K where real files put it (the Q | K | V launch Q3_K | Q3_K | Q4_K or Q5_K, a ffn_down of three types)
+        out["token_embd.weight"] = GGML_Q3_K
+        out["output.weight"] = GGML_Q6_K
+        for i in range(L):
+            for m in mats:
+                t = GGML_Q3_K
+                if m == "attn_v":
+                    t = GGML_Q5_K if i < 2 else GGML_Q4_K
+                elif m == "attn_output":
+                    t = GGML_Q4_K
+                elif m == "ffn_down":
+                    t = GGML_Q5_K if i < L // 16 else GGML_Q4_K if use_more_bits(i, L) else GGML_Q3_K
+                out["blk.%d.%s.weight" % (i, m)] = t
     elif mix == "MIXED":  # every quant type in one small file (tests)
         cyc = [GGML_Q8_0, GGML_Q4_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_F16, GGML_F32]
         out["token_embd.weight"] = GGML_Q4_K
@@ -478,7 +512,7 @@ def tensor_types(shape: LlamaShape, mix: str) -> Dict[str, int]:
         # the reference has no Q5_K branch in embed_tokens (it zero-fills, transformer.cpp:595-598),
         # so a plain-Q5_K test file keeps a Q4_K embedding like real llama.cpp K-quant files do
         out["token_embd.weight"] = GGML_Q4_K if t == GGML_Q5_K else t
-        out["output.weight"] = t
+        out["output.weight"] = GGML_Q6_K if t == GGML_Q3_K else t   # (Q3_K files keep a Q6_K LM head)
         for i in range(L):
             for m in mats:
                 out["blk.%d.%s.weight" % (i, m)] = t

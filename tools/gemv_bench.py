@@ -23,8 +23,9 @@ SHAPES = {  # name: (kind, rows..., in)
     "70b.qkv_fused": ("qkv", (8192, 1024, 1024), 8192), "70b.o+res": ("resid", 8192, 8192),
     "70b.gate|up+silu": ("silu", 28672, 8192), "70b.down+res": ("resid", 8192, 28672),
 }
-GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K, "F16": G.GGML_F16, "BF16": G.GGML_BF16}
+GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K, "Q3_K": G.GGML_Q3_K, "F16": G.GGML_F16, "BF16": G.GGML_BF16}
 DENSE16 = (G.GGML_F16, G.GGML_BF16)
+RP = (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K, G.GGML_Q3_K)   # formats with a decode repack
 
 
 def main():
@@ -51,7 +52,7 @@ def main():
     def launch_bytes(dname, sname):
         kind, rows, in_f = SHAPES[sname]
         rlist = list(rows) if isinstance(rows, tuple) else [rows]
-        if a.rp and GT[dname] in (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K):
+        if a.rp and GT[dname] in RP:
             rpb = [(ops.rp_bytes(G.GGML_TO_DT[GT[dname]], r, in_f) + 255) // 256 * 256 for r in (rlist if kind != "silu" else [rlist[0], rlist[0]])]
             return (sum(rpb) + 4095) // 4096 * 4096
         per = G.row_bytes(GT[dname], in_f) * (sum(rlist) if kind != "silu" else 2 * rlist[0])
@@ -73,7 +74,7 @@ def main():
             per_launch = rb * (sum(rlist) if kind != "silu" else 2 * rlist[0])
             per_launch_al = (per_launch + 4095) // 4096 * 4096
             if a.rp:
-                if gt not in (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K):
+                if gt not in RP:
                     continue
                 rpb = [ops.rp_bytes(dt, r, in_f) for r in (rlist if kind != "silu" else [rlist[0], rlist[0]])]
                 rpb = [(b + 255) // 256 * 256 for b in rpb]
