@@ -5,7 +5,7 @@
 // form (16 tokens per pass, 29-65 TFLOP/s of the 157 TFLOP/s F32 matrix rate) for the formats of the target models.
 //
 // Arithmetic -- exact products, F32 accumulation, activations within one F32 ulp of the reference's:
-//   * a GGUF weight is (integer) x (scale): the INTEGER part (Q8_0: -128..127, Q4_K: 0..15, Q6_K: -32..31) is exact in FP16;
+//   * a GGUF weight is (integer) x (scale): the INTEGER part (Q8_0: -128..127, Q4_K: 0..15, Q6_K: -32..31, Q3_K: -4..3) is exact in FP16;
 //   * an F32 activation x is scaled by a power of two s -- one per token, chosen so that the token's largest |x| s lies in
 //     [2^14, 2^15) -- and split into TWO FP16 pieces: h1 = rn16(x s), h2 = rn16(x s - h1).  The difference is exact in F32 (13
 //     significant bits), so |x s - h1 - h2| <= 2^-23 |x s| -- one F32 ulp of the activation -- for every x within 2^-16 of the
@@ -528,7 +528,68 @@ template <> struct DeqI<NTK_DT_Q6_K> : GemmFmt<NTK_DT_Q6_K> {   // types.h:132-1
     }
 };
 
-// ---- the same three K-quant formats read from the ENGINE'S DECODE REPACK (csrc/gemv_rp.hip: tiles of 16 rows x 256-column super-blocks; round 6) ----
+template <> struct DeqI<NTK_DT_Q3_K> : GemmFmt<NTK_DT_Q3_K> {   // ggml block_q3_K (not in the reference): hmask[32], qs[64], scales[12], half d; w = d (sc - 32) (q - 4)
+    static constexpr int UB = 110, NCH = 8;                            // window: shift (even, <= 14) + 110 <= 128 (< STRIDE = 144)
+    static constexpr int NRING = 1, PPI = 0;
+    // the sixteen 6-bit scales as int8 already reduced by 32 (the record of the decode repack, gemv_rp.hip: the two forms then scale by the same
+    // expressions), d, and the lane's 8 bytes of third bits -- hmask serves all eight steps: step j takes bit j
+    struct Hdr { u32x4 rec; float d; uint32_t hm_lo, hm_hi; };
+    struct MinOp {};
+    __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
+    struct Raw { uint32_t q0, q1, q2, q3, b3lo, b3hi, sc; float d; };
+    // blocks are 110 bytes: a unit starts on a dword boundary or 2 bytes past one (Q6_K's case), whatever the row pitch.  Once per unit, the header takes
+    // aligned dwords from the boundary at or below the unit and shifts by the unit's own misalignment (v_alignbyte takes the shift from a register):
+    // the same code for both parities and for the pitches of the AL = false form.
+    static_assert(STRIDE % 4 == 0, "header() reads the unit's misalignment off its LDS address: row images (and the waves' images, multiples of STRIDE) start on dword boundaries");
+    __device__ static Hdr header(const uint8_t* row, const uint8_t* rowg) {
+        const uint32_t sh = (uint32_t)(uintptr_t)row & 2u;
+        const uint8_t* p = row - sh;
+        const uint8_t* pg = rowg - sh;
+        auto at = [&](uint32_t lo, uint32_t hi) { return __builtin_amdgcn_alignbyte(hi, lo, sh); };
+        const uint32_t h0 = lds32<true>(pg), h1 = lds32<true>(pg + 4), h2 = lds32<true>(pg + 16), h3 = lds32<true>(pg + 20);
+        const uint32_t w0 = lds32<true>(p + 96), w1 = lds32<true>(p + 100), w2 = lds32<true>(p + 104), w3 = lds32<true>(p + 108);
+        // ggml's 12 bytes: scale 4 grp + k = nibble (grp >> 1) of byte 4 (grp & 1) + k, bits 2 grp .. 2 grp + 1 of byte 8 + k on top (gemm_deq.hip.h)
+        const uint32_t a0 = at(w0, w1), a1 = at(w1, w2), a2 = at(w2, w3);
+        auto s8 = [](uint32_t lo4, uint32_t hi2) { return (((lo4 & 0x0F0F0F0Fu) | (hi2 & 0x30303030u)) + 0x60606060u) ^ 0x80808080u; };   // bytes 0..63 -> int8 (byte - 32): no carry between bytes
+        Hdr hd;
+        hd.rec = u32x4{s8(a0, a2 << 4), s8(a1, a2 << 2), s8(a0 >> 4, a2), s8(a1 >> 4, a2 >> 2)};
+        hd.d = h2f((uint16_t)(w3 >> (8 * sh)));
+        hd.hm_lo = at(h0, h1);
+        hd.hm_hi = at(h2, h3);
+        return hd;
+    }
+    // `row` (AL) = the 4-byte aligned address at or 2 bytes below the unit's first byte, k = the unit's parity: as Q6_K
+    // step j = 4 n + jj: the two low bits of the lane's columns are bits 2 jj .. 2 jj + 1 of qs dwords 32 n + 4 g and 32 n + 16 + 4 g
+    template <bool AL> __device__ static Raw load(const uint8_t*, const uint8_t* rowg, const Hdr& hd, int j, int k) {
+        if (!AL) k = 0;
+        const uint8_t* q = rowg + 32 + 32 * (j >> 2);
+        Raw r;
+        r.q0 = lds32<AL>(q); r.q2 = lds32<AL>(q + 16);
+        if (k) { r.q1 = lds32<AL>(q + 4); r.q3 = lds32<AL>(q + 20); }
+        else r.q1 = r.q3 = 0;
+        r.b3lo = ((hd.hm_lo >> j) & 0x01010101u) << 2;
+        r.b3hi = ((hd.hm_hi >> j) & 0x01010101u) << 2;
+        const uint32_t scw = (j >> 1) == 0 ? hd.rec.x : (j >> 1) == 1 ? hd.rec.y : (j >> 1) == 2 ? hd.rec.z : hd.rec.w;   // sc[2 j], sc[2 j + 1]
+        r.sc = (scw >> (16 * (j & 1))) & 0xFFFFu;
+        r.d = hd.d;
+        return r;
+    }
+    template <bool AL> __device__ static AOp convert(const Raw& r, int j, int k) {
+        if (!AL) k = 0;
+        const int sh = 2 * (j & 3);
+        const uint32_t q_lo = k ? mid32(r.q0, r.q1) : r.q0, q_hi = k ? mid32(r.q2, r.q3) : r.q2;
+        const u32x4 qa = cvt8_u8_f16(((q_lo >> sh) & 0x03030303u) | r.b3lo, ((q_hi >> sh) & 0x03030303u) | r.b3hi);
+        const f16x2 m4 = {(_Float16)-4.0f, (_Float16)-4.0f};
+        auto sub4 = [&](uint32_t w) { return __builtin_bit_cast(uint32_t, (f16x2)(__builtin_bit_cast(f16x2, w) + m4)); };
+        AOp o;   // q - 4: exact small integers
+        o.a = u32x4{sub4(qa.x), sub4(qa.y), sub4(qa.z), sub4(qa.w)};
+        o.s0 = r.d * (float)(int)(int8_t)(r.sc & 0xFF);
+        o.s1 = r.d * (float)(int)(int8_t)(r.sc >> 8);
+        return o;
+    }
+};
+
+// ---- the K-quant formats read from the ENGINE'S DECODE REPACK (csrc/gemv_rp.hip: tiles of 16 rows x 256-column super-blocks; round 6) ----
 // With one resident copy of a K-quant matrix (the uploaded GGUF bytes freed after the load-time repack) the prompt GEMM used to get the tensor unpacked
 // into a scratch in front of every launch (ntk_rp_unpack: -1.4 ... -8 % of a 1024-token pass, a fixed 4 ms of an 8B pass).  These decoders read the repack
 // itself: the same integers and the same scale products as the raw decoders above, operand slot for operand slot -- identical bits.  A unit = the ITEM of a
@@ -629,6 +690,46 @@ template <> struct DeqI<NTK_DT_Q6_K + GB_RP> : GemmFmt<NTK_DT_Q6_K + GB_RP> {
         auto sub32 = [&](uint32_t w) { return __builtin_bit_cast(uint32_t, (f16x2)(__builtin_bit_cast(f16x2, w) + m32)); };
         AOp o;   // q - 32: exact small integers
         o.a = u32x4{sub32(qa.x), sub32(qa.y), sub32(qa.z), sub32(qa.w)};
+        o.s0 = r.d * (float)(int)(int8_t)(r.sc & 0xFF);
+        o.s1 = r.d * (float)(int)(int8_t)(r.sc >> 8);
+        return o;
+    }
+};
+
+// Q3_K's repack has NO nibble chunk (gemv_rp.hip): a step of 128 columns is a 512-byte plane of the two low bits (dwords 2 l + h of lane l = 16 kg + i: bits
+// 8 y + 2 v, + 1 of column 4 v + y of the lane's 16) and a 256-byte plane of the third bit (dword l: bit 8 y + q3_hpos(h, v)), so the addresses are this decoder's
+// own, from the item's first byte (row - 16 i).  Sub-block j as above: s = j >> 2, h = (j >> 1) & 1, kg = 2 (j & 1) and + 1, v = g -- per 16-column group ONE aligned
+// dword of each plane; the two bits with a shift by 2 g and a mask, the third with one rotation into bit 2 of every byte (q3_hpos: bit 2 + v for h = 0, bit
+// (6 + v) & 7 for h = 1 -- right by v, or by 4, 5, 30, 31).  The four lane groups read the SAME dwords (16 rows x 8 or 4 bytes, consecutive: 32 or 16 banks, the
+// rest a broadcast): no bank conflict.  Row records: Q6_K's (int8 scales already reduced by 32, d) -- the expressions of the raw decoder: identical bits.
+template <> struct DeqI<NTK_DT_Q3_K + GB_RP> : GemmFmt<NTK_DT_Q3_K + GB_RP> {
+    static constexpr int PPI = ITEM / 16, UB = 0, NCH = 0, NRING = 1;
+    struct Hdr { u32x4 rec; float d; };   // sc[16] - 32 (int8), d
+    struct MinOp {};
+    __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
+    struct Raw { uint32_t q0, q1, f0, f1, sc; float d; };
+    __device__ static Hdr header(const uint8_t* row, const uint8_t*) {
+        const int i = threadIdx.x & 15;
+        return Hdr{*reinterpret_cast<const u32x4*>(row + 2 * S1), h2f(*reinterpret_cast<const uint16_t*>(row + 2 * S1 + 256 - 14 * i))};
+    }
+    template <bool AL> __device__ static Raw load(const uint8_t* row, const uint8_t*, const Hdr& hd, int j, int) {
+        const int i = threadIdx.x & 15;
+        const uint8_t* st = row - 16 * i + (j >> 2) * S1;
+        const uint8_t* q = st + 256 * (j & 1) + 8 * i + 4 * ((j >> 1) & 1);   // dword 2 (16 kg + i) + h, kg = 2 (j & 1)
+        const uint8_t* f = st + 512 + 128 * (j & 1) + 4 * i;                  // dword 16 kg + i
+        const uint32_t scw = (j >> 1) == 0 ? hd.rec.x : (j >> 1) == 1 ? hd.rec.y : (j >> 1) == 2 ? hd.rec.z : hd.rec.w;   // sc[2 j], sc[2 j + 1]
+        return Raw{lds32<true>(q), lds32<true>(q + 128), lds32<true>(f), lds32<true>(f + 64), (scw >> (16 * (j & 1))) & 0xFFFFu, hd.d};
+    }
+    template <bool AL> __device__ static AOp convert(const Raw& r, int j, int) {
+        const uint32_t g = (threadIdx.x >> 4) & 3u;
+        const uint32_t rot = ((j >> 1) & 1) ? (((6u + g) & 7u) + 30u) & 31u : g;   // q3_hpos(h, g) - 2, as a rotation to the right
+        const uint32_t lo = ((r.q0 >> (2 * g)) & 0x03030303u) | (__builtin_amdgcn_alignbit(r.f0, r.f0, rot) & 0x04040404u);
+        const uint32_t hi = ((r.q1 >> (2 * g)) & 0x03030303u) | (__builtin_amdgcn_alignbit(r.f1, r.f1, rot) & 0x04040404u);
+        const u32x4 qa = cvt8_u8_f16(lo, hi);
+        const f16x2 m4 = {(_Float16)-4.0f, (_Float16)-4.0f};
+        auto sub4 = [&](uint32_t w) { return __builtin_bit_cast(uint32_t, (f16x2)(__builtin_bit_cast(f16x2, w) + m4)); };
+        AOp o;   // q - 4: exact small integers
+        o.a = u32x4{sub4(qa.x), sub4(qa.y), sub4(qa.z), sub4(qa.w)};
         o.s0 = r.d * (float)(int)(int8_t)(r.sc & 0xFF);
         o.s1 = r.d * (float)(int)(int8_t)(r.sc >> 8);
         return o;
@@ -2007,9 +2108,11 @@ template <class F> static int with_gemm_format(int weight_dtype, F f) {
         case NTK_DT_Q4_0: return f(std::integral_constant<int, NTK_DT_Q4_0>{});
         case NTK_DT_Q4_K: return f(std::integral_constant<int, NTK_DT_Q4_K>{});
         case NTK_DT_Q5_K: return f(std::integral_constant<int, NTK_DT_Q5_K>{});
+        case NTK_DT_Q3_K: return f(std::integral_constant<int, NTK_DT_Q3_K>{});
         case NTK_DT_Q4_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q4_K + GB_RP>{});
         case NTK_DT_Q5_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q5_K + GB_RP>{});
         case NTK_DT_Q6_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q6_K + GB_RP>{});
+        case NTK_DT_Q3_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q3_K + GB_RP>{});
         default: return f(std::integral_constant<int, NTK_DT_Q6_K>{});
     }
 }
@@ -2056,11 +2159,11 @@ static int gemm_ws_dispatch(const ntk::HostSeg* segs, int nseg, const float* X, 
 
 // The FP16 GEMM behind its descriptor (include/ntk_engine.h: ntk_gemm_desc): 1..3 matrices of one format sharing X, optional residual (one matrix),
 // optional token maxima, optional deferral of the split-K sums to the consuming launch.
-int ntk_gemm_quant_f16(const ntk_gemm_desc* d, void* stream) {
+// the descriptor's matrices and format (dt: + GB_RP for tensors of the decode repack), or the status the call is refused with
+static int gemm_desc_format(const ntk_gemm_desc* d, ntk::HostSeg* sg, long* total_rows, int* format) {
     if (!d || !d->segs || !d->X || !d->workspace) return NTK_E_NULL;
     const int nseg = d->nseg, n_tokens = d->n_tokens, in_features = d->in_features;
     if (nseg < 1 || nseg > ntk::GB_MAX_SEG || n_tokens < 0 || in_features <= 0 || (d->resid && nseg != 1)) return NTK_E_SHAPE;
-    ntk::HostSeg sg[ntk::GB_MAX_SEG];
     long total = 0;
     for (int i = 0; i < nseg; ++i) {
         if (!d->segs[i].W || !d->segs[i].y) return NTK_E_NULL;
@@ -2069,11 +2172,40 @@ int ntk_gemm_quant_f16(const ntk_gemm_desc* d, void* stream) {
         total += d->segs[i].rows;
     }
     int dt = d->segs[0].dtype;
-    if (dt != NTK_DT_Q8_0 && dt != NTK_DT_Q4_0 && dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K) return NTK_E_DTYPE;
+    if (dt != NTK_DT_Q8_0 && dt != NTK_DT_Q4_0 && dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K && dt != NTK_DT_Q3_K) return NTK_E_DTYPE;
     if (d->weights_repacked) {   // segs[i].W = tensors of the decode repack (ntk_rp_pack): the K-quant formats, rows in whole tiles of 16 (as everything here)
-        if (dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K) return NTK_E_DTYPE;
+        if (dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K && dt != NTK_DT_Q3_K) return NTK_E_DTYPE;
         dt += ntk::GB_RP;
     }
+    *total_rows = total; *format = dt;
+    return NTK_OK;
+}
+
+// Which kernel form ntk_gemm_quant_f16 takes for this descriptor (its first pass of <= 1024 tokens): 0 K-slice, 1 weight-streaming, 2 chunk (GemmForm), or
+// the status it refuses the shape with; rows_per_wave (optional): 16 or 32.  The launch's own plan; launches nothing.
+int ntk_gemm_quant_f16_form(const ntk_gemm_desc* d, int* rows_per_wave) {
+    ntk::HostSeg sg[ntk::GB_MAX_SEG];
+    long total = 0;
+    int dt = 0;
+    const int st = gemm_desc_format(d, sg, &total, &dt);
+    if (st != NTK_OK) return st;
+    int rows[ntk::GB_MAX_SEG];
+    for (int i = 0; i < d->nseg; ++i) rows[i] = sg[i].out;
+    const int T = std::min(d->n_tokens, ntk::GB_MAX_CHUNKS * ntk::GB_TOK);
+    ntk::GemmPlan plan{};
+    ntk::with_gemm_format(dt, [&](auto f) { plan = ntk::gemm_f16_plan<decltype(f)::value>(rows, d->nseg, T, d->in_features, d->full_form != 0, ntk::gemm_tune()); return 0; });
+    if (plan.status != NTK_OK) return plan.status;
+    if (rows_per_wave) *rows_per_wave = 16 * plan.rt;
+    return plan.form;
+}
+
+int ntk_gemm_quant_f16(const ntk_gemm_desc* d, void* stream) {
+    ntk::HostSeg sg[ntk::GB_MAX_SEG];
+    long total = 0;
+    int dt = 0;
+    const int st = gemm_desc_format(d, sg, &total, &dt);
+    if (st != NTK_OK) return st;
+    const int nseg = d->nseg, n_tokens = d->n_tokens, in_features = d->in_features;
     if (d->workspace_bytes < ntk_gemm_quant_workspace_bytes(in_features, (int)total) || (reinterpret_cast<uintptr_t>(d->workspace) & 15)) return NTK_E_SHAPE;
     ntk_gemm_partials* defer = d->partials;
     ntk::set_partials(defer, sg, nseg, n_tokens, 1, nullptr);

@@ -77,6 +77,13 @@ template <> struct GemmFmt<NTK_DT_Q6_K> {
     static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
     static constexpr bool RP = false; static constexpr int ITEM = 0, S1 = 0, S2 = 0;
 };
+template <> struct GemmFmt<NTK_DT_Q3_K> {
+    // blocks of 110 bytes at 2-byte alignment: the window of a unit (an even shift <= 14 + 110) is 8 pieces = 32 dwords, and the next row pitch of 4 x an
+    // odd number of dwords above it is 36 dwords (16 rows x 4 column groups of one read then hit 64 different banks: 36 i + g)
+    static constexpr int BW = 256, BB = 110, SPU = 8, STRIDE = 144, ROW_ALIGN = 4;   // row pitch: in_features a multiple of 512
+    static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
+    static constexpr bool RP = false; static constexpr int ITEM = 0, S1 = 0, S2 = 0;
+};
 template <> struct GemmFmt<NTK_DT_Q4_K + GB_RP> {
     static constexpr bool RP = true;
     static constexpr int S1 = 1024, S2 = 320, ITEM = 2 * S1 + S2;
@@ -93,6 +100,13 @@ template <> struct GemmFmt<NTK_DT_Q6_K + GB_RP> {
     static constexpr bool RP = true;
     static constexpr int S1 = 1536, S2 = 288, ITEM = 2 * S1 + S2;
     static constexpr int BW = 256, BB = 210, SPU = 8, STRIDE = ITEM / 16, ROW_ALIGN = 16;
+    static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
+};
+
+template <> struct GemmFmt<NTK_DT_Q3_K + GB_RP> {   // no nibble chunk: S1 = a step's 2-bit plane (512 B) and its third-bit plane (256 B)
+    static constexpr bool RP = true;
+    static constexpr int S1 = 768, S2 = 288, ITEM = 2 * S1 + S2;
+    static constexpr int BW = 256, BB = 110, SPU = 8, STRIDE = ITEM / 16, ROW_ALIGN = 16;
     static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
 };
 
