@@ -50,7 +50,8 @@ enum {
     NTK_DT_F32 = 0, NTK_DT_F16 = 1, NTK_DT_Q8_0 = 2, NTK_DT_Q4_0 = 3, NTK_DT_Q4_K = 4,
     NTK_DT_Q6_K = 5, NTK_DT_Q5_K = 6, NTK_DT_Q2_K = 7, NTK_DT_I32 = 8,
     NTK_DT_BF16 = 9,  /* not in the reference (GGML type 30): appended, its values above stay */
-    NTK_DT_Q3_K = 10  /* not in the reference (GGML type 11): appended likewise */
+    NTK_DT_Q3_K = 10, /* not in the reference (GGML type 11): appended likewise */
+    NTK_DT_IQ4_NL = 11, NTK_DT_IQ4_XS = 12   /* not in the reference (GGML types 20, 23): the codebook 4-bit formats, appended likewise */
 };
 
 int         ntk_abi_version(void);

@@ -159,6 +159,23 @@ __device__ __forceinline__ uint16_t lds_u16_at(const uint8_t* base, int off) {
 __device__ __forceinline__ float ub2f(uint32_t w, int k) { return (float)((w >> (8 * k)) & 0xFFu); }
 __device__ __forceinline__ float sb2f(uint32_t w, int k) { return (float)(int)(int8_t)(w >> (8 * k)); }
 
+// ---- IQ4_NL / IQ4_XS (ggml types 20 / 23; not in the reference): a 4-bit index selects one of sixteen int8 values,
+//      {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}.  The table is four dwords (value 4 t + b = byte b of dword t) that live in
+//      registers; nothing reads it from memory. ----
+constexpr uint32_t IQ4_T0 = 0xBFAD9881u, IQ4_T1 = 0xF6EADDCFu, IQ4_T2 = 0x26190D01u, IQ4_T3 = 0x71594535u;
+__host__ __device__ __forceinline__ int iq4_value(int idx) {   // one value (the exact, one-weight-at-a-time paths)
+    const uint32_t t = idx < 8 ? (idx < 4 ? IQ4_T0 : IQ4_T1) : (idx < 12 ? IQ4_T2 : IQ4_T3);
+    return (int)(int8_t)(uint8_t)(t >> (8 * (idx & 3)));
+}
+// Four values at once: the indices are bits SH .. SH + 3 of the four bytes of `w` (the other bits may hold anything).  v_perm_b32 selects among EIGHT bytes, so
+// the low three index bits look up both halves of the table (one mask, two permutes) and a third permute picks, byte by byte, the half that index bit 3 names:
+// its selector byte y is y + 4 (bit 3) -- a shift and an and-or.  6 vector instructions for SH = 0, 7 otherwise (the shift of the index field).
+template <int SH> __device__ __forceinline__ uint32_t iq4_lookup4(uint32_t w) {
+    const uint32_t s7 = (SH ? w >> SH : w) & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(IQ4_T1, IQ4_T0, s7), hi = __builtin_amdgcn_perm(IQ4_T3, IQ4_T2, s7);
+    return __builtin_amdgcn_perm(hi, lo, ((w >> (SH + 1)) & 0x04040404u) | 0x03020100u);
+}
+
 // K-quant 6-bit (scale, min) pair j of the 12 packed bytes held in three dwords (types.h:112-117)
 __device__ __forceinline__ void kq_scale_min(uint32_t s0, uint32_t s1, uint32_t s2, int j, float& sc, float& mn) {
     const uint64_t lo = (uint64_t)s0 | ((uint64_t)s1 << 32);  // bytes 0..7

@@ -134,6 +134,20 @@ __device__ float embed_elem(const uint8_t* __restrict__ table, int tok, int hidd
             const int q = (int)(((b[32 + 32 * n + l] >> (2 * j)) & 3) | (((b[l] >> (4 * n + j)) & 1) << 2)) - 4;
             return __fmul_rn(__fmul_rn(d, (float)sc), (float)q);
         }
+        case NTK_DT_IQ4_NL: {   // ggml block_iq4_nl (not in the reference): w = d table[idx], Q4_0's nibble order
+            const uint8_t* b = table + ((size_t)tok * (hidden / 32) + e / 32) * 18;
+            const float d = h2f((uint16_t)(b[0] | (b[1] << 8)));
+            const int j = e & 31;
+            return __fmul_rn(d, (float)iq4_value(j < 16 ? (b[2 + j] & 0x0F) : (b[2 + j - 16] >> 4)));
+        }
+        case NTK_DT_IQ4_XS: {   // ggml block_iq4_xs (not in the reference): w = (d (ls - 32)) table[idx]
+            const uint8_t* b = table + ((size_t)tok * (hidden / 256) + e / 256) * 136;
+            const float d = h2f((uint16_t)(b[0] | (b[1] << 8)));
+            const int w = e & 255, ib = w >> 5, j = w & 31;
+            const int ls = (int)(((b[4 + (ib >> 1)] >> (4 * (ib & 1))) & 15) | ((((b[2] | (b[3] << 8)) >> (2 * ib)) & 3) << 4)) - 32;
+            const uint8_t qb = b[8 + 16 * ib + (j & 15)];
+            return __fmul_rn(__fmul_rn(d, (float)ls), (float)iq4_value(j < 16 ? (qb & 0x0F) : (qb >> 4)));
+        }
         default: return 0.0f;   // Q5_K and anything else: the reference zero-fills (transformer.cpp:595-598)
     }
 }
@@ -322,7 +336,8 @@ int ntk_embed_rows(float* out, const void* table, const int* tokens, int n_token
     const int st = last_launch_status();
     if (st != NTK_OK) return st;
     switch (dtype) {   // rows were zero-filled for anything the reference host path has no branch for
-        case NTK_DT_F32: case NTK_DT_F16: case NTK_DT_BF16: case NTK_DT_Q8_0: case NTK_DT_Q4_0: case NTK_DT_Q4_K: case NTK_DT_Q6_K: case NTK_DT_Q3_K: return NTK_OK;
+        case NTK_DT_F32: case NTK_DT_F16: case NTK_DT_BF16: case NTK_DT_Q8_0: case NTK_DT_Q4_0: case NTK_DT_Q4_K: case NTK_DT_Q6_K: case NTK_DT_Q3_K:
+        case NTK_DT_IQ4_NL: case NTK_DT_IQ4_XS: return NTK_OK;
         default: return NTK_E_DTYPE;
     }
 }

@@ -26,6 +26,8 @@ int ggml_type_to_dtype(uint32_t t) {
         case 12: return NTK_DT_Q4_K;
         case 13: return NTK_DT_Q5_K;
         case 14: return NTK_DT_Q6_K;
+        case 20: return NTK_DT_IQ4_NL;   // not in the reference
+        case 23: return NTK_DT_IQ4_XS;   // not in the reference
         case 26: return NTK_DT_I32;
         case 30: return NTK_DT_BF16;   // not in the reference
         default: return NTK_DT_F32;   // the reference's fallback
@@ -33,12 +35,12 @@ int ggml_type_to_dtype(uint32_t t) {
 }
 
 bool ggml_type_known(uint32_t t) {
-    switch (t) { case 0: case 1: case 2: case 8: case 10: case 11: case 12: case 13: case 14: case 26: case 30: return true; default: return false; }
+    switch (t) { case 0: case 1: case 2: case 8: case 10: case 11: case 12: case 13: case 14: case 20: case 23: case 26: case 30: return true; default: return false; }
 }
 
 const char* dtype_name(int dt) {
-    static const char* n[] = {"F32", "F16", "Q8_0", "Q4_0", "Q4_K_M", "Q6_K", "Q5_K", "Q2_K", "I32", "BF16", "Q3_K"};
-    return dt >= 0 && dt <= 10 ? n[dt] : "UNKNOWN";
+    static const char* n[] = {"F32", "F16", "Q8_0", "Q4_0", "Q4_K_M", "Q6_K", "Q5_K", "Q2_K", "I32", "BF16", "Q3_K", "IQ4_NL", "IQ4_XS"};
+    return dt >= 0 && dt <= 12 ? n[dt] : "UNKNOWN";
 }
 
 void ModelConfig::print() const {   // same fields the reference prints (config.cpp:52-65)

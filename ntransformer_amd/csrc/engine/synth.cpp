@@ -51,6 +51,8 @@ BlockInfo block_of(int gt) {
         case 12: return {256, 144};
         case 13: return {256, 176};
         case 14: return {256, 210};
+        case 20: return {32, 18};
+        case 23: return {256, 136};
         case 30: return {1, 2};   // BF16
         default: return {0, 0};
     }
@@ -97,6 +99,16 @@ void fill_unit(uint8_t* dst, int gt, uint64_t key, uint64_t unit, double tgt) {
             put16(dst + 108, f2h((float)(tgt / (2.35 * 18.5) * jit)));
             break;
         }
+        case 20: {  // IQ4_NL: d, qs[16] of table indices; RMS of the sixteen table values 67.4
+            fill_random(dst + 2, 16, st);
+            put16(dst, f2h((float)(tgt / 67.4 * jit)));
+            break;
+        }
+        case 23: {  // IQ4_XS: d, scales_h, scales_l[4], qs[128]; RMS of the table values 67.4, of (ls - 32) 18.5
+            fill_random(dst + 2, 134, st);
+            put16(dst, f2h((float)(tgt / (67.4 * 18.5) * jit)));
+            break;
+        }
         default: break;
     }
 }
@@ -124,6 +136,8 @@ int mix_type(const std::string& mix) {
     if (mix == "Q5_K") return 13;
     if (mix == "Q6_K") return 14;
     if (mix == "Q3_K" || mix == "Q3_K_M") return 11;
+    if (mix == "IQ4_NL") return 20;
+    if (mix == "IQ4_XS") return 23;
     if (mix == "F16") return 1;
     if (mix == "BF16") return 30;
     if (mix == "F32") return 0;
@@ -196,6 +210,9 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     // Q3_K_M: llama.cpp's rule as remembered (its source is not at hand; gguf.py tensor_types states the same): Q3_K beside Q4_K, Q5_K and Q6_K
     // where real files put it.  Plain Q3_K keeps a Q6_K LM head, as those files do.
     const bool k3m = fl.mix == "Q3_K_M";
+    // IQ4_XS: the file mix of that name, llama.cpp's rule as remembered (its source is not at hand; gguf.py tensor_types states the same): attn_v and the
+    // first eighth of the ffn_down layers on Q5_K, a Q6_K LM head, IQ4_XS everywhere else (the embedding too).  IQ4_NL is plain: every matrix of the type.
+    const bool xs = fl.mix == "IQ4_XS";
     const int base = km ? 12 : mix_type(fl.mix);
     if (base < 0 || s.heads <= 0 || s.kv_heads <= 0 || (fl.head_dim ? fl.head_dim < 0 || (fl.head_dim & 1) : s.hidden % s.heads)) return false;
     if (fl.experts && (fl.experts < 1 || fl.experts > 256 || fl.used < 1 || fl.used > std::min(fl.experts, 16) || fl.expert_inter < 0)) return false;
@@ -211,8 +228,8 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     for (int i = 0; i < s.layers; ++i) {
         const std::string p = "blk." + std::to_string(i) + ".";
         const bool more = km && (sample_of > 0 ? use_more_bits(sample[i], sample_of) : use_more_bits(i, s.layers));
-        const int v_t = k3m ? (i < 2 ? 13 : 12) : more ? 14 : (km && s.heads / s.kv_heads >= 4 && s.hidden >= 8192 ? 13 : base);
-        const int down_t = k3m ? (i < s.layers / 16 ? 13 : use_more_bits(i, s.layers) ? 12 : 11) : more ? 14 : base;
+        const int v_t = xs ? 13 : k3m ? (i < 2 ? 13 : 12) : more ? 14 : (km && s.heads / s.kv_heads >= 4 && s.hidden >= 8192 ? 13 : base);
+        const int down_t = xs ? (i < s.layers / 8 ? 13 : base) : k3m ? (i < s.layers / 16 ? 13 : use_more_bits(i, s.layers) ? 12 : 11) : more ? 14 : base;
         add(p + "attn_norm.weight", 0, s.hidden, 1, 0);
         add(p + "attn_q.weight", base, s.hidden, q_dim, 1);
         add(p + "attn_k.weight", base, s.hidden, kv_dim, 1);
@@ -240,7 +257,7 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
         add(p + "ffn_down.weight", down_t, s.inter, s.hidden, 1);
     }
     add("output_norm.weight", 0, s.hidden, 1, 0);
-    if (!fl.tied) add("output.weight", km || base == 11 ? 14 : base, s.hidden, s.vocab, 2.0);
+    if (!fl.tied) add("output.weight", km || base == 11 || xs ? 14 : base, s.hidden, s.vocab, 2.0);
     return true;
 }
 

@@ -18,6 +18,8 @@ template <> struct GFmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, 
 template <> struct GFmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, SB = 176; };
 template <> struct GFmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, SB = 210; };
 template <> struct GFmt<NTK_DT_Q3_K> { static constexpr int BW = 256, BB = 110, SB = 110; };
+template <> struct GFmt<NTK_DT_IQ4_NL> { static constexpr int BW = 32, BB = 18, SB = 144; };
+template <> struct GFmt<NTK_DT_IQ4_XS> { static constexpr int BW = 256, BB = 136, SB = 136; };
 // Unquantised 16-bit rows (IEEE half, bfloat16): a "block" is 32 consecutive weights in 64 bytes, no scale.  A chunk of a row is then 8 KiB, and
 // sixteen of them with the padded pitch would not fit the CU's 160 KiB beside the reduction buffers; these formats require 16-byte-aligned rows
 // instead (W aligned; a row is a multiple of 64 bytes), stage exactly 8 KiB per row at a pitch of 8 KiB and keep the reads conflict-free by
@@ -145,6 +147,31 @@ template <> struct Deq<NTK_DT_Q3_K> {   // ggml block_q3_K (not in the reference
                       ((q[1] >> sh) & 0x03030303u) | (((h[1] >> s) & 0x01010101u) << 2), n);
 #pragma unroll
         for (int j = 0; j < 8; ++j) a[j] = sc * (n[j] - 4.0f);
+    }
+};
+
+// IQ4_NL / IQ4_XS (ggml block_iq4_nl / block_iq4_xs, not in the reference): the sub-block's 16 index bytes in Q4_0's nibble order, through the register table
+// (iq4_lookup4, common.hip.h); w = d table[idx] / (d (ls - 32)) table[idx], the products in gguf.dequantize's order
+__device__ __forceinline__ void iq4_group(const uint8_t* st, int qoff, int g, float sc, float (&a)[8]) {
+    uint32_t q[2];
+    lds_read_dwords<2>(q, st, qoff + 8 * (g & 1));
+    const int sh = 4 * (g >> 1);
+    const uint32_t k0 = iq4_lookup4<0>(q[0] >> sh), k1 = iq4_lookup4<0>(q[1] >> sh);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { a[j] = sc * sb2f(k0, j); a[4 + j] = sc * sb2f(k1, j); }
+}
+template <> struct Deq<NTK_DT_IQ4_NL> {
+    __device__ static void run(const uint8_t* st, int shift, int s, int g, float (&a)[8]) {
+        const int ob = shift + 18 * s;
+        iq4_group(st, ob + 2, g, h2f(lds_u16_at(st, ob)), a);
+    }
+};
+template <> struct Deq<NTK_DT_IQ4_XS> {   // sub-block s: ls = 4 bits of scales_l[s / 2], 2 bits of scales_h on top
+    __device__ static void run(const uint8_t* st, int shift, int s, int g, float (&a)[8]) {
+        uint32_t hd[2];   // d | scales_h << 16, scales_l
+        lds_read_dwords<2>(hd, st, shift);
+        const int ls = (int)(((hd[1] >> (4 * s)) & 15u) | (((hd[0] >> (16 + 2 * s)) & 3u) << 4)) - 32;
+        iq4_group(st, shift + 8 + 16 * s, g, h2f((uint16_t)(hd[0] & 0xFFFFu)) * (float)ls, a);
     }
 };
 

@@ -750,7 +750,8 @@ __global__ __launch_bounds__(256) void gemv_dense_kernel(float* __restrict__ y, 
 // host side
 // ------------------------------------------------------------------------------------------------
 static bool is_quant(int dt) {
-    return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K;
+    return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K ||
+           dt == NTK_DT_IQ4_NL || dt == NTK_DT_IQ4_XS;
 }
 
 struct GemvLaunch {
@@ -1042,6 +1043,8 @@ static int dispatch_quant(int dt, const ntk_gemv_seg* segs, int nseg, const floa
         case NTK_DT_Q5_K: return launch_quant<NTK_DT_Q5_K>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
         case NTK_DT_Q6_K: return launch_quant<NTK_DT_Q6_K>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st, xi_mode);
         case NTK_DT_Q3_K: return launch_quant<NTK_DT_Q3_K>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
+        case NTK_DT_IQ4_NL: return launch_quant<NTK_DT_IQ4_NL>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
+        case NTK_DT_IQ4_XS: return launch_quant<NTK_DT_IQ4_XS>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
         default: return NTK_E_DTYPE;
     }
 }

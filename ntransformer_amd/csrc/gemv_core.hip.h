@@ -41,6 +41,8 @@ template <> struct Fmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, N
 template <> struct Fmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, NL = 3, MINW = 4; };
 template <> struct Fmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, NL = 4, MINW = 4; };
 template <> struct Fmt<NTK_DT_Q3_K> { static constexpr int BW = 256, BB = 110, NL = 2, MINW = 4; };   // 16 blocks of 110 bytes + 15: two chunks
+template <> struct Fmt<NTK_DT_IQ4_NL> { static constexpr int BW = 32, BB = 18, NL = 3, MINW = 4; };    // Q4_0's geometry
+template <> struct Fmt<NTK_DT_IQ4_XS> { static constexpr int BW = 256, BB = 136, NL = 3, MINW = 4; };  // 16 blocks of 136 bytes + 15: three chunks
 // (Round 3 also built the row stream of gemv.hip on an LDS-DMA ring -- two or three row slices in flight per wave instead of one -- and measured
 // NOTHING: Q4_K gate|up 16.7 -> 16.3 us, LM head 52.8 -> 52.7, 70B gate|up 48.7 -> 49.1 (profiles/r03_gemv_lds_dma_ring_experiment.txt):
 // the long K-quant launches were bound by VALU issue, not by bytes in flight.  That form was removed in round 4, when the matrix-core
@@ -459,6 +461,62 @@ template <bool A16> struct Dot<NTK_DT_Q3_K, A16> {
         bs = fmaf(ub2f(sc, 1) - 32.0f, fmaf(-4.0f, sx16[1], S[1]), bs);
         bs = fmaf(ub2f(sc, 2) - 32.0f, fmaf(-4.0f, sx16[2], S[2]), bs);
         bs = fmaf(ub2f(sc, 3) - 32.0f, fmaf(-4.0f, sx16[3], S[3]), bs);
+        return d * bs;
+    }
+};
+
+// IQ4_NL / IQ4_XS (ggml block_iq4_nl: d qs[16], 18 bytes at any even alignment; block_iq4_xs: d scales_h scales_l[4] qs[128], 136 bytes at 4-byte
+// alignment; neither is in the reference).  A 32-weight sub-block is 16 bytes of table indices in Q4_0's nibble order; the table is signed and has no
+// offset, so nothing leaves through the run sums of x: four index bytes become four table bytes in registers (iq4_lookup4, common.hip.h) and convert
+// as signed bytes.  One sub-block: sum_k table[idx_k] x_k over its 32 columns, x2[0..15] = the sub-block's (even, odd) activation pairs.
+__device__ __forceinline__ float iq4_dot32(const uint32_t (&q)[4], const f32x2* x2) {
+    float a0 = 0.0f, a1 = 0.0f, b0 = 0.0f, b1 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t lo = iq4_lookup4<0>(q[i]), hi = iq4_lookup4<4>(q[i]);   // columns 4 i .. 4 i + 3 / 16 + 4 i ..
+        const f32x2 xa = x2[2 * i], xb = x2[2 * i + 1], xc = x2[8 + 2 * i], xd = x2[8 + 2 * i + 1];
+        a0 = fmaf(sb2f(lo, 0), xa.x, a0); a1 = fmaf(sb2f(lo, 1), xa.y, a1); a0 = fmaf(sb2f(lo, 2), xb.x, a0); a1 = fmaf(sb2f(lo, 3), xb.y, a1);
+        b0 = fmaf(sb2f(hi, 0), xc.x, b0); b1 = fmaf(sb2f(hi, 1), xc.y, b1); b0 = fmaf(sb2f(hi, 2), xd.x, b0); b1 = fmaf(sb2f(hi, 3), xd.y, b1);
+    }
+    return (a0 + a1) + (b0 + b1);
+}
+
+template <bool A16> struct Dot<NTK_DT_IQ4_NL, A16> {   // lane = two blocks, as Dot<Q4_0>: w = d table[idx]
+    __device__ static float run(const uint8_t* st, int shift, int lane, int ncols, const f32x2 (&x2)[32],
+                                const float (&)[4], const float (&)[2]) {
+        float acc = 0.0f;
+        const int o = shift + 36 * lane;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (ncols > 32 * h) {
+                const int ob = o + 18 * h;
+                const float d = h2f(lds_u16_at(st, ob));
+                uint32_t q[4];
+                lds_read_dwords<4>(q, st, ob + 2);
+                acc = fmaf(d, iq4_dot32(q, &x2[16 * h]), acc);
+            }
+        }
+        return acc;
+    }
+};
+
+template <bool A16> struct Dot<NTK_DT_IQ4_XS, A16> {   // lane = (block, c): sub-blocks 2 c and 2 c + 1; w = d (ls - 32) table[idx]
+    __device__ static float run(const uint8_t* st, int shift, int lane, int ncols, const f32x2 (&x2)[32],
+                                const float (&)[4], const float (&)[2]) {
+        if (ncols <= 0) return 0.0f;
+        const int c = lane & 3, ob = shift + 136 * (lane >> 2);
+        uint32_t hd[2];   // d | scales_h << 16, scales_l
+        lds_read_dwords<2>(hd, st, ob);
+        const float d = h2f((uint16_t)(hd[0] & 0xFFFFu));
+        const uint32_t sl = hd[1] >> (8 * c), sh = hd[0] >> (16 + 4 * c);   // the pair's two low nibbles, its two 2-bit tops
+        float bs = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            uint32_t q[4];
+            lds_read_dwords<4>(q, st, ob + 8 + 32 * c + 16 * t);
+            const int ls = (int)(((sl >> (4 * t)) & 15u) | (((sh >> (2 * t)) & 3u) << 4)) - 32;
+            bs = fmaf((float)ls, iq4_dot32(q, &x2[16 * t]), bs);
+        }
         return d * bs;
     }
 };

@@ -25,14 +25,18 @@
 //              [0, 512)   dwords 2 l + h: bits 8 y + 2 v (+1) = bits 0..1 of the quant of column 128 s + 64 h + 16 kg + 4 v + y   (Q6_K's top-bit plane, one level down)
 //              [512, 768) dword l: bit 8 y + 2 + v (h = 0) / 8 y + ((6 + v) & 7) (h = 1) = bit 2 of the quant of that column -- positions from which every one of
 //              the eight operand dwords takes its bit with ONE shift (none for h = 0, v = 0) into bit 2 of each byte
-//   Bytes: Q4_K 2368 per item (GGUF 2304: 1.028 x), Q5_K 2880 (2816: 1.023 x), Q6_K 3360 (3360: 1.000 x), Q3_K 1824 (1760: 1.036 x).
+//        IQ4_XS (w = d (ls - 32) table[idx], a fixed table of sixteen int8 values, no minimum / offset term): Q4_K's nibble chunk holds the table INDICES of
+//              columns c and c + 64; the row record is 8 bytes -- the eight 6-bit scales as int8 already reduced by 32 -- then 16 x d: S2 = 160.
+//   Bytes: Q4_K 2368 per item (GGUF 2304: 1.028 x), Q5_K 2880 (2816: 1.023 x), Q6_K 3360 (3360: 1.000 x), Q3_K 1824 (1760: 1.036 x), IQ4_XS 2208 (2176: 1.015 x).
 //   Rows are padded to whole tiles with zero weights.
 //
 // MFMA roles: first operand (M = 16) = digit planes of x from LDS, entry m = 4 jj + p (sub-block jj of the 64 columns, digit p; p = 3
 // unused), zero outside its own sub-block; second operand (N = 16) = the 16 weight rows.  Accumulator lane (row i = lane & 15,
 // mg = lane >> 4) register r = digit r of sub-block mg: a lane scales ITS row by ITS sub-block's scale (v_bfe + 3 v_mad_i32_i24),
 // sums the super-block in integers, and converts once per super-block.  The minimum / offset term is one more MFMA per super-block:
-// the row's m[8] (sc[16]) against the digits of the sub-block sums of X.
+// the row's m[8] (sc[16]) against the digits of the sub-block sums of X.  IQ4_XS has no such term: four MFMAs per item, whose B operands are the table's
+// int8 values themselves -- the index nibbles go through a 16-entry table held in four register dwords (iq4_lookup4, common.hip.h; 13 vector instructions
+// per 8 weights where Q4_K's masks are 3: DESIGN 3.1).
 #include "common.hip.h"
 #include <algorithm>
 #include <cstdio>
@@ -46,18 +50,21 @@ typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 
 template <int DT> struct Rp;
-template <> struct Rp<NTK_DT_Q4_K> { static constexpr int S1 = 1024, S2 = 320, BB = 144, NSUB = 8; };
-template <> struct Rp<NTK_DT_Q5_K> { static constexpr int S1 = 1280, S2 = 320, BB = 176, NSUB = 8; };
-template <> struct Rp<NTK_DT_Q6_K> { static constexpr int S1 = 1536, S2 = 288, BB = 210, NSUB = 16; };
-template <> struct Rp<NTK_DT_Q3_K> { static constexpr int S1 = 768, S2 = 288, BB = 110, NSUB = 16; };
+// (REC: bytes of a row's record in P2; MIN: the format has a minimum / offset term -- the fifth MFMA of an item)
+template <> struct Rp<NTK_DT_Q4_K> { static constexpr int S1 = 1024, S2 = 320, BB = 144, NSUB = 8, REC = 16; static constexpr bool MIN = true; };
+template <> struct Rp<NTK_DT_Q5_K> { static constexpr int S1 = 1280, S2 = 320, BB = 176, NSUB = 8, REC = 16; static constexpr bool MIN = true; };
+template <> struct Rp<NTK_DT_Q6_K> { static constexpr int S1 = 1536, S2 = 288, BB = 210, NSUB = 16, REC = 16; static constexpr bool MIN = true; };
+template <> struct Rp<NTK_DT_Q3_K> { static constexpr int S1 = 768, S2 = 288, BB = 110, NSUB = 16, REC = 16; static constexpr bool MIN = true; };
+template <> struct Rp<NTK_DT_IQ4_XS> { static constexpr int S1 = 1024, S2 = 160, BB = 136, NSUB = 8, REC = 8; static constexpr bool MIN = false; };
 // (the format exists for its bytes: the repack may cost 4 % over the GGUF blocks of a whole tile, no more)
 static_assert(25 * (2 * Rp<NTK_DT_Q3_K>::S1 + Rp<NTK_DT_Q3_K>::S2) <= 26 * 16 * Rp<NTK_DT_Q3_K>::BB, "Q3_K repack: at most 1.04 x the GGUF bytes");
+static_assert(25 * (2 * Rp<NTK_DT_IQ4_XS>::S1 + Rp<NTK_DT_IQ4_XS>::S2) <= 26 * 16 * Rp<NTK_DT_IQ4_XS>::BB, "IQ4_XS repack: at most 1.04 x the GGUF bytes");
 // bit of the Q3_K third-bit plane that holds (half h, dword v) of byte y's column
 __host__ __device__ constexpr int q3_hpos(int h, int v) { return h ? ((6 + v) & 7) : 2 + v; }
 
-static bool rp_supported(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K; }
-static size_t rp_s1(int dt) { return dt == NTK_DT_Q4_K ? 1024 : dt == NTK_DT_Q5_K ? 1280 : dt == NTK_DT_Q3_K ? 768 : 1536; }
-static size_t rp_s2(int dt) { return dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K ? 288 : 320; }
+static bool rp_supported(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K || dt == NTK_DT_IQ4_XS; }
+static size_t rp_s1(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_IQ4_XS ? 1024 : dt == NTK_DT_Q5_K ? 1280 : dt == NTK_DT_Q3_K ? 768 : 1536; }
+static size_t rp_s2(int dt) { return dt == NTK_DT_IQ4_XS ? 160 : dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K ? 288 : 320; }
 
 // ------------------------------------------------------------------------------------------------------------------
 // raw GGUF accessors (reference src/core/types.h:112-137): the quant integer of column cc of a super-block
@@ -73,6 +80,9 @@ template <int DT> __device__ __forceinline__ int raw_q(const uint8_t* blk, int c
     } else if constexpr (DT == NTK_DT_Q3_K) {   // ggml block_q3_K: hmask[32] qs[64] scales[12] d
         const int n = cc >> 7, j = (cc >> 5) & 3, l = cc & 31;
         return ((blk[32 + 32 * n + l] >> (2 * j)) & 3) | (((blk[l] >> (4 * n + j)) & 1) << 2);
+    } else if constexpr (DT == NTK_DT_IQ4_XS) {   // ggml block_iq4_xs: d scales_h scales_l[4] qs[128]; the table INDEX, Q4_0's nibble order per 32 columns
+        const int by = blk[8 + 16 * (cc >> 5) + (cc & 15)];
+        return (cc & 16) ? (by >> 4) : (by & 15);
     } else {
         const int n = cc >> 7, quarter = (cc >> 5) & 3, l = cc & 31;
         const int by = blk[64 * n + l + ((quarter & 1) ? 32 : 0)];
@@ -126,7 +136,11 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
         uint16_t d = 0, dmin = 0;
         for (int k = 0; k < 16; ++k) rec[k] = 0;
         if (lv) {
-            if constexpr (DT == NTK_DT_Q3_K) {   // the sixteen 6-bit scales as ggml unpacks its 12 bytes, reduced by 32
+            if constexpr (DT == NTK_DT_IQ4_XS) {   // the eight 6-bit scales (4 bits of scales_l, 2 of scales_h), reduced by 32
+                const uint32_t sh = (uint32_t)(b2[2] | (b2[3] << 8));
+                for (int k = 0; k < 8; ++k) rec[k] = (uint8_t)((((b2[4 + (k >> 1)] >> (4 * (k & 1))) & 15) | (((sh >> (2 * k)) & 3) << 4)) - 32);
+                d = (uint16_t)(b2[0] | (b2[1] << 8));
+            } else if constexpr (DT == NTK_DT_Q3_K) {   // the sixteen 6-bit scales as ggml unpacks its 12 bytes, reduced by 32
                 const uint8_t* a = b2 + 96;
                 for (int k = 0; k < 4; ++k) {
                     rec[k] = (uint8_t)(((a[k] & 15) | (((a[8 + k] >> 0) & 3) << 4)) - 32);
@@ -149,8 +163,8 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
                 d = (uint16_t)(b2[0] | (b2[1] << 8)); dmin = (uint16_t)(b2[2] | (b2[3] << 8));
             }
         }
-        for (int k = 0; k < 16; ++k) p2[16 * t + k] = rec[k];
-        if constexpr (F::NSUB == 16) *reinterpret_cast<uint16_t*>(p2 + 256 + 2 * t) = d;
+        for (int k = 0; k < F::REC; ++k) p2[F::REC * t + k] = rec[k];
+        if constexpr (F::NSUB == 16 || !F::MIN) *reinterpret_cast<uint16_t*>(p2 + 16 * F::REC + 2 * t) = d;
         else *reinterpret_cast<uint32_t*>(p2 + 256 + 4 * t) = (uint32_t)d | ((uint32_t)dmin << 16);
     }
 }
@@ -231,7 +245,25 @@ __global__ __launch_bounds__(256) void rp_unpack_kernel(uint8_t* __restrict__ ra
     const int i = t & 15;
     uint8_t* row = outb + i * PITCH;
     auto ld32 = [&](const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); };
-    if constexpr (DT == NTK_DT_Q3_K) {   // hmask[32] qs[64] scales[12] d   (ggml block_q3_K)
+    if constexpr (DT == NTK_DT_IQ4_XS) {   // d scales_h scales_l[4] qs[128]   (ggml block_iq4_xs)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {    // qs[16 ib + 4 w ..+3], ib = (t >> 6) + 4 s: columns 32 ib + 4 w .. (low nibbles) and 16 more (high) = nibble h = (ib >> 1) & 1
+            const int w = (t >> 4) & 3, ib = (t >> 6) + 4 * s, h = (ib >> 1) & 1;   // of lanes kg = 2 (ib & 1) and 2 (ib & 1) + 1, step s
+            const uint8_t* sp = p1 + (size_t)s * F::S1 + 4 * w;
+            const uint32_t A = ld32(sp + 16 * (16 * (2 * (ib & 1)) + i)) >> (4 * h), B = ld32(sp + 16 * (16 * (2 * (ib & 1) + 1) + i)) >> (4 * h);
+            *reinterpret_cast<uint32_t*>(row + 8 + 16 * ib + 4 * w) = (A & 0x0F0F0F0Fu) | ((B & 0x0F0F0F0Fu) << 4);
+        }
+        if (t < 16) {                    // d, scales_h, scales_l: ls - 32 keeps the low six bits of ls with bit 5 flipped
+            uint32_t sl = 0, sh = 0;
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t ls = ((uint32_t)p2[8 * i + k] ^ 0x20u) & 0x3Fu;
+                sl |= (ls & 15u) << (4 * k);
+                sh |= (ls >> 4) << (2 * k);
+            }
+            *reinterpret_cast<uint32_t*>(row) = (uint32_t)*reinterpret_cast<const uint16_t*>(p2 + 128 + 2 * i) | (sh << 16);
+            *reinterpret_cast<uint32_t*>(row + 4) = sl;
+        }
+    } else if constexpr (DT == NTK_DT_Q3_K) {   // hmask[32] qs[64] scales[12] d   (ggml block_q3_K)
         {                                // qs[32 n + 4 w ..+3]: two bits of each of the four 32-column quarters of half n (as Q6_K's qh, from the 2-bit plane)
             const int w = (t >> 4) & 7, n = t >> 7;
             uint32_t v = 0;
@@ -348,7 +380,11 @@ __global__ __launch_bounds__(256) void rp_dequant_kernel(float* __restrict__ out
         if constexpr (DT == NTK_DT_Q5_K) q |= (int)((*reinterpret_cast<const uint32_t*>(p1 + 1024 + 4 * l) >> (8 * y + 4 * h + v)) & 1u) << 4;
         if constexpr (DT == NTK_DT_Q6_K) q |= (int)((*reinterpret_cast<const uint32_t*>(p1 + 1024 + 8 * l + 4 * h) >> (8 * y + 2 * v)) & 3u) << 4;
         float w;
-        if constexpr (DT == NTK_DT_Q3_K) {   // w = (d (s - 32)) (q - 4)
+        if constexpr (DT == NTK_DT_IQ4_XS) {   // w = (d (ls - 32)) table[q]
+            const float d = h2f(*reinterpret_cast<const uint16_t*>(p2 + 128 + 2 * i));
+            const float sc = (float)(int)(int8_t)p2[8 * i + (c >> 5)];
+            w = __fmul_rn(__fmul_rn(d, sc), (float)iq4_value(q));
+        } else if constexpr (DT == NTK_DT_Q3_K) {   // w = (d (s - 32)) (q - 4)
             const float d = h2f(*reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i));
             const float sc = (float)(int)(int8_t)p2[16 * i + (c >> 4)];
             w = __fmul_rn(__fmul_rn(d, sc), (float)(q - 4));
@@ -468,7 +504,7 @@ template <int DT> struct RpItem {
     u4 rec;         // the row record
     uint32_t dd;    // d | dmin << 16  (Q6_K: d)
     uint32_t hb0, hb1;   // Q5_K; Q3_K: the third-bit plane
-    u2 hh0, hh1;         // Q6_K; Q3_K: the 2-bit plane (n0 / n1 stay unused)
+    u2 hh0, hh1;         // Q6_K; Q3_K: the 2-bit plane (n0 / n1 stay unused); IQ4_XS: hh0 = its 8-byte row record (rec stays unused)
 };
 
 template <int DT, bool NORM>
@@ -543,9 +579,14 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
             it.hh1 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p1 + F::S1 + 1024 + 8 * lane));
         }
         // (non-temporal like the rest of the weight stream: 12 % of the bytes must not push the KV cache and the activations out of L2)
+        if constexpr (!F::MIN) {   // IQ4_XS: eight int8 scales and d -- no minimum bytes, no dmin
+            it.hh0 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p2 + 8 * i16));
+            it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p2 + 128 + 2 * i16));
+        } else {
         it.rec = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p2 + 16 * i16));
         if constexpr (NSUB == 16) it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i16));
         else it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p2 + 256 + 4 * i16));
+        }
         l_idx += NW;
     };
 
@@ -655,6 +696,11 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
             if constexpr (DT == NTK_DT_Q4_K) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { b0[k] = (int)(raw[k] & 0x0F0F0F0Fu); b1[k] = (int)((raw[k] >> 4) & 0x0F0F0F0Fu); }
+            } else if constexpr (DT == NTK_DT_IQ4_XS) {
+                // table indices -> the table's int8 values, in registers: per dword of four indices one mask, two permutes over the table's halves, a shift and an and-or
+                // for the selector of the third permute (6), one more shift for the high nibbles (7): 13 vector instructions per 8 weights (Q4_K 3, Q3_K 7.25: DESIGN 3.1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { b0[k] = (int)iq4_lookup4<0>(raw[k]); b1[k] = (int)iq4_lookup4<4>(raw[k]); }
             } else if constexpr (DT == NTK_DT_Q5_K) {
                 const uint32_t hb = s ? it.hb1 : it.hb0;   // byte y, bit 4 h + v
 #pragma unroll
@@ -685,6 +731,28 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
             }
         }
         // minimum (Q4_K / Q5_K: dmin sum_j m_j sum x) / offset (Q6_K: 32 d sum_j sc_j sum x, Q3_K: 4 d sum_j (s_j - 32) sum x) term: the row's bytes x the digits of the sums
+        // (IQ4_XS has no such term: its items neither load these bytes nor issue the fifth instruction)
+        if constexpr (!F::MIN) {
+            const v4i a0 = *reinterpret_cast<const v4i*>(xa), a1 = *reinterpret_cast<const v4i*>(xa + 64);
+            const v4i a2 = *reinterpret_cast<const v4i*>(xa + 128), a3 = *reinterpret_cast<const v4i*>(xa + 192);
+            const float inv = invt[sbk];
+            const v4i c0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b[0], z4, 0, 0, 0);
+            const v4i c1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b[1], z4, 0, 0, 0);
+            const v4i c2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a2, b[2], z4, 0, 0, 0);
+            const v4i c3 = __builtin_amdgcn_mfma_i32_16x16x64_i8(a3, b[3], z4, 0, 0, 0);
+            // Q4_K's byte positions (sub-block 4 s + 2 h + mg: byte 2 h + mg of dword s) in an 8-byte record of SIGNED scales.
+            // Integer headroom: a digit is at most 128 in magnitude and a table value 127, so a sub-block sum of 32 products reaches 128 * 127 * 32 = 520 192 < 2^23:
+            // it fits the signed 24-bit multiply.  Times |ls - 32| <= 32, times the four products of a sum: 66 584 576 < 2^31.  The sums may exceed 2^24, so their
+            // conversions to float below may round, by at most 2^-24 relative each (Q4_K's sums, below 2^24, convert exactly).
+            const int s0 = __builtin_amdgcn_sbfe((int)it.hh0[0], o0, 8u), s1 = __builtin_amdgcn_sbfe((int)it.hh0[0], o1, 8u);
+            const int s2 = __builtin_amdgcn_sbfe((int)it.hh0[1], o0, 8u), s3 = __builtin_amdgcn_sbfe((int)it.hh0[1], o1, 8u);
+            const int i0 = __mul24(c0[0], s0) + __mul24(c1[0], s1) + __mul24(c2[0], s2) + __mul24(c3[0], s3);
+            const int i1 = __mul24(c0[1], s0) + __mul24(c1[1], s1) + __mul24(c2[1], s2) + __mul24(c3[1], s3);
+            const int i2 = __mul24(c0[2], s0) + __mul24(c1[2], s1) + __mul24(c2[2], s2) + __mul24(c3[2], s3);
+            const float S = fmaf(fmaf((float)i2, 256.0f, (float)i1), 256.0f, (float)i0);
+            racc = fmaf(S, h2f((uint16_t)(it.dd & 0xFFFFu)) * inv, racc);
+            return;
+        }
         v4i bc;
         if constexpr (NSUB == 8) bc = v4i{kg == 0 ? (int)it.rec[2] : 0, kg == 0 ? (int)it.rec[3] : 0, 0, 0};
         else bc = v4i{kg == 0 ? (int)it.rec[0] : 0, kg == 0 ? (int)it.rec[1] : 0, kg == 0 ? (int)it.rec[2] : 0, kg == 0 ? (int)it.rec[3] : 0};
@@ -974,6 +1042,7 @@ int ntk_rp_pack(void* dst, const void* raw, int rows, int in_features, int dtype
     if (dtype == NTK_DT_Q4_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q4_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q5_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q3_K>, g, b, 0, st, d, r, rows, nsb, p2);
+    else if (dtype == NTK_DT_IQ4_XS) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_IQ4_XS>, g, b, 0, st, d, r, rows, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q6_K>, g, b, 0, st, d, r, rows, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -993,6 +1062,7 @@ int ntk_rp_unpack(void* raw, const void* rp, int rows, int in_features, int dtyp
     if (dtype == NTK_DT_Q4_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q4_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q5_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q3_K>, g, b, 0, st, d, r, rows, nsb, p2);
+    else if (dtype == NTK_DT_IQ4_XS) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_IQ4_XS>, g, b, 0, st, d, r, rows, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q6_K>, g, b, 0, st, d, r, rows, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -1009,6 +1079,7 @@ int ntk_rp_dequant(float* out, const void* rp, int rows, int in_features, int dt
     if (dtype == NTK_DT_Q4_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q4_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q5_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q3_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
+    else if (dtype == NTK_DT_IQ4_XS) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_IQ4_XS>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q6_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -1077,7 +1148,8 @@ int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in
     const bool nm = norm_w != nullptr;
     if (dta == dtb) {
         fn = dta == NTK_DT_Q4_K ? rp_fn<NTK_DT_Q4_K, NTK_DT_Q4_K>(nm) : dta == NTK_DT_Q5_K ? rp_fn<NTK_DT_Q5_K, NTK_DT_Q5_K>(nm)
-           : dta == NTK_DT_Q3_K ? rp_fn<NTK_DT_Q3_K, NTK_DT_Q3_K>(nm) : rp_fn<NTK_DT_Q6_K, NTK_DT_Q6_K>(nm);
+           : dta == NTK_DT_Q3_K ? rp_fn<NTK_DT_Q3_K, NTK_DT_Q3_K>(nm) : dta == NTK_DT_IQ4_XS ? rp_fn<NTK_DT_IQ4_XS, NTK_DT_IQ4_XS>(nm)
+           : rp_fn<NTK_DT_Q6_K, NTK_DT_Q6_K>(nm);
     } else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q6_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q6_K>(nm);
     else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q5_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q5_K>(nm);
     else if (dta == NTK_DT_Q6_K && dtb == NTK_DT_Q4_K) fn = rp_fn<NTK_DT_Q6_K, NTK_DT_Q4_K>(nm);
@@ -1086,6 +1158,10 @@ int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in
     else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q3_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q3_K>(nm);
     else if (dta == NTK_DT_Q3_K && dtb == NTK_DT_Q5_K) fn = rp_fn<NTK_DT_Q3_K, NTK_DT_Q5_K>(nm);
     else if (dta == NTK_DT_Q5_K && dtb == NTK_DT_Q3_K) fn = rp_fn<NTK_DT_Q5_K, NTK_DT_Q3_K>(nm);
+    else if (dta == NTK_DT_IQ4_XS && dtb == NTK_DT_Q5_K) fn = rp_fn<NTK_DT_IQ4_XS, NTK_DT_Q5_K>(nm);   // the Q | K | V launches of IQ4_XS files (attn_v on Q5_K)
+    else if (dta == NTK_DT_Q5_K && dtb == NTK_DT_IQ4_XS) fn = rp_fn<NTK_DT_Q5_K, NTK_DT_IQ4_XS>(nm);
+    else if (dta == NTK_DT_IQ4_XS && dtb == NTK_DT_Q4_K) fn = rp_fn<NTK_DT_IQ4_XS, NTK_DT_Q4_K>(nm);
+    else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_IQ4_XS) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_IQ4_XS>(nm);
     else return NTK_E_DTYPE;
     if (!fn) return NTK_E_LAUNCH;
 #ifdef NTK_TUNE

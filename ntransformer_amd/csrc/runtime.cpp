@@ -94,6 +94,8 @@ size_t ntk_row_bytes(int dtype, int64_t n) {
         case NTK_DT_Q5_K: return n % 256 ? 0 : (size_t)(n / 256) * 176;
         case NTK_DT_Q6_K: return n % 256 ? 0 : (size_t)(n / 256) * 210;
         case NTK_DT_Q3_K: return n % 256 ? 0 : (size_t)(n / 256) * 110;
+        case NTK_DT_IQ4_NL: return n % 32 ? 0 : (size_t)(n / 32) * 18;
+        case NTK_DT_IQ4_XS: return n % 256 ? 0 : (size_t)(n / 256) * 136;
         case NTK_DT_Q2_K: return n % 256 ? 0 : (size_t)(n / 256) * 84;
         default: return 0;
     }

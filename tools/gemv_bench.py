@@ -23,9 +23,10 @@ SHAPES = {  # name: (kind, rows..., in)
     "70b.qkv_fused": ("qkv", (8192, 1024, 1024), 8192), "70b.o+res": ("resid", 8192, 8192),
     "70b.gate|up+silu": ("silu", 28672, 8192), "70b.down+res": ("resid", 8192, 28672),
 }
-GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K, "Q3_K": G.GGML_Q3_K, "F16": G.GGML_F16, "BF16": G.GGML_BF16}
+GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K, "Q3_K": G.GGML_Q3_K,
+      "IQ4_XS": G.GGML_IQ4_XS, "IQ4_NL": G.GGML_IQ4_NL, "F16": G.GGML_F16, "BF16": G.GGML_BF16}
 DENSE16 = (G.GGML_F16, G.GGML_BF16)
-RP = (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K, G.GGML_Q3_K)   # formats with a decode repack
+RP = (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K, G.GGML_Q3_K, G.GGML_IQ4_XS)   # formats with a decode repack
 
 
 def main():
