@@ -312,7 +312,7 @@ int ntk_gemm_quant(float* Y, const void* W, const float* X, int n_tokens, int ou
  * subnormals as they are, tools/micro/mfma_f16_subnormal.hip); the FP16 x FP16 products are exact in the F32 accumulator, block scales / K-quant
  * minima are applied to the F32 block sums and 1 / s to the finished sum (exact).  Against ntk_gemv the summation order differs and the
  * activations carry that one-ulp rounding.
- * Limits: Q8_0, Q4_0, Q4_K, Q5_K, Q6_K and Q3_K (NTK_E_DTYPE otherwise -- IQ4_NL and IQ4_XS among them: use ntk_gemm_quant), one format per call; in_features a multiple of 128 (Q8_0) /
+ * Limits: Q8_0, Q4_0, Q4_K, Q5_K, Q6_K, Q3_K, IQ4_NL and IQ4_XS (NTK_E_DTYPE otherwise: use ntk_gemm_quant), one format per call; in_features a multiple of 128 (Q8_0) /
  * 256 (the others), rows % 16 == 0 and rows * row_bytes < 4 GiB (NTK_E_SHAPE); W, X, Y, resid 16-byte aligned (NTK_E_ALIGN).
  * (Row pitches that are not a multiple of 4 bytes -- Q8_0 with in_features % 64 != 0, Q6_K / Q3_K with in_features % 512 != 0 -- run the
  * same kernel with 2-byte aligned LDS reads, several times slower; no projection of the target models has one.)
@@ -337,7 +337,7 @@ int ntk_gemm_quant(float* Y, const void* W, const float* X, int n_tokens, int ou
  *                   ntk_reduce_silu_mul_rowmax: output[t] = silu(gate[t]) * up[t] of a deferred two-matrix gate | up launch, row_max as ntk_silu_mul_rowmax.
  *                 Identical bits to the separate launches (same sums in the same order).
  *   weights_repacked  != 0: segs[i].W point at the engine's DECODE REPACK of the matrices (ntk_rp_pack: tiles of 16 rows x 256-column super-blocks) instead
- *                 of raw GGUF blocks -- Q4_K / Q5_K / Q6_K / Q3_K (NTK_E_DTYPE otherwise).  Round 6: with one resident copy of a K-quant matrix the prompt pass
+ *                 of raw GGUF blocks -- Q4_K / Q5_K / Q6_K / Q3_K / IQ4_XS (NTK_E_DTYPE otherwise: IQ4_NL has no repack).  Round 6: with one resident copy of a K-quant matrix the prompt pass
  *                 needs no unpack any more.  The same integers and scale products in the same order: IDENTICAL bits to the raw form.
  *   full_form     != 0: the launch takes the form, K split and chunk pairing of a FULL pass (1024 tokens) whatever n_tokens is, never the short-prompt
  *                 forms: a token's outputs are then the same bits however the caller cuts its tokens into calls (Model::score: the LM head over
@@ -360,7 +360,7 @@ typedef struct ntk_gemm_desc {
     int                 reuse_x;
     const float*        row_max;
     ntk_gemm_partials*  partials;
-    int                 weights_repacked;   /* != 0: segs[i].W are tensors of the decode repack (ntk_rp_pack; Q4_K / Q5_K / Q6_K / Q3_K), read as they lie */
+    int                 weights_repacked;   /* != 0: segs[i].W are tensors of the decode repack (ntk_rp_pack; Q4_K / Q5_K / Q6_K / Q3_K / IQ4_XS), read as they lie */
     int                 full_form;          /* != 0: the form of a full 1024-token pass whatever n_tokens is (chunking-independent bits) */
 } ntk_gemm_desc;
 size_t ntk_gemm_quant_workspace_bytes(int in_features, int out_features);

@@ -92,9 +92,12 @@ struct OperandPlanes {
 };
 
 // the formats ntk_gemm_quant_f16 has a decoder for, and the shapes it takes
-static bool f16_fmt(int dt) { return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K; }
+static bool f16_fmt(int dt) {
+    return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K || dt == NTK_DT_IQ4_NL || dt == NTK_DT_IQ4_XS;
+}
 static bool f16_ok(const DevTensor& w) {
-    const bool kq = w.dtype == NTK_DT_Q4_0 || w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K || w.dtype == NTK_DT_Q3_K;
+    const bool kq = w.dtype == NTK_DT_Q4_0 || w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K || w.dtype == NTK_DT_Q3_K || w.dtype == NTK_DT_IQ4_NL ||
+                    w.dtype == NTK_DT_IQ4_XS;
     return (w.dtype == NTK_DT_Q8_0 || kq) && w.in_f % (kq ? 256 : 128) == 0 && w.out_f % 16 == 0 && (w.ptr || w.rp);
 }
 // a K-quant matrix whose GGUF bytes were freed after the load-time repack (one resident copy): the FP16 GEMM reads it FROM THE REPACK
@@ -102,7 +105,7 @@ static bool f16_ok(const DevTensor& w) {
 // the 16-bit matrices and shapes ntk_gemm_dense16 takes
 static bool dense16_ok(const DevTensor& w) { return is_dense16(w.dtype) && w.in_f % 32 == 0 && w.out_f % 16 == 0 && w.ptr; }
 static bool rp_only(const DevTensor& w) {
-    return !w.ptr && w.rp && (w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K || w.dtype == NTK_DT_Q3_K) && w.out_f % 16 == 0;
+    return !w.ptr && w.rp && (w.dtype == NTK_DT_Q4_K || w.dtype == NTK_DT_Q5_K || w.dtype == NTK_DT_Q6_K || w.dtype == NTK_DT_Q3_K || w.dtype == NTK_DT_IQ4_XS) && w.out_f % 16 == 0;
 }
 
 // layers [first, last) of the 1:1 path on hidden_[T][H] at positions start_pos.. (positions_ already on the device)

@@ -5,7 +5,7 @@
 // form (16 tokens per pass, 29-65 TFLOP/s of the 157 TFLOP/s F32 matrix rate) for the formats of the target models.
 //
 // Arithmetic -- exact products, F32 accumulation, activations within one F32 ulp of the reference's:
-//   * a GGUF weight is (integer) x (scale): the INTEGER part (Q8_0: -128..127, Q4_K: 0..15, Q6_K: -32..31, Q3_K: -4..3) is exact in FP16;
+//   * a GGUF weight is (integer) x (scale): the INTEGER part (Q8_0: -128..127, Q4_K: 0..15, Q6_K: -32..31, Q3_K: -4..3, the IQ4 table: -127..113) is exact in FP16;
 //   * an F32 activation x is scaled by a power of two s -- one per token, chosen so that the token's largest |x| s lies in
 //     [2^14, 2^15) -- and split into TWO FP16 pieces: h1 = rn16(x s), h2 = rn16(x s - h1).  The difference is exact in F32 (13
 //     significant bits), so |x s - h1 - h2| <= 2^-23 |x s| -- one F32 ulp of the activation -- for every x within 2^-16 of the
@@ -420,6 +420,45 @@ template <> struct DeqI<NTK_DT_Q4_0> : GemmFmt<NTK_DT_Q4_0> {   // types.h:97-10
     }
 };
 
+// ggml block_iq4_nl (not in the reference): Q4_0's block -- half d, 16 bytes whose low / high nibbles belong to columns j / j + 16 -- with w = d table[nibble],
+// the nibble an index into sixteen int8 values (-127 .. 113: exact in FP16).  Q4_0's unit, window, load() and alignment rule; only the way from the nibbles
+// to the FP16 integers differs: four at a time through the register table (iq4_lookup4, common.hip.h: 6 - 7 instructions per dword where Q4_0 masks once
+// and adds -8), then the signed conversion.
+template <> struct DeqI<NTK_DT_IQ4_NL> : DeqI<NTK_DT_Q4_0> {
+    static_assert(GemmFmt<NTK_DT_IQ4_NL>::BB == BB && GemmFmt<NTK_DT_IQ4_NL>::SPU == SPU && GemmFmt<NTK_DT_IQ4_NL>::STRIDE == STRIDE &&
+                  GemmFmt<NTK_DT_IQ4_NL>::ROW_ALIGN == ROW_ALIGN && GemmFmt<NTK_DT_IQ4_NL>::PF == PF, "the plan's numbers for IQ4_NL are Q4_0's");
+    template <bool AL> __device__ static AOp convert(const Raw& r, int j, int) {
+        const uint32_t q = (!AL || (j & 1)) ? r.w0 : mid32(r.w0, r.w1);
+        AOp o;
+        o.a = cvt8_s8_f16(iq4_lookup4<0>(q), iq4_lookup4<4>(q));   // the same four bytes: columns 4 g .. + 3 (low nibbles) and 16 + 4 g .. + 3 (high)
+        o.s0 = o.s1 = h2f((uint16_t)r.d);
+        return o;
+    }
+};
+
+// ggml block_iq4_xs (not in the reference): half d, uint16 scales_h, scales_l[4], qs[128] -- 136 bytes, so a unit starts on an 8-byte boundary whatever the row
+// pitch: shift 0 or 8 inside its 16-byte window and EVERY dword read below is aligned (no AL = false form exists for this format).  Sub-block j = 16 index
+// bytes at 8 + 16 j in Q4_0's nibble order; w = (d (ls_j - 32)) table[idx], ls_j = nibble j of scales_l with bits 2 j, 2 j + 1 of scales_h on top.
+template <> struct DeqI<NTK_DT_IQ4_XS> : GemmFmt<NTK_DT_IQ4_XS> {
+    static constexpr int UB = 136, NCH = 9;                            // window: shift (0 or 8) + 136 <= 144 (= STRIDE)
+    static constexpr int NRING = 1, PPI = 0;
+    struct Hdr { uint32_t dh, sl; };   // d | scales_h << 16, scales_l
+    struct MinOp {};
+    __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
+    struct Raw { uint32_t q; float s; };
+    __device__ static Hdr header(const uint8_t* row, const uint8_t*) { return Hdr{lds32<true>(row), lds32<true>(row + 4)}; }
+    template <bool AL> __device__ static Raw load(const uint8_t*, const uint8_t* rowg, const Hdr& hd, int j, int) {
+        const int ls = (int)(((hd.sl >> (4 * j)) & 15u) | (((hd.dh >> (16 + 2 * j)) & 3u) << 4)) - 32;
+        return Raw{lds32<true>(rowg + 8 + 16 * j), h2f((uint16_t)(hd.dh & 0xFFFFu)) * (float)ls};   // (gguf.dequantize's first product; the table value is the MFMA's)
+    }
+    template <bool AL> __device__ static AOp convert(const Raw& r, int, int) {
+        AOp o;
+        o.a = cvt8_s8_f16(iq4_lookup4<0>(r.q), iq4_lookup4<4>(r.q));
+        o.s0 = o.s1 = r.s;
+        return o;
+    }
+};
+
 template <> struct DeqI<NTK_DT_Q4_K> : GemmFmt<NTK_DT_Q4_K> {   // types.h:112-117: half d, dmin; 12 packed 6-bit (scale, min); 128 bytes of nibbles
     static constexpr int UB = 144, NCH = 9;                            // rows are 16-byte aligned: no shift (STRIDE = UB)
     static constexpr int NRING = 1, PPI = 0;
@@ -732,6 +771,33 @@ template <> struct DeqI<NTK_DT_Q3_K + GB_RP> : GemmFmt<NTK_DT_Q3_K + GB_RP> {
         o.a = u32x4{sub4(qa.x), sub4(qa.y), sub4(qa.z), sub4(qa.w)};
         o.s0 = r.d * (float)(int)(int8_t)(r.sc & 0xFF);
         o.s1 = r.d * (float)(int)(int8_t)(r.sc >> 8);
+        return o;
+    }
+};
+
+// IQ4_XS's repack IS Q4_K's nibble chunk with the table indices in it: load() and the nibble selection are DeqI<Q4_K + GB_RP>'s, the lookup stands where the
+// mask stood.  The records are this format's own (gemv_rp.hip): 16 rows x 8 int8 scales already reduced by 32, then 16 x d -- row i's record 8 i and its d
+// 128 + 2 i bytes behind the two steps.  d (float)sc is the raw decoder's product (its ls - 32 is this int8): identical bits.
+template <> struct DeqI<NTK_DT_IQ4_XS + GB_RP> : GemmFmt<NTK_DT_IQ4_XS + GB_RP> {
+    static constexpr int PPI = ITEM / 16, UB = 0, NCH = 0, NRING = 1;
+    struct Hdr { uint32_t sc0, sc1; float d; };   // sc[8] - 32 (int8), d
+    struct MinOp {};
+    __device__ static MinOp min_operand(const Hdr&, int) { return MinOp{}; }
+    struct Raw { uint32_t lo, hi; float s; };
+    __device__ static Hdr header(const uint8_t* row, const uint8_t*) {
+        const int i = threadIdx.x & 15;
+        const uint8_t* rec = row + 2 * S1 - 8 * i;   // row = the item + 16 i
+        return Hdr{lds32<true>(rec), lds32<true>(rec + 4), h2f(*reinterpret_cast<const uint16_t*>(row + 2 * S1 + 128 - 14 * i))};
+    }
+    template <bool AL> __device__ static Raw load(const uint8_t*, const uint8_t* rowg, const Hdr& hd, int j, int) {
+        const uint8_t* p = rowg + (j >> 2) * S1 + 512 * (j & 1);
+        const uint32_t scw = j < 4 ? hd.sc0 : hd.sc1;
+        return Raw{lds32<true>(p), lds32<true>(p + 256), hd.d * (float)(int)(int8_t)(scw >> (8 * (j & 3)))};
+    }
+    template <bool AL> __device__ static AOp convert(const Raw& r, int j, int) {
+        AOp o;   // sub-blocks 2, 3 (mod 4) sit in the high nibbles
+        o.a = ((j >> 1) & 1) ? cvt8_s8_f16(iq4_lookup4<4>(r.lo), iq4_lookup4<4>(r.hi)) : cvt8_s8_f16(iq4_lookup4<0>(r.lo), iq4_lookup4<0>(r.hi));
+        o.s0 = o.s1 = r.s;
         return o;
     }
 };
@@ -2109,10 +2175,13 @@ template <class F> static int with_gemm_format(int weight_dtype, F f) {
         case NTK_DT_Q4_K: return f(std::integral_constant<int, NTK_DT_Q4_K>{});
         case NTK_DT_Q5_K: return f(std::integral_constant<int, NTK_DT_Q5_K>{});
         case NTK_DT_Q3_K: return f(std::integral_constant<int, NTK_DT_Q3_K>{});
+        case NTK_DT_IQ4_NL: return f(std::integral_constant<int, NTK_DT_IQ4_NL>{});
+        case NTK_DT_IQ4_XS: return f(std::integral_constant<int, NTK_DT_IQ4_XS>{});
         case NTK_DT_Q4_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q4_K + GB_RP>{});
         case NTK_DT_Q5_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q5_K + GB_RP>{});
         case NTK_DT_Q6_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q6_K + GB_RP>{});
         case NTK_DT_Q3_K + GB_RP: return f(std::integral_constant<int, NTK_DT_Q3_K + GB_RP>{});
+        case NTK_DT_IQ4_XS + GB_RP: return f(std::integral_constant<int, NTK_DT_IQ4_XS + GB_RP>{});
         default: return f(std::integral_constant<int, NTK_DT_Q6_K>{});
     }
 }
@@ -2172,9 +2241,11 @@ static int gemm_desc_format(const ntk_gemm_desc* d, ntk::HostSeg* sg, long* tota
         total += d->segs[i].rows;
     }
     int dt = d->segs[0].dtype;
-    if (dt != NTK_DT_Q8_0 && dt != NTK_DT_Q4_0 && dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K && dt != NTK_DT_Q3_K) return NTK_E_DTYPE;
-    if (d->weights_repacked) {   // segs[i].W = tensors of the decode repack (ntk_rp_pack): the K-quant formats, rows in whole tiles of 16 (as everything here)
-        if (dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K && dt != NTK_DT_Q3_K) return NTK_E_DTYPE;
+    if (dt != NTK_DT_Q8_0 && dt != NTK_DT_Q4_0 && dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K && dt != NTK_DT_Q3_K && dt != NTK_DT_IQ4_NL &&
+        dt != NTK_DT_IQ4_XS)
+        return NTK_E_DTYPE;
+    if (d->weights_repacked) {   // segs[i].W = tensors of the decode repack (ntk_rp_pack): the formats that have one (IQ4_NL has none), rows in whole tiles of 16 (as everything here)
+        if (dt != NTK_DT_Q4_K && dt != NTK_DT_Q5_K && dt != NTK_DT_Q6_K && dt != NTK_DT_Q3_K && dt != NTK_DT_IQ4_XS) return NTK_E_DTYPE;
         dt += ntk::GB_RP;
     }
     *total_rows = total; *format = dt;

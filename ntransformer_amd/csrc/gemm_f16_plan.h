@@ -84,6 +84,18 @@ template <> struct GemmFmt<NTK_DT_Q3_K> {
     static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
     static constexpr bool RP = false; static constexpr int ITEM = 0, S1 = 0, S2 = 0;
 };
+template <> struct GemmFmt<NTK_DT_IQ4_NL> {   // Q4_0's block with a table index in every nibble: Q4_0's numbers (in_features % 256 == 0 puts every row on 16 bytes)
+    static constexpr int BW = 32, BB = 18, SPU = 8, STRIDE = 176, ROW_ALIGN = 4;
+    static constexpr bool SPLIT16 = false, HAS_MIN = false, PF = true;
+    static constexpr bool RP = false; static constexpr int ITEM = 0, S1 = 0, S2 = 0;
+};
+template <> struct GemmFmt<NTK_DT_IQ4_XS> {
+    // super-blocks of 136 bytes: every row pitch is a multiple of 8, a unit starts 0 or 8 bytes into its 16-byte window and the window is 9 pieces = 36 dwords
+    // = 4 x 9: already a row pitch of 4 x an odd number of dwords (16 rows x 4 column groups of one read hit 64 different banks: 36 i + g)
+    static constexpr int BW = 256, BB = 136, SPU = 8, STRIDE = 144, ROW_ALIGN = 8;   // every row pitch
+    static constexpr bool SPLIT16 = false, HAS_MIN = false, PF = true;
+    static constexpr bool RP = false; static constexpr int ITEM = 0, S1 = 0, S2 = 0;
+};
 template <> struct GemmFmt<NTK_DT_Q4_K + GB_RP> {
     static constexpr bool RP = true;
     static constexpr int S1 = 1024, S2 = 320, ITEM = 2 * S1 + S2;
@@ -108,6 +120,12 @@ template <> struct GemmFmt<NTK_DT_Q3_K + GB_RP> {   // no nibble chunk: S1 = a s
     static constexpr int S1 = 768, S2 = 288, ITEM = 2 * S1 + S2;
     static constexpr int BW = 256, BB = 110, SPU = 8, STRIDE = ITEM / 16, ROW_ALIGN = 16;
     static constexpr bool SPLIT16 = true, HAS_MIN = false, PF = false;
+};
+template <> struct GemmFmt<NTK_DT_IQ4_XS + GB_RP> {   // Q4_K's nibble chunk (the table indices); records of 8 int8 scales, then 16 x d
+    static constexpr bool RP = true;
+    static constexpr int S1 = 1024, S2 = 160, ITEM = 2 * S1 + S2;
+    static constexpr int BW = 256, BB = 136, SPU = 8, STRIDE = ITEM / 16, ROW_ALIGN = 16;
+    static constexpr bool SPLIT16 = false, HAS_MIN = false, PF = true;
 };
 
 // ---- LDS of the three kernel forms ----------------------------------------------------------------------------------------------------
