@@ -550,6 +550,21 @@ int ntk_moe_gemm_gate_up(float* act, const float* xn, const void* w_gate, int dt
                          void* scratch, size_t scratch_bytes, int T, int hidden, int inter, int E, int K, void* stream);
 int ntk_moe_gemm_down(float* y, const float* resid, const float* act, const void* w_down, int dt_down, const int* ids, const float* w, const int* offsets,
                       const int* pairs, float* part, int T, int hidden, int inter, int E, int K, void* stream);
+/* The ROW form (csrc/moe_row.hip): the whole routed FFN of ONE row, y[0 .. hidden) = resid + sum_k w[k] x (Wd[e_k] . act[k]), in three launches built for
+ * T = 1 -- the router's logits with one wave per expert; gate | up with the selection redone at the head of every workgroup, xn staged once per workgroup
+ * in LDS and the next rows fetched while a row's chains run; down with the K act rows in LDS, the products in LDS and the combine in the same launch.  The
+ * bits of y are those of ntk_moe_route -> ntk_moe_gate_up -> ntk_moe_down at T = 1 on the same inputs (one wave per weight row and the same chains:
+ * csrc/moe_core.hip.h); y may be resid.  ws / ws_bytes: a workspace laid out by ntk_moe_workspace_layout(1, E, K, inter, hidden, ..); afterwards its IDS, W
+ * and ACT sections hold what ntk_moe_route and ntk_moe_gate_up would have left at T = 1; OFFSETS, PAIRS and XN are not written (xn may be the XN section),
+ * and PART holds the E logits (it must hold them: K hidden >= E).  Nothing depends on the routing but device memory: the launches can be captured.
+ * Refusals as above, outputs untouched: NTK_E_NULL, NTK_E_DTYPE, NTK_E_SHAPE (counts, sizes, columns that are not whole blocks, a workspace that is too
+ * small, ntk_moe_row_lds_bytes beyond NTK_MOE_ROW_LDS_MAX), NTK_E_ALIGN (y, resid, xn or ws not 16-byte aligned, weights at an odd address).
+ * ntk_moe_row_lds_bytes: the dynamic LDS the larger of the two launches asks for (gate | up: xn and two row images per wave; down: K act rows and one row
+ * image per wave); 0: a type that is not taken, columns that are not whole blocks, K outside 1 .. 16.  A layer beyond NTK_MOE_ROW_LDS_MAX is not eligible. */
+#define NTK_MOE_ROW_LDS_MAX (160 * 1024 - 1536)
+size_t ntk_moe_row_lds_bytes(int dt_gate, int dt_up, int dt_down, int hidden, int inter, int K);
+int ntk_moe_ffn_row(float* y, const float* resid, const float* xn, const float* router, const void* w_gate, int dt_gate, const void* w_up, int dt_up,
+                    const void* w_down, int dt_down, int hidden, int inter, int E, int K, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -316,6 +316,10 @@ int   nt_engine_qk_norm(nt_engine_t e);
  * expert count E and the experts per token K, 0 for a model without such a layer, whose launches are unchanged; -1 without a loaded engine.
  * nt_gguf_describe reports "expert_count", "expert_used_count", "expert_feed_forward_length" (0 where the file names none) and "moe_layers". */
 int   nt_engine_moe(nt_engine_t e, int* experts, int* used);
+/* How many layers' ONE-row passes (the decode token, a 1-token prompt, a one-row batched step) take the row form of the routed FFN (ntk_moe_ffn_row,
+ * csrc/moe_row.hip: the same bits as the three launches) under the current option "moe_row" ("1", the default | "0"; any time): the eligible
+ * mixture-of-experts layers, 0 with the option off or for a model without such a layer; -1 without a loaded engine. */
+int   nt_engine_moe_row(nt_engine_t e);
 /* The rotation a LOADED engine runs with, as JSON: "rope_theta", "rope_scaling_type" ("none" | "linear" | "llama3"; a file's "yarn" / unknown type is
  * reported as it is named, and is not applied), "rope_freq_scale", "rope_factors" (per-pair divisors folded into the frequency table: 0 or head_dim / 2),
  * "rope_orig_ctx".  Returns bytes needed (excl. NUL) or negative. */

@@ -167,6 +167,8 @@ def lib() -> C.CDLL:
         "ntk_moe_gemm_scratch_bytes": (sz, [i, i, i, i, i]),
         "ntk_moe_gemm_gate_up": (i, [vp, vp, vp, i, vp, i, vp, vp, vp, sz, i, i, i, i, i, vp]),
         "ntk_moe_gemm_down": (i, [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "ntk_moe_row_lds_bytes": (sz, [i, i, i, i, i, i]),
+        "ntk_moe_ffn_row": (i, [vp, vp, vp, vp, vp, i, vp, i, vp, i, i, i, i, i, vp, sz, vp]),
         "ntk_debug_sclk": (i, [vp, vp]),
         "ntk_debug_sclk_begin": (i, [vp, vp, vp]),
         "ntk_debug_sclk_end": (i, [vp, vp]),

@@ -81,6 +81,11 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (v != "0" && v != "1") { E(e)->set_error("moe_gemm must be 0 or 1"); return NTK_E_SHAPE; }
         E(e)->model().set_moe_gemm(on);
     }
+    else if (k == "moe_row") {   // "1" (default) | "0": one-row passes over mixture-of-experts layers on the row form (csrc/moe_row.hip), or the three T-row launches; the same bits; any time (the A/B switch)
+        const std::string v = value;
+        if (v != "0" && v != "1") { E(e)->set_error("moe_row must be 0 or 1"); return NTK_E_SHAPE; }
+        return E(e)->model().set_moe_row(on);
+    }
     else if (k == "moe_gemm_min_rows") {   // 1 .. 1024: the rows of a pass from which the grouped GEMM is taken (default: the measured threshold, Model::kMoeGemmMinRows); any time
         char* end = nullptr;
         const long n = strtol(value, &end, 10);
@@ -519,6 +524,8 @@ int nt_engine_moe(nt_engine_t e, int* experts, int* used) {
     if (used) *used = n ? m.config().expert_used_count : 0;
     return n;
 }
+
+int nt_engine_moe_row(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().moe_row_layers() : -1; }
 
 int nt_rope_llama3_factors(int head_dim, float theta, float factor, float low_freq_factor, float high_freq_factor, int orig_ctx, float* out) {
     return nt::rope_llama3_factors(head_dim, theta, factor, low_freq_factor, high_freq_factor, orig_ctx, out);   // host only

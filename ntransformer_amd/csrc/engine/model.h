@@ -43,6 +43,7 @@ struct LayerWeights {
     // 3-D expert tensors as raw GGUF bytes (expert e: the block of out_f rows at e x out_f x row bytes; in_f / out_f are ONE expert's extents).  All four or none.
     DevTensor router, gate_exps, up_exps, down_exps;
     bool is_moe() const { return router.ptr != nullptr; }
+    bool moe_row_ok = false;    // decided at load: the one-row form (csrc/moe_row.hip) takes the layer -- expert types, its LDS need, the addresses
     bool moe_gemm_ok = false;   // decided at load: the three expert tensors are types, shapes and addresses the grouped prompt GEMM (csrc/moe_gemm.hip) takes
 };
 // the seven projection matrices of a layer, for whoever visits them all: for (auto m : kLayerMatrices) use(L.*m);
@@ -259,6 +260,11 @@ public:
         moe_gemm_min_rows_ = n;
         return NTK_OK;
     }
+    // A ONE-row pass over such a layer -- the captured decode token, an eager step, a 1-token forward, a one-row batched step -- takes ntk_moe_ffn_row
+    // (csrc/moe_row.hip: the row form, the same bits) behind the same ntk_rmsnorm where option moe_row is on and the layer is eligible
+    // (LayerWeights::moe_row_ok; another layer keeps the three launches without a word).  Any time (the A/B switch): a change drops the captured tokens.
+    int set_moe_row(bool on);
+    int moe_row_layers() const { int n = 0; if (moe_row_) for (const auto& L : layers_) n += L.is_moe() && L.moe_row_ok ? 1 : 0; return n; }
     bool kv_q8() const { return kv_q8_; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
     uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included
@@ -474,6 +480,9 @@ private:
     int moe_rows_ = 0;               // ... the rows it was sized for
     void* moe_gemm_scratch_ = nullptr;   // ntk_moe_gemm_scratch_bytes for moe_rows_ rows (null where that is 0)
     size_t moe_gemm_scratch_bytes_ = 0;
+    uint8_t* moe_row_ws_ = nullptr;  // the row form's workspace (ntk_moe_workspace_layout for ONE row: its sections lie elsewhere than moe_ws_'s)
+    size_t moe_row_ws_bytes_ = 0;
+    bool moe_row_ = true;            // option moe_row
     bool moe_gemm_ = true;           // option moe_gemm
     int moe_gemm_min_rows_ = kMoeGemmMinRows;   // option moe_gemm_min_rows (1 is accepted and means 2: a one-row pass never takes the GEMM)
     void* stream_ = nullptr;

@@ -201,6 +201,17 @@ int Model::moe_ffn(const LayerWeights& L, float* io, int T, bool marks) {
     for (int t0 = 0; t0 < T; t0 += moe_rows_) {
         const int n = std::min(moe_rows_, T - t0);
         float* const x = io + (size_t)t0 * H;
+        if (n == 1 && moe_row_ && L.moe_row_ok) {   // one row: the row form, on its own one-row workspace (the same bits)
+            float* const xn1 = reinterpret_cast<float*>(moe_row_ws_);   // (section XN lies at offset 0)
+            mark(2, true);
+            NT_TRY(ntk_rmsnorm(xn1, x, (const float*)L.ffn_norm.ptr, 1, H, cfg_.norm_eps, s));
+            mark(2, false);
+            mark(0, true);
+            NT_TRY(ntk_moe_ffn_row(x, x, xn1, (const float*)L.router.ptr, L.gate_exps.ptr, L.gate_exps.dtype, L.up_exps.ptr, L.up_exps.dtype, L.down_exps.ptr,
+                                   L.down_exps.dtype, H, Ie, E, K, moe_row_ws_, moe_row_ws_bytes_, s));
+            mark(0, false);
+            continue;
+        }
         mark(2, true);
         NT_TRY(ntk_rmsnorm(xn, x, (const float*)L.ffn_norm.ptr, n, H, cfg_.norm_eps, s));
         mark(2, false);

@@ -562,6 +562,17 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
             };
             L.moe_gemm_ok = L.is_moe() && takes(L.gate_exps) && takes(L.up_exps) && takes(L.down_exps);
         }
+        // the one-row form: a workspace of its own (one row's layout), and the layers it takes -- the same types and addresses, its LDS need within the CU's,
+        // the logits fitting the products' section
+        size_t row_off[NTK_MOE_WS_SECTIONS];
+        moe_row_ws_bytes_ = ntk_moe_workspace_layout(1, cfg_.expert_count, cfg_.expert_used_count, cfg_.expert_ff_length, cfg_.hidden_size, row_off);
+        moe_row_ws_ = (uint8_t*)dev_alloc(moe_row_ws_bytes_, true);
+        if (!moe_row_ws_) { err_ = "buffer allocation failed (mixture-of-experts row workspace)"; return NTK_E_NOMEM; }
+        for (auto& L : layers_) {
+            if (!L.moe_gemm_ok) continue;   // (moe_gemm_ok: types, whole blocks, even addresses)
+            const size_t lds = ntk_moe_row_lds_bytes(L.gate_exps.dtype, L.up_exps.dtype, L.down_exps.dtype, cfg_.hidden_size, cfg_.expert_ff_length, cfg_.expert_used_count);
+            L.moe_row_ok = lds != 0 && lds <= NTK_MOE_ROW_LDS_MAX && (size_t)cfg_.expert_used_count * cfg_.hidden_size >= (size_t)cfg_.expert_count;
+        }
     }
     if (tp_world_ > 1) {   // communication buffer: flags + two slots of one prompt's worth of hidden vectors
         tp_max_floats_ = S * H;

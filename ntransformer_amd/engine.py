@@ -147,6 +147,7 @@ def _bind():
     L.nt_engine_qkv_bias.argtypes = [vp]
     L.nt_engine_qk_norm.argtypes = [vp]
     L.nt_engine_moe.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.nt_engine_moe_row.argtypes = [vp]
     L._engine_bound = True
     return L
 
@@ -256,6 +257,11 @@ class Engine:
     def moe(self) -> int:
         """how many layers of the loaded model are mixture-of-experts layers (nt_engine_moe): 0 for a dense model; moe_experts() gives (E, K)"""
         return int(self.L.nt_engine_moe(self.h, None, None))
+
+    def moe_row(self) -> int:
+        """how many layers' one-row passes take the row form of the routed FFN under the current option moe_row (nt_engine_moe_row): 0 with the option off
+        or for a dense model"""
+        return int(self.L.nt_engine_moe_row(self.h))
 
     def moe_experts(self):
         """(expert count E, experts per token K) of the loaded model; (0, 0) for a dense model"""

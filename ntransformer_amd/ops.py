@@ -237,6 +237,18 @@ def moe_gemm_down(y, resid, act, w_down, dt_down, ids, w, offsets, pairs, part, 
                                        inter, E, K, stream), "moe_gemm_down")
 
 
+def moe_row_lds_bytes(dt_gate, dt_up, dt_down, hidden, inter, K) -> int:
+    """ntk_moe_row_lds_bytes: the dynamic LDS the row form's larger launch asks for (0: a type or shape it does not take)"""
+    return int(_lib.lib().ntk_moe_row_lds_bytes(int(dt_gate), int(dt_up), int(dt_down), hidden, inter, K))
+
+
+def moe_ffn_row(y, resid, xn, router, w_gate, dt_gate, w_up, dt_up, w_down, dt_down, hidden, inter, E, K, ws, ws_bytes, stream=None):
+    """ntk_moe_ffn_row: the routed FFN of ONE row, y [hidden] = resid + sum_k w[k] x (Wd[e_k] . act[k]), the bits of moe_route -> moe_gate_up -> moe_down at
+    T = 1; ws: a workspace laid out by ntk_moe_workspace_layout(1, ..), whose IDS, W and ACT sections hold the routing and the act rows afterwards; y may be resid"""
+    check(_lib.lib().ntk_moe_ffn_row(_p(y), _p(resid), _p(xn), _p(router), _p(w_gate), int(dt_gate), _p(w_up), int(dt_up), _p(w_down), int(dt_down), hidden,
+                                     inter, E, K, _p(ws), int(ws_bytes), stream), "moe_ffn_row")
+
+
 def q8l_bytes(rows, in_features) -> int:
     return int(_lib.lib().ntk_q8l_bytes(rows, in_features))
 

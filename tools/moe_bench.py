@@ -13,8 +13,12 @@
              one process, median of 3, at 2 / 4 / 8 / 16 / 32 / 64 / 256 / 1024 tokens on `--models`; and the threshold the table yields: the smallest
              measured row count from which the GEMM form is faster at that and every larger measured count, per model and on all of them
              (Model::kMoeGemmMinRows is set from it).
+  --ab-moe-row   the one-row form (csrc/moe_row.hip).  Per layer at T = 1: ntk_moe_route + ntk_moe_gate_up + ntk_moe_down against ntk_moe_ffn_row on the
+             Qwen3-30B-A3B layer shape (Q8_0) and the Mixtral 8x7B layer shape (Q4_K gate | up, Q6_K down), one process, the two alternated, median of 5,
+             the launch model's figure beside each for orientation.  Then decode tokens/s of `--models` with option moe_row = 0 and 1, alternated three
+             times in one session.
 The shader clock is read through ntk_debug_sclk where the build has it.
-usage: python tools/moe_bench.py [--engine] [--kernels] [--ab-moe-gemm] [--models qwen3-30b-a3b:Q8_0,mixtral-8x7b:Q4_K_M] [--layers N] [--out profiles/moe.txt]"""
+usage: python tools/moe_bench.py [--engine] [--kernels] [--ab-moe-gemm] [--ab-moe-row] [--models qwen3-30b-a3b:Q8_0,mixtral-8x7b:Q4_K_M] [--layers N] [--out profiles/moe.txt]"""
 import argparse
 import ctypes as C
 import os
@@ -190,23 +194,91 @@ def bench_kernels():
         ws.free(); hid.free()
 
 
+ROW_SHAPES = (("qwen3-30b-a3b", 2048, 768, 128, 8, G.GGML_Q8_0, G.GGML_Q8_0), ("mixtral-8x7b", 4096, 14336, 8, 2, G.GGML_Q4_K, G.GGML_Q6_K))
+
+
+def bench_ab_row_layer():
+    say("one layer at T = 1: route + gate|up + down against ntk_moe_ffn_row, event-timed, the two alternated, median of 5; model: 3.8 us + MB / 6.9 TB/s per launch")
+    for name, H, ie, n_exp, K, t_gu, t_d in ROW_SHAPES:
+        r = np.random.Generator(np.random.Philox(key=[20261126, H]))
+        one = lambda t, rows, cols: np.frombuffer(G.synth_tensor(r, t, rows, cols), np.uint8)
+        # (every expert the bytes of one drawn expert: the time does not depend on the values)
+        wg, wu = (DB.from_numpy(np.tile(one(t_gu, ie, H), n_exp)) for _ in range(2))
+        wd = DB.from_numpy(np.tile(one(t_d, H, ie), n_exp))
+        router = DB.from_numpy((2.0 / np.sqrt(H) * r.standard_normal((n_exp, H))).astype(np.float32))
+        off, total = ops.moe_workspace_layout(1, n_exp, K, ie, H)
+        ws = DB.zeros(total)
+        p = {k: ws.at(v) for k, v in off.items()}
+        ws.upload(r.standard_normal(H).astype(np.float32), off["xn"])
+        hid = DB.from_numpy(r.standard_normal(H).astype(np.float32))
+        dg, dd = G.GGML_TO_DT[t_gu], G.GGML_TO_DT[t_d]
+
+        def three():
+            ops.moe_route(p["xn"], router, 1, H, n_exp, K, p["ids"], p["w"], p["offsets"], p["pairs"])
+            ops.moe_gate_up(p["act"], p["xn"], wg, dg, wu, dg, p["offsets"], p["pairs"], 1, H, ie, n_exp, K)
+            ops.moe_down(hid, hid, p["act"], wd, dd, p["ids"], p["w"], p["offsets"], p["pairs"], p["part"], 1, H, ie, n_exp, K)
+
+        def row(): ops.moe_ffn_row(hid, hid, p["xn"], router, wg, dg, wu, dg, wd, dd, H, ie, n_exp, K, ws, total)
+        three(); row(); ops.synchronize()
+        ts = {three: [], row: []}
+        for _ in range(5):
+            for fn in (three, row):
+                ts[fn].append(timed_us(fn, 100, rounds=1))
+        mb_g, mb_d = K * 2 * ie * G.row_bytes(t_gu, H) / 1e6, K * H * G.row_bytes(t_d, ie) / 1e6
+        m3, m1 = float(np.median(ts[three])), float(np.median(ts[row]))
+        say("  %-14s three launches %8.2f us [%s] | row form %8.2f us [%s] | x %.2f | model: route 3.8 + gate|up %.1f + down %.1f us (%.2f + %.2f MB)" %
+            (name, m3, " ".join("%.1f" % t for t in ts[three]), m1, " ".join("%.1f" % t for t in ts[row]), m3 / m1, 3.8 + mb_g / 6.9, 3.8 + mb_d / 6.9, mb_g, mb_d))
+        for b in (wg, wu, wd, router, ws, hid):
+            b.free()
+
+
+def bench_ab_row_decode(models, layers):
+    for item in models.split(","):
+        name, mix = item.split(":")
+        spec = E.synth_spec(name, mix, layers=layers)
+        eng = E.Engine()
+        t0 = time.perf_counter()
+        eng.load_synthetic(spec, 4096)
+        rng = np.random.Generator(np.random.Philox(key=[20261101, 3]))
+        prompt = [spec.bos] + [int(t) for t in rng.integers(0, min(spec.vocab, 32000), 15)]
+        say("%s %s: %d layers (%d routed, %d on the row form), loaded in %.0f s; decode, 128 greedy steps, graph replay, moe_row 0 / 1 alternated three times" %
+            (name, mix, eng.n_layers, eng.moe(), eng.moe_row(), time.perf_counter() - t0))
+        gen = lambda n: eng.generate_tokens(prompt, n, temperature=0.0, repeat_penalty=1.0, stop_at_eos=False)
+        per = {0: [], 1: []}
+        for i in range(4):          # (the first round warms both forms up and is dropped)
+            for on in (0, 1):
+                eng.set_option("moe_row", on)
+                gen(2)
+                t0 = time.perf_counter(); gen(1); t1 = time.perf_counter() - t0
+                t0 = time.perf_counter(); gen(129); t129 = time.perf_counter() - t0
+                if i:
+                    per[on].append(128.0 / (t129 - t1))
+        say("    moe_row 0: %s tokens/s | moe_row 1: %s tokens/s | slowest 1 / fastest 0: %.3f" %
+            (" ".join("%.1f" % v for v in per[0]), " ".join("%.1f" % v for v in per[1]), min(per[1]) / max(per[0])))
+        eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--engine", action="store_true")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--ab-moe-gemm", action="store_true")
+    ap.add_argument("--ab-moe-row", action="store_true")
     ap.add_argument("--models", default="qwen3-30b-a3b:Q8_0,mixtral-8x7b:Q4_K_M")
     ap.add_argument("--layers", type=int, default=None, help="fewer layers than the published model (a quicker run; said in the output)")
     ap.add_argument("--out", default=None, help="append the result lines to this file")
     a = ap.parse_args()
     ops.init(0)
     say("shader clock: %s" % sclk())
-    if a.kernels or not (a.engine or a.ab_moe_gemm):
+    if a.kernels or not (a.engine or a.ab_moe_gemm or a.ab_moe_row):
         bench_kernels()
-    if a.engine or not (a.kernels or a.ab_moe_gemm):
+    if a.engine or not (a.kernels or a.ab_moe_gemm or a.ab_moe_row):
         bench_engine(a.models, a.layers)
     if a.ab_moe_gemm:
         bench_ab(a.models, a.layers)
+    if a.ab_moe_row:
+        bench_ab_row_layer()
+        bench_ab_row_decode(a.models, a.layers)
     if a.out:
         with open(a.out, "a") as f:
             f.write("\n".join(lines) + "\n")
