@@ -248,6 +248,39 @@ int ntk_attention_decode_q8_batch(float* output, const float* q, const float* k,
                                   float theta_base, float freq_scale, int nsplit, float* scratch, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The FP8 KV cache (csrc/attention_fp8.hip; no reference counterpart).  A cache element is one OCP E4M3 byte ("fn": maximum 448, no infinities,
+ * S.1111.111 = NaN): the F32 post-RoPE k / the F32 v rounded to nearest even and saturated at +-448 by gfx950's own conversion; NaN in, NaN out.
+ * Device layout: ONE buffer per layer and side of ntk_kv_fp8_cache_bytes bytes, 16-byte aligned: uint8 [max_seq][n_kv_heads * head_dim], no
+ * scales -- 1 byte per element.  head_dim % 8 == 0; k and v rows 16-byte aligned (NTK_E_ALIGN otherwise).  E4M3 -> F16 is exact, and every
+ * kernel below computes with exactly those halves.
+ *   ntk_kv_store_fp8          F32 rows k, v [seq_len][n_kv_heads * head_dim] (k already rotated) -> cache rows [start_pos, start_pos + seq_len);
+ *                             rows from max_seq on are dropped
+ *   ntk_rope_kv_store_fp8     ntk_rope_kv_store with the FP8 store: q rotated in place, k on the way to the cache (_tab: the frequency table)
+ *   ntk_attention_decode_fp8  the contract of ntk_attention_decode_q8 over the FP8 caches: RoPE of q and the new k, encode + store the new row,
+ *                             GQA attention over rows 0 .. *d_pos on the F16 matrix cores, partial states in `scratch` + the combine launch.
+ *                             Any position from 0, any nsplit in 1 .. 1024; rows past *d_pos may hold any bytes, NaN codes included.
+ *                             head_dim 128 and <= 16 query heads per KV head (NTK_E_SHAPE otherwise).  *d_pos lives on the device and is
+ *                             NOT validated, as in ntk_attention_decode_q8: the caller keeps it in [0, max_seq) (the engine does).  From
+ *                             max_seq on no address leaves the buffer -- row indices are clamped to max_seq - 1, the store is dropped --
+ *                             but the output is over repeated rows and means nothing.
+ *   ntk_kv_dequant_fp8_f16    cache rows [0, n_rows) -> F16 K and V images [n_rows][n_kv_heads * head_dim], exactly
+ * ------------------------------------------------------------------------------------------- */
+size_t ntk_kv_fp8_cache_bytes(int max_seq, int n_kv_heads, int head_dim);
+int ntk_kv_store_fp8(void* k_cache, void* v_cache, const float* k, const float* v, int seq_len, int n_kv_heads, int head_dim, int start_pos,
+                     int max_seq, void* stream);
+int ntk_rope_kv_store_fp8(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
+                          float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
+                          void* stream);
+int ntk_rope_kv_store_fp8_tab(float* q, const float* k, const float* v, const int* positions, int seq_len, int n_heads, int n_kv_heads, int head_dim,
+                              float theta_base, float freq_scale, int interleaved, void* k_cache, void* v_cache, int start_pos, int max_seq,
+                              const float* inv_freq, void* stream);
+int ntk_attention_decode_fp8(float* output, const float* q, const float* k, const float* v, void* k_cache, void* v_cache, const int* d_pos,
+                             const float* inv_freq, int n_heads, int n_kv_heads, int head_dim, int max_seq, float scale, float theta_base,
+                             float freq_scale, int nsplit, float* scratch, void* stream);
+int ntk_kv_dequant_fp8_f16(void* k_f16, void* v_f16, const void* k_cache, const void* v_cache, int n_rows, int n_kv_heads, int head_dim,
+                           int max_seq, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * KV cache sequence operations (csrc/kv_ops.hip; no reference counterpart): the CONTEXT SHIFT.  In every one of n_layers layers, rows
  * [src0, src0 + n_rows) of both caches move to [dst0, dst0 + n_rows), 0 <= dst0 < src0, src0 + n_rows <= max_seq.  V rows move byte for byte (Q8:
  * quants and scales).  K rows -- cached AFTER RoPE -- are rotated by delta = dst0 - src0 positions, which makes them the keys the model would have

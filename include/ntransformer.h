@@ -83,6 +83,12 @@ int  nt_engine_load_shared(nt_engine_t e, nt_engine_t src, int max_context);
  * the 8-bit rows on the matrix cores using half(d) * q exactly; prompt passes (and "fused" = "0") dequantise rows [0, start_pos + n) into the F16 image
  * -- rounded to half, the chunk's own rows included -- and run the F16 attention kernels over it.  Refused at load (NTK_E_SHAPE + last_error): head_dim
  * other than 128, more than 16 query heads per KV head, tensor parallelism;
+ * "kv_cache" = "fp8": the KV cache as OCP E4M3 bytes (RNE from the F32 post-RoPE k and the F32 v, saturating at +-448; no scales: 1 byte per element,
+ * plus the same one-layer F16 image).  Coarser than "q8_0" (3 mantissa bits, no block scale) and opt-in like it.  Decode steps convert the rows to half
+ * exactly on their way into the F16 matrix cores; prompt passes decode rows [0, start_pos + n) into the image, exactly.  One sequence per engine: refused
+ * with NTK_E_SHAPE + last_error are, at load, the geometries "q8_0" refuses, tensor parallelism and "sequences" > 1, and afterwards the batched entry
+ * points (nt_engine_decode_batch / _sample, nt_engine_forward_batch and with it "batch_prefill"), nt_engine_kv_shift and nt_engine_kv_copy; the F16 and
+ * Q8_0 nt_engine_debug_kv_* forms answer NTK_E_DTYPE (use nt_engine_debug_kv_read_fp8 / _write_fp8);
  * "sequences" = "1" .. "16" (default "1"): sequence slots of this engine for the batched decode step below.  Slot 0 is the KV cache every other entry point
  * uses, exactly as without the option; slots 1 .. N - 1 are extra F16 caches of the same layout, allocated at load (counted in nt_engine_kv_cache_bytes)
  * beside a [16][vocab] F32 logits buffer and the batched sampler's buffers (under 1 MB; neither is counted there).  Set it BEFORE the load (afterwards:
@@ -281,6 +287,9 @@ int  nt_engine_debug_kv_write_slot(nt_engine_t e, int slot, int layer, int pos0,
  * side.  Each pair returns NTK_E_DTYPE on an engine of the other cache format. */
 int  nt_engine_debug_kv_read_q8(nt_engine_t e, int layer, int pos0, int n, void* k_blocks_out, void* v_blocks_out);
 int  nt_engine_debug_kv_write_q8(nt_engine_t e, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks);
+/* ... of a "kv_cache" = "fp8" engine: the rows' E4M3 bytes, [n][n_kv_heads * head_dim] per side (NTK_E_DTYPE on an engine of another format) */
+int  nt_engine_debug_kv_read_fp8(nt_engine_t e, int layer, int pos0, int n, void* k_bytes_out, void* v_bytes_out);
+int  nt_engine_debug_kv_write_fp8(nt_engine_t e, int layer, int pos0, int n, const void* k_bytes, const void* v_bytes);
 /* ... of sequence slot `slot` of a q8_0 engine ("batch_kv_q8"; slot 0: the calls above): the checks of the F16 slot pair -- a slot outside
  * 0 .. "sequences" - 1: NTK_E_SHAPE -- and NTK_E_DTYPE on an F16 engine */
 int  nt_engine_debug_kv_read_q8_slot(nt_engine_t e, int slot, int layer, int pos0, int n, void* k_blocks_out, void* v_blocks_out);

@@ -147,6 +147,12 @@ def lib() -> C.CDLL:
         "ntk_rope_kv_store_q8": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp]),
         "ntk_attention_decode_q8": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_kv_dequant_q8_f16": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
+        "ntk_kv_fp8_cache_bytes": (C.c_size_t, [i, i, i]),
+        "ntk_kv_store_fp8": (i, [vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "ntk_rope_kv_store_fp8": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp]),
+        "ntk_rope_kv_store_fp8_tab": (i, [vp, vp, vp, vp, i, i, i, i, f, f, i, vp, vp, i, i, vp, vp]),
+        "ntk_attention_decode_fp8": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, vp, vp]),
+        "ntk_kv_dequant_fp8_f16": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "ntk_attention_decode_q8_batch": (i, [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, i, f, f, f, i, vp, vp]),
         "ntk_kv_shift": (i, [vp, vp, i, i, i, i, i, i, i, vp, f, f, i, vp]),
         "ntk_kv_shift_q8": (i, [vp, vp, i, i, i, i, i, i, i, vp, f, f, i, vp]),

@@ -36,7 +36,7 @@ static void usage(const char* prog) {
             "  --no-batched-prefill     Prompt tokens one by one (the reference's GEMV loops) instead of 16 per weight pass\n"
             "  --no-dense-fuse          F16 / BF16 matrices on the 1:1 launchers instead of the fused 16-bit GEMV and the batched prompt GEMM (A/B switch)\n"
             "  --no-moe-gemm            Prompt passes over mixture-of-experts layers on the expert GEMV instead of the grouped matrix-core GEMM (A/B switch)\n"
-            "  --kv-cache <f16|q8_0>    KV cache format (default: f16; q8_0 = 8-bit Q8_0 blocks, 1.0625 bytes per element)\n"
+            "  --kv-cache <f16|q8_0|fp8> KV cache format (default: f16; q8_0 = 8-bit Q8_0 blocks, 1.0625 bytes per element; fp8 = E4M3 bytes, 1 per element)\n"
             "  --rope-scaling <s>       file (default: the GGUF's rope_freqs.weight and linear scaling) | none | linear:<factor> |\n"
             "                           llama3:<factor>,<low>,<high>,<orig_ctx> (Llama-3.1 frequency factors computed by the engine)\n"
             "  --rope-freq-base <float> RoPE theta, overriding the model's\n"
@@ -133,7 +133,7 @@ int main(int argc, char** argv) {
         else if (a == "--synthetic") { if (auto v = val()) synthetic = v; }
         else if (a == "--kv-cache") {
             const char* v = val();
-            if (!v || engine.model().set_kv_cache(v) != NTK_OK) { fprintf(stderr, "Error: --kv-cache takes f16 or q8_0\n"); return 1; }
+            if (!v || engine.model().set_kv_cache(v) != NTK_OK) { fprintf(stderr, "Error: --kv-cache takes f16, q8_0 or fp8\n"); return 1; }
         }
         else if (a == "--rope-scaling" || a == "--rope-freq-base" || a == "--rope-freq-scale") {
             const char* v = val();

@@ -95,7 +95,7 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
     else if (k == "persistent" || k == "fuse_attention") {   // accepted and without effect: the structures they selected were retired
         if (on) fprintf(stderr, "note: \"%s\" selected an experiment that lost to the fused launches and was removed (profiles/NEGATIVE_RESULTS.md); the option does nothing\n", key);
     }
-    else if (k == "kv_cache") return before_load([&] { return E(e)->model().set_kv_cache(value); });   // "f16" (default) | "q8_0": before the load only
+    else if (k == "kv_cache") return before_load([&] { return E(e)->model().set_kv_cache(value); });   // "f16" (default) | "q8_0" | "fp8": before the load only
     else if (k == "rope_scaling") return before_load([&] { return E(e)->model().set_rope_scaling(value); });   // file (default) | none | linear:<f> | llama3:<f>,<low>,<high>,<ctx>: before the load only (model.h)
     else if (k == "rope_freq_base") return before_load([&] { return E(e)->model().set_rope_freq_base(value); });   // theta > 0, overriding the file's
     else if (k == "rope_freq_scale") return before_load([&] { return E(e)->model().set_rope_freq_scale(value); });   // the linear scale > 0, overriding the file's
@@ -351,6 +351,14 @@ int nt_engine_debug_kv_read_q8_slot(nt_engine_t e, int slot, int layer, int pos0
 int nt_engine_debug_kv_write_q8_slot(nt_engine_t e, int slot, int layer, int pos0, int n, const void* k_blocks, const void* v_blocks) {
     if (!e || !E(e)->loaded()) return NTK_E_NULL;
     return E(e)->model().debug_kv_q8(layer, pos0, n, static_cast<uint8_t*>(const_cast<void*>(k_blocks)), static_cast<uint8_t*>(const_cast<void*>(v_blocks)), true, slot);
+}
+int nt_engine_debug_kv_read_fp8(nt_engine_t e, int layer, int pos0, int n, void* k_bytes, void* v_bytes) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_fp8(layer, pos0, n, static_cast<uint8_t*>(k_bytes), static_cast<uint8_t*>(v_bytes), false);
+}
+int nt_engine_debug_kv_write_fp8(nt_engine_t e, int layer, int pos0, int n, const void* k_bytes, const void* v_bytes) {
+    if (!e || !E(e)->loaded()) return NTK_E_NULL;
+    return E(e)->model().debug_kv_fp8(layer, pos0, n, static_cast<uint8_t*>(const_cast<void*>(k_bytes)), static_cast<uint8_t*>(const_cast<void*>(v_bytes)), true);
 }
 
 const char* nt_engine_decode_path(nt_engine_t e) { return e && E(e)->loaded() ? E(e)->model().decode_path() : ""; }

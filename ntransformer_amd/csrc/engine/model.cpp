@@ -260,10 +260,9 @@ int Model::set_static_activations(bool on) {
 }
 
 int Model::set_kv_cache(const std::string& kind) {
-    if (kind != "f16" && kind != "q8_0") { err_ = "kv_cache: unknown format '" + kind + "' (f16 or q8_0)"; return NTK_E_DTYPE; }
+    if (kind != "f16" && kind != "q8_0" && kind != "fp8") { err_ = "kv_cache: unknown format '" + kind + "' (f16, q8_0 or fp8)"; return NTK_E_DTYPE; }
     if (!layers_.empty()) { err_ = "kv_cache must be set before the model is loaded"; return NTK_E_SHAPE; }
-    const bool q8 = kind == "q8_0";
-    kv_q8_ = q8;
+    kv_format_ = kind == "fp8" ? KvFormat::fp8 : kind == "q8_0" ? KvFormat::q8_0 : KvFormat::f16;
     return NTK_OK;
 }
 

@@ -218,6 +218,10 @@ public:
     // refused afterwards.  q8_0 needs head_dim 128, <= 16 query heads per KV head and no tensor parallelism: the load refuses otherwise.
     // Decode: ntk_attention_decode_q8 + the combine launch in every regime (splits: kv_q8_splits).  Prompt pass / 1:1 sequence: 8-bit store, then
     // rows [0, start_pos + T) dequantised (rounded to half) into the scratch that the unchanged F16 attention kernels read.
+    // "fp8" (csrc/attention_fp8.hip: one OCP E4M3 byte per element, no scales, + the same one-layer F16 image, filled exactly): the geometry rules of
+    // q8_0; decode is ntk_attention_decode_fp8 + the combine launch in every regime with the q8_0 split counts; the prompt pass stores in FP8 and
+    // decodes rows [0, start_pos + T) into the image.  One sequence only: sequences > 1, decode_batch / forward_batch, kv_shift, kv_copy and tensor
+    // parallelism are refused with a message.
     int set_kv_cache(const std::string& kind);
     // RoPE frequency scaling (rope_scaling.h).  Three options, BEFORE the load, kept across loads, refused afterwards (NTK_E_SHAPE + error();
     // malformed text too): "rope_scaling" = file (default: the GGUF's rope_freqs.weight divisors and its linear scaling keys) | none (ignore them) |
@@ -265,14 +269,18 @@ public:
     // (LayerWeights::moe_row_ok; another layer keeps the three launches without a word).  Any time (the A/B switch): a change drops the captured tokens.
     int set_moe_row(bool on);
     int moe_row_layers() const { int n = 0; if (moe_row_) for (const auto& L : layers_) n += L.is_moe() && L.moe_row_ok ? 1 : 0; return n; }
-    bool kv_q8() const { return kv_q8_; }
+    bool kv_q8() const { return kv_format_ == KvFormat::q8_0; }
+    bool kv_fp8() const { return kv_format_ == KvFormat::fp8; }
+    const char* kv_format_name() const { return kv_fp8() ? "fp8" : kv_q8() ? "q8_0" : "f16"; }
     static int kv_q8_splits(int regime) { return regime == 0 ? 4 : regime == 1 ? 16 : 32; }
-    uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the q8_0 mode's one F16 image included
+    uint64_t kv_cache_bytes() const { return kv_.bytes(); }   // resident KV bytes of this engine: every slot, the one F16 image of the q8_0 and fp8 modes included
     int debug_kv_inputs_capture(int layer);
     int debug_kv_inputs_read(int n, float* k, float* v);
     // cache rows [pos0, pos0 + n) of a layer of sequence slot `slot` as canonical 34-byte GGUF block_q8_0, [n][n_kv_heads * head_dim / 32] blocks per
     // side (q8_0 mode only: NTK_E_DTYPE otherwise; a slot out of range: NTK_E_SHAPE)
     int debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write, int slot = 0);
+    // ... of the FP8 cache: [n][n_kv_heads * head_dim] E4M3 bytes per side (fp8 mode only: NTK_E_DTYPE otherwise)
+    int debug_kv_fp8(int layer, int pos0, int n, uint8_t* k_bytes, uint8_t* v_bytes, bool write);
     void set_prefill_row_max(bool on) { prefill_row_max_ = on; }
     void set_prefill_fused_split(bool on) { prefill_fused_split_ = on; }
     // Split-KV decode attention as ONE launch (the last workgroup of a head merges the partial states: attention_merge.hip.h) or -- the default --
@@ -422,7 +430,7 @@ private:
 
     // buffers (reference transformer.cpp:330-391)
     KvCache kv_;                    // every slot's K / V cache in the loaded format (kv_cache.h); slot 0 is the one the fused path decodes on
-    bool kv_q8_ = false;            // the option (kept across loads)
+    KvFormat kv_format_ = KvFormat::f16;   // the option (kept across loads)
     int sequences_ = 1;             // the option (kept across loads)
     float* batch_logits_ = nullptr; // [kMaxSequences][V]: decode_batch's logits
     int* batch_in_ = nullptr;       // [3][kMaxSequences] device ints: tokens | positions | -1 (ntk_logprob_rows' "no target")

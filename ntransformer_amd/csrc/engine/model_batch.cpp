@@ -63,7 +63,8 @@ int Model::batch_logits(const int* slots, const int* tokens, const int* position
 
 int Model::decode_batch(const int* slots, const int* tokens, const int* positions, int B, float* logits_out, int* next_out) {
     NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
-    if ((kv_q8_ && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if ((kv_q8() && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if (kv_fp8()) { err_ = "decode_batch: not available with kv_cache=fp8"; return NTK_E_SHAPE; }
     NT_TRY(batch_buffers());
     const int V = cfg_.vocab_size, N = kMaxSequences;
     void* s = stream_;
@@ -97,7 +98,8 @@ int Model::validate_forward_batch(const int* slots, const int* lens, const int* 
 int Model::forward_batch(const int* slots, const int* tokens, const int* lens, const int* start_pos, int n, float* logits_out, int* next_out) {
     NT_TRY(validate_forward_batch(slots, lens, start_pos, n, sequences_, cfg_.max_seq_len, &err_));
     if (!tokens) { err_ = "forward_batch: null argument"; return NTK_E_NULL; }
-    if (kv_q8_ || tp_world_ > 1) { err_ = "forward_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if (kv_q8() || tp_world_ > 1) { err_ = "forward_batch: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if (kv_fp8()) { err_ = "forward_batch: not available with kv_cache=fp8"; return NTK_E_SHAPE; }
     const int H = cfg_.hidden_size, V = cfg_.vocab_size, N = kMaxSequences;
     ntk_kv_segments segs{};   // rows, lengths and first positions; layers_1to1 fills in each layer's caches
     segs.n_seg = n;
@@ -147,7 +149,8 @@ int Model::batch_sample_buffers() {
 int Model::decode_batch_sample(const int* slots, const int* tokens, const int* positions, int B, const ntk_sample_rows& rows, const int* const* recent,
                                float* logits_out, float* const* row_logits, int* next_out) {
     NT_TRY(validate_batch(slots, tokens, positions, B, sequences_, cfg_.max_seq_len, cfg_.vocab_size, &err_));
-    if ((kv_q8_ && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch_sample: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if ((kv_q8() && !batch_kv_q8_) || tp_world_ > 1) { err_ = "decode_batch_sample: not available with kv_cache=q8_0 or tensor parallelism"; return NTK_E_SHAPE; }
+    if (kv_fp8()) { err_ = "decode_batch_sample: not available with kv_cache=fp8"; return NTK_E_SHAPE; }
     if (!next_out) { err_ = "decode_batch_sample: null argument"; return NTK_E_NULL; }
     const int V = cfg_.vocab_size;
     int pitch = 0;   // of this step's windows: the longest one a penalty reads

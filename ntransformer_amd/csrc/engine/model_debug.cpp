@@ -45,7 +45,8 @@ int Model::debug_run_layers(const float* hidden_in, int T, int start_pos, int fi
 // cache rows [pos0, pos0 + n) of one layer, [n][n_kv_heads * head_dim] halves each (reference layout, transformer.cpp:340-346)
 int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool write, int slot) {
     if (!k || !v) return NTK_E_NULL;
-    if (kv_q8_) { err_ = "debug_kv: the KV cache is q8_0 (use the _q8 form)"; return NTK_E_DTYPE; }
+    if (kv_q8()) { err_ = "debug_kv: the KV cache is q8_0 (use the _q8 form)"; return NTK_E_DTYPE; }
+    if (kv_fp8()) { err_ = "debug_kv: the KV cache is fp8 (use the _fp8 form)"; return NTK_E_DTYPE; }
     if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= kv_.slots()) return NTK_E_SHAPE;
     KvRange r[2];
     kv_.row_ranges(pos0, n, r);   // (f16: one range)
@@ -61,7 +62,7 @@ int Model::debug_kv(int layer, int pos0, int n, uint16_t* k, uint16_t* v, bool w
 // keeps quants and scales in two planes (csrc/attention_q8.hip): the rows' slices of both are contiguous, the blocks are (de)interleaved here.
 int Model::debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v_blocks, bool write, int slot) {
     if (!k_blocks || !v_blocks) return NTK_E_NULL;
-    if (!kv_q8_) { err_ = "debug_kv_q8: the KV cache is f16"; return NTK_E_DTYPE; }
+    if (!kv_q8()) { err_ = std::string("debug_kv_q8: the KV cache is ") + kv_format_name(); return NTK_E_DTYPE; }
     if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len || slot < 0 || slot >= kv_.slots()) return NTK_E_SHAPE;
     if (n == 0) return NTK_OK;
     const size_t nb = (size_t)cfg_.n_kv_heads * cfg_.head_dim / 32;   // blocks of a row
@@ -93,6 +94,22 @@ int Model::debug_kv_q8(int layer, int pos0, int n, uint8_t* k_blocks, uint8_t* v
         }
     }
     return NTK_OK;
+}
+
+// ... of the FP8 cache: the rows' E4M3 bytes, [n][n_kv_heads * head_dim] per side (one range: kv_layout.h)
+int Model::debug_kv_fp8(int layer, int pos0, int n, uint8_t* k_bytes, uint8_t* v_bytes, bool write) {
+    if (!k_bytes || !v_bytes) return NTK_E_NULL;
+    if (!kv_fp8()) { err_ = std::string("debug_kv_fp8: the KV cache is ") + kv_format_name(); return NTK_E_DTYPE; }
+    if (layer < 0 || layer >= cfg_.n_layers || pos0 < 0 || n < 0 || pos0 + n > cfg_.max_seq_len) return NTK_E_SHAPE;
+    if (n == 0) return NTK_OK;
+    KvRange r[2];
+    kv_.row_ranges(pos0, n, r);   // (fp8: one range)
+    uint8_t* const kd = static_cast<uint8_t*>(kv_.k(0, layer)) + r[0].off;
+    uint8_t* const vd = static_cast<uint8_t*>(kv_.v(0, layer)) + r[0].off;
+    void* s = stream_;
+    NT_TRY(write ? ntk_memcpy_h2d_async(kd, k_bytes, r[0].bytes, s) : ntk_memcpy_d2h_async(k_bytes, kd, r[0].bytes, s));
+    NT_TRY(write ? ntk_memcpy_h2d_async(vd, v_bytes, r[0].bytes, s) : ntk_memcpy_d2h_async(v_bytes, vd, r[0].bytes, s));
+    return ntk_stream_synchronize(s);
 }
 
 // Parity instrumentation: from now on every 1:1 pass (forward / debug_run_layers mode 0) leaves the F32 k (BEFORE the rotation) and v projections of

@@ -154,7 +154,10 @@ int Model::enqueue_layers(int first, int last_layer) {
             prof_mark(2, false);
         }
         prof_mark(1, true);
-        if (kv_q8_)
+        if (kv_fp8())
+            NT_TRY(ntk_attention_decode_fp8(act.attn_out, act.q, act.k, act.v, kv_.k(0, i), kv_.v(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
+                                            cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
+        else if (kv_q8())
             NT_TRY(ntk_attention_decode_q8(act.attn_out, act.q, act.k, act.v, kv_.k(0, i), kv_.v(0, i), d_pos_, rope_inv_freq_, nh, nkv, hd,
                                            cfg_.max_seq_len, scale, cfg_.rope_theta, cfg_.rope_freq_scale, kv_q8_splits(attn_regime_), attn_scratch_, s));
         else if (attn_regime_ == 0)

@@ -24,11 +24,12 @@ int Model::validate_kv_copy(int src_slot, int dst_slot, int pos0, int n, int seq
 int Model::kv_shift(int slot, int keep, int discard, int n_past) {
     if (layers_.empty()) { err_ = "kv_shift: no model is loaded"; return NTK_E_NULL; }
     if (tp_world_ > 1) { err_ = "kv_shift: not supported with tensor parallelism"; return NTK_E_SHAPE; }
+    if (kv_fp8()) { err_ = "kv_shift: not supported with kv_cache=fp8"; return NTK_E_SHAPE; }
     NT_TRY(validate_kv_shift(slot, keep, discard, n_past, sequences_, cfg_.max_seq_len, &err_));
     const int src0 = keep + discard, n_rows = n_past - src0;
     if (n_rows > 0) {
         const int L = cfg_.n_layers, S = cfg_.max_seq_len, nkv = cfg_.n_kv_heads, hd = cfg_.head_dim;
-        const int rc = kv_q8_ ? ntk_kv_shift_q8(kv_.k(slot), kv_.v(slot), L, S, nkv, hd, src0, keep, n_rows, rope_inv_freq_, cfg_.rope_theta,
+        const int rc = kv_q8() ? ntk_kv_shift_q8(kv_.k(slot), kv_.v(slot), L, S, nkv, hd, src0, keep, n_rows, rope_inv_freq_, cfg_.rope_theta,
                                                 cfg_.rope_freq_scale, cfg_.rope_interleaved, stream_)
                             : ntk_kv_shift(static_cast<uint16_t*>(kv_.k(slot)), static_cast<uint16_t*>(kv_.v(slot)), L, S, nkv, hd, src0, keep, n_rows,
                                            rope_inv_freq_, cfg_.rope_theta, cfg_.rope_freq_scale, cfg_.rope_interleaved, stream_);
@@ -40,6 +41,7 @@ int Model::kv_shift(int slot, int keep, int discard, int n_past) {
 int Model::kv_copy(int src_slot, int dst_slot, int pos0, int n) {
     if (layers_.empty()) { err_ = "kv_copy: no model is loaded"; return NTK_E_NULL; }
     if (tp_world_ > 1) { err_ = "kv_copy: not supported with tensor parallelism"; return NTK_E_SHAPE; }
+    if (kv_fp8()) { err_ = "kv_copy: not supported with kv_cache=fp8"; return NTK_E_SHAPE; }
     NT_TRY(validate_kv_copy(src_slot, dst_slot, pos0, n, sequences_, cfg_.max_seq_len, &err_));
     if (n == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream_);

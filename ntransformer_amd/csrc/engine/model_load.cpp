@@ -493,7 +493,7 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
     // the attention kernels address a layer's cache rows with 32-bit byte offsets (attention.hip): a context whose per-layer cache reaches
     // 3.75 GiB is refused here, at load, rather than as NTK_E_SHAPE from the first decode step (8 KV heads of 128: 1.9 M positions)
     if (S * per * sizeof(uint16_t) >= 0xF0000000ull) { err_ = "context too long: one layer's K cache must stay below 3.75 GiB (32-bit row offsets)"; return NTK_E_SHAPE; }
-    if (kv_q8_) {   // the 8-bit cache (csrc/attention_q8.hip) + ONE layer's F16 image for the prompt path
+    if (kv_q8()) {   // the 8-bit cache (csrc/attention_q8.hip) + ONE layer's F16 image for the prompt path
         if (cfg_.head_dim != 128 || cfg_.n_kv_heads <= 0 || cfg_.n_heads % cfg_.n_kv_heads != 0 || cfg_.n_heads / cfg_.n_kv_heads > 16) {
             err_ = "kv_cache=q8_0 needs head_dim 128 and at most 16 query heads per KV head (this model: head_dim " + std::to_string(cfg_.head_dim) +
                    ", " + std::to_string(cfg_.n_kv_heads > 0 ? cfg_.n_heads / cfg_.n_kv_heads : 0) + " query heads per KV head)";
@@ -501,13 +501,23 @@ int Model::alloc_buffers() {   // transformer.cpp:330-391
         }
         if (tp_world_ > 1) { err_ = "kv_cache=q8_0 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
     }
+    if (kv_fp8()) {   // the FP8 cache (csrc/attention_fp8.hip) + the same image
+        if (cfg_.head_dim != 128 || cfg_.n_kv_heads <= 0 || cfg_.n_heads % cfg_.n_kv_heads != 0 || cfg_.n_heads / cfg_.n_kv_heads > 16) {
+            err_ = "kv_cache=fp8 needs head_dim 128 and at most 16 query heads per KV head (this model: head_dim " + std::to_string(cfg_.head_dim) +
+                   ", " + std::to_string(cfg_.n_kv_heads > 0 ? cfg_.n_heads / cfg_.n_kv_heads : 0) + " query heads per KV head)";
+            return NTK_E_SHAPE;
+        }
+        if (tp_world_ > 1) { err_ = "kv_cache=fp8 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
+        if (sequences_ > 1) { err_ = "sequences > 1 is not supported with kv_cache=fp8"; return NTK_E_SHAPE; }
+    }
     if (sequences_ > 1) {   // the extra sequence slots: caches of slot 0's layout
-        if (kv_q8_ && !batch_kv_q8_) { err_ = "sequences > 1 is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
+        if (kv_q8() && !batch_kv_q8_) { err_ = "sequences > 1 is not supported with kv_cache=q8_0"; return NTK_E_SHAPE; }
         if (tp_world_ > 1) { err_ = "sequences > 1 is not supported with tensor parallelism"; return NTK_E_SHAPE; }
         // a batched step is a prompt pass of up to `sequences` rows through buffers of max_seq rows (hidden_, residual_, workspace_, row_max_, kv_capture_)
         if ((size_t)sequences_ > S) { err_ = "sequences = " + std::to_string(sequences_) + " needs a context of at least as many positions (this load: " + std::to_string(S) + ")"; return NTK_E_SHAPE; }
     }
-    NT_TRY(kv_.allocate(KvGeom{cfg_.n_layers, cfg_.max_seq_len, cfg_.n_kv_heads, cfg_.head_dim}, kv_q8_, sequences_, [&](size_t bytes, bool zero) { return dev_alloc(bytes, zero); }, &err_));
+    const KvGeom geom{cfg_.n_layers, cfg_.max_seq_len, cfg_.n_kv_heads, cfg_.head_dim};
+    NT_TRY(kv_.allocate(geom, kv_format_, sequences_, [&](size_t bytes, bool zero) { return dev_alloc(bytes, zero); }, &err_));
     hidden_ = (float*)dev_alloc(std::max<size_t>(S, 2) * H * 4, false);
     residual_ = (float*)dev_alloc(std::max<size_t>(S, 2) * H * 4, false);
     logits_ = (float*)dev_alloc((size_t)cfg_.vocab_size * 4, false);

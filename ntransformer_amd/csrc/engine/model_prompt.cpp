@@ -366,7 +366,7 @@ int Model::attend(int layer, int T, int start_pos, const KvTarget& kv, const Vie
         ntk_kv_batch caches{};
         kv_.fill(caches, kv.slots, T, layer);
         const int* const positions = batch_in_ + kMaxSequences;
-        if (kv_q8_) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
+        if (kv_q8()) {   // ... over the 8-bit caches ("batch_kv_q8"): the single-row decode launch's splits for the batch's largest position
             return ntk_attention_decode_q8_batch(act.attn_out, act.q, act.k, act.v, &caches, positions, T, rope_inv_freq_, nh, nkv, hd, S, scale, theta, fscale,
                                                  kv_q8_splits(attention_regime(kv.max_pos, hd)), batch_attn_scratch_, s);
         }
@@ -377,7 +377,7 @@ int Model::attend(int layer, int T, int start_pos, const KvTarget& kv, const Vie
     }
     uint16_t* const kc = kv_.attend_k(kv.slot, layer);   // (q8_0: the one-layer F16 image, shared by all slots: rebuilt below, for this slot, every pass)
     uint16_t* const vc = kv_.attend_v(kv.slot, layer);
-    if (kv_q8_) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
+    if (kv_q8()) {   // 8-bit store, then rows [0, start_pos + T) rounded to half into the one-layer scratch the unchanged F16 kernels read
         void* kc8 = kv_.k(kv.slot, layer);
         void* vc8 = kv_.v(kv.slot, layer);
         if (T >= 4) {
@@ -387,6 +387,16 @@ int Model::attend(int layer, int T, int start_pos, const KvTarget& kv, const Vie
             ok(ntk_kv_store_q8(kc8, vc8, act.k, act.v, T, nkv, hd, start_pos, S, s));
         }
         ok(ntk_kv_dequant_q8_f16(kc, vc, kc8, vc8, start_pos + T, nkv, hd, S, s));
+    } else if (kv_fp8()) {   // the same two steps in FP8: the store, then rows [0, start_pos + T) decoded exactly into the image
+        void* kc8 = kv_.k(kv.slot, layer);
+        void* vc8 = kv_.v(kv.slot, layer);
+        if (T >= 4) {
+            ok(ntk_rope_kv_store_fp8_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, kc8, vc8, start_pos, S, rope_tab(), s));
+        } else {
+            ok(ntk_rope_tab(act.q, act.k, positions_, 1, T, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, rope_tab(), s));
+            ok(ntk_kv_store_fp8(kc8, vc8, act.k, act.v, T, nkv, hd, start_pos, S, s));
+        }
+        ok(ntk_kv_dequant_fp8_f16(kc, vc, kc8, vc8, start_pos + T, nkv, hd, S, s));
     } else if (fused_store && T >= 4 && hd <= 256) {   // (the prompt form of the rotation: ntk_rope takes it from 4 tokens on, too)
         ok(ntk_rope_kv_store_tab(act.q, act.k, act.v, positions_, T, nh, nkv, hd, theta, fscale, cfg_.rope_interleaved, kc, vc, start_pos, S, rope_tab(), s));
     } else {

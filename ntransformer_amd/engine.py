@@ -129,6 +129,8 @@ def _bind():
     L.nt_engine_debug_kv_write.argtypes = [vp, i, i, i, vp, vp]
     L.nt_engine_debug_kv_read_q8.argtypes = [vp, i, i, i, vp, vp]
     L.nt_engine_debug_kv_write_q8.argtypes = [vp, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_read_fp8.argtypes = [vp, i, i, i, vp, vp]
+    L.nt_engine_debug_kv_write_fp8.argtypes = [vp, i, i, i, vp, vp]
     L.nt_engine_debug_kv_read_q8_slot.argtypes = [vp, i, i, i, i, vp, vp]
     L.nt_engine_debug_kv_write_q8_slot.argtypes = [vp, i, i, i, i, vp, vp]
     L.nt_engine_debug_kv_inputs_capture.argtypes = [vp, i]
@@ -215,7 +217,7 @@ class Engine:
         return int(self.L.nt_engine_tp_error(self.h))
 
     def set_option(self, key: str, value) -> None:
-        # ("kv_cache" takes "f16" / "q8_0", "rope_scaling" its own strings; "rope_freq_base" / "rope_freq_scale" a float)
+        # ("kv_cache" takes "f16" / "q8_0" / "fp8", "rope_scaling" its own strings; "rope_freq_base" / "rope_freq_scale" a float)
         if isinstance(value, str):
             text = value
         elif key in ("rope_freq_base", "rope_freq_scale"):
@@ -486,6 +488,18 @@ class Engine:
         v = np.ascontiguousarray(v_blocks, dtype=np.uint8)
         self._check(self.L.nt_engine_debug_kv_write_q8_slot(self.h, int(slot), layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p),
                                                             v.ctypes.data_as(C.c_void_p)), "kv_write_q8_slot")
+
+    def kv_read_fp8(self, layer: int, pos0: int, n: int, row_elems: int):
+        """(K, V) rows [pos0, pos0+n) of a kv_cache=fp8 engine as E4M3 bytes, uint8 [n, row_elems]"""
+        k = np.empty((n, row_elems), np.uint8)
+        v = np.empty((n, row_elems), np.uint8)
+        self._check(self.L.nt_engine_debug_kv_read_fp8(self.h, layer, pos0, n, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "kv_read_fp8")
+        return k, v
+
+    def kv_write_fp8(self, layer: int, pos0: int, k_bytes: np.ndarray, v_bytes: np.ndarray) -> None:
+        k = np.ascontiguousarray(k_bytes, dtype=np.uint8)
+        v = np.ascontiguousarray(v_bytes, dtype=np.uint8)
+        self._check(self.L.nt_engine_debug_kv_write_fp8(self.h, layer, pos0, k.shape[0], k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "kv_write_fp8")
 
     def kv_inputs_capture(self, layer: int) -> None:
         self._check(self.L.nt_engine_debug_kv_inputs_capture(self.h, layer), "kv_inputs_capture")

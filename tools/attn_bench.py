@@ -4,9 +4,10 @@ Llama-3.1 8B / 70B head geometries.  KV bytes per launch = 2 * (pos + 1) * n_kv_
 once in the algorithmic count).  hipGraph-timed, 64 launches over rotating layer caches (--layers, default 40: 671 MB of cache at 4096
 positions, past the 256 MB Infinity Cache like the 32 / 80 layers of a model; rounds 1-3 rotated over 8 = 134 MB, which the
 Infinity Cache held).
+--kv fp8 / all: the FP8 cache too (ntk_attention_decode_fp8, csrc/attention_fp8.hip; KV bytes = 2 * (pos + 1) * n_kv_heads * head_dim);
 --kv q8_0 / both: the 8-bit cache (ntk_attention_decode_q8, csrc/attention_q8.hip; KV bytes = 2 * (pos + 1) * n_kv_heads * head_dim * 17 / 16);
 "both" times the F16 and the 8-bit form of every case back to back in the same run (5 timed graph launches each, median), and prints the shader clock.
-usage: python tools/attn_bench.py [--json out.json] [--layers N] [--long] [--kv f16|q8_0|both]   (--long: only the split regime, 600 .. 4095 positions)"""
+usage: python tools/attn_bench.py [--json out.json] [--layers N] [--long] [--kv f16|q8_0|fp8|both|all]   (--long: only the split regime, 600 .. 4095 positions)"""
 import argparse
 import ctypes as C
 import json
@@ -16,7 +17,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from ntransformer_amd import _lib, kv_q8, ops  # noqa: E402
+from ntransformer_amd import _lib, kv_fp8, kv_q8, ops  # noqa: E402
 from ntransformer_amd.ops import DeviceBuffer as DB  # noqa: E402
 
 
@@ -29,9 +30,9 @@ def main():
     ap.add_argument("--models", default="8b,70b")
     ap.add_argument("--merged", action="store_true", help="time every split case in both forms: with the combine launch and as one launch (ntk_attention_decode_split_merged)")
     ap.add_argument("--max-seq", type=int, default=4096, help="context the caches are allocated for (round 5: 8192 ... 131072; use fewer --layers)")
-    ap.add_argument("--kv", default="f16", choices=("f16", "q8_0", "both"), help="cache format(s) to time")
+    ap.add_argument("--kv", default="f16", choices=("f16", "q8_0", "fp8", "both", "all"), help="cache format(s) to time")
     a = ap.parse_args()
-    kinds = ("f16", "q8_0") if a.kv == "both" else (a.kv,)
+    kinds = ("f16", "q8_0") if a.kv == "both" else ("f16", "q8_0", "fp8") if a.kv == "all" else (a.kv,)
     ops.init(0)
     L = _lib.lib()
     HIP = C.CDLL("libamdhip64.so")
@@ -50,6 +51,13 @@ def main():
             kc8, vc8 = [kv_q8.Q8Cache(max_seq, nkv, hd) for _ in range(nl)], [kv_q8.Q8Cache(max_seq, nkv, hd) for _ in range(nl)]
             for c in kc8 + vc8:
                 c.write_blocks(0, hb)
+            del hb
+        kcf = vcf = None
+        if "fp8" in kinds:   # (the same: one host image of unit-variance codes, nl device copies)
+            hb = kv_fp8.encode_e4m3(rng.standard_normal((max_seq, per), dtype=np.float32))
+            kcf, vcf = [kv_fp8.Fp8Cache(max_seq, nkv, hd) for _ in range(nl)], [kv_fp8.Fp8Cache(max_seq, nkv, hd) for _ in range(nl)]
+            for c in kcf + vcf:
+                c.write_rows(0, hb)
             del hb
         if "f16" not in kinds:
             kc = vc = None
@@ -82,6 +90,9 @@ def main():
                 if kind == "q8_0":
                     _lib.check(L.ntk_attention_decode_q8(out.ptr, q.ptr, k.ptr, v.ptr, kc8[i % nl].ptr, vc8[i % nl].ptr, dpos.ptr, None, nh, nkv, hd,
                                                          max_seq, 1.0 / np.sqrt(hd), 500000.0, 1.0, nsplit, scratch.ptr, None), "q8")
+                elif kind == "fp8":
+                    _lib.check(L.ntk_attention_decode_fp8(out.ptr, q.ptr, k.ptr, v.ptr, kcf[i % nl].ptr, vcf[i % nl].ptr, dpos.ptr, None, nh, nkv, hd,
+                                                          max_seq, 1.0 / np.sqrt(hd), 500000.0, 1.0, nsplit, scratch.ptr, None), "fp8")
                 elif nsplit == 1:
                     ops.attention_decode_fused(out, q, k, v, kc[i % nl], vc[i % nl], dpos, nh, nkv, hd, max_seq, 1.0 / np.sqrt(hd), 500000.0)
                 else:
@@ -102,9 +113,9 @@ def main():
                 times.append(ms.value)
             HIP.hipGraphExecDestroy(gexec); HIP.hipGraphDestroy(graph)
             us = float(np.median(times)) * 1e3 / n
-            kvb = 2 * (pos + 1) * per * 2 if kind == "f16" else 2 * (pos + 1) * per * 17 // 16
+            kvb = 2 * (pos + 1) * per * 2 if kind == "f16" else 2 * (pos + 1) * per if kind == "fp8" else 2 * (pos + 1) * per * 17 // 16
             row = {"model": name, "kv": kind, "pos": pos, "nsplit": nsplit, "merged": merged, "us": round(us, 2), "kv_MB": round(kvb / 1e6, 3), "GBs": round(kvb / us / 1e3, 1)}
-            form = "8-bit cache + combine launch" if kind == "q8_0" else "single pass" if nsplit == 1 else ("split, one launch" if merged else "split + combine launch")
+            form = "8-bit cache + combine launch" if kind in ("q8_0", "fp8") else "single pass" if nsplit == 1 else ("split, one launch" if merged else "split + combine launch")
             if a.kv != "f16":
                 row["sclk_mhz"] = round(ops.sclk_mhz(), 0)
                 form += ", sclk %d MHz, runs %s" % (row["sclk_mhz"], " / ".join("%.2f" % (t * 1e3 / n) for t in times))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""kv_cache=q8_0 against kv_cache=f16, end to end, on synthetic models (one copy of the weights, two sequences: nt_engine_load_shared).
+"""kv_cache=q8_0 / fp8 against kv_cache=f16, end to end, on synthetic models (one copy of the weights, two sequences: nt_engine_load_shared).
 
   speed    8B Q8_0: greedy decode tokens/s (nt_engine_decode_greedy_steps, the loop bench.py times for its ctx workloads) at position 128 and
            behind 3900- and 32768-token prompts, both modes alternating, 3 timed runs of --steps tokens each after a warm-up run.
@@ -7,7 +7,9 @@
            x 1000 / x 4000): max and RMS over the vocabulary of (logit_q8 - logit_f16) / RMS(logit_f16) after prompts of 64 / 1024 / 3900 random
            tokens, and the agreement of the two greedy streams over 256 tokens behind the 1024-token prompt.
 
-usage: python tools/kv_q8_eval.py speed|quality [--steps 64]"""
+--kv q8_0 (default) | fp8 | q8_0,fp8: the 8-bit format(s) compared with f16 -- all of them sequences over the one copy of the weights, alternated run by run.
+
+usage: python tools/kv_q8_eval.py speed|quality [--steps 64] [--kv q8_0,fp8]"""
 import argparse
 import os
 import sys
@@ -21,15 +23,23 @@ from ntransformer_amd import engine as E  # noqa: E402
 from ntransformer_amd import ops  # noqa: E402
 
 
-def pair(load, ctx):
-    """(f16 engine, q8_0 engine) over one copy of the weights"""
+def group(load, ctx, kinds):
+    """{"f16": engine, kind: engine, ...} over one copy of the weights (the f16 engine holds them)"""
     f = E.Engine()
     f.set_option("synth_threads", 16)
     load(f, ctx)
-    q = E.Engine()
-    q.set_option("kv_cache", "q8_0")
-    q.load_shared(f, ctx)
-    return f, q
+    engines = {"f16": f}
+    for kind in kinds:
+        q = E.Engine()
+        q.set_option("kv_cache", kind)
+        q.load_shared(f, ctx)
+        engines[kind] = q
+    return engines
+
+
+def close(engines):
+    for name in reversed(list(engines)):   # (the f16 engine, which holds the weights, last)
+        engines[name].close()
 
 
 def prefill(e, toks):
@@ -39,35 +49,36 @@ def prefill(e, toks):
     return lg
 
 
-def speed(steps):
+def speed(steps, kinds):
     spec = E.synth_spec("8b", "Q8_0")
-    f, q = pair(lambda e, ctx: e.load_synthetic(spec, ctx), 32768 + 4 * steps + 64)
+    eng = group(lambda e, ctx: e.load_synthetic(spec, ctx), 32768 + 4 * steps + 64, kinds)
     r = np.random.default_rng(1)
     print("8B Q8_0 synthetic, greedy decode tokens/s (3 runs of %d tokens, median; all runs listed)" % steps)
     for n_prompt in (128, 3900, 32768):
         toks = [int(t) for t in r.integers(0, 128000, n_prompt)]
         row = {}
-        for name, e in (("f16", f), ("q8_0", q)):
+        for name, e in eng.items():
             t0 = time.perf_counter()
             lg = prefill(e, toks)
             row[name + "_prefill_s"] = time.perf_counter() - t0
             row[name + "_tok"] = int(np.argmax(lg))
-        runs = {"f16": [], "q8_0": []}
+        runs = {name: [] for name in eng}
         for rep in range(4):                       # (run 0 warms up: graph capture)
-            for name, e in (("f16", f), ("q8_0", q)):
+            for name, e in eng.items():
                 t0 = time.perf_counter()
                 e.decode_greedy_steps(row[name + "_tok"], n_prompt, steps)
                 dt = time.perf_counter() - t0
                 if rep:
                     runs[name].append(steps / dt)
         sclk = ops.sclk_mhz()
-        for name in ("f16", "q8_0"):
+        for name in eng:
             print("prompt %6d  kv_cache=%-5s %8.1f tok/s  (runs %s; prompt pass %.2f s; bytes/token %.3f GB)"
                   % (n_prompt, name, float(np.median(runs[name])), " / ".join("%.1f" % x for x in runs[name]), row[name + "_prefill_s"],
-                     (f if name == "f16" else q).bytes_per_token(n_prompt) / 1e9), flush=True)
-        print("prompt %6d  q8_0 / f16 = %.3f   sclk right after: %.0f MHz" % (n_prompt, np.median(runs["q8_0"]) / np.median(runs["f16"]), sclk), flush=True)
-    print("KV cache resident: f16 %.2f GB, q8_0 %.2f GB (incl. the one-layer F16 image)" % (f.kv_cache_bytes() / 1e9, q.kv_cache_bytes() / 1e9))
-    q.close(); f.close()
+                     eng[name].bytes_per_token(n_prompt) / 1e9), flush=True)
+        print("prompt %6d  %s   sclk right after: %.0f MHz"
+              % (n_prompt, "  ".join("%s / f16 = %.3f" % (k, np.median(runs[k]) / np.median(runs["f16"])) for k in kinds), sclk), flush=True)
+    print("KV cache resident: " + ", ".join("%s %.2f GB" % (k, e.kv_cache_bytes() / 1e9) for k, e in eng.items()) + " (8-bit: incl. the one-layer F16 image)")
+    close(eng)
 
 
 def massive_path():
@@ -79,39 +90,46 @@ def massive_path():
     return path
 
 
-def quality():
+def quality(kinds):
     models = [("8B Q8_0", lambda e, ctx: e.load_synthetic(E.synth_spec("8b", "Q8_0"), ctx)),
               ("8B Q4_K_M", lambda e, ctx: e.load_synthetic(E.synth_spec("8b", "Q4_K_M"), ctx)),
               ("massive activations (8B width, Q4_K_M, 6 layers)", None)]
     r = np.random.default_rng(2)
     prompts = {n: [int(t) for t in r.integers(0, 128000, n)] for n in (64, 1024, 3900)}
-    print("%-50s %7s %12s %12s %10s" % ("model", "prompt", "max d/RMS", "RMS d/RMS", "RMS logit"))
+    print("%-50s %5s %7s %12s %12s %10s" % ("model", "kv", "prompt", "max d/RMS", "RMS d/RMS", "RMS logit"))
     for name, load in models:
         if load is None:
             path = massive_path()
             load = lambda e, ctx, path=path: e.load(path, ctx)
-        f, q = pair(load, 4352)
+        eng = group(load, 4352, kinds)
+        f = eng["f16"]
         for n, toks in prompts.items():
-            a, b = prefill(f, toks).astype(np.float64), prefill(q, toks).astype(np.float64)
+            a = prefill(f, toks).astype(np.float64)
             rms = float(np.sqrt((a * a).mean()))
-            d = (b - a) / rms
-            print("%-50s %7d %12.3e %12.3e %10.3f   argmax %s" % (name, n, float(np.abs(d).max()), float(np.sqrt((d * d).mean())), rms,
-                                                                   "same" if int(np.argmax(a)) == int(np.argmax(b)) else "DIFFERENT"), flush=True)
+            for kind in kinds:
+                d = (prefill(eng[kind], toks).astype(np.float64) - a) / rms
+                print("%-50s %5s %7d %12.3e %12.3e %10.3f   argmax %s" % (name, kind, n, float(np.abs(d).max()), float(np.sqrt((d * d).mean())), rms,
+                                                                          "same" if int(np.argmax(a)) == int(np.argmax(a + d * rms)) else "DIFFERENT"), flush=True)
         toks = prompts[1024]
-        first_tok = int(np.argmax(prefill(f, toks)))   # the same first token for both: only the caches differ
+        first_tok = int(np.argmax(prefill(f, toks)))   # the same first token for all: only the caches differ
         ta = f.decode_greedy_steps(first_tok, 1024, 256)
-        prefill(q, toks)
-        tb = q.decode_greedy_steps(first_tok, 1024, 256)
-        same = [x == y for x, y in zip(ta, tb)]
-        first = same.index(False) if False in same else 256
-        print("%-50s greedy streams behind 1024 tokens: %d of 256 equal, first difference at step %s" % (name, sum(same), first if first < 256 else "none"), flush=True)
-        q.close(); f.close()
+        for kind in kinds:
+            prefill(eng[kind], toks)
+            tb = eng[kind].decode_greedy_steps(first_tok, 1024, 256)
+            same = [x == y for x, y in zip(ta, tb)]
+            first = same.index(False) if False in same else 256
+            print("%-50s %5s greedy streams behind 1024 tokens: %d of 256 equal, first difference at step %s"
+                  % (name, kind, sum(same), first if first < 256 else "none"), flush=True)
+        close(eng)
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=("speed", "quality"))
     ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--kv", default="q8_0", help="the 8-bit format(s) compared with f16: q8_0, fp8 or q8_0,fp8")
     a = ap.parse_args()
+    kinds = a.kv.split(",")
+    assert kinds and all(k in ("q8_0", "fp8") for k in kinds), "--kv takes q8_0, fp8 or q8_0,fp8"
     ops.init(0)
-    speed(a.steps) if a.what == "speed" else quality()
+    speed(a.steps, kinds) if a.what == "speed" else quality(kinds)
