@@ -118,7 +118,9 @@ int ntk_masked_softmax(float* output, const float* input, const uint8_t* mask, i
  * Limits (NTK_E_SHAPE beyond them; the Llama-3.1 8B / 70B shapes are far inside): in_features <= 32768 for the quantised
  * dtypes (8 column slices of 4096), out_features * row_bytes < 4 GiB per matrix (32-bit byte offsets inside a launch).
  * The quantised kernels fetch W in aligned 16-byte pieces: the piece holding the first / last byte of the matrix is read
- * whole (up to 15 bytes either side, inside the same 16-byte line -- never another page); those bytes are not used. */
+ * whole (up to 15 bytes either side, inside the same 16-byte line -- never another page); those bytes are not used.
+ * NTK_DT_Q2_K: NTK_E_DTYPE, as the reference's launcher (a KV-cache type name there, no GEMV); its decoders are reached
+ * through ntk_gemv_fused / ntk_gemv_rp / ntk_gemm_quant / ntk_embed_rows (ntk_engine.h). */
 int ntk_gemv(float* y, const void* W, const float* x, int out_features, int in_features, int weight_dtype,
              void* stream);
 /* launch_gemv_add, kernels.h:40-42 / gemm.cu:846-871.  y += W . x, F16 weights only. */

@@ -44,7 +44,7 @@ typedef struct ntk_gemv_seg {
     float*      y;      /* output [rows]                            */
     int         rows;
     int         dtype;  /* one format per call, or two for the plain (no resid / SiLU) form: Q4_K with Q6_K or Q5_K, Q3_K with Q4_K or Q5_K,
-                           IQ4_XS with Q4_K or Q5_K (repacked form only);
+                           IQ4_XS with Q4_K or Q5_K (repacked form only), Q2_K with Q4_K or Q3_K (repacked form only);
                            NTK_DT_F16 / NTK_DT_BF16 (unquantised rows of 16-bit words): one of them per call */
 } ntk_gemv_seg;
 
@@ -71,7 +71,8 @@ int ntk_q8l_unpack(void* raw, const void* packed, int rows, int in_features, voi
  * Q6_K, Q3_K (three bits per weight as a 2-bit and a 1-bit plane: 1824 bytes per 16 rows x 256 columns, 1.036 x GGUF); in_features % 256 == 0 and <= 32768; rows padded to tiles of 16 inside the buffer.  Same integers, same scales (ntk_rp_dequant gives
  * the GGUF dequantisation bit for bit), 1.028 x / 1.023 x / 1.000 x the GGUF bytes.  IQ4_XS (w = d (ls - 32) k[idx], k a fixed table of sixteen int8 values: the nibble chunk
  * holds the table indices, the row record eight signed scales -- 2208 bytes per 16 rows x 256 columns, 1.015 x GGUF; no minimum term, so four matrix instructions per item;
- * the indices become table bytes in registers).  Arithmetic: x -> per 256-column super-block three
+ * the indices become table bytes in registers).  Q2_K (w = d sc q - dmin m over sixteen 16-column sub-blocks: the 2-bit plane alone and the sixteen
+ * scale | minimum bytes as they lie -- 1344 bytes per 16 rows x 256 columns, the GGUF size; the minima are the fifth matrix instruction's operand).  Arithmetic: x -> per 256-column super-block three
  * signed base-256 digit planes of rint(x 2^(22-e)) (e = exponent of the block's largest |x|: <= 2^-22 of it per term), exact integer dot
  * products per sub-block on v_mfma_i32_16x16x64_i8, the reference's factorisation (gemm.cu:190-244, 297-354, 421-459) around them.
  *   ntk_rp_bytes        size of the repacked form (0: unsupported dtype / shape)
@@ -83,7 +84,7 @@ size_t ntk_rp_bytes(int dtype, int rows, int in_features);
 int ntk_rp_pack(void* dst, const void* raw, int rows, int in_features, int dtype, void* stream);
 int ntk_rp_dequant(float* out, const void* rp, int rows, int in_features, int dtype, void* stream);
 /* the raw GGUF blocks [rows][in] back from the repacked form, byte for byte (the engine keeps ONE resident copy of a K-quant matrix and unpacks into
- * a scratch in front of the launches that read raw blocks); raw: 4-byte aligned (Q6_K, Q3_K: 2; IQ4_XS: 4); stream ordered */
+ * a scratch in front of the launches that read raw blocks); raw: 4-byte aligned (Q6_K, Q3_K: 2; IQ4_XS, Q2_K: 4); stream ordered */
 int ntk_rp_unpack(void* raw, const void* rp, int rows, int in_features, int dtype, void* stream);
 int ntk_gemv_rp(float* y, const void* rp, const float* x, int out_features, int in_features, int weight_dtype, void* stream);
 int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in_features, const float* norm_w, float eps,
@@ -110,7 +111,7 @@ float* ntk_decode_arena_slot(int slot);
 int ntk_debug_gemv_static_x(void);
 
 /* parity instrumentation of the above: the LDS image its prologue builds from x (4 in + 68 in/256 bytes: three digit planes, a zero plane,
- * 64 bytes of sub-block-sum digits and one 2^(e-22) per super-block; nsub = 8: 32-column sub-blocks (Q4_K / Q5_K), 16: Q6_K / Q3_K), and
+ * 64 bytes of sub-block-sum digits and one 2^(e-22) per super-block; nsub = 8: 32-column sub-blocks (Q4_K / Q5_K), 16: Q6_K / Q3_K / Q2_K), and
  * D[16][16] = A[16][64] . B[64][16] on the matrix instruction under the lane maps the kernel assumes */
 int ntk_debug_rp_prologue(uint8_t* out, const float* x, const float* norm_w, float eps, int in_features, int nsub, int nwaves, void* stream);
 int ntk_debug_mfma_i8_probe(int* D, const int8_t* A, const int8_t* B, void* stream);
@@ -345,7 +346,7 @@ int ntk_gemm_quant(float* Y, const void* W, const float* X, int n_tokens, int ou
  * subnormals as they are, tools/micro/mfma_f16_subnormal.hip); the FP16 x FP16 products are exact in the F32 accumulator, block scales / K-quant
  * minima are applied to the F32 block sums and 1 / s to the finished sum (exact).  Against ntk_gemv the summation order differs and the
  * activations carry that one-ulp rounding.
- * Limits: Q8_0, Q4_0, Q4_K, Q5_K, Q6_K, Q3_K, IQ4_NL and IQ4_XS (NTK_E_DTYPE otherwise: use ntk_gemm_quant), one format per call; in_features a multiple of 128 (Q8_0) /
+ * Limits: Q8_0, Q4_0, Q4_K, Q5_K, Q6_K, Q3_K, IQ4_NL and IQ4_XS (NTK_E_DTYPE otherwise -- Q2_K among them: use ntk_gemm_quant), one format per call; in_features a multiple of 128 (Q8_0) /
  * 256 (the others), rows % 16 == 0 and rows * row_bytes < 4 GiB (NTK_E_SHAPE); W, X, Y, resid 16-byte aligned (NTK_E_ALIGN).
  * (Row pitches that are not a multiple of 4 bytes -- Q8_0 with in_features % 64 != 0, Q6_K / Q3_K with in_features % 512 != 0 -- run the
  * same kernel with 2-byte aligned LDS reads, several times slower; no projection of the target models has one.)

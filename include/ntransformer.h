@@ -58,7 +58,7 @@ typedef struct nt_synth_spec { /* seeded synthetic Llama-shaped model (no checkp
     int hidden, inter, layers, heads, kv_heads, vocab, ctx;
     float eps, theta;
     int bos, eos;
-    const char* mix;           /* "Q8_0" "Q4_0" "Q4_K" "Q5_K" "Q6_K" "Q3_K" "IQ4_NL" "IQ4_XS" (plain, or as a file mix after a shape) "F16" "F32" "Q4_K_M" "Q3_K_M" */
+    const char* mix;           /* "Q8_0" "Q4_0" "Q4_K" "Q5_K" "Q6_K" "Q3_K" "IQ4_NL" "IQ4_XS" (plain, or as a file mix after a shape) "F16" "F32" "Q2_K" "Q4_K_M" "Q3_K_M" "Q2_K_MIX" */
     uint64_t seed;
 } nt_synth_spec;
 

@@ -43,7 +43,7 @@ static void usage(const char* prog) {
             "  --rope-freq-scale <float> RoPE linear position scale, overriding the model's\n"
             "  --context-shift          At the end of the context drop half of the oldest positions and go on (default: stop there)\n"
             "  --keep <int>             Leading positions a context shift never drops (default: 1, the BOS)\n"
-            "  --synthetic <shape:mix>  8b|70b|tiny|qwen2.5-7b|qwen3-8b|qwen3-4b|qwen3-30b-a3b|mixtral-8x7b : Q8_0|Q4_K_M|Q3_K_M|IQ4_XS|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
+            "  --synthetic <shape:mix>  8b|70b|tiny|qwen2.5-7b|qwen3-8b|qwen3-4b|qwen3-30b-a3b|mixtral-8x7b : Q8_0|Q4_K_M|Q3_K_M|Q2_K_MIX|IQ4_XS|Q6_K|F16|BF16|...  seeded synthetic weights, no file\n"
             "Accepted for CLI compatibility, no effect on the output (weights are always resident in 288 GB HBM;\n"
             "speculative decoding only changes speed, and plain decode is what runs):\n"
             "  --streaming --draft-model <p> --draft-k <n> --self-spec\n"

@@ -140,6 +140,12 @@ __device__ float embed_elem(const uint8_t* __restrict__ table, int tok, int hidd
             const int j = e & 31;
             return __fmul_rn(d, (float)iq4_value(j < 16 ? (b[2 + j] & 0x0F) : (b[2 + j - 16] >> 4)));
         }
+        case NTK_DT_Q2_K: {   // ggml block_q2_K (in the reference a name only): w = (d sc) q - dmin m
+            const uint8_t* b = table + ((size_t)tok * (hidden / 256) + e / 256) * 84;
+            const int w = e & 255, sm = b[w >> 4], q = (b[16 + 32 * (w >> 7) + (w & 31)] >> (2 * ((w >> 5) & 3))) & 3;
+            const float d = h2f((uint16_t)(b[80] | (b[81] << 8))), dmin = h2f((uint16_t)(b[82] | (b[83] << 8)));
+            return __fsub_rn(__fmul_rn(__fmul_rn(d, (float)(sm & 15)), (float)q), __fmul_rn(dmin, (float)(sm >> 4)));
+        }
         case NTK_DT_IQ4_XS: {   // ggml block_iq4_xs (not in the reference): w = (d (ls - 32)) table[idx]
             const uint8_t* b = table + ((size_t)tok * (hidden / 256) + e / 256) * 136;
             const float d = h2f((uint16_t)(b[0] | (b[1] << 8)));
@@ -337,7 +343,7 @@ int ntk_embed_rows(float* out, const void* table, const int* tokens, int n_token
     if (st != NTK_OK) return st;
     switch (dtype) {   // rows were zero-filled for anything the reference host path has no branch for
         case NTK_DT_F32: case NTK_DT_F16: case NTK_DT_BF16: case NTK_DT_Q8_0: case NTK_DT_Q4_0: case NTK_DT_Q4_K: case NTK_DT_Q6_K: case NTK_DT_Q3_K:
-        case NTK_DT_IQ4_NL: case NTK_DT_IQ4_XS: return NTK_OK;
+        case NTK_DT_IQ4_NL: case NTK_DT_IQ4_XS: case NTK_DT_Q2_K: return NTK_OK;
         default: return NTK_E_DTYPE;
     }
 }

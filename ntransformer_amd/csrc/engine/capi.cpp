@@ -61,7 +61,10 @@ int nt_engine_set_option(nt_engine_t e, const char* key, const char* value) {
         if (rc != NTK_OK) E(e)->set_error(E(e)->model().error());
         return rc;
     };
-    if (k == "fused") E(e)->options().fused = on;
+    if (k == "fused") {   // (after the load of a model with Q2_K matrices: 0 is refused, as the load refuses it -- Engine::refuse_unfused_q2_k)
+        if (E(e)->loaded()) { const int rc = E(e)->refuse_unfused_q2_k(on); if (rc != NTK_OK) return rc; }
+        E(e)->options().fused = on;
+    }
     else if (k == "graph") E(e)->options().graph = on;
     else if (k == "batched_prefill") { E(e)->options().batched_prefill = on; E(e)->model().set_batched_prefill(on); }
     else if (k == "device_sampling") E(e)->options().device_sampling = on;

@@ -12,10 +12,18 @@ namespace nt {
 using Clock = std::chrono::high_resolution_clock;
 static float ms_since(Clock::time_point t0) { return std::chrono::duration<float, std::milli>(Clock::now() - t0).count(); }
 
+int Engine::refuse_unfused_q2_k(bool fused) {
+    const std::string name = fused ? std::string() : model_.first_matrix_of(NTK_DT_Q2_K);
+    if (name.empty()) return NTK_OK;
+    err_ = "Unsupported tensor type for " + name + " with option fused = 0: the one-to-one sequence runs the reference's GEMV launcher, which has no Q2_K (the default, fused = 1, runs it)";
+    return NTK_E_DTYPE;
+}
+
 int Engine::load(const std::string& path, int max_context) {
     loaded_ = false;
-    const int st = model_.load(path, max_context);
+    int st = model_.load(path, max_context);
     if (st != NTK_OK) { err_ = model_.error(); return st; }
+    if ((st = refuse_unfused_q2_k(opt_.fused)) != NTK_OK) { model_.unload(); return st; }
     tok_.init(model_.vocab(), model_.config().bos_token_id, model_.config().eos_token_id);   // engine.cpp:21
     loaded_ = true;
     return NTK_OK;
@@ -24,8 +32,9 @@ int Engine::load(const std::string& path, int max_context) {
 int Engine::load_synthetic(const SynthSpec& spec, int max_context) {
     loaded_ = false;
     int nt = opt_.synth_threads > 0 ? opt_.synth_threads : (int)std::thread::hardware_concurrency();
-    const int st = model_.load_synthetic(spec, max_context, nt > 0 ? nt : 8);
+    int st = model_.load_synthetic(spec, max_context, nt > 0 ? nt : 8);
     if (st != NTK_OK) { err_ = model_.error(); return st; }
+    if ((st = refuse_unfused_q2_k(opt_.fused)) != NTK_OK) { model_.unload(); return st; }
     tok_.init(model_.vocab(), model_.config().bos_token_id, model_.config().eos_token_id);
     loaded_ = true;
     return NTK_OK;
@@ -34,8 +43,9 @@ int Engine::load_synthetic(const SynthSpec& spec, int max_context) {
 int Engine::load_shared(Engine& src, int max_context) {
     loaded_ = false;
     if (!src.loaded_) { err_ = "load_shared: the source engine is not loaded"; return NTK_E_NULL; }
-    const int st = model_.share_weights(src.model_, max_context);
+    int st = model_.share_weights(src.model_, max_context);
     if (st != NTK_OK) { err_ = model_.error(); return st; }
+    if ((st = refuse_unfused_q2_k(opt_.fused)) != NTK_OK) { model_.unload(); return st; }
     tok_.init(model_.vocab(), model_.config().bos_token_id, model_.config().eos_token_id);
     loaded_ = true;
     return NTK_OK;

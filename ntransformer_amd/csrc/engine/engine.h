@@ -87,6 +87,9 @@ public:
     const std::string& error() const { return err_; }
     void set_error(const std::string& e) { err_ = e; }
     bool loaded() const { return loaded_; }
+    // Option fused = 0 asks for the reference's one-to-one operator sequence, whose GEMV (ntk_gemv, as the reference's launcher) has no Q2_K: a model with
+    // such a matrix is refused under it where the two meet -- at load, or when the option comes after -- and not at the first token.
+    int refuse_unfused_q2_k(bool fused);   // NTK_E_DTYPE and error() when `fused` is off and the loaded model has one
 
 private:
     int run(std::vector<int>& tokens, const GenerateConfig& cfg, std::string* text, TokenCallback cb, bool print, bool stop_at_eos);

@@ -132,6 +132,14 @@ int Model::set_moe_row(bool on) {
     return NTK_OK;
 }
 
+std::string Model::first_matrix_of(int dtype) const {
+    static const char* const names[7] = {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down"};
+    for (size_t i = 0; i < layers_.size(); ++i)
+        for (size_t k = 0; k < kLayerMatrices.size(); ++k)
+            if ((layers_[i].*kLayerMatrices[k]).nbytes && (layers_[i].*kLayerMatrices[k]).dtype == dtype) return "blk." + std::to_string(i) + "." + names[k] + ".weight";
+    return output_.nbytes && output_.dtype == dtype ? std::string(output_tied_ ? "token_embd.weight" : "output.weight") : std::string();
+}
+
 bool Model::fusable(int dt) const { return is_quant(dt) || (dense_fused_ && is_dense16(dt)); }
 
 int Model::set_repack(int level) {

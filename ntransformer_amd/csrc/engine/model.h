@@ -208,6 +208,9 @@ public:
     const GgufVocab& vocab() const { return vocab_; }
     const std::string& error() const { return err_; }
     uint64_t weight_bytes() const { return weight_bytes_; }
+    // the GGUF name of the first projection matrix (the LM head last) of this dtype, "" if none: who refuses a format by name asks here
+    std::string first_matrix_of(int dtype) const;
+    void unload() { free_all(); }   // everything a load took, back (a load the engine refuses after the model accepted it)
     // algorithmic bytes one decode token must move at position `pos`
     uint64_t bytes_per_token(int pos) const;
     // Prompts (seq_len > 1) project all tokens of a chunk with one pass over each weight matrix (ntk_gemm_quant) instead

@@ -25,7 +25,7 @@ struct PassStatus {
 
 inline bool is_quant(int dt) {
     return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K ||
-           dt == NTK_DT_IQ4_NL || dt == NTK_DT_IQ4_XS;
+           dt == NTK_DT_IQ4_NL || dt == NTK_DT_IQ4_XS || dt == NTK_DT_Q2_K;
 }
 
 // unquantised rows of 16-bit words: the fused decode GEMV (gemv_dense16.hip) and the F32-MFMA prompt GEMM take them beside the quantised formats

@@ -68,7 +68,10 @@ int Model::finish_pass(const char* failed, int rc) {
 }
 
 int Model::gemv_logged(float* y, const DevTensor& w, const void* wp, const float* x) {
-    const int st = ntk_gemv(y, wp, x, (int)w.out_f, (int)w.in_f, w.dtype, stream_);
+    // (Q2_K: the reference's operator surface refuses it, ntk_gemv with it; a row of the per-token loop goes through the fused entry point's raw-block decoder)
+    const ntk_gemv_seg seg{wp, y, (int)w.out_f, w.dtype};
+    const int st = w.dtype == NTK_DT_Q2_K ? ntk_gemv_fused(&seg, 1, x, (int)w.in_f, nullptr, 0.0f, nullptr, 0, stream_)
+                                          : ntk_gemv(y, wp, x, (int)w.out_f, (int)w.in_f, w.dtype, stream_);
     if (st == NTK_E_DTYPE) fprintf(stderr, "Unsupported dtype for GEMV: %s\n", dtype_name(w.dtype));   // gemm.cu:801-803
     return st;
 }

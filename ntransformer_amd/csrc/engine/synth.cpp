@@ -47,6 +47,7 @@ BlockInfo block_of(int gt) {
         case 1: return {1, 2};
         case 2: return {32, 18};
         case 8: return {32, 34};
+        case 10: return {256, 84};
         case 11: return {256, 110};
         case 12: return {256, 144};
         case 13: return {256, 176};
@@ -99,6 +100,13 @@ void fill_unit(uint8_t* dst, int gt, uint64_t key, uint64_t unit, double tgt) {
             put16(dst + 108, f2h((float)(tgt / (2.35 * 18.5) * jit)));
             break;
         }
+        case 10: {  // Q2_K: scales[16] (scale | minimum << 4), qs[64], d, dmin; dmin = 1.5 d centres d sc q - dmin m, whose deviation is then 13.87 d
+            fill_random(dst, 80, st);
+            const double d = tgt / 13.87 * jit;
+            put16(dst + 80, f2h((float)d));
+            put16(dst + 82, f2h((float)(1.5 * d)));
+            break;
+        }
         case 20: {  // IQ4_NL: d, qs[16] of table indices; RMS of the sixteen table values 67.4
             fill_random(dst + 2, 16, st);
             put16(dst, f2h((float)(tgt / 67.4 * jit)));
@@ -136,6 +144,7 @@ int mix_type(const std::string& mix) {
     if (mix == "Q5_K") return 13;
     if (mix == "Q6_K") return 14;
     if (mix == "Q3_K" || mix == "Q3_K_M") return 11;
+    if (mix == "Q2_K" || mix == "Q2_K_MIX") return 10;
     if (mix == "IQ4_NL") return 20;
     if (mix == "IQ4_XS") return 23;
     if (mix == "F16") return 1;
@@ -213,6 +222,10 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     // IQ4_XS: the file mix of that name, llama.cpp's rule as remembered (its source is not at hand; gguf.py tensor_types states the same): attn_v and the
     // first eighth of the ffn_down layers on Q5_K, a Q6_K LM head, IQ4_XS everywhere else (the embedding too).  IQ4_NL is plain: every matrix of the type.
     const bool xs = fl.mix == "IQ4_XS";
+    // Q2_K_MIX: the tensor types of llama.cpp's Q2_K file type as remembered (its source is not at hand; gguf.py tensor_types states the same): attn_v on
+    // Q4_K with four or more query heads per KV head, else Q3_K; attn_output and ffn_down on Q3_K; a Q6_K LM head; Q2_K everywhere else (the embedding
+    // too).  Plain Q2_K: every matrix of the type, and the Q6_K LM head.
+    const bool k2m = fl.mix == "Q2_K_MIX";
     const int base = km ? 12 : mix_type(fl.mix);
     if (base < 0 || s.heads <= 0 || s.kv_heads <= 0 || (fl.head_dim ? fl.head_dim < 0 || (fl.head_dim & 1) : s.hidden % s.heads)) return false;
     if (fl.experts && (fl.experts < 1 || fl.experts > 256 || fl.used < 1 || fl.used > std::min(fl.experts, 16) || fl.expert_inter < 0)) return false;
@@ -228,8 +241,8 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
     for (int i = 0; i < s.layers; ++i) {
         const std::string p = "blk." + std::to_string(i) + ".";
         const bool more = km && (sample_of > 0 ? use_more_bits(sample[i], sample_of) : use_more_bits(i, s.layers));
-        const int v_t = xs ? 13 : k3m ? (i < 2 ? 13 : 12) : more ? 14 : (km && s.heads / s.kv_heads >= 4 && s.hidden >= 8192 ? 13 : base);
-        const int down_t = xs ? (i < s.layers / 8 ? 13 : base) : k3m ? (i < s.layers / 16 ? 13 : use_more_bits(i, s.layers) ? 12 : 11) : more ? 14 : base;
+        const int v_t = k2m ? (s.heads / s.kv_heads >= 4 ? 12 : 11) : xs ? 13 : k3m ? (i < 2 ? 13 : 12) : more ? 14 : (km && s.heads / s.kv_heads >= 4 && s.hidden >= 8192 ? 13 : base);
+        const int down_t = k2m ? 11 : xs ? (i < s.layers / 8 ? 13 : base) : k3m ? (i < s.layers / 16 ? 13 : use_more_bits(i, s.layers) ? 12 : 11) : more ? 14 : base;
         add(p + "attn_norm.weight", 0, s.hidden, 1, 0);
         add(p + "attn_q.weight", base, s.hidden, q_dim, 1);
         add(p + "attn_k.weight", base, s.hidden, kv_dim, 1);
@@ -243,7 +256,7 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
             add(p + "attn_q_norm.weight", 0, hd, 1, -0.5);
             add(p + "attn_k_norm.weight", 0, hd, 1, -0.5);
         }
-        add(p + "attn_output.weight", k3m ? 12 : base, q_dim, s.hidden, 1);
+        add(p + "attn_output.weight", k3m ? 12 : k2m ? 11 : base, q_dim, s.hidden, 1);
         add(p + "ffn_norm.weight", 0, s.hidden, 1, 0);
         if (fl.experts) {   // the routed FFN: the router and the experts' matrices, expert after expert in one tensor each
             add(p + "ffn_gate_inp.weight", 0, s.hidden, fl.experts, 2.0);
@@ -257,7 +270,7 @@ bool synth_plan(const SynthSpec& s, std::vector<SynthTensor>& out) {
         add(p + "ffn_down.weight", down_t, s.inter, s.hidden, 1);
     }
     add("output_norm.weight", 0, s.hidden, 1, 0);
-    if (!fl.tied) add("output.weight", km || base == 11 || xs ? 14 : base, s.hidden, s.vocab, 2.0);
+    if (!fl.tied) add("output.weight", km || base == 11 || base == 10 || xs ? 14 : base, s.hidden, s.vocab, 2.0);
     return true;
 }
 

@@ -24,7 +24,7 @@ struct SynthSpec {
     int ctx = 131072;
     float eps = 1e-5f, theta = 500000.0f;
     int bos = 128000, eos = 128009;
-    std::string mix = "Q8_0";   // Q8_0 | Q4_0 | Q4_K | Q5_K | Q6_K | Q3_K | IQ4_NL | IQ4_XS | F16 | F32 | Q4_K_M | Q3_K_M, optionally behind a flavour prefix (synth_flavour)
+    std::string mix = "Q8_0";   // Q8_0 | Q4_0 | Q4_K | Q5_K | Q6_K | Q3_K | Q2_K | IQ4_NL | IQ4_XS | F16 | F32 | Q4_K_M | Q3_K_M | Q2_K_MIX, optionally behind a flavour prefix (synth_flavour)
     uint64_t seed = 20260925;
 };
 

@@ -18,6 +18,7 @@ template <> struct GFmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, 
 template <> struct GFmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, SB = 176; };
 template <> struct GFmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, SB = 210; };
 template <> struct GFmt<NTK_DT_Q3_K> { static constexpr int BW = 256, BB = 110, SB = 110; };
+template <> struct GFmt<NTK_DT_Q2_K> { static constexpr int BW = 256, BB = 84, SB = 84; };
 template <> struct GFmt<NTK_DT_IQ4_NL> { static constexpr int BW = 32, BB = 18, SB = 144; };
 template <> struct GFmt<NTK_DT_IQ4_XS> { static constexpr int BW = 256, BB = 136, SB = 136; };
 // Unquantised 16-bit rows (IEEE half, bfloat16): a "block" is 32 consecutive weights in 64 bytes, no scale.  A chunk of a row is then 8 KiB, and
@@ -127,6 +128,21 @@ template <> struct Deq<NTK_DT_Q6_K> {   // gemm.cu:421-459: sub-block s = 4 half
                       ((q[1] >> sh) & 0x0F0F0F0Fu) | (((h[1] >> (2 * ty)) & 0x03030303u) << 4), n);
 #pragma unroll
         for (int j = 0; j < 8; ++j) a[j] = sc * (n[j] - 32.0f);
+    }
+};
+
+template <> struct Deq<NTK_DT_Q2_K> {   // ggml block_q2_K (in the reference a name only): sub-block s = 4 n + j; w = d (sc[2 s + l/16] & 15) q - dmin (sc[2 s + l/16] >> 4)
+    __device__ static void run(const uint8_t* st, int shift, int s, int g, float (&a)[8]) {
+        uint32_t q[2], dd[1];
+        lds_read_dwords<2>(q, st, shift + 16 + 32 * (s >> 2) + 8 * g);
+        lds_read_dwords<1>(dd, st, shift + 80);
+        const uint32_t sm = st[shift + 2 * s + (g >> 1)];
+        const float dsc = h2f((uint16_t)(dd[0] & 0xFFFFu)) * (float)(sm & 15u), dmn = h2f((uint16_t)(dd[0] >> 16)) * (float)(sm >> 4);
+        const int sh = 2 * (s & 3);
+        float n[8];
+        bytes8_to_f32((q[0] >> sh) & 0x03030303u, (q[1] >> sh) & 0x03030303u, n);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = fmaf(dsc, n[j], -dmn);
     }
 };
 

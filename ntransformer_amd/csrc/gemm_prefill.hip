@@ -262,6 +262,7 @@ extern "C" int ntk_gemm_quant(float* Y, const void* W, const float* X, int n_tok
             case NTK_DT_Q5_K: rc = ntk::launch_gemm<NTK_DT_Q5_K>(y, W, x, T, out_features, in_features, rs, st); break;
             case NTK_DT_Q6_K: rc = ntk::launch_gemm<NTK_DT_Q6_K>(y, W, x, T, out_features, in_features, rs, st); break;
             case NTK_DT_Q3_K: rc = ntk::launch_gemm<NTK_DT_Q3_K>(y, W, x, T, out_features, in_features, rs, st); break;
+            case NTK_DT_Q2_K: rc = ntk::launch_gemm<NTK_DT_Q2_K>(y, W, x, T, out_features, in_features, rs, st); break;
             case NTK_DT_IQ4_NL: rc = ntk::launch_gemm<NTK_DT_IQ4_NL>(y, W, x, T, out_features, in_features, rs, st); break;
             case NTK_DT_IQ4_XS: rc = ntk::launch_gemm<NTK_DT_IQ4_XS>(y, W, x, T, out_features, in_features, rs, st); break;
             case NTK_DT_F16: rc = ntk::launch_gemm<NTK_DT_F16>(y, W, x, T, out_features, in_features, rs, st); break;

@@ -751,7 +751,7 @@ __global__ __launch_bounds__(256) void gemv_dense_kernel(float* __restrict__ y, 
 // ------------------------------------------------------------------------------------------------
 static bool is_quant(int dt) {
     return dt == NTK_DT_Q8_0 || dt == NTK_DT_Q4_0 || dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K ||
-           dt == NTK_DT_IQ4_NL || dt == NTK_DT_IQ4_XS;
+           dt == NTK_DT_IQ4_NL || dt == NTK_DT_IQ4_XS || dt == NTK_DT_Q2_K;
 }
 
 struct GemvLaunch {
@@ -1043,6 +1043,7 @@ static int dispatch_quant(int dt, const ntk_gemv_seg* segs, int nseg, const floa
         case NTK_DT_Q5_K: return launch_quant<NTK_DT_Q5_K>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
         case NTK_DT_Q6_K: return launch_quant<NTK_DT_Q6_K>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st, xi_mode);
         case NTK_DT_Q3_K: return launch_quant<NTK_DT_Q3_K>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
+        case NTK_DT_Q2_K: return launch_quant<NTK_DT_Q2_K>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
         case NTK_DT_IQ4_NL: return launch_quant<NTK_DT_IQ4_NL>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
         case NTK_DT_IQ4_XS: return launch_quant<NTK_DT_IQ4_XS>(segs, nseg, x, in, norm_w, eps, resid, silu_pair, st);
         default: return NTK_E_DTYPE;
@@ -1102,7 +1103,8 @@ int ntk_gemv(float* y, const void* W, const float* x, int out_features, int in_f
     hipStream_t st = ntk::resolve_stream(stream);
     if (weight_dtype == NTK_DT_F32 || weight_dtype == NTK_DT_F16 || weight_dtype == NTK_DT_BF16)
         return ntk::launch_dense<false>(y, W, x, out_features, in_features, weight_dtype, st);
-    if (!ntk::is_quant(weight_dtype)) return NTK_E_DTYPE;
+    // (Q2_K has a decoder in the fused entry points below, but this is the reference's operator surface, whose launcher refuses the type: gemm.cu:801-803)
+    if (!ntk::is_quant(weight_dtype) || weight_dtype == NTK_DT_Q2_K) return NTK_E_DTYPE;
     ntk_gemv_seg seg{W, y, out_features, weight_dtype};
     return ntk::dispatch_quant(weight_dtype, &seg, 1, x, in_features, nullptr, 0.0f, nullptr, 0, st);
 }

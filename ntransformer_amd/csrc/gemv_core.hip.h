@@ -41,6 +41,7 @@ template <> struct Fmt<NTK_DT_Q4_K> { static constexpr int BW = 256, BB = 144, N
 template <> struct Fmt<NTK_DT_Q5_K> { static constexpr int BW = 256, BB = 176, NL = 3, MINW = 4; };
 template <> struct Fmt<NTK_DT_Q6_K> { static constexpr int BW = 256, BB = 210, NL = 4, MINW = 4; };
 template <> struct Fmt<NTK_DT_Q3_K> { static constexpr int BW = 256, BB = 110, NL = 2, MINW = 4; };   // 16 blocks of 110 bytes + 15: two chunks
+template <> struct Fmt<NTK_DT_Q2_K> { static constexpr int BW = 256, BB = 84, NL = 2, MINW = 4; };    // 16 blocks of 84 bytes + 15: two chunks
 template <> struct Fmt<NTK_DT_IQ4_NL> { static constexpr int BW = 32, BB = 18, NL = 3, MINW = 4; };    // Q4_0's geometry
 template <> struct Fmt<NTK_DT_IQ4_XS> { static constexpr int BW = 256, BB = 136, NL = 3, MINW = 4; };  // 16 blocks of 136 bytes + 15: three chunks
 // (Round 3 also built the row stream of gemv.hip on an LDS-DMA ring -- two or three row slices in flight per wave instead of one -- and measured
@@ -462,6 +463,45 @@ template <bool A16> struct Dot<NTK_DT_Q3_K, A16> {
         bs = fmaf(ub2f(sc, 2) - 32.0f, fmaf(-4.0f, sx16[2], S[2]), bs);
         bs = fmaf(ub2f(sc, 3) - 32.0f, fmaf(-4.0f, sx16[3], S[3]), bs);
         return d * bs;
+    }
+};
+
+// Q2_K (ggml block_q2_K: scales[16] qs[64] d dmin, 84 bytes: rows are 4-byte aligned at every width; in the reference only a KV-cache type name).  lane =
+// (block, c) as Dot<Q3_K>: the lane's two 32-column groups are bit pairs 4 (c & 1) and 4 (c & 1) + 2 of the 32 qs bytes of half c >> 1, its four 16-column runs
+// are sub-blocks 4 c .. 4 c + 3 -- ONE dword of the scale bytes, low nibbles the scales, high nibbles the minima.  w = d sc q - dmin m: the minima leave through
+// sx16, as Q4_K's through sx32.
+template <bool A16> struct Dot<NTK_DT_Q2_K, A16> {
+    __device__ static float run(const uint8_t* st, int shift, int lane, int ncols, const f32x2 (&x2)[32],
+                                const float (&sx16)[4], const float (&)[2]) {
+        if (ncols <= 0) return 0.0f;
+        const int c = lane & 3, ob = shift + 84 * (lane >> 2);
+        uint32_t a[1], dd[1];
+        lds_read_dwords<1>(a, st, ob + 4 * c);
+        lds_read_dwords<1>(dd, st, ob + 80);
+        const float d = h2f((uint16_t)(dd[0] & 0xFFFFu)), dmin = h2f((uint16_t)(dd[0] >> 16));
+        const uint32_t sc = a[0] & 0x0F0F0F0Fu, mn = (a[0] >> 4) & 0x0F0F0F0Fu;
+        float S[4];   // [2 group + run]
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {   // the two 16-column runs of each group
+            uint32_t q[4];
+            lds_read_dwords<4>(q, st, ob + 16 + 32 * (c >> 1) + 16 * hh);
+            float l0 = 0.0f, l1 = 0.0f, h0 = 0.0f, h1 = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t qs = q[i] >> (4 * (c & 1));
+                const uint32_t lo = opaque(qs & 0x03030303u), hi = opaque((qs >> 2) & 0x03030303u);
+                const f32x2 xa = x2[8 * hh + 2 * i], xb = x2[8 * hh + 2 * i + 1], xc = x2[16 + 8 * hh + 2 * i], xd = x2[16 + 8 * hh + 2 * i + 1];
+                l0 = fmaf(ub2f(lo, 0), xa.x, l0); l1 = fmaf(ub2f(lo, 1), xa.y, l1); l0 = fmaf(ub2f(lo, 2), xb.x, l0); l1 = fmaf(ub2f(lo, 3), xb.y, l1);
+                h0 = fmaf(ub2f(hi, 0), xc.x, h0); h1 = fmaf(ub2f(hi, 1), xc.y, h1); h0 = fmaf(ub2f(hi, 2), xd.x, h0); h1 = fmaf(ub2f(hi, 3), xd.y, h1);
+            }
+            S[hh] = l0 + l1;
+            S[2 + hh] = h0 + h1;
+        }
+        float bs = ub2f(sc, 0) * S[0], ms = ub2f(mn, 0) * sx16[0];
+        bs = fmaf(ub2f(sc, 1), S[1], bs); ms = fmaf(ub2f(mn, 1), sx16[1], ms);
+        bs = fmaf(ub2f(sc, 2), S[2], bs); ms = fmaf(ub2f(mn, 2), sx16[2], ms);
+        bs = fmaf(ub2f(sc, 3), S[3], bs); ms = fmaf(ub2f(mn, 3), sx16[3], ms);
+        return fmaf(-dmin, ms, d * bs);
     }
 };
 

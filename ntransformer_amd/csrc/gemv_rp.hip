@@ -27,7 +27,11 @@
 //              the eight operand dwords takes its bit with ONE shift (none for h = 0, v = 0) into bit 2 of each byte
 //        IQ4_XS (w = d (ls - 32) table[idx], a fixed table of sixteen int8 values, no minimum / offset term): Q4_K's nibble chunk holds the table INDICES of
 //              columns c and c + 64; the row record is 8 bytes -- the eight 6-bit scales as int8 already reduced by 32 -- then 16 x d: S2 = 160.
-//   Bytes: Q4_K 2368 per item (GGUF 2304: 1.028 x), Q5_K 2880 (2816: 1.023 x), Q6_K 3360 (3360: 1.000 x), Q3_K 1824 (1760: 1.036 x), IQ4_XS 2208 (2176: 1.015 x).
+//        Q2_K (w = d sc q - dmin m, sixteen 16-column sub-blocks with a 4-bit scale AND a 4-bit minimum each): Q3_K's 2-bit plane alone, 512 bytes per step; the
+//              row record is the block's sixteen scale bytes AS THEY LIE (low nibble sc_j, high nibble m_j, j = column / 16), then 16 x {d, dmin}: S2 = 320 and an
+//              item is the GGUF size to the byte.  Left packed because the kernel loses nothing by it: a lane's scale is a 4-bit field extract where Q6_K's is an
+//              8-bit one, and the minimum operand costs four shift-and-masks per item (widened to int8 records: 256 bytes more per item, 1.19 x, to save those four).
+//   Bytes: Q2_K 1344 per item (GGUF 1344: 1.000 x), Q4_K 2368 per item (GGUF 2304: 1.028 x), Q5_K 2880 (2816: 1.023 x), Q6_K 3360 (3360: 1.000 x), Q3_K 1824 (1760: 1.036 x), IQ4_XS 2208 (2176: 1.015 x).
 //   Rows are padded to whole tiles with zero weights.
 //
 // MFMA roles: first operand (M = 16) = digit planes of x from LDS, entry m = 4 jj + p (sub-block jj of the 64 columns, digit p; p = 3
@@ -36,7 +40,9 @@
 // sums the super-block in integers, and converts once per super-block.  The minimum / offset term is one more MFMA per super-block:
 // the row's m[8] (sc[16]) against the digits of the sub-block sums of X.  IQ4_XS has no such term: four MFMAs per item, whose B operands are the table's
 // int8 values themselves -- the index nibbles go through a 16-entry table held in four register dwords (iq4_lookup4, common.hip.h; 13 vector instructions
-// per 8 weights where Q4_K's masks are 3: DESIGN 3.1).
+// per 8 weights where Q4_K's masks are 3: DESIGN 3.1).  Q2_K's minimum term rides on the instruction form of Q6_K's offset term -- the fifth MFMA with sixteen
+// k-slots, here the row's sixteen minimum nibbles against the digits of the sixteen sub-block sums, under dmin instead of 32 d; its weights are unsigned, so there
+// is no constant offset beside it.  A shift and a mask per four weights, less the two shifts by zero per step: 3.5 vector instructions per 8 weights.
 #include "common.hip.h"
 #include <algorithm>
 #include <cstdio>
@@ -55,15 +61,20 @@ template <> struct Rp<NTK_DT_Q4_K> { static constexpr int S1 = 1024, S2 = 320, B
 template <> struct Rp<NTK_DT_Q5_K> { static constexpr int S1 = 1280, S2 = 320, BB = 176, NSUB = 8, REC = 16; static constexpr bool MIN = true; };
 template <> struct Rp<NTK_DT_Q6_K> { static constexpr int S1 = 1536, S2 = 288, BB = 210, NSUB = 16, REC = 16; static constexpr bool MIN = true; };
 template <> struct Rp<NTK_DT_Q3_K> { static constexpr int S1 = 768, S2 = 288, BB = 110, NSUB = 16, REC = 16; static constexpr bool MIN = true; };
+template <> struct Rp<NTK_DT_Q2_K> { static constexpr int S1 = 512, S2 = 320, BB = 84, NSUB = 16, REC = 16; static constexpr bool MIN = true; };
 template <> struct Rp<NTK_DT_IQ4_XS> { static constexpr int S1 = 1024, S2 = 160, BB = 136, NSUB = 8, REC = 8; static constexpr bool MIN = false; };
 // (the format exists for its bytes: the repack may cost 4 % over the GGUF blocks of a whole tile, no more)
 static_assert(25 * (2 * Rp<NTK_DT_Q3_K>::S1 + Rp<NTK_DT_Q3_K>::S2) <= 26 * 16 * Rp<NTK_DT_Q3_K>::BB, "Q3_K repack: at most 1.04 x the GGUF bytes");
 static_assert(25 * (2 * Rp<NTK_DT_IQ4_XS>::S1 + Rp<NTK_DT_IQ4_XS>::S2) <= 26 * 16 * Rp<NTK_DT_IQ4_XS>::BB, "IQ4_XS repack: at most 1.04 x the GGUF bytes");
+static_assert(25 * (2 * Rp<NTK_DT_Q2_K>::S1 + Rp<NTK_DT_Q2_K>::S2) <= 26 * 16 * Rp<NTK_DT_Q2_K>::BB, "Q2_K repack: at most 1.04 x the GGUF bytes");
+// formats whose records end in 16 x {d, dmin} (the others: 16 x d); formats whose step is the 2-bit plane and no nibble chunk
+template <int DT> constexpr bool RP_DMIN = DT == NTK_DT_Q4_K || DT == NTK_DT_Q5_K || DT == NTK_DT_Q2_K;
+template <int DT> constexpr bool RP_PLANE2 = DT == NTK_DT_Q3_K || DT == NTK_DT_Q2_K;
 // bit of the Q3_K third-bit plane that holds (half h, dword v) of byte y's column
 __host__ __device__ constexpr int q3_hpos(int h, int v) { return h ? ((6 + v) & 7) : 2 + v; }
 
-static bool rp_supported(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K || dt == NTK_DT_IQ4_XS; }
-static size_t rp_s1(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_IQ4_XS ? 1024 : dt == NTK_DT_Q5_K ? 1280 : dt == NTK_DT_Q3_K ? 768 : 1536; }
+static bool rp_supported(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_Q5_K || dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K || dt == NTK_DT_IQ4_XS || dt == NTK_DT_Q2_K; }
+static size_t rp_s1(int dt) { return dt == NTK_DT_Q4_K || dt == NTK_DT_IQ4_XS ? 1024 : dt == NTK_DT_Q5_K ? 1280 : dt == NTK_DT_Q3_K ? 768 : dt == NTK_DT_Q2_K ? 512 : 1536; }
 static size_t rp_s2(int dt) { return dt == NTK_DT_IQ4_XS ? 160 : dt == NTK_DT_Q6_K || dt == NTK_DT_Q3_K ? 288 : 320; }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -80,6 +91,8 @@ template <int DT> __device__ __forceinline__ int raw_q(const uint8_t* blk, int c
     } else if constexpr (DT == NTK_DT_Q3_K) {   // ggml block_q3_K: hmask[32] qs[64] scales[12] d
         const int n = cc >> 7, j = (cc >> 5) & 3, l = cc & 31;
         return ((blk[32 + 32 * n + l] >> (2 * j)) & 3) | (((blk[l] >> (4 * n + j)) & 1) << 2);
+    } else if constexpr (DT == NTK_DT_Q2_K) {   // ggml block_q2_K: scales[16] qs[64] d dmin
+        return (blk[16 + 32 * (cc >> 7) + (cc & 31)] >> (2 * ((cc >> 5) & 3))) & 3;
     } else if constexpr (DT == NTK_DT_IQ4_XS) {   // ggml block_iq4_xs: d scales_h scales_l[4] qs[128]; the table INDEX, Q4_0's nibble order per 32 columns
         const int by = blk[8 + 16 * (cc >> 5) + (cc & 15)];
         return (cc & 16) ? (by >> 4) : (by & 15);
@@ -113,15 +126,15 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
             const int v = b >> 2, y = b & 3;
             if constexpr (DT == NTK_DT_Q5_K) hb |= (uint32_t)((q0 >> 4) & 1) << (8 * y + v) | (uint32_t)((q1 >> 4) & 1) << (8 * y + 4 + v);
             if constexpr (DT == NTK_DT_Q6_K) { hh[0] |= (uint32_t)((q0 >> 4) & 3) << (8 * y + 2 * v); hh[1] |= (uint32_t)((q1 >> 4) & 3) << (8 * y + 2 * v); }
+            if constexpr (RP_PLANE2<DT>) { hh[0] |= (uint32_t)(q0 & 3) << (8 * y + 2 * v); hh[1] |= (uint32_t)(q1 & 3) << (8 * y + 2 * v); }
             if constexpr (DT == NTK_DT_Q3_K) {
-                hh[0] |= (uint32_t)(q0 & 3) << (8 * y + 2 * v); hh[1] |= (uint32_t)(q1 & 3) << (8 * y + 2 * v);
                 hb |= (uint32_t)((q0 >> 2) & 1) << (8 * y + q3_hpos(0, v)) | (uint32_t)((q1 >> 2) & 1) << (8 * y + q3_hpos(1, v));
             }
         }
     }
-    if constexpr (DT == NTK_DT_Q3_K) {   // the two bit planes, no nibble chunk
+    if constexpr (RP_PLANE2<DT>) {   // the bit planes (Q2_K: the 2-bit plane alone), no nibble chunk
         *reinterpret_cast<u2*>(p1 + 8 * l) = u2{hh[0], hh[1]};
-        *reinterpret_cast<uint32_t*>(p1 + 512 + 4 * l) = hb;
+        if constexpr (DT == NTK_DT_Q3_K) *reinterpret_cast<uint32_t*>(p1 + 512 + 4 * l) = hb;
     } else {
         *reinterpret_cast<u4*>(p1 + 16 * l) = u4{w[0], w[1], w[2], w[3]};
     }
@@ -140,6 +153,9 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
                 const uint32_t sh = (uint32_t)(b2[2] | (b2[3] << 8));
                 for (int k = 0; k < 8; ++k) rec[k] = (uint8_t)((((b2[4 + (k >> 1)] >> (4 * (k & 1))) & 15) | (((sh >> (2 * k)) & 3) << 4)) - 32);
                 d = (uint16_t)(b2[0] | (b2[1] << 8));
+            } else if constexpr (DT == NTK_DT_Q2_K) {   // the sixteen (scale, minimum) nibble pairs as they lie
+                for (int k = 0; k < 16; ++k) rec[k] = b2[k];
+                d = (uint16_t)(b2[80] | (b2[81] << 8)); dmin = (uint16_t)(b2[82] | (b2[83] << 8));
             } else if constexpr (DT == NTK_DT_Q3_K) {   // the sixteen 6-bit scales as ggml unpacks its 12 bytes, reduced by 32
                 const uint8_t* a = b2 + 96;
                 for (int k = 0; k < 4; ++k) {
@@ -164,7 +180,7 @@ __global__ __launch_bounds__(128) void rp_pack_kernel(uint8_t* __restrict__ dst,
             }
         }
         for (int k = 0; k < F::REC; ++k) p2[F::REC * t + k] = rec[k];
-        if constexpr (F::NSUB == 16 || !F::MIN) *reinterpret_cast<uint16_t*>(p2 + 16 * F::REC + 2 * t) = d;
+        if constexpr (!RP_DMIN<DT>) *reinterpret_cast<uint16_t*>(p2 + 16 * F::REC + 2 * t) = d;
         else *reinterpret_cast<uint32_t*>(p2 + 256 + 4 * t) = (uint32_t)d | ((uint32_t)dmin << 16);
     }
 }
@@ -263,7 +279,7 @@ __global__ __launch_bounds__(256) void rp_unpack_kernel(uint8_t* __restrict__ ra
             *reinterpret_cast<uint32_t*>(row) = (uint32_t)*reinterpret_cast<const uint16_t*>(p2 + 128 + 2 * i) | (sh << 16);
             *reinterpret_cast<uint32_t*>(row + 4) = sl;
         }
-    } else if constexpr (DT == NTK_DT_Q3_K) {   // hmask[32] qs[64] scales[12] d   (ggml block_q3_K)
+    } else if constexpr (RP_PLANE2<DT>) {   // hmask[32] qs[64] scales[12] d   (ggml block_q3_K); scales[16] qs[64] d dmin   (ggml block_q2_K)
         {                                // qs[32 n + 4 w ..+3]: two bits of each of the four 32-column quarters of half n (as Q6_K's qh, from the 2-bit plane)
             const int w = (t >> 4) & 7, n = t >> 7;
             uint32_t v = 0;
@@ -272,29 +288,34 @@ __global__ __launch_bounds__(256) void rp_unpack_kernel(uint8_t* __restrict__ ra
                 const uint32_t src = ld32(p1 + (size_t)n * F::S1 + 8 * (16 * (2 * (j & 1) + (w >> 2)) + i) + 4 * (j >> 1));
                 v |= ((src >> (2 * (w & 3))) & 0x03030303u) << (2 * j);
             }
-            *reinterpret_cast<uint32_t*>(row + 32 + 32 * n + 4 * w) = v;
+            *reinterpret_cast<uint32_t*>(row + (DT == NTK_DT_Q3_K ? 32 : 16) + 32 * n + 4 * w) = v;
         }
-        if (t < 128) {                   // hmask[4 w ..+3]: bit 4 n + j of a byte <- the third-bit plane of step n, the same lanes
-            const int w = t >> 4;
-            uint32_t v = 0;
+        if constexpr (DT == NTK_DT_Q2_K) {   // the sixteen scale bytes and {d, dmin}: the record's dwords
+            if (t < 64) *reinterpret_cast<uint32_t*>(row + 4 * (t >> 4)) = ld32(p2 + 16 * i + 4 * (t >> 4));
+            if (t < 16) *reinterpret_cast<uint32_t*>(row + 80) = ld32(p2 + 256 + 4 * i);
+        } else {
+            if (t < 128) {                   // hmask[4 w ..+3]: bit 4 n + j of a byte <- the third-bit plane of step n, the same lanes
+                const int w = t >> 4;
+                uint32_t v = 0;
 #pragma unroll
-            for (int nj = 0; nj < 8; ++nj) {
-                const int n = nj >> 2, j = nj & 3;
-                const uint32_t src = ld32(p1 + (size_t)n * F::S1 + 512 + 4 * (16 * (2 * (j & 1) + (w >> 2)) + i));
-                v |= ((src >> q3_hpos(j >> 1, w & 3)) & 0x01010101u) << nj;
+                for (int nj = 0; nj < 8; ++nj) {
+                    const int n = nj >> 2, j = nj & 3;
+                    const uint32_t src = ld32(p1 + (size_t)n * F::S1 + 512 + 4 * (16 * (2 * (j & 1) + (w >> 2)) + i));
+                    v |= ((src >> q3_hpos(j >> 1, w & 3)) & 0x01010101u) << nj;
+                }
+                *reinterpret_cast<uint32_t*>(row + 4 * w) = v;
             }
-            *reinterpret_cast<uint32_t*>(row + 4 * w) = v;
+            if (t < 48) {                    // the 12 scale bytes: s - 32 keeps the low six bits of s with bit 5 flipped
+                const uint32_t S0 = (ld32(p2 + 16 * i) ^ 0x20202020u) & 0x3F3F3F3Fu, S1 = (ld32(p2 + 16 * i + 4) ^ 0x20202020u) & 0x3F3F3F3Fu;
+                const uint32_t S2 = (ld32(p2 + 16 * i + 8) ^ 0x20202020u) & 0x3F3F3F3Fu, S3 = (ld32(p2 + 16 * i + 12) ^ 0x20202020u) & 0x3F3F3F3Fu;
+                const int u = t >> 4;
+                const uint32_t a = u == 0 ? (S0 & 0x0F0F0F0Fu) | ((S2 & 0x0F0F0F0Fu) << 4)
+                                 : u == 1 ? (S1 & 0x0F0F0F0Fu) | ((S3 & 0x0F0F0F0Fu) << 4)
+                                          : ((S0 >> 4) & 0x03030303u) | (((S1 >> 4) & 0x03030303u) << 2) | (((S2 >> 4) & 0x03030303u) << 4) | (((S3 >> 4) & 0x03030303u) << 6);
+                *reinterpret_cast<uint32_t*>(row + 96 + 4 * u) = a;
+            }
+            if (t < 16) *reinterpret_cast<uint16_t*>(row + 108) = *reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i);
         }
-        if (t < 48) {                    // the 12 scale bytes: s - 32 keeps the low six bits of s with bit 5 flipped
-            const uint32_t S0 = (ld32(p2 + 16 * i) ^ 0x20202020u) & 0x3F3F3F3Fu, S1 = (ld32(p2 + 16 * i + 4) ^ 0x20202020u) & 0x3F3F3F3Fu;
-            const uint32_t S2 = (ld32(p2 + 16 * i + 8) ^ 0x20202020u) & 0x3F3F3F3Fu, S3 = (ld32(p2 + 16 * i + 12) ^ 0x20202020u) & 0x3F3F3F3Fu;
-            const int u = t >> 4;
-            const uint32_t a = u == 0 ? (S0 & 0x0F0F0F0Fu) | ((S2 & 0x0F0F0F0Fu) << 4)
-                             : u == 1 ? (S1 & 0x0F0F0F0Fu) | ((S3 & 0x0F0F0F0Fu) << 4)
-                                      : ((S0 >> 4) & 0x03030303u) | (((S1 >> 4) & 0x03030303u) << 2) | (((S2 >> 4) & 0x03030303u) << 4) | (((S3 >> 4) & 0x03030303u) << 6);
-            *reinterpret_cast<uint32_t*>(row + 96 + 4 * u) = a;
-        }
-        if (t < 16) *reinterpret_cast<uint16_t*>(row + 108) = *reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i);
     } else if constexpr (DT == NTK_DT_Q6_K) {   // ql[128] qh[64] scales[16] d   (types.h:132-137)
         if (t < 128) {                   // ql[64 s + 16 kg ..]: the lane's 16-byte chunk of step s
             const int kg = (t >> 4) & 3, s = t >> 6;
@@ -370,9 +391,9 @@ __global__ __launch_bounds__(256) void rp_dequant_kernel(float* __restrict__ out
         const uint8_t* p2 = rp + p2_off + item * F::S2;
         const int v = b >> 2, y = b & 3;
         int q;
-        if constexpr (DT == NTK_DT_Q3_K) {
-            q = (int)((*reinterpret_cast<const uint32_t*>(p1 + 8 * l + 4 * h) >> (8 * y + 2 * v)) & 3u) |
-                (int)((*reinterpret_cast<const uint32_t*>(p1 + 512 + 4 * l) >> (8 * y + q3_hpos(h, v))) & 1u) << 2;
+        if constexpr (RP_PLANE2<DT>) {
+            q = (int)((*reinterpret_cast<const uint32_t*>(p1 + 8 * l + 4 * h) >> (8 * y + 2 * v)) & 3u);
+            if constexpr (DT == NTK_DT_Q3_K) q |= (int)((*reinterpret_cast<const uint32_t*>(p1 + 512 + 4 * l) >> (8 * y + q3_hpos(h, v))) & 1u) << 2;
         } else {
             const int by = p1[16 * l + b];
             q = h ? (by >> 4) : (by & 15);
@@ -384,6 +405,9 @@ __global__ __launch_bounds__(256) void rp_dequant_kernel(float* __restrict__ out
             const float d = h2f(*reinterpret_cast<const uint16_t*>(p2 + 128 + 2 * i));
             const float sc = (float)(int)(int8_t)p2[8 * i + (c >> 5)];
             w = __fmul_rn(__fmul_rn(d, sc), (float)iq4_value(q));
+        } else if constexpr (DT == NTK_DT_Q2_K) {   // w = (d sc) q - dmin m
+            const uint32_t dd = *reinterpret_cast<const uint32_t*>(p2 + 256 + 4 * i), sm = p2[16 * i + (c >> 4)];
+            w = __fsub_rn(__fmul_rn(__fmul_rn(h2f((uint16_t)(dd & 0xFFFFu)), (float)(sm & 15u)), (float)q), __fmul_rn(h2f((uint16_t)(dd >> 16)), (float)(sm >> 4)));
         } else if constexpr (DT == NTK_DT_Q3_K) {   // w = (d (s - 32)) (q - 4)
             const float d = h2f(*reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i));
             const float sc = (float)(int)(int8_t)p2[16 * i + (c >> 4)];
@@ -504,7 +528,7 @@ template <int DT> struct RpItem {
     u4 rec;         // the row record
     uint32_t dd;    // d | dmin << 16  (Q6_K: d)
     uint32_t hb0, hb1;   // Q5_K; Q3_K: the third-bit plane
-    u2 hh0, hh1;         // Q6_K; Q3_K: the 2-bit plane (n0 / n1 stay unused); IQ4_XS: hh0 = its 8-byte row record (rec stays unused)
+    u2 hh0, hh1;         // Q6_K; Q3_K, Q2_K: the 2-bit plane (n0 / n1 stay unused); IQ4_XS: hh0 = its 8-byte row record (rec stays unused)
 };
 
 template <int DT, bool NORM>
@@ -561,7 +585,10 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         const unsigned off = (unsigned)tile * (unsigned)nsb + (unsigned)(li - l_v * nsb);
         const uint8_t* p1 = base + (size_t)off * (2 * F::S1);
         const uint8_t* p2 = base + sg.p2_off + (size_t)off * F::S2;
-        if constexpr (DT == NTK_DT_Q3_K) {   // 12 bytes per lane and step: the 2-bit plane, the third-bit plane
+        if constexpr (DT == NTK_DT_Q2_K) {   // 8 bytes per lane and step: the 2-bit plane
+            it.hh0 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p1 + 8 * lane));
+            it.hh1 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p1 + F::S1 + 8 * lane));
+        } else if constexpr (DT == NTK_DT_Q3_K) {   // 12 bytes per lane and step: the 2-bit plane, the third-bit plane
             it.hh0 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p1 + 8 * lane));
             it.hh1 = __builtin_nontemporal_load(reinterpret_cast<const u2*>(p1 + F::S1 + 8 * lane));
             it.hb0 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p1 + 512 + 4 * lane));
@@ -584,7 +611,7 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
             it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p2 + 128 + 2 * i16));
         } else {
         it.rec = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p2 + 16 * i16));
-        if constexpr (NSUB == 16) it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i16));
+        if constexpr (!RP_DMIN<DT>) it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p2 + 256 + 2 * i16));
         else it.dd = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p2 + 256 + 4 * i16));
         }
         l_idx += NW;
@@ -689,8 +716,8 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         v4i b[4];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            u4 raw = {0u, 0u, 0u, 0u};   // the step's nibble chunk (Q3_K has none: its items leave n0 / n1 unloaded)
-            if constexpr (DT != NTK_DT_Q3_K) raw = s ? it.n1 : it.n0;
+            u4 raw = {0u, 0u, 0u, 0u};   // the step's nibble chunk (Q3_K, Q2_K have none: their items leave n0 / n1 unloaded)
+            if constexpr (!RP_PLANE2<DT>) raw = s ? it.n1 : it.n0;
             v4i& b0 = b[2 * s];
             v4i& b1 = b[2 * s + 1];
             if constexpr (DT == NTK_DT_Q4_K) {
@@ -708,6 +735,12 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
                     b0[k] = (int)(((hb << (4 - k)) & 0x10101010u) | (raw[k] & 0x0F0F0F0Fu));
                     b1[k] = (int)(((hb >> k) & 0x10101010u) | ((raw[k] >> 4) & 0x0F0F0F0Fu));
                 }
+            } else if constexpr (DT == NTK_DT_Q2_K) {
+                // 2-bit plane -> int8 operands 0..3: a shift and a mask per dword of four weights, less the two shifts by zero -- 14 vector instructions per
+                // 32 weights (3.5 per 8; Q4_K 3, Q3_K 7.25: DESIGN 3.1)
+                const u2 lo = s ? it.hh1 : it.hh0;         // byte y, bits 2 v .. 2 v + 1
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { b0[k] = (int)((lo[0] >> (2 * k)) & 0x03030303u); b1[k] = (int)((lo[1] >> (2 * k)) & 0x03030303u); }
             } else if constexpr (DT == NTK_DT_Q3_K) {
                 // bit planes -> int8 operands: shift + and for the two low bits, shift + and-or for the third: 4 per dword, less the three shifts by
                 // zero -- 29 vector instructions per 32 weights (7.25 per 8; Q4_K 3, Q6_K 6.5: DESIGN 3.1)
@@ -755,6 +788,9 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         }
         v4i bc;
         if constexpr (NSUB == 8) bc = v4i{kg == 0 ? (int)it.rec[2] : 0, kg == 0 ? (int)it.rec[3] : 0, 0, 0};
+        else if constexpr (DT == NTK_DT_Q2_K)   // the sixteen minimum nibbles as bytes (Q2_K: dmin sum_j m_j sum x over sixteen sub-blocks)
+            bc = v4i{kg == 0 ? (int)((it.rec[0] >> 4) & 0x0F0F0F0Fu) : 0, kg == 0 ? (int)((it.rec[1] >> 4) & 0x0F0F0F0Fu) : 0,
+                     kg == 0 ? (int)((it.rec[2] >> 4) & 0x0F0F0F0Fu) : 0, kg == 0 ? (int)((it.rec[3] >> 4) & 0x0F0F0F0Fu) : 0};
         else bc = v4i{kg == 0 ? (int)it.rec[0] : 0, kg == 0 ? (int)it.rec[1] : 0, kg == 0 ? (int)it.rec[2] : 0, kg == 0 ? (int)it.rec[3] : 0};
         const v4i a0 = *reinterpret_cast<const v4i*>(xa), a1 = *reinterpret_cast<const v4i*>(xa + 64);
         const v4i a2 = *reinterpret_cast<const v4i*>(xa + 128), a3 = *reinterpret_cast<const v4i*>(xa + 192);
@@ -770,6 +806,9 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         if constexpr (NSUB == 8) {   // sub-block 4 s + 2 h + mg: byte 2 h + mg of dword s of the record
             s0 = (int)__builtin_amdgcn_ubfe(it.rec[0], o0, 8u); s1 = (int)__builtin_amdgcn_ubfe(it.rec[0], o1, 8u);
             s2 = (int)__builtin_amdgcn_ubfe(it.rec[1], o0, 8u); s3 = (int)__builtin_amdgcn_ubfe(it.rec[1], o1, 8u);
+        } else if constexpr (DT == NTK_DT_Q2_K) {   // the same byte, its low nibble (unsigned; the high one is the minimum)
+            s0 = (int)__builtin_amdgcn_ubfe(it.rec[0], o0, 4u); s1 = (int)__builtin_amdgcn_ubfe(it.rec[1], o0, 4u);
+            s2 = (int)__builtin_amdgcn_ubfe(it.rec[2], o0, 4u); s3 = (int)__builtin_amdgcn_ubfe(it.rec[3], o0, 4u);
         } else {                     // sub-block 8 s + 4 h + mg: byte mg of dword 2 s + h
             s0 = __builtin_amdgcn_sbfe((int)it.rec[0], o0, 8u); s1 = __builtin_amdgcn_sbfe((int)it.rec[1], o0, 8u);
             s2 = __builtin_amdgcn_sbfe((int)it.rec[2], o0, 8u); s3 = __builtin_amdgcn_sbfe((int)it.rec[3], o0, 8u);
@@ -782,7 +821,7 @@ __device__ __forceinline__ void rp_body(const RpParams& p, const int seg_lo, con
         racc = fmaf(S, d * inv, racc);
         const float corr = fmaf(fmaf(fmaf((float)cc[3], 256.0f, (float)cc[2]), 256.0f, (float)cc[1]), 256.0f, (float)cc[0]);
         float fneg;
-        if constexpr (NSUB == 8) fneg = -h2f((uint16_t)(it.dd >> 16)) * inv; else fneg = (DT == NTK_DT_Q3_K ? -4.0f : -32.0f) * d * inv;
+        if constexpr (RP_DMIN<DT>) fneg = -h2f((uint16_t)(it.dd >> 16)) * inv; else fneg = (DT == NTK_DT_Q3_K ? -4.0f : -32.0f) * d * inv;
         racc = fmaf(corr, fneg, racc);
     };
 
@@ -1043,6 +1082,7 @@ int ntk_rp_pack(void* dst, const void* raw, int rows, int in_features, int dtype
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q5_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q3_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_IQ4_XS) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_IQ4_XS>, g, b, 0, st, d, r, rows, nsb, p2);
+    else if (dtype == NTK_DT_Q2_K) hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q2_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_pack_kernel<NTK_DT_Q6_K>, g, b, 0, st, d, r, rows, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -1063,6 +1103,7 @@ int ntk_rp_unpack(void* raw, const void* rp, int rows, int in_features, int dtyp
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q5_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q3_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else if (dtype == NTK_DT_IQ4_XS) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_IQ4_XS>, g, b, 0, st, d, r, rows, nsb, p2);
+    else if (dtype == NTK_DT_Q2_K) hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q2_K>, g, b, 0, st, d, r, rows, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_unpack_kernel<NTK_DT_Q6_K>, g, b, 0, st, d, r, rows, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -1080,6 +1121,7 @@ int ntk_rp_dequant(float* out, const void* rp, int rows, int in_features, int dt
     else if (dtype == NTK_DT_Q5_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q5_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else if (dtype == NTK_DT_Q3_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q3_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else if (dtype == NTK_DT_IQ4_XS) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_IQ4_XS>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
+    else if (dtype == NTK_DT_Q2_K) hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q2_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     else hipLaunchKernelGGL(ntk::rp_dequant_kernel<NTK_DT_Q6_K>, g, b, 0, st, out, r, rows, in_features, nsb, p2);
     return ntk::last_launch_status();
 }
@@ -1149,6 +1191,7 @@ int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in
     if (dta == dtb) {
         fn = dta == NTK_DT_Q4_K ? rp_fn<NTK_DT_Q4_K, NTK_DT_Q4_K>(nm) : dta == NTK_DT_Q5_K ? rp_fn<NTK_DT_Q5_K, NTK_DT_Q5_K>(nm)
            : dta == NTK_DT_Q3_K ? rp_fn<NTK_DT_Q3_K, NTK_DT_Q3_K>(nm) : dta == NTK_DT_IQ4_XS ? rp_fn<NTK_DT_IQ4_XS, NTK_DT_IQ4_XS>(nm)
+           : dta == NTK_DT_Q2_K ? rp_fn<NTK_DT_Q2_K, NTK_DT_Q2_K>(nm)
            : rp_fn<NTK_DT_Q6_K, NTK_DT_Q6_K>(nm);
     } else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q6_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q6_K>(nm);
     else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q5_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q5_K>(nm);
@@ -1162,6 +1205,10 @@ int ntk_gemv_rp_fused(const ntk_gemv_seg* segs, int nseg, const float* x, int in
     else if (dta == NTK_DT_Q5_K && dtb == NTK_DT_IQ4_XS) fn = rp_fn<NTK_DT_Q5_K, NTK_DT_IQ4_XS>(nm);
     else if (dta == NTK_DT_IQ4_XS && dtb == NTK_DT_Q4_K) fn = rp_fn<NTK_DT_IQ4_XS, NTK_DT_Q4_K>(nm);
     else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_IQ4_XS) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_IQ4_XS>(nm);
+    else if (dta == NTK_DT_Q2_K && dtb == NTK_DT_Q4_K) fn = rp_fn<NTK_DT_Q2_K, NTK_DT_Q4_K>(nm);   // the Q | K | V launches of Q2_K files (attn_v on Q4_K or Q3_K)
+    else if (dta == NTK_DT_Q4_K && dtb == NTK_DT_Q2_K) fn = rp_fn<NTK_DT_Q4_K, NTK_DT_Q2_K>(nm);
+    else if (dta == NTK_DT_Q2_K && dtb == NTK_DT_Q3_K) fn = rp_fn<NTK_DT_Q2_K, NTK_DT_Q3_K>(nm);
+    else if (dta == NTK_DT_Q3_K && dtb == NTK_DT_Q2_K) fn = rp_fn<NTK_DT_Q3_K, NTK_DT_Q2_K>(nm);
     else return NTK_E_DTYPE;
     if (!fn) return NTK_E_LAUNCH;
 #ifdef NTK_TUNE

@@ -33,6 +33,7 @@ T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I6
 GGML_F32, GGML_F16, GGML_Q4_0, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K = 0, 1, 2, 8, 12, 13, 14
 GGML_BF16 = 30   # not in the reference: bfloat16, the format checkpoints are published in
 GGML_Q3_K = 11   # not in the reference: the 3-bit K-quant of llama.cpp's Q3_K_S / _M / _L files
+GGML_Q2_K = 10   # the 2-bit K-quant of llama.cpp's Q2_K files (the reference maps the type and has no kernel for it)
 GGML_IQ4_NL, GGML_IQ4_XS = 20, 23   # not in the reference: the 4-bit formats over a non-linear table of sixteen int8 values
 
 # nt::DType numeric values (types.h:24-35) -- the C ABI contract
@@ -43,18 +44,18 @@ DT_IQ4_NL, DT_IQ4_XS = 11, 12   # NTK_DT_IQ4_NL / NTK_DT_IQ4_XS: likewise
 
 GGML_TO_DT = {GGML_F32: DT_F32, GGML_F16: DT_F16, GGML_Q4_0: DT_Q4_0, GGML_Q8_0: DT_Q8_0,
               GGML_Q4_K: DT_Q4_K, GGML_Q5_K: DT_Q5_K, GGML_Q6_K: DT_Q6_K, GGML_BF16: DT_BF16, GGML_Q3_K: DT_Q3_K,
-              GGML_IQ4_NL: DT_IQ4_NL, GGML_IQ4_XS: DT_IQ4_XS}
+              GGML_IQ4_NL: DT_IQ4_NL, GGML_IQ4_XS: DT_IQ4_XS, GGML_Q2_K: DT_Q2_K}
 DT_TO_GGML = {v: k for k, v in GGML_TO_DT.items()}
 DT_NAME = {DT_F32: "F32", DT_F16: "F16", DT_Q8_0: "Q8_0", DT_Q4_0: "Q4_0", DT_Q4_K: "Q4_K",
-           DT_Q6_K: "Q6_K", DT_Q5_K: "Q5_K", DT_BF16: "BF16", DT_Q3_K: "Q3_K", DT_IQ4_NL: "IQ4_NL", DT_IQ4_XS: "IQ4_XS"}
+           DT_Q6_K: "Q6_K", DT_Q5_K: "Q5_K", DT_BF16: "BF16", DT_Q3_K: "Q3_K", DT_IQ4_NL: "IQ4_NL", DT_IQ4_XS: "IQ4_XS", DT_Q2_K: "Q2_K"}
 NAME_TO_GGML = {"F32": GGML_F32, "F16": GGML_F16, "Q4_0": GGML_Q4_0, "Q8_0": GGML_Q8_0,
                 "Q4_K": GGML_Q4_K, "Q5_K": GGML_Q5_K, "Q6_K": GGML_Q6_K, "BF16": GGML_BF16, "Q3_K": GGML_Q3_K,
-                "IQ4_NL": GGML_IQ4_NL, "IQ4_XS": GGML_IQ4_XS}
+                "IQ4_NL": GGML_IQ4_NL, "IQ4_XS": GGML_IQ4_XS, "Q2_K": GGML_Q2_K}
 
 # (elements per block, bytes per block)
 BLOCK = {GGML_F32: (1, 4), GGML_F16: (1, 2), GGML_Q4_0: (32, 18), GGML_Q8_0: (32, 34),
          GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176), GGML_Q6_K: (256, 210), GGML_BF16: (1, 2), GGML_Q3_K: (256, 110),
-         GGML_IQ4_NL: (32, 18), GGML_IQ4_XS: (256, 136)}
+         GGML_IQ4_NL: (32, 18), GGML_IQ4_XS: (256, 136), GGML_Q2_K: (256, 84)}
 
 # the table of IQ4_NL / IQ4_XS: a 4-bit index selects one of these int8 values (RMS 67.4 over uniform indices)
 IQ4_KVALUES = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], dtype=np.int8)
@@ -311,6 +312,10 @@ def synth_tensor(rng: np.random.Generator, ggml_type: int, out_f: int, in_f: int
     elif ggml_type == GGML_Q3_K:                         # hmask[32] qs[64] scales[12] d: RMS of (q - 4) 2.35, of (s - 32) 18.5
         blk[:, 0:108] = rng.integers(0, 256, (nb, 108), dtype=np.uint8)
         blk[:, 108:110] = _f16_bytes(tgt / (2.35 * 18.5) * jit)
+    elif ggml_type == GGML_Q2_K:                         # scales[16] (scale | minimum << 4) qs[64] d dmin, every field over its full range
+        blk[:, 0:80] = rng.integers(0, 256, (nb, 80), dtype=np.uint8)
+        blk[:, 80:82] = _f16_bytes(tgt / 13.87 * jit)    # dmin = 1.5 d centres d sc q - dmin m (mean sc q = 11.25, mean m = 7.5); its deviation is then 13.87 d
+        blk[:, 82:84] = _f16_bytes(1.5 * tgt / 13.87 * jit)
     elif ggml_type == GGML_IQ4_NL:                       # d qs[16]: RMS of the table values 67.4
         blk[:, 2:18] = rng.integers(0, 256, (nb, 16), dtype=np.uint8)
         blk[:, 0:2] = _f16_bytes(tgt / 67.4 * jit)
@@ -404,6 +409,15 @@ def dequantize(raw: np.ndarray | bytes, ggml_type: int, n: int) -> np.ndarray:
                             (a[:, 0:4] >> 4) | (((hi >> 4) & 3) << 4), (a[:, 4:8] >> 4) | (((hi >> 6) & 3) << 4)], 1) - 32   # [nb, 16]
         w = (d * s.astype(np.float32)).reshape(nb, 2, 4, 2, 1) * q.astype(np.float32).reshape(nb, 2, 4, 2, 16)
         return w.reshape(-1).astype(np.float32)
+    if ggml_type == GGML_Q2_K:
+        # ggml block_q2_K: column 128 n + 32 j + l is bits 2 j of qs[32 n + l]; its sub-block 8 n + 2 j + l // 16 has a 4-bit scale (low nibble of its
+        # scale byte) and a 4-bit minimum (high nibble); w = (d sc) q - dmin m, each product and the difference rounded to float32
+        sm = b[:, 0:16].astype(np.int32)
+        qs = b[:, 16:80].reshape(nb, 2, 1, 32).astype(np.int32)
+        d, dmin = b[:, 80:82].copy().view("<f2").astype(np.float32), b[:, 82:84].copy().view("<f2").astype(np.float32)
+        q = ((qs >> (2 * np.arange(4)[None, None, :, None])) & 3).astype(np.float32).reshape(nb, 16, 16)
+        w = (d * (sm & 15).astype(np.float32))[:, :, None] * q - (dmin * (sm >> 4).astype(np.float32))[:, :, None]
+        return w.reshape(-1).astype(np.float32)
     if ggml_type in (GGML_IQ4_NL, GGML_IQ4_XS):
         # a 32-weight sub-block is 16 bytes of table indices in Q4_0's nibble order (weights 0..15 the low nibbles, 16..31 the high ones);
         # IQ4_NL: w = d k[idx];  IQ4_XS: w = (d (ls - 32)) k[idx] with the 6-bit ls of sub-block ib = 4 bits of scales_l[ib / 2], 2 of scales_h
@@ -495,7 +509,7 @@ def use_more_bits(i: int, n: int) -> bool:
 
 
 def tensor_types(shape: LlamaShape, mix: str) -> Dict[str, int]:
-    """name -> ggml type for a quantisation mix: a plain type name, 'Q4_K_M', 'Q3_K_M' or 'IQ4_XS' (the file mix of that name)."""
+    """name -> ggml type for a quantisation mix: a plain type name, 'Q4_K_M', 'Q3_K_M', 'Q2_K_MIX' or 'IQ4_XS' (the file mix of that name)."""
     L = shape.layers
     out: Dict[str, int] = {}
     mats = ["attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down"]
@@ -526,6 +540,16 @@ def tensor_types(shape: LlamaShape, mix: str) -> Dict[str, int]:
                 elif m == "ffn_down":
                     t = GGML_Q5_K if i < L // 16 else GGML_Q4_K if use_more_bits(i, L) else GGML_Q3_K
                 out["blk.%d.%s.weight" % (i, m)] = t
+    elif mix == "Q2_K_MIX":
+        # the tensor types of llama.cpp's Q2_K file type as remembered -- its source is not at hand, so this may differ from it in detail: attn_v on Q4_K with
+        # four or more query heads per KV head, else Q3_K; attn_output and ffn_down on Q3_K; a Q6_K LM head; Q2_K everywhere else (the embedding too)
+        gqa = shape.heads // shape.kv_heads
+        out["token_embd.weight"] = GGML_Q2_K
+        out["output.weight"] = GGML_Q6_K
+        for i in range(L):
+            for m in mats:
+                t = (GGML_Q4_K if gqa >= 4 else GGML_Q3_K) if m == "attn_v" else GGML_Q3_K if m in ("attn_output", "ffn_down") else GGML_Q2_K
+                out["blk.%d.%s.weight" % (i, m)] = t
     elif mix == "IQ4_XS":
         # llama.cpp's IQ4_XS file rule as remembered -- its source is not at hand, so this may differ from it in detail: attn_v and the first eighth of the
         # ffn_down layers on Q5_K, a Q6_K LM head, IQ4_XS everywhere else (the Q | K | V launch is IQ4_XS | IQ4_XS | Q5_K)
@@ -549,7 +573,7 @@ def tensor_types(shape: LlamaShape, mix: str) -> Dict[str, int]:
         # the reference has no Q5_K branch in embed_tokens (it zero-fills, transformer.cpp:595-598),
         # so a plain-Q5_K test file keeps a Q4_K embedding like real llama.cpp K-quant files do
         out["token_embd.weight"] = GGML_Q4_K if t == GGML_Q5_K else t
-        out["output.weight"] = GGML_Q6_K if t == GGML_Q3_K else t   # (Q3_K files keep a Q6_K LM head)
+        out["output.weight"] = GGML_Q6_K if t in (GGML_Q3_K, GGML_Q2_K) else t   # (Q3_K and Q2_K files keep a Q6_K LM head)
         for i in range(L):
             for m in mats:
                 out["blk.%d.%s.weight" % (i, m)] = t

@@ -23,10 +23,10 @@ SHAPES = {  # name: (kind, rows..., in)
     "70b.qkv_fused": ("qkv", (8192, 1024, 1024), 8192), "70b.o+res": ("resid", 8192, 8192),
     "70b.gate|up+silu": ("silu", 28672, 8192), "70b.down+res": ("resid", 8192, 28672),
 }
-GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K, "Q3_K": G.GGML_Q3_K,
+GT = {"Q8_0": G.GGML_Q8_0, "Q4_0": G.GGML_Q4_0, "Q4_K": G.GGML_Q4_K, "Q5_K": G.GGML_Q5_K, "Q6_K": G.GGML_Q6_K, "Q3_K": G.GGML_Q3_K, "Q2_K": G.GGML_Q2_K,
       "IQ4_XS": G.GGML_IQ4_XS, "IQ4_NL": G.GGML_IQ4_NL, "F16": G.GGML_F16, "BF16": G.GGML_BF16}
 DENSE16 = (G.GGML_F16, G.GGML_BF16)
-RP = (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K, G.GGML_Q3_K, G.GGML_IQ4_XS)   # formats with a decode repack
+RP = (G.GGML_Q4_K, G.GGML_Q5_K, G.GGML_Q6_K, G.GGML_Q3_K, G.GGML_IQ4_XS, G.GGML_Q2_K)   # formats with a decode repack
 
 
 def main():
@@ -96,7 +96,7 @@ def main():
                     ops.gemv_rp_fused(segs, x, in_f, norm_w=nw if kind in ("qkv", "silu") else None, eps=1e-5,
                                       resid=ys[0] if kind == "resid" else None, silu_pair=kind == "silu")
                     return
-                if kind == "plain" and (a.lm or gt in DENSE16):
+                if kind == "plain" and (a.lm or gt in DENSE16 or gt == G.GGML_Q2_K):   # (ntk_gemv refuses Q2_K: its raw decoder is the fused entry point's)
                     fused([(base, ys[0], rlist[0], dt)], x, in_f)
                 elif kind == "norm":
                     fused([(base, ys[0], rlist[0], dt)], x, in_f, norm_w=nw, eps=1e-5)

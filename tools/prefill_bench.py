@@ -17,7 +17,7 @@ from ntransformer_amd.ops import DeviceBuffer as DB  # noqa: E402
 
 SHAPES = {"8b.q/o": (4096, 4096), "8b.kv": (1024, 4096), "8b.gate/up": (14336, 4096), "8b.down": (4096, 14336),
           "70b.q/o": (8192, 8192), "70b.gate/up": (28672, 8192), "70b.down": (8192, 28672)}
-GT = {"Q8_0": G.GGML_Q8_0, "Q4_K": G.GGML_Q4_K, "Q6_K": G.GGML_Q6_K, "Q3_K": G.GGML_Q3_K, "IQ4_XS": G.GGML_IQ4_XS, "IQ4_NL": G.GGML_IQ4_NL, "F16": G.GGML_F16, "BF16": G.GGML_BF16}   # (F16 / BF16 in the per-matrix table: the F32-MFMA form; the engine part: --ab-dense-mfma16)
+GT = {"Q8_0": G.GGML_Q8_0, "Q4_K": G.GGML_Q4_K, "Q6_K": G.GGML_Q6_K, "Q3_K": G.GGML_Q3_K, "Q2_K": G.GGML_Q2_K, "IQ4_XS": G.GGML_IQ4_XS, "IQ4_NL": G.GGML_IQ4_NL, "F16": G.GGML_F16, "BF16": G.GGML_BF16}   # (F16 / BF16 in the per-matrix table: the F32-MFMA form; the engine part: --ab-dense-mfma16)
 
 
 def timed(fn, reps):
@@ -31,11 +31,11 @@ def timed(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mix", default="Q8_0", help="engine part: the synthetic model's tensor-type mix (Q8_0, Q4_K_M, Q3_K_M, IQ4_XS, IQ4_NL, Q6_K, F16, ...)")
+    ap.add_argument("--mix", default="Q8_0", help="engine part: the synthetic model's tensor-type mix (Q8_0, Q4_K_M, Q3_K_M, Q2_K_MIX, IQ4_XS, IQ4_NL, Q6_K, F16, ...)")
     ap.add_argument("--json", default=None)
     ap.add_argument("--no-engine", action="store_true")
     ap.add_argument("--no-kernels", action="store_true", help="skip the per-matrix table")
-    ap.add_argument("--mixes", default="Q8_0,Q4_K,Q6_K", help="per-matrix table: weight formats (also Q3_K, IQ4_XS, IQ4_NL, F16, BF16)")
+    ap.add_argument("--mixes", default="Q8_0,Q4_K,Q6_K", help="per-matrix table: weight formats (also Q3_K, Q2_K -- F32-MFMA form only --, IQ4_XS, IQ4_NL, F16, BF16)")
     ap.add_argument("--tokens", default="16,64,256,1024", help="engine part: prompt lengths")
     ap.add_argument("--modes", default="2,1,0", help="engine part: 2 = FP16 GEMM, 1 = F32-MFMA GEMM, 0 = per-token loop (<= 64 tokens only)")
     ap.add_argument("--ab-row-max", action="store_true", help="engine part, mode 2: alternate prefill_row_max = 1 / 0 three times (the RMSNorm / SiLU launches leave the token maxima for the GEMM pre-pass, or the pre-pass makes its own pass over X)")
@@ -79,7 +79,9 @@ def main():
                           % (dname, sname, TT, t_bf * 1e6, 2.0 * TT * out_f * in_f / t_bf / 1e12, 4.0 * TT * out_f * in_f / t_bf / 1e12, t_bf * 1e6 / TT, t_gemm * 1e6 / 16), flush=True)
             if a.bf16_only: continue
             def loop():
-                for t in range(T): ops.launch_gemv(Y.at(4 * t * out_f), W, X.at(4 * t * in_f), out_f, in_f, dt)
+                for t in range(T):
+                    if gt == G.GGML_Q2_K: ops.gemv_fused([(W, Y.at(4 * t * out_f), out_f, dt)], X.at(4 * t * in_f), in_f)   # (ntk_gemv refuses the type)
+                    else: ops.launch_gemv(Y.at(4 * t * out_f), W, X.at(4 * t * in_f), out_f, in_f, dt)
             t_loop = timed(loop, 5)
             mb = out_f * rb / 1e6
             row = {"dtype": dname, "shape": sname, "MB": round(mb, 2), "gemm_us": round(t_gemm * 1e6, 1), "gemv_loop_us": round(t_loop * 1e6, 1),
